@@ -8,8 +8,9 @@ backward-data, element-wise VJPs emitting split tensors), every A / G factor, ac
 only sees the 512 x 10 head.  N > 1: one process per GPU, each rank its own K minibatches (weak scaling), one RCCL
 all-reduce of the accumulated factors inside the timed region (the fit's epoch end).
 
-Usage:  python bench.py --gpus N --steps K --warmup W      (N > 1: launched by torch.distributed.run)
-Prints ONE JSON line on rank 0.
+Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]      (N > 1: launched by torch.distributed.run)
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step`); --dump-outputs writes what the timed fit returned; --full adds every other leg and check.
 """
 from __future__ import annotations
 
@@ -51,6 +52,12 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bound of the CPU-baseline leg")
     ap.add_argument("--no-overlap", action="store_true", help="A-factor kernels on the main stream (A/B switch)")
     ap.add_argument("--no-sweep", action="store_true", help="one autograd reverse pass per seed instead of the seed-batched sweep")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure as well: the serial re-run check, the roofline / per-kernel leg, "
+                         "the drop-in loop, eigendecomposition, predictive legs, the 50 000-sample fit, the other configs, the CPU "
+                         "baselines and the multi-GPU collective checks (the --no-* switches select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed fit returned (loss, Kronecker factors) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -84,6 +91,37 @@ def fit_steps(backend, batches, n_steps, world, overlap=True, serial=False):
         fit_steps.last_exchange = info
     loss, H = acc.finalize()
     return loss, H
+
+
+DUMP_BYTES = 48 << 20  # bound of the factor files of one dump (the loss adds a few bytes)
+
+
+def dump_outputs(out_dir, loss, H):
+    """What the timed fit hands its caller — the loss and the Kronecker factors ``H.kfacs`` — as ``out_dir/loss.npy`` and
+    ``out_dir/kfac_<block>_<factor>.npy`` in their own float dtype.  A factor larger than its share of DUMP_BYTES is written as
+    ``kfac_<block>_<factor>_sample.npy``: its flattened entries at sorted indices drawn by a generator seeded with the block and
+    factor number, i.e. the same entries from run to run and from build to build."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, t):
+        t = t.detach().cpu()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.double()
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+    put("loss", loss)
+    n_factors = sum(len(blk) for blk in H.kfacs)
+    for bi, blk in enumerate(H.kfacs):
+        for fi, F in enumerate(blk):
+            keep = DUMP_BYTES // max(n_factors, 1) // F.element_size()
+            if F.numel() <= keep:
+                put(f"kfac_{bi:02d}_{fi}", F)
+            else:
+                g = torch.Generator().manual_seed(1000 * bi + fi)
+                idx = torch.randint(F.numel(), (keep,), generator=g).unique()  # (sorted)
+                put(f"kfac_{bi:02d}_{fi}_sample", F.reshape(-1)[idx.to(F.device)])
 
 
 def cpu_baseline(seconds: float):
@@ -456,6 +494,125 @@ def pmc_traffic(kernel_prefix: str, kernel_suffix: str = "", table: str = "bench
 SELFTEST = os.environ.get("LK_BENCH_SELFTEST") == "1"
 
 
+def roofline_figures(prof, prof_steps, serial_ms, instrumented_ms):
+    """(--full) The roofline leg's per-launch HIP-event times as kernel families against their roofs, the dominant family,
+    and where a step goes without overlap: returns (roofline, roofline_families, step_breakdown)."""
+    # roofline of the dominant kernel family: the implicit-im2col MFMA Gram kernel (A factors)
+    def agg(name):
+        evs = prof.get(name, [])
+        ms = sum(ev[0].elapsed_time(ev[1]) for ev in evs)
+        work = sum(ev[2] for ev in evs)
+        nb = [ev[3] for ev in evs if len(ev) > 3 and ev[3] is not None]
+        return ms, work, len(evs), (sum(nb) / len(nb) if nb and len(nb) == len(evs) else None)
+
+    # kernel families of the step: (profile key, what, bound, PMC kernel-name prefix).  MFMA families are priced on
+    # the symmetric-half flop K*n*(n+1) of the product they compute; the pixel-pair family computes the same A
+    # factors with 13/40.5 of those multiply-adds and is bound by the read-modify-write of its blocks, so it is
+    # priced on its algorithmic bytes (2 x blocks + input) against HBM.
+    PEAK_HBM_GBS = 8000.0
+    F16X2 = ("fp32-level products from two-piece fp16 operands: three v_mfma_f32_32x32x16_f16 per fp32 product block; "
+             "`achieved` = algorithmic fp32 flop / s, `peak` = 2500 / 3 TFLOP/s (the dense fp16 MFMA peak over the three "
+             "MFMAs of the scheme), i.e. `frac` IS the fraction of the fp16 matrix peak the kernel sustains")
+    fams = {
+        "convp16": ("lk::conv_winp_f16x2_kernel: persistent window form of the implicit-GEMM convolution on NHWC split "
+                    "tensors — the 3x3 / stride-1 backward-data launches of the seed-batched reverse sweep (batch 9 x 128, "
+                    "13 per step) with the element-wise VJP fused into the epilogue; " + F16X2, "mfma16",
+                    "void lk::conv_winp_f16x2_kernel"),
+        "convs16": ("lk::conv_strided_f16x2_kernel: backward-data of the three down-sampling blocks (3x3 / stride 2, all "
+                    "four residue classes, + the 1x1 shortcut) with the fused VJP epilogue, one launch per block; " + F16X2,
+                    "mfma16", "lk::conv_strided_f16x2_kernel"),
+        "conv16": ("lk::conv_f16x2_kernel: the generic implicit-GEMM convolution — the forward pass (batch 128, eval-mode "
+                   "BatchNorm / residual add / ReLU in its epilogue) and what the two fused backward forms do not cover; "
+                   + F16X2, "mfma16", "lk::conv_f16x2_kernel"),
+        "gram16": ("lk::gram16_kernel (+ fixed-order reduce): G factors as Grams of the NHWC split cotangents through "
+                   "transposing LDS reads; symmetric-half flop K*n*(n+1); " + F16X2, "mfma16", "lk::gram16_kernel", ",0>"),
+        "vjp16": ("lk::vjp_nhwc_split_kernel: element-wise VJP (mask x folded BatchNorm scale x residual add) of all "
+                  "seeds, emitting split tensors", "hbm", "lk::vjp_nhwc_split_kernel"),
+        "bnact16": ("lk::bn_act_fwd_nhwc_kernel: forward BatchNorm-eval + add + ReLU, emitting fp32, mask, split planes",
+                    "hbm", "lk::bn_act_fwd_nhwc_kernel"),
+        "gram_nt": ("lk::gram_kernel<MODE_NTB> (+ slab reduce): G factors from NCHW cotangents (graphs outside the NHWC "
+                    "sweep); six bf16 MFMAs per fp32 product block", "mfma", "void lk::gram_kernel<5,"),
+        "pixpair": ("lk::gram_kernel<MODE_TNP>: banded pixel-pair accumulation of the 3x3-conv A factors "
+                    "(block read-modify-write)", "hbm", "void lk::gram_kernel<4,"),
+        "pixpair16": ("lk::gram16_kernel<.., TNP> / lk::pixpair13_kernel (64-channel maps: one workgroup per pixel, its panel staged "
+                      "once for all 13 shifts): banded pixel-pair accumulation of the 3x3-conv A factors from the split "
+                      "images (block read-modify-write once per eight stacked minibatches; three fp16 MFMAs per fp32 "
+                      "product block); priced on its algorithmic bytes, 2 x blocks + input", "hbm",
+                      (("lk::gram16_kernel", ",1>"), ("lk::pixpair13_kernel", ""))),
+        "gram_conv": ("lk::gram_kernel<MODE_CONV> (+ slab reduce): implicit-im2col A-factor accumulation, "
+                      "exact-fp32 MFMA", "mfma", "void lk::gram_kernel<2,"),
+        "im2col16": ("lk::im2col_split_f16x2_kernel: the patch matrix of the strided / stem convolutions as split planes (its Gram — "
+                     "their A factor — then runs on lk::gram16_kernel, counted under gram16)", "hbm", "lk::im2col_split_f16x2_kernel"),
+        "shiftcorr": ("lk_conv3x3_shiftcorr_f32: shift-correlation A factors", "mfma", "void lk::gram_kernel<3,"),
+        "gram_tn": ("lk::gram_kernel<MODE_TN>: Linear-layer factors", "mfma", "void lk::gram_kernel<0,"),
+    }
+    fam_out, dominant = {}, None
+    for key, spec in fams.items():
+        what, bound, prefix = spec[:3]
+        suffix = spec[3] if len(spec) > 3 else ""
+        ms, work, n, alg_bytes = agg(key)
+        if n == 0 or ms <= 0:
+            continue
+        if bound == "mfma":
+            achieved, peak, unit = work / (ms * 1e-3) / 1e12, PEAK_F32_MFMA_TFLOPS, "TFLOP/s"
+        elif bound == "mfma16":
+            achieved, peak, unit, bound = work / (ms * 1e-3) / 1e12, PEAK_F16X2_TFLOPS, "TFLOP/s", "mfma"
+        else:
+            achieved, peak, unit = work / (ms * 1e-3) / 1e9, PEAK_HBM_GBS, "GB/s"
+        traffic, traffic_src = pmc_traffic(prefix, suffix)
+        fam_out[key] = {"kernel": what, "bound": bound, "achieved": achieved, "peak": peak, "unit": unit,
+                        "frac": achieved / peak, "traffic": traffic, "traffic_unit": "HBM bytes per launch",
+                        "traffic_source": traffic_src, "launches": n, "avg_launch_ms": ms / n,
+                        "ms_per_step": ms / prof_steps}
+        if unit == "TFLOP/s":
+            # Which roof the launch sits under is COMPUTED, not declared (round 4 labelled the persistent convolution
+            # "mfma" while its counters said 4.4 TB/s): flop per launch over the bytes the launch actually moved (PMC; the
+            # algorithmic bytes when no counter table matches these kernel sources) against the ridge peak flop / 8 TB/s.
+            f = fam_out[key]
+            secs = ms / n * 1e-3
+            moved = traffic if traffic is not None else alg_bytes
+            f["peak_fp32_mfma"] = PEAK_F32_MFMA_TFLOPS  # the exact-fp32 matrix peak the SURVEY's roofline (8d) names
+            f["frac_of_fp32_mfma_peak"] = achieved / PEAK_F32_MFMA_TFLOPS
+            f["algorithmic_bytes_per_launch"] = alg_bytes
+            if moved:
+                intensity = work / n / moved
+                ridge = peak * 1e12 / (PEAK_HBM_GBS * 1e9)
+                f["bound"] = "hbm" if intensity < ridge else "mfma"
+                f["bound_from"] = {"flop_per_byte": intensity, "ridge_flop_per_byte": ridge,
+                                   "bytes": "pmc" if traffic is not None else "algorithmic"}
+                f["frac_hbm"] = moved / secs / (PEAK_HBM_GBS * 1e9)
+                if traffic is not None and alg_bytes:
+                    f["traffic_over_algorithmic"] = traffic / alg_bytes
+        if dominant is None or ms > fam_out[dominant]["ms_per_step"] * prof_steps:
+            dominant = key
+    roof = dict(fam_out[dominant]) if dominant else {"bound": "mfma", "achieved": 0.0, "peak": PEAK_F32_MFMA_TFLOPS,
+                                                      "unit": "TFLOP/s", "frac": 0.0, "traffic": None}
+    roof["family"] = dominant
+    conv_keys = [k for k in ("convp16", "convs16", "conv16") if k in fam_out]
+    if conv_keys:  # (all convolution launches together: the figure rounds 2 and 3 quoted for `conv16`)
+        c_ms = sum(fam_out[k]["ms_per_step"] for k in conv_keys)
+        c_tf = sum(fam_out[k]["achieved"] * fam_out[k]["ms_per_step"] for k in conv_keys) / c_ms
+        roof["all_convolution_launches"] = {"families": conv_keys, "ms_per_step": c_ms, "achieved": c_tf,
+                                            "frac": c_tf / PEAK_F16X2_TFLOPS,
+                                            "launches": sum(fam_out[k]["launches"] for k in conv_keys)}
+    roof["flop_convention"] = ("convolution: 2 * Cout * Cin * (output pixel, tap) pairs that fall INSIDE the image "
+                               "(zero-padding taps are not counted: the figure does not move with the padding); "
+                               "Gram families: symmetric half K*n*(n+1)")
+    own_ms = sum(v["ms_per_step"] for v in fam_out.values())
+    breakdown = None
+    if serial_ms is not None:
+        # where a step goes when nothing overlaps (the instrumented pass): our kernel families, and the rest (rocBLAS
+        # for the 512 x 10 head, torch element-wise glue, launch gaps).  No MIOpen kernel is left in the step.
+        breakdown = {"serial_ms_per_step": serial_ms, "own_kernels_ms": own_ms, "other_ms": max(serial_ms - own_ms, 0.0),
+                     "own_share": min(own_ms / serial_ms, 1.0) if serial_ms > 0 else None,
+                     "instrumented_serial_ms_per_step": instrumented_ms,
+                     "note": "one stream, no overlap (incl. the once-per-fit finalisation spread over the steps); "
+                             "own_kernels_ms: sum of per-launch HIP-event times of the instrumented pass; "
+                             "serial_ms_per_step: the same schedule without the events (the instrumented pass is "
+                             "host-bound); the timed region overlaps two minibatches and the factor kernels"}
+    return roof, fam_out, breakdown
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -517,13 +674,17 @@ def main():
     loss, H = fit_steps(backend, batches, args.steps, world, overlap)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before any other leg runs on this backend)
+        dump_outputs(args.dump_outputs, loss, H)
+
+    # ---- everything below up to the result line, and the untimed extras after it, run with --full only ----------------
 
     # ---- check (rank 0): the factors of the TIMED run against the same K minibatches re-run with every scheduling
     # feature off (no side stream, no lagged join, one pixel-pair launch per minibatch, per-launch reductions) — an
     # ordering bug in the overlapped schedule would produce a fast wrong number.  Each factor block relative to its
     # own largest element; the fp64 / reference-level parity of the same configuration is tests/test_gpu_timed_config.py
     check = None
-    if rank == 0 and world == 1 and not args.no_check:
+    if args.full and rank == 0 and world == 1 and not args.no_check:
         loss_s, H_s = fit_steps(backend, batches, args.steps, 1, serial=True)
         worst, worst_at = 0.0, None
         for bi, (F_, S_) in enumerate(zip(H.kfacs, H_s.kfacs)):
@@ -544,8 +705,8 @@ def main():
     # durations are the kernels' own (the throughput above is measured without this instrumentation)
     prof = {}
     prof_steps = min(args.steps, 5)
-    serial_ms = None
-    if rank == 0 and not SELFTEST:
+    serial_ms = instrumented_ms = None
+    if args.full and rank == 0 and not SELFTEST:
         fit_steps(backend, batches, 2, 1, overlap=False)  # (the accumulators of this leg warm up outside the clock)
         torch.cuda.synchronize()
         K.profile = prof
@@ -571,128 +732,6 @@ def main():
     result = None
     if rank == 0:
         samples = world * BATCH * args.steps
-        # roofline of the dominant kernel family: the implicit-im2col MFMA Gram kernel (A factors)
-        def agg(name):
-            evs = prof.get(name, [])
-            ms = sum(ev[0].elapsed_time(ev[1]) for ev in evs)
-            work = sum(ev[2] for ev in evs)
-            nb = [ev[3] for ev in evs if len(ev) > 3 and ev[3] is not None]
-            return ms, work, len(evs), (sum(nb) / len(nb) if nb and len(nb) == len(evs) else None)
-
-        # kernel families of the step: (profile key, what, bound, PMC kernel-name prefix).  MFMA families are priced on
-        # the symmetric-half flop K*n*(n+1) of the product they compute; the pixel-pair family computes the same A
-        # factors with 13/40.5 of those multiply-adds and is bound by the read-modify-write of its blocks, so it is
-        # priced on its algorithmic bytes (2 x blocks + input) against HBM.
-        PEAK_HBM_GBS = 8000.0
-        F16X2 = ("fp32-level products from two-piece fp16 operands: three v_mfma_f32_32x32x16_f16 per fp32 product block; "
-                 "`achieved` = algorithmic fp32 flop / s, `peak` = 2500 / 3 TFLOP/s (the dense fp16 MFMA peak over the three "
-                 "MFMAs of the scheme), i.e. `frac` IS the fraction of the fp16 matrix peak the kernel sustains")
-        fams = {
-            "convp16": ("lk::conv_winp_f16x2_kernel: persistent window form of the implicit-GEMM convolution on NHWC split "
-                        "tensors — the 3x3 / stride-1 backward-data launches of the seed-batched reverse sweep (batch 9 x 128, "
-                        "13 per step) with the element-wise VJP fused into the epilogue; " + F16X2, "mfma16",
-                        "void lk::conv_winp_f16x2_kernel"),
-            "convs16": ("lk::conv_strided_f16x2_kernel: backward-data of the three down-sampling blocks (3x3 / stride 2, all "
-                        "four residue classes, + the 1x1 shortcut) with the fused VJP epilogue, one launch per block; " + F16X2,
-                        "mfma16", "lk::conv_strided_f16x2_kernel"),
-            "conv16": ("lk::conv_f16x2_kernel: the generic implicit-GEMM convolution — the forward pass (batch 128, eval-mode "
-                       "BatchNorm / residual add / ReLU in its epilogue) and what the two fused backward forms do not cover; "
-                       + F16X2, "mfma16", "lk::conv_f16x2_kernel"),
-            "gram16": ("lk::gram16_kernel (+ fixed-order reduce): G factors as Grams of the NHWC split cotangents through "
-                       "transposing LDS reads; symmetric-half flop K*n*(n+1); " + F16X2, "mfma16", "lk::gram16_kernel", ",0>"),
-            "vjp16": ("lk::vjp_nhwc_split_kernel: element-wise VJP (mask x folded BatchNorm scale x residual add) of all "
-                      "seeds, emitting split tensors", "hbm", "lk::vjp_nhwc_split_kernel"),
-            "bnact16": ("lk::bn_act_fwd_nhwc_kernel: forward BatchNorm-eval + add + ReLU, emitting fp32, mask, split planes",
-                        "hbm", "lk::bn_act_fwd_nhwc_kernel"),
-            "gram_nt": ("lk::gram_kernel<MODE_NTB> (+ slab reduce): G factors from NCHW cotangents (graphs outside the NHWC "
-                        "sweep); six bf16 MFMAs per fp32 product block", "mfma", "void lk::gram_kernel<5,"),
-            "pixpair": ("lk::gram_kernel<MODE_TNP>: banded pixel-pair accumulation of the 3x3-conv A factors "
-                        "(block read-modify-write)", "hbm", "void lk::gram_kernel<4,"),
-            "pixpair16": ("lk::gram16_kernel<.., TNP> / lk::pixpair13_kernel (64-channel maps: one workgroup per pixel, its panel staged "
-                          "once for all 13 shifts): banded pixel-pair accumulation of the 3x3-conv A factors from the split "
-                          "images (block read-modify-write once per eight stacked minibatches; three fp16 MFMAs per fp32 "
-                          "product block); priced on its algorithmic bytes, 2 x blocks + input", "hbm",
-                          (("lk::gram16_kernel", ",1>"), ("lk::pixpair13_kernel", ""))),
-            "gram_conv": ("lk::gram_kernel<MODE_CONV> (+ slab reduce): implicit-im2col A-factor accumulation, "
-                          "exact-fp32 MFMA", "mfma", "void lk::gram_kernel<2,"),
-            "im2col16": ("lk::im2col_split_f16x2_kernel: the patch matrix of the strided / stem convolutions as split planes (its Gram — "
-                         "their A factor — then runs on lk::gram16_kernel, counted under gram16)", "hbm", "lk::im2col_split_f16x2_kernel"),
-            "shiftcorr": ("lk_conv3x3_shiftcorr_f32: shift-correlation A factors", "mfma", "void lk::gram_kernel<3,"),
-            "gram_tn": ("lk::gram_kernel<MODE_TN>: Linear-layer factors", "mfma", "void lk::gram_kernel<0,"),
-        }
-        fam_out, dominant = {}, None
-        for key, spec in fams.items():
-            what, bound, prefix = spec[:3]
-            suffix = spec[3] if len(spec) > 3 else ""
-            ms, work, n, alg_bytes = agg(key)
-            if n == 0 or ms <= 0:
-                continue
-            if bound == "mfma":
-                achieved, peak, unit = work / (ms * 1e-3) / 1e12, PEAK_F32_MFMA_TFLOPS, "TFLOP/s"
-            elif bound == "mfma16":
-                achieved, peak, unit, bound = work / (ms * 1e-3) / 1e12, PEAK_F16X2_TFLOPS, "TFLOP/s", "mfma"
-            else:
-                achieved, peak, unit = work / (ms * 1e-3) / 1e9, PEAK_HBM_GBS, "GB/s"
-            traffic, traffic_src = pmc_traffic(prefix, suffix)
-            fam_out[key] = {"kernel": what, "bound": bound, "achieved": achieved, "peak": peak, "unit": unit,
-                            "frac": achieved / peak, "traffic": traffic, "traffic_unit": "HBM bytes per launch",
-                            "traffic_source": traffic_src, "launches": n, "avg_launch_ms": ms / n,
-                            "ms_per_step": ms / prof_steps}
-            if unit == "TFLOP/s":
-                # Which roof the launch sits under is COMPUTED, not declared (round 4 labelled the persistent convolution
-                # "mfma" while its counters said 4.4 TB/s): flop per launch over the bytes the launch actually moved (PMC; the
-                # algorithmic bytes when no counter table matches these kernel sources) against the ridge peak flop / 8 TB/s.
-                f = fam_out[key]
-                secs = ms / n * 1e-3
-                moved = traffic if traffic is not None else alg_bytes
-                f["peak_fp32_mfma"] = PEAK_F32_MFMA_TFLOPS  # the exact-fp32 matrix peak the SURVEY's roofline (8d) names
-                f["frac_of_fp32_mfma_peak"] = achieved / PEAK_F32_MFMA_TFLOPS
-                f["algorithmic_bytes_per_launch"] = alg_bytes
-                if moved:
-                    intensity = work / n / moved
-                    ridge = peak * 1e12 / (PEAK_HBM_GBS * 1e9)
-                    f["bound"] = "hbm" if intensity < ridge else "mfma"
-                    f["bound_from"] = {"flop_per_byte": intensity, "ridge_flop_per_byte": ridge,
-                                       "bytes": "pmc" if traffic is not None else "algorithmic"}
-                    f["frac_hbm"] = moved / secs / (PEAK_HBM_GBS * 1e9)
-                    if traffic is not None and alg_bytes:
-                        f["traffic_over_algorithmic"] = traffic / alg_bytes
-            if dominant is None or ms > fam_out[dominant]["ms_per_step"] * prof_steps:
-                dominant = key
-        roof = dict(fam_out[dominant]) if dominant else {"bound": "mfma", "achieved": 0.0, "peak": PEAK_F32_MFMA_TFLOPS,
-                                                          "unit": "TFLOP/s", "frac": 0.0, "traffic": None}
-        roof["family"] = dominant
-        conv_keys = [k for k in ("convp16", "convs16", "conv16") if k in fam_out]
-        if conv_keys:  # (all convolution launches together: the figure rounds 2 and 3 quoted for `conv16`)
-            c_ms = sum(fam_out[k]["ms_per_step"] for k in conv_keys)
-            c_tf = sum(fam_out[k]["achieved"] * fam_out[k]["ms_per_step"] for k in conv_keys) / c_ms
-            roof["all_convolution_launches"] = {"families": conv_keys, "ms_per_step": c_ms, "achieved": c_tf,
-                                                "frac": c_tf / PEAK_F16X2_TFLOPS,
-                                                "launches": sum(fam_out[k]["launches"] for k in conv_keys)}
-        roof["flop_convention"] = ("convolution: 2 * Cout * Cin * (output pixel, tap) pairs that fall INSIDE the image "
-                                   "(zero-padding taps are not counted: the figure does not move with the padding); "
-                                   "Gram families: symmetric half K*n*(n+1)")
-        own_ms = sum(v["ms_per_step"] for v in fam_out.values())
-        # the whole step by SURVEY.md section 8d's convention: 23.2 GFLOP per sample end to end (forward + C input-gradient
-        # passes + factor products, full-GEMM count) against the exact-fp32 matrix peak that section named as the roof, and
-        # against the ceiling of the scheme actually used.  Above 1.0 of the fp32 figure is not a kernel skipping work (see
-        # `check` and tests/test_gpu_timed_config.py): the products run on the fp16 pipe at three MFMAs each, and the step does
-        # fewer flops than that count (9 seeds instead of 10, symmetric halves, pixel-pair A factors at 13 / 40.5).
-        step_tf = 23.2e9 * BATCH / (dt / args.steps) / 1e12
-        whole_step = {"flop_per_sample_section_8d": 23.2e9, "achieved_tflops_by_that_count": step_tf,
-                      "frac_of_fp32_mfma_peak": step_tf / PEAK_F32_MFMA_TFLOPS, "frac_of_f16x2_ceiling": step_tf / PEAK_F16X2_TFLOPS,
-                      "peak_fp32_mfma": PEAK_F32_MFMA_TFLOPS, "peak_f16x2": PEAK_F16X2_TFLOPS}
-        breakdown = None
-        if serial_ms is not None:
-            # where a step goes when nothing overlaps (the instrumented pass): our kernel families, and the rest (rocBLAS
-            # for the 512 x 10 head, torch element-wise glue, launch gaps).  No MIOpen kernel is left in the step.
-            breakdown = {"serial_ms_per_step": serial_ms, "own_kernels_ms": own_ms, "other_ms": max(serial_ms - own_ms, 0.0),
-                         "own_share": min(own_ms / serial_ms, 1.0) if serial_ms > 0 else None,
-                         "instrumented_serial_ms_per_step": instrumented_ms,
-                         "note": "one stream, no overlap (incl. the once-per-fit finalisation spread over the steps); "
-                                 "own_kernels_ms: sum of per-launch HIP-event times of the instrumented pass; "
-                                 "serial_ms_per_step: the same schedule without the events (the instrumented pass is "
-                                 "host-bound); the timed region overlaps two minibatches and the factor kernels"}
         result = {
             "metric": "KFAC-GGN fit samples/sec, ResNet-18",
             "value": samples / dt,
@@ -710,14 +749,25 @@ def main():
                                    "per-GPU minibatch 128, synthetic N(0,1) 3x32x32, 10 classes, N=50000",
                        "per_gpu_batch": BATCH, "parallelism": f"dp{world}",
                        "minibatches_in_flight": int(__import__("laplace_amd.backend", fromlist=["KronAccumulator"]).KronAccumulator.default_lanes)},
-            "roofline": roof,  # the family with the largest share of the WHOLE step (measured without stream overlap)
-            "roofline_families": fam_out,
-            "whole_step": whole_step,
-            "step_breakdown": breakdown,
-            "check": check,
         }
+        if args.full:
+            roof, fam_out, breakdown = roofline_figures(prof, prof_steps, serial_ms, instrumented_ms)
+            result["roofline"] = roof  # the family with the largest share of the WHOLE step (measured without stream overlap)
+            result["roofline_families"] = fam_out
+            result["step_breakdown"] = breakdown
+            result["check"] = check
+            # the whole step by SURVEY.md section 8d's convention: 23.2 GFLOP per sample end to end (forward + C input-gradient
+            # passes + factor products, full-GEMM count) against the exact-fp32 matrix peak that section named as the roof, and
+            # against the ceiling of the scheme actually used.  Above 1.0 of the fp32 figure is not a kernel skipping work (see
+            # `check` and tests/test_gpu_timed_config.py): the products run on the fp16 pipe at three MFMAs each, and the step does
+            # fewer flops than that count (9 seeds instead of 10, symmetric halves, pixel-pair A factors at 13 / 40.5).
+            step_tf = 23.2e9 * BATCH / (dt / args.steps) / 1e12
+            whole_step = {"flop_per_sample_section_8d": 23.2e9, "achieved_tflops_by_that_count": step_tf,
+                          "frac_of_fp32_mfma_peak": step_tf / PEAK_F32_MFMA_TFLOPS, "frac_of_f16x2_ceiling": step_tf / PEAK_F16X2_TFLOPS,
+                          "peak_fp32_mfma": PEAK_F32_MFMA_TFLOPS, "peak_f16x2": PEAK_F16X2_TFLOPS}
+            result["whole_step"] = whole_step
     # ---- untimed extras on rank 0 (separate line items per BASELINE.md) --------------------------------------
-    if rank == 0 and world == 1 and not SELFTEST:
+    if args.full and rank == 0 and world == 1 and not SELFTEST:
         # what the reference's own `fit` executes with backend=HipGGN: `self.H += backend.kron(X, y, N)` per minibatch
         # (laplace/baselaplace.py:969-985) — one Kron per batch in the public layout, then the factor-wise add
         from laplace_amd.kron import HipKron
@@ -740,7 +790,7 @@ def main():
         sync()
         result["dropin_fit_samples_per_s"] = n_lit * BATCH / (time.perf_counter() - t0)
     pred_dec = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_eigh:
             sync()
             t0 = time.perf_counter()
@@ -841,7 +891,7 @@ def main():
                 result["predictive_kron_c4"]["cpu_baseline"] = cpu_predictive_baseline(pred_dec, 1.0, args.cpu_seconds)
             result["cpu_baseline"] = cpu_baseline(0.0 if SELFTEST else args.cpu_seconds)
         pred_dec = None
-    if world > 1:
+    if args.full and world > 1:
         # the fit's ONE collective: message size against what the model's factor shapes say it must be (a wrong pack /
         # a missed factor shows here, not as a silently wrong posterior), and its stand-alone time on the same buffer size
         from laplace_amd.laplace import expected_exchange_bytes
@@ -862,7 +912,7 @@ def main():
                                    "note": "one all-reduce per fit (packed upper triangles of the 43 factors + loss)"}
             assert info.get("bytes") == want, f"curvature exchange moved {info.get('bytes')} bytes, expected {want}"
         del buf
-    if world > 1 and not args.no_eigh:
+    if args.full and world > 1 and not args.no_eigh:
         # the factors are identical on every rank after the all-reduce: shard the eigensolves over the GPUs
         barrier()
         t0 = time.perf_counter()

@@ -11,7 +11,7 @@ import laplace_amd._lib as L, laplace_amd.backend as Bk, laplace_amd.sweep_nhwc 
 ns = {'HipKernels': L.HipKernels, 'KronAccumulator': Bk.KronAccumulator, 'SplitSweep': Sw.SplitSweep, 'HipGGN': Bk.HipGGN}
 cls, attr = '$ATTR'.split('.')
 setattr(ns[cls], attr, $v)
-sys.argv = ['bench.py'] + '$FLAGS'.split()
+sys.argv = ['bench.py', '--full'] + '$FLAGS'.split()
 runpy.run_path('bench.py', run_name='__main__')" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']

@@ -3,7 +3,7 @@
 #   1. the whole -m gpu suite; the parity numbers its rel() helpers measured -> gpurun_out/<R>_parity_errors_<tag>.log
 #   2. PMC traffic passes over the bench command (FETCH_SIZE / WRITE_SIZE in separate runs, kernel-trace only)
 #   3. rocprofv3 --kernel-trace --stats of the driver's bench command, and of 20 serial steady-state steps
-#   4. the bench lines: the driver's `--steps 20 --warmup 5` and the default flags
+#   4. the bench lines (--full): `--steps 20 --warmup 5` and the default steps
 #   5. smoke()
 # Writes under gpurun_out/; copy what is to be judged into profiles/.
 # usage: bash tools/gpu_evidence.sh <round, e.g. r05> [tag] [notests] [nodefault]
@@ -13,12 +13,13 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 S=gpurun_out/${R5}_summary_$TAG.log; : > $S
+O=$(dirname "$S")  # the pass's output folder
 if [[ " $* " != *" notests "* ]]; then
   timeout 1500 python -m pytest tests -m gpu -q -rs --durations=10 > gpurun_out/${R5}_gpu_tests_$TAG.log 2>&1; echo "tests rc=$?" >> $S
   tail -4 gpurun_out/${R5}_gpu_tests_$TAG.log >> $S
   cp gpurun_out/parity_errors.log gpurun_out/${R5}_parity_errors_$TAG.log 2>/dev/null
 fi
-LIGHT="--no-cpu-baseline --no-predictive --no-eigh --no-extras --no-check"
+LIGHT="--full --no-cpu-baseline --no-predictive --no-eigh --no-extras --no-check"
 rm -rf gpurun_out/pmc gpurun_out/prof_$TAG gpurun_out/ks_$TAG
 for c in FETCH_SIZE WRITE_SIZE; do
   cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $c -d $R/gpurun_out/pmc -o pmc_$c -- python $R/bench.py --steps 2 --warmup 1 $LIGHT > $R/gpurun_out/pmc_$c.log 2>&1
@@ -46,10 +47,10 @@ cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $R/gpurun_out/ks_$TAG -o p --
 cd $R
 python tools/rocpd_stats.py $(find gpurun_out/ks_$TAG -name "*.db" | head -1) gpurun_out/${R5}_steps_serial_kernel_stats_$TAG.md > /dev/null 2>&1
 rm -rf gpurun_out/ks_$TAG
-timeout 900 python bench.py --steps 20 --warmup 5 > gpurun_out/${R5}_bench_k20_$TAG.log 2>&1; echo "bench k20 rc=$?" >> $S
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$O"/${R5}_bench_k20_$TAG.log 2>&1; echo "bench k20 rc=$?" >> $S
 grep '^{' gpurun_out/${R5}_bench_k20_$TAG.log | tail -1 > gpurun_out/${R5}_bench_c4_k20_$TAG.json
 if [[ " $* " != *" nodefault "* ]]; then
-  timeout 900 python bench.py > gpurun_out/${R5}_bench_$TAG.log 2>&1; echo "bench rc=$?" >> $S
+  timeout 900 python bench.py --full > "$O"/${R5}_bench_$TAG.log 2>&1; echo "bench rc=$?" >> $S
   grep '^{' gpurun_out/${R5}_bench_$TAG.log | tail -1 > gpurun_out/${R5}_bench_c4_$TAG.json
 fi
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" >> $S 2>&1
