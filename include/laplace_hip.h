@@ -561,6 +561,33 @@ size_t lk_dense_quadform_ll_workspace_bytes(int64_t B, int64_t C, int64_t D);
 int lk_dense_quadform_ll_f32(const float* phi, const float* Sigma, int64_t B, int64_t C, int64_t D, int has_bias,
                              float* fvar, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prior-precision grid search (BaseLaplace.optimize_prior_precision(method="gridsearch"), baselaplace.py:487-561) in one
+ * pass: only the diagonal of the output covariance, var [G][B][C] (+=), at all G prior precisions deltas[G].  Weight of
+ * parameter (o, i) at grid point g, by `mode`:
+ *   0  Kron           1 / (l1_o l2_i + delta_g)                 w0 = l1 [Do], w1 = l2 [Di / Dk]
+ *   1  damped Kron    1 / ((l1_o + sqrt delta_g)(l2_i + sqrt delta_g))   (matrix.py:397-399, 441-444)
+ *   2  diagonal       1 / (h_oi + delta_g)                        w0 = h [Do][Di / Dk] (prior-free precision), w1 unused
+ * Every sum runs in a fixed order (no float atomics): repeated calls give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+/* nn.Linear layer: var[g][n][c] += sum_o u[c][n][o]^2 sum_i v[n][i]^2 W_g(o,i)  (+ sum_o ub[c][n][o]^2 / (wb_o + delta_g) if
+ * ub != NULL).  u [C][B][Do], v [B][Di] as for lk_kron_quadform_linear_f32 (eigenbasis projections; raw gradients /
+ * activations for mode 2). */
+int lk_quadform_linear_grid_f32(const float* u, const float* v, const float* w0, const float* w1, const float* deltas,
+                                int64_t G, int mode, int64_t B, int64_t C, int64_t Do, int64_t Di, const float* ub,
+                                const float* wb, float* var, void* stream);
+/* Weight-sharing layer: var[g][n][c] += sum_{o,i} (sum_l u[n][c][o][l] v[n][i][l])^2 W_g(o,i).  u [B][C][Do][L] (seed_major:
+ * [C][B][Do][L]), v [B][Dk][L]; any C.  The tile products of lk_kron_quadform_shared_f32 (fp32 accuracy) are formed once;
+ * only the weighted reduction runs per grid point. */
+size_t lk_quadform_shared_grid_workspace_bytes(int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t G);
+int lk_quadform_shared_grid_f32(const float* u, const float* v, const float* w0, const float* w1, const float* deltas,
+                                int64_t G, int mode, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L,
+                                int seed_major, float* var, void* ws, size_t ws_bytes, void* stream);
+/* Probit link + NLL: loss_sum[g] += sum_n -log(max(softmax(kappa f_mu[n])[labels[n]], 1e-30)),
+ * kappa_c = 1 / sqrt(1 + pi/8 var[g][n][c]) (baselaplace.py:649-651); f_mu [B][C], labels int64 [B], loss_sum double [G]. */
+int lk_probit_nll_grid_f32(const float* f_mu, const float* var, const int64_t* labels, int64_t G, int64_t B, int64_t C,
+                           double* loss_sum, void* stream);
+
 /* ---- the fit's one collective (replaces nothing in the reference, which has no multi-GPU fit: the loop of
  * laplace/baselaplace.py:969-985 sharded over ranks needs ONE sum of the accumulated factors at epoch end) -------------------
  * Thin wrappers over RCCL (ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllReduce(ncclFloat, ncclSum, in place)),

@@ -132,6 +132,11 @@ SIGNATURES = {
     "lk_dense_quadform_ll_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "lk_jac_last_layer_f32": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp]),
     "lk_dense_quadform_ll_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    "lk_quadform_linear_grid_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "lk_quadform_shared_grid_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "lk_quadform_shared_grid_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz,
+                                           _vp]),
+    "lk_probit_nll_grid_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
 }
 
 
@@ -1413,6 +1418,64 @@ class HipKernels:
             "lk_diag_quadform_linear_f32",
         )
         return fvar
+
+    # ---- prior-precision grid (csrc/lk_grid.hip): var [G, B, C] of all grid points in one pass ----------------------------
+    #: weight forms of the grid kernels: Kron, damped Kron, diagonal
+    GRID_KRON, GRID_KRON_DAMPED, GRID_DIAG = 0, 1, 2
+
+    def quadform_linear_grid(self, u, v, w0, w1, deltas, mode, var, ub=None, wb=None):
+        """nn.Linear layer, ``u [C, B, Do]``, ``v [B, Di]``; ``w0, w1`` = ``l1 [Do], l2 [Di]`` (Kron modes) or ``h [Do, Di], None``
+        (diagonal); optional bias block ``ub [C, B, Do]`` with ``wb [Do]``; ``var [G, B, C] +=``"""
+        for t, nm in ((u, "u"), (v, "v"), (w0, "w0"), (deltas, "deltas"), (var, "var")):
+            _check(t, nm)
+        if w1 is not None:
+            _check(w1, "w1")
+        if ub is not None:
+            _check(ub, "ub"), _check(wb, "wb")
+        C, B, Do = u.shape
+        Di = v.shape[1]
+        G = deltas.numel()
+        if v.shape[0] != B or var.shape != (G, B, C):
+            raise LaplaceHipError("quadform_linear_grid: u [C, B, Do], v [B, Di], var [G, B, C]")
+        self._rc(self.lib.lk_quadform_linear_grid_f32(_ptr(u), _ptr(v), _ptr(w0), _ptr(w1), _ptr(deltas), G, int(mode), B, C, Do,
+                                                      Di, _ptr(ub), _ptr(wb), _ptr(var), self._stream(u.device)),
+                 "lk_quadform_linear_grid_f32")
+        return var
+
+    def quadform_shared_grid(self, u, v, w0, w1, deltas, mode, var, seed_major=False):
+        """weight-sharing layer, ``u [B, C, Do, L]`` (``seed_major``: ``[C, B, Do, L]``), ``v [B, Dk, L]``; weights as
+        :meth:`quadform_linear_grid` (``h [Do, Dk]`` for the diagonal form); ``var [G, B, C] +=``"""
+        for t, nm in ((u, "u"), (v, "v"), (w0, "w0"), (deltas, "deltas"), (var, "var")):
+            _check(t, nm)
+        if w1 is not None:
+            _check(w1, "w1")
+        if seed_major:
+            C, B, Do, L = u.shape
+        else:
+            B, C, Do, L = u.shape
+        Dk = v.shape[1]
+        G = deltas.numel()
+        if v.shape != (B, Dk, L) or var.shape != (G, B, C):
+            raise LaplaceHipError("quadform_shared_grid: v [B, Dk, L], var [G, B, C]")
+        ws = self._workspace(self.lib.lk_quadform_shared_grid_workspace_bytes(B, C, Do, Dk, G), u.device)
+        self._rc(self._timed("quadgrid", 2.0 * B * C * L * Do * Dk + 2.0 * B * C * Do * Dk * G, u.device,
+                             lambda: self.lib.lk_quadform_shared_grid_f32(
+                                 _ptr(u), _ptr(v), _ptr(w0), _ptr(w1), _ptr(deltas), G, int(mode), B, C, Do, Dk, L,
+                                 int(bool(seed_major)), _ptr(var), _ptr(ws), ws.numel(), self._stream(u.device))),
+                 "lk_quadform_shared_grid_f32")
+        return var
+
+    def probit_nll_grid(self, f_mu, var, y, loss_sum):
+        """``loss_sum [G] (float64) +=`` the probit-link NLL of the batch at every grid point; ``f_mu [B, C]``,
+        ``var [G, B, C]``, ``y [B]`` (int64)"""
+        _check(f_mu, "f_mu"), _check(var, "var"), _check(y, "y", torch.int64), _check(loss_sum, "loss_sum", torch.float64)
+        B, C = f_mu.shape
+        G = loss_sum.numel()
+        if var.shape != (G, B, C) or y.shape != (B,):
+            raise LaplaceHipError("probit_nll_grid: f_mu [B, C], var [G, B, C], y [B], loss_sum [G]")
+        self._rc(self.lib.lk_probit_nll_grid_f32(_ptr(f_mu), _ptr(var), _ptr(y), G, B, C, _ptr(loss_sum),
+                                                 self._stream(f_mu.device)), "lk_probit_nll_grid_f32")
+        return loss_sum
 
     def diag_quadform_js(self, Js, var):
         _check(Js, "Js"), _check(var, "var")

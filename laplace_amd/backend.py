@@ -47,13 +47,13 @@ from laplace_amd.refapi import EFInterface, GGNInterface
 _OWN_ROTATION = True
 
 
-def shared_operands(tap, g, B, C, Q1=None, Q2=None, bounds=None):
+def shared_operands(tap, g, B, C, Q1=None, Q2=None, bounds=None, planes: bool = True):
     """``u [B, C, Do, L]`` and ``v [B, Dk, L]`` (both position-contiguous) of a weight-sharing layer (Conv2d, or Linear
     along a sequence), whose per-sample Jacobian of output / seed ``c`` is ``sum_l u[n, c, :, l] v[n, :, l]^T``
     (:mod:`laplace_amd.predictive`), rotated into the eigenbases ``Q1`` / ``Q2`` if given; plus the position-summed
     output gradient ``[C, B, Do]`` for the bias.  ``bounds``: a dict that receives the FORM the operands come back in —
     ``planes``: both are SplitTensors (lk_conv_nhwc_f16x2_planes: ``u [C * B, Do, L]`` seed-major with one scale, ``v [B, Dk, L]``
-    with one scale per sample), ``u_seed_major``: fp32 with ``u [C, B, Do, L]``."""
+    with one scale per sample), ``u_seed_major``: fp32 with ``u [C, B, Do, L]``.  ``planes=False`` keeps both operands fp32."""
     m = tap.module
     a = tap.a.to(torch.float32)
     if tap.kind == "conv2d":
@@ -65,7 +65,8 @@ def shared_operands(tap, g, B, C, Q1=None, Q2=None, bounds=None):
         rotated = False
         own_v = (Q2 is not None and _OWN_ROTATION and hasattr(K, "conv_nhwc_f16x2") and cv._geometry_ok(m)
                  and m.in_channels % 32 == 0 and Dk % 8 == 0)
-        if (isinstance(g, SplitTensor) and Q1 is not None and bounds is not None and not tap.has_bias and _OWN_ROTATION and own_v
+        if (planes and isinstance(g, SplitTensor) and Q1 is not None and bounds is not None and not tap.has_bias and _OWN_ROTATION
+                and own_v
                 and getattr(K, "use_quad_planes", False) and Do % 32 == 0 and (g.shape[1] * g.shape[2]) % 16 == 0
                 and C <= K.quadform_shared_max_outputs
                 # (the planes kernel indexes u with 32 bits: a predictive batch beyond that takes the chunked fp32 route below

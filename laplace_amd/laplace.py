@@ -371,12 +371,13 @@ class _HipLaplace:
                                  lr: float = 1e-1, init_prior_prec=1.0, prior_structure: str = "diag", val_loader=None,
                                  loss=None, log_prior_prec_min: float = -4, log_prior_prec_max: float = 4,
                                  grid_size: int = 100, link_approx: str = "probit", n_samples: int = 100,
-                                 verbose: bool = False, progress_bar: bool = False):
+                                 verbose: bool = False, progress_bar: bool = False, batched: bool = False):
         """Same call as the reference's (baselaplace.py:363-509).  ``method='marglik'``: Adam on the log prior
         precision (scalar / layer-wise / per-parameter: a scalar ``init_prior_prec`` is expanded to
         ``prior_structure``, a tensor keeps its own structure); every step is one ``lk_kron_logdet_blocks_f32`` call
         over all blocks of the posterior for the Kron flavours, with the analytic derivative in the prior precision.
-        ``method='gridsearch'``: :meth:`gridsearch_prior_precision` on ``val_loader``."""
+        ``method='gridsearch'``: :meth:`gridsearch_prior_precision` on ``val_loader`` (``batched``: all grid points in one
+        pass over it, :meth:`validation_loss_grid`)."""
         if method == "marglik":
             pp = torch.as_tensor(init_prior_prec, device=self._device, dtype=self._dtype).reshape(-1)
             if len(pp) == 1 and prior_structure != "scalar":
@@ -396,7 +397,7 @@ class _HipLaplace:
             if val_loader is None:
                 raise ValueError("gridsearch requires a validation set DataLoader")
             self.gridsearch_prior_precision(val_loader, log_prior_prec_min, log_prior_prec_max, grid_size, pred_type,
-                                            link_approx, n_samples, loss)
+                                            link_approx, n_samples, loss, batched=batched)
         else:
             raise ValueError("For now only marglik and gridsearch is implemented.")
         if verbose:
@@ -583,31 +584,35 @@ class _HipLaplace:
     @torch.no_grad()
     def gridsearch_prior_precision(self, val_loader, log_prior_prec_min: float = -4, log_prior_prec_max: float = 4,
                                    grid_size: int = 100, pred_type: str = "glm", link_approx: str = "probit",
-                                   n_samples: int = 100, loss=None):
+                                   n_samples: int = 100, loss=None, batched: bool = False):
         """Pick the scalar prior precision of ``logspace(min, max, grid_size)`` with the best validation loss
         (default: NLL for classification, MSE for regression, as the reference's ``RunningNLLMetric`` /
-        ``MeanSquaredError``).  A grid point whose posterior is not positive definite scores ``inf``."""
-        from collections.abc import MutableMapping
+        ``MeanSquaredError``).  A grid point whose posterior is not positive definite scores ``inf``.
 
-        def batches():
-            for data in val_loader:
-                if isinstance(data, MutableMapping):  # HuggingFace-style batch: labels under dict_key_y
-                    yield data, data[self.backend.dict_key_y].to(self._device)
-                else:
-                    yield data[0].to(self._device), data[1].to(self._device)
-
+        ``batched=True`` evaluates every grid point in one pass over ``val_loader`` (:meth:`validation_loss_grid`) and
+        runs the per-point loop below wherever that route does not apply."""
+        interval = torch.logspace(log_prior_prec_min, log_prior_prec_max, grid_size)
+        if batched:
+            try:
+                losses = self.validation_loss_grid(val_loader, interval, pred_type, link_approx, loss)
+            except NotImplementedError:
+                pass
+            else:
+                results = losses.tolist()  # the one host read-back of the search
+                best = int(torch.tensor(results).argmin())
+                self.prior_precision = interval[best]
+                return self.prior_precision
         cached = None
         if self.subset_of_weights == "last_layer" and pred_type == "glm" and self.backend.last_layer:
             # the backbone does not depend on the prior: one feature pass per validation batch for the whole grid
-            cached = [(self.backend.cache_features(X), y) for X, y in batches()]
-        interval = torch.logspace(log_prior_prec_min, log_prior_prec_max, grid_size)
+            cached = [(self.backend.cache_features(X), y) for X, y in self._val_batches(val_loader)]
         results = []
         for pp in interval:
             self.prior_precision = pp
             try:
                 tot = torch.zeros((), dtype=torch.float64, device=self._device)
                 cnt = 0
-                for X, y in (cached if cached is not None else batches()):
+                for X, y in (cached if cached is not None else self._val_batches(val_loader)):
                     out = self(X, pred_type=pred_type, link_approx=link_approx, n_samples=n_samples)
                     if loss is not None:
                         tot += loss(out, y) * len(y)
@@ -626,6 +631,65 @@ class _HipLaplace:
         best = int(torch.tensor(results).argmin())
         self.prior_precision = interval[best]
         return self.prior_precision
+
+    def _val_batches(self, val_loader):
+        from collections.abc import MutableMapping
+
+        for data in val_loader:
+            if isinstance(data, MutableMapping):  # HuggingFace-style batch: labels under dict_key_y
+                yield data, data[self.backend.dict_key_y].to(self._device)
+            else:
+                yield data[0].to(self._device), data[1].to(self._device)
+
+    #: largest ``[G, B, C]`` block of grid variances (fp32) one validation batch may take; larger grids go in chunks of
+    #: grid points (the forward pass and reverse sweep are then repeated per chunk)
+    grid_var_budget_bytes = 256 << 20
+
+    def _glm_variance_grid(self, X, deltas):
+        """``(f_mu, var [G, B, C])``: the diagonal GLM predictive variance at every prior precision of ``deltas``"""
+        raise NotImplementedError(f"no batched grid route for the {self._structure} structure")
+
+    @torch.no_grad()
+    def validation_loss_grid(self, val_loader, prior_precisions, pred_type: str = "glm", link_approx: str = "probit",
+                             loss=None) -> torch.Tensor:
+        """Mean validation loss at every scalar prior precision of ``prior_precisions [G]``, as the per-point loop of
+        :meth:`gridsearch_prior_precision` computes it (NLL under the probit link for classification, MSE of the mean
+        for regression; NaN scores inf), in ONE pass over ``val_loader``: forward pass, reverse sweep, eigenbasis
+        rotations and tile products run once per batch, only the prior-dependent weighting and the link / loss run per
+        grid point (csrc/lk_grid.hip).  Returns a float64 device tensor ``[G]``; nothing is read back to the host.
+
+        Raises ``NotImplementedError`` outside that scope: ``pred_type='nn'``, link approximations other than
+        ``'probit'``, a custom ``loss``, the full structure, and models the fused predictive does not cover."""
+        if pred_type != "glm":
+            raise NotImplementedError("batched grid: only the GLM predictive")
+        if loss is not None:
+            raise NotImplementedError("batched grid: custom loss callables take the per-point loop")
+        if self.likelihood == "classification" and link_approx != "probit":
+            raise NotImplementedError("batched grid: only the probit link (mc / bridge need samples or the full covariance)")
+        if self.H is None:
+            raise AttributeError("Laplace not fit. Run fit() first.")
+        deltas = torch.as_tensor(prior_precisions).to(device=self._device, dtype=torch.float32).reshape(-1)
+        G = deltas.numel()
+        K = _pred.get_kernels()
+        tot = torch.zeros(G, dtype=torch.float64, device=self._device)
+        cnt = 0
+        last_layer = self.subset_of_weights == "last_layer" and self.backend.last_layer
+        for X, y in self._val_batches(val_loader):
+            if last_layer:
+                X = self.backend.cache_features(X)  # one feature pass for all chunks of the grid
+            if self.likelihood == "regression":
+                # the loop's loss is the MSE of f_mu: the same at every grid point
+                f_mu, _ = self._glm_variance_grid(X, deltas[:1])
+                tot += ((f_mu - y.reshape(f_mu.shape)) ** 2).sum()
+            else:
+                per = max(1, self.grid_var_budget_bytes // (4 * len(y) * max(int(self.n_outputs or 1), 1)))
+                yl = y.reshape(-1).to(torch.int64).contiguous()
+                for g0 in range(0, G, per):
+                    f_mu, var = self._glm_variance_grid(X, deltas[g0:g0 + per])
+                    K.probit_nll_grid(f_mu.to(torch.float32).contiguous(), var, yl, tot[g0:g0 + per])
+            cnt += len(y)
+        res = tot / max(cnt, 1)
+        return torch.where(torch.isnan(res), torch.full_like(res, float("inf")), res)
 
 
 class HipKronLaplace(_HipLaplace):
@@ -737,6 +801,9 @@ class HipKronLaplace(_HipLaplace):
         z = self.posterior_precision.bmm(z, exponent=-0.5)
         return self.mean.reshape(1, self.n_params) + z.reshape(n_samples, self.n_params)
 
+    def _glm_variance_grid(self, X, deltas):
+        return _pred.glm_variance_kron_grid(self.backend, X, self.H * self._H_factor, deltas)
+
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
         post = self.posterior_precision
         try:
@@ -789,6 +856,9 @@ class HipDiagLaplace(_HipLaplace):
 
     def functional_variance(self, Js):
         return torch.einsum("ncp,p,nkp->nck", Js, self.posterior_variance, Js)
+
+    def _glm_variance_grid(self, X, deltas):
+        return _pred.glm_variance_diag_grid(self.backend, X, self._H_factor * self.H, deltas)
 
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
         try:

@@ -109,17 +109,18 @@ def _shared_quadform(K, call, u, v, fvar, weight_sharing_only: bool):
     return True
 
 
-def glm_variance_kron(backend, x, post):
-    """``(f_mu, f_var)`` under a :class:`HipKronDecomposed` posterior precision ``post``
-    (= ``H * H_factor + prior_precision``), i.e. KronLaplace.functional_variance."""
+def _kron_sweep(backend, x):
+    """forward pass + one seed-batched reverse sweep: ``(f, tape, per-tap output gradients)``"""
     _fp32_only(backend)
-    K = get_kernels()
     f, tape, grad_fn = backend._forward(x, keep_tap_splits=True)  # the eigenbasis rotations re-use the split inputs
     if tape.uncovered:
         raise NotImplementedError("fused Kron predictive needs Linear/Conv2d-only models")
-    B, C = f.shape
-    grads = _grads(grad_fn, _identity_seeds(f))
-    fvar = torch.zeros(B, C, C, dtype=torch.float32, device=f.device)
+    return f, tape, _grads(grad_fn, _identity_seeds(f))
+
+
+def _kron_blocks(post, tape, grads):
+    """per tap ``(tap, g, Q1, Q2, l1, l2, delta, Qb, lb, delta_b)``: its output gradients and its posterior blocks (the
+    bias block's entries None without a bias)"""
     blk = 0
     for tap, g in zip(tape.taps, grads):
         if len(post.eigenvalues[blk]) != 2:
@@ -127,17 +128,28 @@ def glm_variance_kron(backend, x, post):
             tape.release()
             raise NotImplementedError("merged single-factor weight block: use the Jacobian route")
         (Q1, Q2), (l1, l2), delta = post.eigenvectors[blk], post.eigenvalues[blk], post.deltas[blk]
+        blk += 1
+        Qb = lb = delta_b = None
+        if tap.has_bias:
+            Qb, lb, delta_b = post.eigenvectors[blk][0], post.eigenvalues[blk][0], post.deltas[blk]
+            blk += 1
+        yield tap, g, Q1, Q2, l1, l2, delta, Qb, lb, delta_b
+
+
+def glm_variance_kron(backend, x, post):
+    """``(f_mu, f_var)`` under a :class:`HipKronDecomposed` posterior precision ``post``
+    (= ``H * H_factor + prior_precision``), i.e. KronLaplace.functional_variance."""
+    K = get_kernels()
+    f, tape, grads = _kron_sweep(backend, x)
+    B, C = f.shape
+    fvar = torch.zeros(B, C, C, dtype=torch.float32, device=f.device)
+    for tap, g, Q1, Q2, l1, l2, delta, Qb, lb, delta_b in _kron_blocks(post, tape, grads):
         if post.damping:
             # laplace/utils/matrix.py:397-399, 441-444: the damped block is (Q1 (l1 + sqrt d) Q1^T) x (Q2 (l2 + sqrt d) Q2^T) —
             # eigenvalues outer(l1 + sqrt d, l2 + sqrt d) instead of outer(l1, l2) + d: the same kernels with shifted
             # eigenvalues and no additive term
             sq = torch.sqrt(delta.detach().to(l1.dtype))
             l1, l2, delta = l1 + sq, l2 + sq, torch.zeros_like(delta)
-        blk += 1
-        Qb = lb = delta_b = None
-        if tap.has_bias:
-            Qb, lb, delta_b = post.eigenvectors[blk][0], post.eigenvalues[blk][0], post.deltas[blk]
-            blk += 1
         d1 = delta.detach().reshape(1).contiguous()
         if tap.kind == "linear" and tap.a.ndim == 2:
             a = tap.a.to(torch.float32)
@@ -213,6 +225,81 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
             fvar += K.diag_quadform_js(Jl, var.contiguous())
     tape.release()
     return f, fvar
+
+
+def _grid_deltas(deltas, dev):
+    d = torch.as_tensor(deltas).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    if d.numel() == 0:
+        raise ValueError("empty prior-precision grid")
+    return d
+
+
+def _bias_grid(var, ub, wb, deltas):
+    """``var [G, B, C] +=`` the bias block ``sum_o ub[c, n, o]^2 / (wb_o + delta_g)`` (one small GEMM)"""
+    var += torch.einsum("cno,og->gnc", ub * ub, 1.0 / (wb.to(torch.float32)[:, None] + deltas[None, :]))
+
+
+def glm_variance_kron_grid(backend, x, post, deltas):
+    """``(f_mu, var [G, B, C])``: the diagonal of :func:`glm_variance_kron`'s ``f_var`` at every prior precision of
+    ``deltas [G]``, for the prior-free decomposition ``post`` (= ``H * H_factor``).  Forward pass, reverse sweep, rotations
+    and tile products run once; only the delta-dependent weighting runs per grid point (csrc/lk_grid.hip)."""
+    K = get_kernels()
+    if bool((post.deltas != 0).any()):
+        raise ValueError("glm_variance_kron_grid takes the prior-free decomposition H * H_factor")
+    f, tape, grads = _kron_sweep(backend, x)
+    B, C = f.shape
+    dg = _grid_deltas(deltas, f.device)
+    var = torch.zeros(dg.numel(), B, C, dtype=torch.float32, device=f.device)
+    mode = K.GRID_KRON_DAMPED if post.damping else K.GRID_KRON
+    for tap, g, Q1, Q2, l1, l2, _, Qb, lb, _ in _kron_blocks(post, tape, grads):
+        l1c, l2c = l1.to(torch.float32).contiguous(), l2.to(torch.float32).contiguous()
+        if tap.kind == "linear" and tap.a.ndim == 2:
+            a = tap.a.to(torch.float32)
+            Do = g.shape[-1]
+            g2 = g.reshape(C * B, Do)
+            u = (g2 @ Q1).reshape(C, B, Do).contiguous()
+            v = (a @ Q2).contiguous()
+            ub = (g2 @ Qb).reshape(C, B, Do).contiguous() if Qb is not None else None
+            K.quadform_linear_grid(u, v, l1c, l2c, dg, mode, var, ub, None if lb is None else lb.to(torch.float32).contiguous())
+        else:
+            bnd = {}
+            u, v, gsum = _shared_operands(tap, g, B, C, Q1, Q2, bounds=bnd, planes=False)
+            K.quadform_shared_grid(u, v, l1c, l2c, dg, mode, var, seed_major=bool(bnd.get("u_seed_major")))
+            if Qb is not None:
+                _bias_grid(var, gsum @ Qb, lb, dg)
+    tape.release()
+    return f, var
+
+
+def glm_variance_diag_grid(backend, x, h: torch.Tensor, deltas):
+    """``(f_mu, var [G, B, C])``: the diagonal of :func:`glm_variance_diag`'s ``f_var`` under the posterior variances
+    ``1 / (h + delta_g)`` for every prior precision of ``deltas [G]``; ``h [P]`` = ``H * H_factor`` (prior-free)."""
+    _fp32_only(backend)
+    K = get_kernels()
+    f, tape, grad_fn = backend._forward(x)
+    if tape.uncovered:
+        raise NotImplementedError("fused diagonal predictive needs Linear/Conv2d-only models")
+    B, C = f.shape
+    grads = grad_fn(_identity_seeds(f))
+    h = h.detach().to(torch.float32).contiguous()
+    dg = _grid_deltas(deltas, f.device)
+    var = torch.zeros(dg.numel(), B, C, dtype=torch.float32, device=f.device)
+    for tap, g in zip(tape.taps, grads):
+        m = tap.module
+        hw = h[tap.w_off:tap.w_off + m.weight.numel()]
+        if tap.kind == "linear" and tap.a.ndim == 2:
+            gc = g.contiguous()
+            hb = h[tap.b_off:tap.b_off + m.out_features].contiguous() if tap.has_bias else None
+            K.quadform_linear_grid(gc, tap.a.to(torch.float32).contiguous(), hw.contiguous(), None, dg, K.GRID_DIAG, var,
+                                   gc if hb is not None else None, hb)
+        else:
+            u, v, gsum = _shared_operands(tap, g, B, C)
+            Do = u.shape[2]
+            K.quadform_shared_grid(u, v, hw.reshape(Do, v.shape[1]).contiguous(), None, dg, K.GRID_DIAG, var)
+            if tap.has_bias:
+                _bias_grid(var, gsum, h[tap.b_off:tap.b_off + Do], dg)
+    tape.release()
+    return f, var
 
 
 def glm_variance_full_last_layer(backend, x, Sigma: torch.Tensor):
