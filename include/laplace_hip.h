@@ -390,6 +390,19 @@ int lk_jac_conv_f32(const float* x_nchw, const float* g, int64_t B, int64_t Cc, 
                     int64_t Do, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                     float* Js, int64_t P, int64_t col0, int64_t bcol0, void* stream);
 
+/* Per-sample Jacobian of an affine normalisation layer y = w * xhat + b (eval-mode BatchNorm1d/2d, LayerNorm,
+ * GroupNorm) w.r.t. w and b, written into Js[B][S][P] (replaces the norm-parameter columns of the jacrev materialisation
+ * of CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129, and - with lk_sq_colsum_f32 on the block - of
+ * GGNInterface.diag / EFInterface.diag, curvature.py:413-433, 494-505):
+ *   Js[n][s][wcol0 + ch] = sum_l g * xhat      (skipped when wcol0 < 0)
+ *   Js[n][s][bcol0 + ch] = sum_l g             (skipped when bcol0 < 0)
+ * g:    [S][B][Ch][L] (layout 0, channels first: NCHW cotangents, GroupNorm, BatchNorm1d on [B, C, L])
+ *    or [S][B][L][Ch] (layout 1, channels last: LayerNorm over the last dim(s), NHWC cotangents), fp32 in both;
+ * xhat: [B][..] in the same layout, ONE copy shared by all S seeds (xhat does not depend on w, b).
+ * Every other column of Js is left untouched.  Deterministic (no atomics; one owner per output, fixed reduction tree). */
+int lk_jac_norm_affine_f32(const float* g, const float* xhat, int64_t S, int64_t B, int64_t L, int64_t Ch, int layout,
+                           float* Js, int64_t P, int64_t wcol0, int64_t bcol0, void* stream);
+
 /* h[p] += alpha * sum_r Js[r][col0 + p]^2 for p < width (rows r = (sample, class)); the conv-layer
  * diagonal GGN / EF is the squared per-sample weight Jacobian summed over samples. */
 int lk_sq_colsum_f32(const float* Js, int64_t rows, int64_t P, int64_t col0, int64_t width, float alpha,

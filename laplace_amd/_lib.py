@@ -107,6 +107,7 @@ SIGNATURES = {
         [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _i64, _i64, _vp],
     ),
     "lk_sq_colsum_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
+    "lk_jac_norm_affine_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _i64, _vp]),
     "lk_bn_act_fwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_vjp_scale_mask_f32": (_int, [_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_ll_ggn_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1116,6 +1117,23 @@ class HipKernels:
             self.lib.lk_jac_conv_f32(_ptr(x), _ptr(g), B, Cc, Cin, H, W, Do, kh, kw, sh, sw, ph, pw, dh, dw, _ptr(Js), P,
                                      int(col0), int(bcol0), self._stream(x.device)),
             "lk_jac_conv_f32",
+        )
+
+    def jac_norm_affine(self, g, xhat, Ch, layout, Js, wcol0, bcol0=-1):
+        """``Js[n, s, wcol0 + ch] = sum_l g * xhat``, ``Js[n, s, bcol0 + ch] = sum_l g`` for an affine normalisation
+        layer; ``g`` is ``[S, B, Ch, ...]`` (``layout`` 0) or ``[S, B, ..., Ch]`` (``layout`` 1), ``xhat`` one sample
+        batch ``[B, ...]`` in the same layout (csrc/lk_norm.hip)."""
+        _check(g, "g"), _check(xhat, "xhat"), _check(Js, "Js")
+        S, B = g.shape[:2]
+        if xhat.numel() * S != g.numel() or xhat.shape[0] != B or Js.shape[:2] != (B, S):
+            raise LaplaceHipError("jac_norm_affine: g [S, B, ...], xhat [B, ...] and Js [B, S, P] do not match")
+        L = xhat.numel() // max(B * int(Ch), 1)
+        if B * L * int(Ch) != xhat.numel():
+            raise LaplaceHipError("jac_norm_affine: xhat is not [B, Ch, L] / [B, L, Ch]")
+        self._rc(
+            self.lib.lk_jac_norm_affine_f32(_ptr(g), _ptr(xhat), S, B, L, int(Ch), int(layout), _ptr(Js), Js.shape[-1],
+                                            int(wcol0), int(bcol0), self._stream(g.device)),
+            "lk_jac_norm_affine_f32",
         )
 
     def sq_colsum(self, Js, col0, width, alpha, h):

@@ -36,7 +36,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from laplace_amd._lib import SplitTensor, get_kernels, is_channels_last, keep_layout
-from laplace_amd.capture import Tape
+from laplace_amd.capture import NormTapReused, Tape, norm_servable
 from laplace_amd.sweep import SeedBatchedSweep, SweepUnsupported
 from laplace_amd.sweep_nhwc import SplitSweep
 from laplace_amd.kron import HipKron
@@ -135,6 +135,10 @@ def shared_operands(tap, g, B, C, Q1=None, Q2=None, bounds=None, planes: bool = 
     return u.contiguous(), v.contiguous(), gsum
 
 
+class Unserved(NotImplementedError):
+    """a tracked parameter has no device rule in this call: the public entry point hands over to the reference's route"""
+
+
 class CachedFeatures:
     """Head input ``phi [B, D]`` and output ``f [B, C]`` of one batch; accepted wherever a last-layer backend takes ``x``."""
 
@@ -205,7 +209,7 @@ class _HipCurvatureMixin:
                     a.copy_(b)  # (casts)
             cur[0] = sig
         twin = cur[1]
-        for k in ("use_sweep", "use_split_sweep", "generator"):
+        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "generator"):
             if k in self.__dict__:
                 setattr(twin, k, self.__dict__[k])
         return twin, dt
@@ -240,10 +244,13 @@ class _HipCurvatureMixin:
             return tuple(_HipCurvatureMixin._cast(o, dt) for o in out)
         return out
 
-    def _forward(self, x, keep_tap_splits: bool = False):
+    def _forward(self, x, keep_tap_splits: bool = False, norm: bool = False):
         """Returns (f [B,C] detached, tape, grad_fn) where grad_fn(seeds[S,B,C]) -> per-tap [S,B,...].
-        ``keep_tap_splits``: the NHWC sweep also keeps the split copies of the tapped inputs (``tap.a_split``)."""
+        ``keep_tap_splits``: the NHWC sweep also keeps the split copies of the tapped inputs (``tap.a_split``).
+        ``norm``: the normalisation layers are tapped too (``grad_fn`` then returns ``tape.taps + tape.norm_taps``
+        gradients, in that order) when :meth:`_norm_route` allows it."""
         tape = self._tape()
+        norm = bool(norm and not self.last_layer and self._norm_route(tape))
         if self.last_layer:
             # f = last_layer(phi): the gradient w.r.t. the head's output IS the seed -> no reverse pass
             swept = (x.f, x.phi) if isinstance(x, CachedFeatures) else self._features_swept(x, tape)
@@ -259,10 +266,14 @@ class _HipCurvatureMixin:
             B = phi.shape[0]
             f = f.detach().reshape(B, -1).contiguous()
             return f, tape, lambda seeds, stack=True: [seeds.contiguous()]
-        swept = self._forward_swept(x, tape, keep_tap_splits)
+        swept = self._forward_swept(x, tape, keep_tap_splits, norm)
         if swept is not None:
             return swept
-        f = tape.forward(x)
+        try:
+            f = tape.forward(x, norm=norm)
+        except NormTapReused:
+            tape.norm_off = True  # (a norm layer applied twice per forward: this model stays on the generic route)
+            return self._forward(x, keep_tap_splits)
         self._check_dtype(f)
         if f.ndim == 1:
             f = f.unsqueeze(-1)
@@ -271,6 +282,9 @@ class _HipCurvatureMixin:
         return (f.detach().contiguous(), tape,
                 lambda seeds, stack=True, f_graph=f: tape.output_grads(f_graph, seeds, stack=stack))
 
+    #: ``False``: parameters of normalisation layers are not served by csrc/lk_norm.hip; a model that tracks one takes the
+    #: reference's generic route, as it does when the active kernel object has no ``jac_norm_affine``
+    use_norm_kernels = True
     #: ``False`` forces the autograd tape (one reverse pass per seed).  (Path selectors are plain attributes — of the class
     #: for a process-wide default, of an object for one backend; nothing here reads the environment.)
     use_sweep = True
@@ -316,21 +330,24 @@ class _HipCurvatureMixin:
         fs.release()
         return f, phi
 
-    def _forward_swept(self, x, tape, keep_tap_splits: bool = False):
+    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, norm: bool = False):
         """Seed-batched reverse sweep (laplace_amd/sweep.py) when the model is fx-traceable and built from
-        modules with a closed-form VJP; ``None`` -> caller uses the autograd tape."""
+        modules with a closed-form VJP; ``None`` -> caller uses the autograd tape.  ``norm``: the sweep that also taps the
+        normalisation layers, built and cached beside the Linear / Conv2d one (``tape.norm_sweep``)."""
         if not self.use_sweep or not torch.is_tensor(x) or not tape.taps:
             return None
-        sweep = getattr(tape, "sweep", None)
+        slot = "norm_sweep" if norm else "sweep"
+        taps = tape.taps + tape.norm_taps if norm else tape.taps
+        sweep = getattr(tape, slot, None)
         if sweep is None:
             try:
                 # NHWC split-fp16 sweep (own convolution kernels) where the graph allows it, else the NCHW sweep
                 cls = SplitSweep if self.use_split_sweep else SeedBatchedSweep
-                sweep = cls(self._model, {t.name: t.module for t in tape.taps}, kernels=get_kernels)
+                sweep = cls(self._model, {t.name: t.module for t in taps}, kernels=get_kernels)
             except SweepUnsupported as e:
                 sweep = False
                 tape.sweep_reason = str(e)
-            tape.sweep = sweep
+            setattr(tape, slot, sweep)
         if sweep is False:
             return None
         try:
@@ -348,7 +365,7 @@ class _HipCurvatureMixin:
             f = f.unsqueeze(-1)
         if f.ndim != 2:
             raise NotImplementedError(f"model output must be [batch, outputs]; got {tuple(f.shape)}")
-        for t in tape.taps:
+        for t in taps:
             t.a = sweep.taps[t.name]["a"]
             t.a_split = getattr(sweep, "tap_splits", {}).get(t.name)  # NHWC SplitTensor of the same activation, if any
 
@@ -366,15 +383,15 @@ class _HipCurvatureMixin:
                     grads = sweep.backward(seeds, on_tap=on_tap, defer_bn_scale=defer_bn_scale, keep_split=True)
                 else:
                     grads = sweep.backward(seeds, on_tap=on_tap, defer_bn_scale=defer_bn_scale)
-                return [grads[t.name] for t in tape.taps]
+                return [grads[t.name] for t in taps]
             parts = []
             for s0 in range(0, S, chunk):
                 grads = sweep.backward(seeds[s0:s0 + chunk].contiguous(), on_tap=on_tap, defer_bn_scale=defer_bn_scale)
                 if on_tap is None:
-                    parts.append([grads[t.name] for t in tape.taps])
+                    parts.append([grads[t.name] for t in taps])
             if on_tap is not None:
                 return None
-            return [torch.cat([p[i] for p in parts]) for i in range(len(tape.taps))]
+            return [torch.cat([p[i] for p in parts]) for i in range(len(taps))]
 
         grad_fn.streams_taps = True  # accepts on_tap: gradients are delivered layer by layer
         grad_fn.accepts_keep_split = True  # can hand conv-tap gradients back as NHWC SplitTensors
@@ -561,6 +578,10 @@ class _HipCurvatureMixin:
     def _layer_jacobian(self, tap, g, Js):
         """Writes this module's columns of ``Js[B, S, P]``; ``g`` is ``[S, B, ...]``."""
         K = get_kernels()
+        if tap.kind == "norm":
+            xhat, Ch, layout = self._norm_xhat(tap)
+            K.jac_norm_affine(g.contiguous(), xhat, Ch, layout, Js, tap.w_off, tap.b_off)
+            return
         a = tap.a.to(torch.float32)
         if tap.kind == "linear" and a.ndim == 2:
             K.jac_linear(a.contiguous(), g.contiguous(), Js, tap.w_off, tap.b_off)
@@ -570,20 +591,66 @@ class _HipCurvatureMixin:
 
     def _rows(self, x, seeds_fn):
         """``Z[B, S, P]`` = seed-contracted per-sample Jacobians (all tracked params must be covered)."""
-        f, tape, grad_fn = self._forward(x)
-        if tape.uncovered:
-            raise NotImplementedError("parameters outside nn.Linear / nn.Conv2d are not covered by the HIP kernels")
+        f, tape, grad_fn = self._forward(x, norm=True)
+        if self._unserved(tape):
+            tape.release()
+            raise Unserved("parameters outside nn.Linear / nn.Conv2d / the affine normalisation layers are not covered "
+                           "by the HIP kernels")
         seeds = seeds_fn(f)
         grads = grad_fn(seeds)
         B, S = f.shape[0], seeds.shape[0]
         Z = torch.zeros(B, S, tape.n_params, dtype=torch.float32, device=f.device)
-        for tap, g in zip(tape.taps, grads):
+        for tap, g in zip(self._served_taps(tape), grads):
             self._layer_jacobian(tap, g, Z)
         tape.release()
         return Z, f
 
     def _supported(self) -> bool:
-        return not self._tape().uncovered
+        return not self._unserved(self._tape())
+
+    # ---- normalisation layers -----------------------------------------------------------------------------------------
+    def _norm_route(self, tape) -> bool:
+        """Are the tracked norm parameters served by the device kernel in THIS call?  Needs the switch, a kernel object that
+        provides the entry point (the emulation of the CPU test tier may not), and every norm tap servable as it stands
+        (``model.train()`` between two calls changes that)."""
+        return bool(tape.norm_taps and self.use_norm_kernels and not getattr(tape, "norm_off", False)
+                    and getattr(get_kernels(), "jac_norm_affine", None) is not None
+                    and all(norm_servable(t.module) for t in tape.norm_taps))
+
+    def _unserved(self, tape):
+        """tracked parameters that no device rule serves in this call (``tape.uncovered`` when the norm route is off)"""
+        return tape.unserved if self._norm_route(tape) else tape.uncovered
+
+    def _served_taps(self, tape):
+        return tape.taps + tape.norm_taps if self._norm_route(tape) and not self.last_layer else tape.taps
+
+    @staticmethod
+    def _norm_xhat(tap):
+        """``(xhat, Ch, layout)`` of a norm tap: the normalised input (what the affine map multiplies), the number of
+        affine channels and the kernel's layout (0: ``[B, Ch, L]``, 1: ``[B, L, Ch]``).  It has the size of the
+        activation and is shared by all seeds, so stock element-wise ops form it."""
+        m = tap.module
+        a = tap.a.to(torch.float32)
+        if isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d)):
+            shape = (1, -1) + (1,) * (a.dim() - 2)
+            rstd = torch.rsqrt(m.running_var.detach().to(torch.float32) + m.eps)
+            xhat = (a - m.running_mean.detach().to(torch.float32).reshape(shape)) * rstd.reshape(shape)
+            return xhat.contiguous(), int(m.num_features), 0
+        if isinstance(m, nn.GroupNorm):
+            return F.group_norm(a, m.num_groups, None, None, m.eps).contiguous(), int(m.num_channels), 0
+        Ch = 1
+        for d in m.normalized_shape:
+            Ch *= int(d)
+        return F.layer_norm(a, m.normalized_shape, None, None, m.eps).contiguous(), Ch, 1
+
+    def _norm_block(self, tap, g):
+        """``(Jl [B, S, n_w + n_b], n_w, n_b)``: the layer's own Jacobian block (tiny: two values per channel)"""
+        xhat, Ch, layout = self._norm_xhat(tap)
+        S, B = g.shape[0], g.shape[1]
+        n_w, n_b = (Ch if tap.w_off >= 0 else 0), (Ch if tap.b_off >= 0 else 0)
+        Jl = torch.zeros(B, S, n_w + n_b, dtype=torch.float32, device=g.device)
+        get_kernels().jac_norm_affine(g.contiguous(), xhat, Ch, layout, Jl, 0 if n_w else -1, n_w if n_b else -1)
+        return Jl, n_w, n_b
 
     # ---- shared implementations ------------------------------------------------------------------
     def _kron_impl(self, x, y, N, seeds_fn, hess_scale_fn, kfac_approx):
@@ -624,15 +691,24 @@ class _HipCurvatureMixin:
 
     def _diag_impl(self, x, y, seeds_fn, alpha):
         K = get_kernels()
-        f, tape, grad_fn = self._forward(x)
-        if tape.uncovered:
+        f, tape, grad_fn = self._forward(x, norm=True)
+        if self._unserved(tape):
+            tape.release()
             return None
         loss = torch.zeros(1, dtype=torch.float32, device=f.device)
         seeds, _ = seeds_fn(f, y, loss)
         grads = grad_fn(seeds)
         h = torch.zeros(tape.n_params, dtype=torch.float32, device=f.device)
         B, S = f.shape[0], seeds.shape[0]
-        for tap, g in zip(tape.taps, grads):
+        for tap, g in zip(self._served_taps(tape), grads):
+            if tap.kind == "norm":
+                # the layer's block [B, S, 2 Ch] is tiny: write it and square-sum its columns (as the narrow convolutions)
+                Jl, n_w, n_b = self._norm_block(tap, g)
+                if n_w:
+                    K.sq_colsum(Jl, 0, n_w, alpha, h[tap.w_off:tap.w_off + n_w])
+                if n_b:
+                    K.sq_colsum(Jl, n_w, n_b, alpha, h[tap.b_off:tap.b_off + n_b])
+                continue
             a = tap.a.to(torch.float32)
             m = tap.module
             if tap.kind == "linear" and a.ndim == 2:
@@ -1719,7 +1795,10 @@ class HipGGN(_HipCurvatureMixin, GGNInterface):
             loss = torch.zeros(1, dtype=torch.float32, device=f.device)
             return self._ggn_seeds(f, y, loss)[0]
 
-        Z, _ = self._rows(x, seeds_fn)
+        try:
+            Z, _ = self._rows(x, seeds_fn)
+        except Unserved:
+            return super().full(x, y, **kwargs)
         return loss[0], self._full_from_rows(Z, 1.0)
 
     # last-layer Jacobians — replaces CurvatureInterface.last_layer_jacobians (curvature.py:131-167) for a Linear head:
@@ -1754,7 +1833,10 @@ class HipGGN(_HipCurvatureMixin, GGNInterface):
             eye = torch.eye(C, dtype=f.dtype, device=f.device)
             return eye[:, None, :].expand(C, B, C).contiguous()
 
-        Js, f = self._rows(x, seeds_fn)
+        try:
+            Js, f = self._rows(x, seeds_fn)
+        except Unserved:
+            return super().jacobians(x, enable_backprop)
         if self.subnetwork_indices is not None:
             Js = Js[:, :, self.subnetwork_indices]
         return Js, f
@@ -1803,7 +1885,10 @@ class HipEF(_HipCurvatureMixin, EFInterface):
             loss = torch.zeros(1, dtype=torch.float32, device=f.device)
             return self._ef_seed(f, y, loss)
 
-        Z, _ = self._rows(x, seeds_fn)
+        try:
+            Z, _ = self._rows(x, seeds_fn)
+        except Unserved:
+            return super().full(x, y, **kwargs)
         return loss[0], self._full_from_rows(Z, float(self.factor))
 
     def gradients(self, x, y):
@@ -1819,7 +1904,10 @@ class HipEF(_HipCurvatureMixin, EFInterface):
             loss = torch.zeros(1, dtype=torch.float32, device=f.device)
             return self._ef_seed(f, y, loss)
 
-        Z, _ = self._rows(x, seeds_fn)
+        try:
+            Z, _ = self._rows(x, seeds_fn)
+        except Unserved:
+            return super().gradients(x, y)
         Gs = Z[:, 0, :]
         if self.subnetwork_indices is not None:
             Gs = Gs[:, self.subnetwork_indices]

@@ -18,14 +18,16 @@ import torch
 from torch import nn
 
 SUPPORTED = (nn.Linear, nn.Conv2d)
+#: affine normalisation layers: their weight / bias Jacobian is a per-channel reduction of ``g * xhat`` (csrc/lk_norm.hip)
+NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm)
 
 
 @dataclass
 class Tap:
     name: str
     module: nn.Module
-    kind: str  # 'linear' | 'conv2d'
-    w_off: int  # column offset of the weight in the flattened parameter vector
+    kind: str  # 'linear' | 'conv2d' | 'norm'
+    w_off: int  # column offset of the weight in the flattened parameter vector (a norm tap: -1 if absent / frozen)
     b_off: int  # column offset of the bias, -1 if the module has no (tracked) bias
     a: torch.Tensor | None = None  # module input (detached)
     a_split: object | None = None  # the same input as an NHWC SplitTensor, when the forward pass produced one
@@ -34,6 +36,18 @@ class Tap:
     @property
     def has_bias(self) -> bool:
         return self.b_off >= 0
+
+
+class NormTapReused(NotImplementedError):
+    """a tapped normalisation layer ran twice in one forward: the caller goes back to the route without norm taps"""
+
+
+def norm_servable(m: nn.Module) -> bool:
+    """Is the layer, as it stands NOW, an affine map of a per-sample ``xhat``?  A BatchNorm in training mode or without
+    running statistics normalises with the statistics of the batch: its Jacobian mixes samples."""
+    if isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d)):
+        return not m.training and m.running_mean is not None and m.running_var is not None
+    return True
 
 
 def _conv_checks(m: nn.Conv2d, name: str):
@@ -72,13 +86,39 @@ class Tape:
                                  offsets[id(mod.weight)], b_off))
         # tracked parameters that no supported module owns (norm layers, embeddings, lone biases ...)
         self.uncovered = [p for p in params if id(p) not in covered]
+        # affine normalisation layers with a tracked weight and / or bias, in a list of their own: `taps` stays the list
+        # of Linear / Conv2d layers that the KFAC accumulator, the Kron predictive and the last-layer shortcut walk
+        self.norm_taps: list[Tap] = []
+        for name, mod in model.named_modules():
+            if not isinstance(mod, NORM):
+                continue
+            w_off = b_off = -1
+            if getattr(mod, "weight", None) is not None and id(mod.weight) in offsets and id(mod.weight) not in covered:
+                w_off = offsets[id(mod.weight)]
+            if getattr(mod, "bias", None) is not None and id(mod.bias) in offsets and id(mod.bias) not in covered:
+                b_off = offsets[id(mod.bias)]
+            if w_off >= 0 or b_off >= 0:
+                self.norm_taps.append(Tap(name, mod, "norm", w_off, b_off))
 
-    def forward(self, x):
-        """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph)."""
+    @property
+    def unserved(self):
+        """``uncovered`` minus what the norm taps own — decided per call: a BatchNorm switched to training mode (or one
+        without running statistics) is not served, and neither are embeddings, lone parameters, ..."""
+        owned = set()
+        for t in self.norm_taps:
+            if norm_servable(t.module):
+                owned.update(id(p) for p in (t.module.weight, t.module.bias) if p is not None)
+        return [p for p in self.uncovered if id(p) not in owned]
+
+    def forward(self, x, norm: bool = False):
+        """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph).  ``norm``: tap the norm layers too."""
         handles, seen = [], set()
-        for tap in self.taps:
+        self._active = self.taps + self.norm_taps if norm else self.taps
+        for tap in self._active:
             def hook(m, inp, out, tap=tap):
                 if id(m) in seen:
+                    if tap.kind == "norm":
+                        raise NormTapReused(f"{tap.name}: module is applied more than once per forward")
                     raise NotImplementedError(f"{tap.name}: module is applied more than once per forward")
                 seen.add(id(m))
                 tap.a = inp[0].detach()
@@ -93,7 +133,7 @@ class Tape:
         finally:
             for h in handles:
                 h.remove()
-        for tap in self.taps:
+        for tap in self._active:
             if tap.out is None:
                 raise RuntimeError(f"{tap.name}: module did not run in the forward pass")
         return f
@@ -108,12 +148,13 @@ class Tape:
         reverse pass per seed because functorch has no fused batching rule for MIOpen's conv backward
         (it loops internally and then pays an extra concatenation).
         """
-        outs = [t.out for t in self.taps]
+        taps = getattr(self, "_active", self.taps)  # (the taps of the forward this pass belongs to)
+        outs = [t.out for t in taps]
         if any(torch.is_tensor(o) for o in outs):
             raise RuntimeError("a tapped module's output does not require grad (frozen parameters upstream and "
                                "downstream?)")
         S = seeds.shape[0]
-        has_conv = any(t.kind == "conv2d" for t in self.taps)
+        has_conv = any(t.kind == "conv2d" for t in taps)
         if S == 1:
             return [g.unsqueeze(0).contiguous() for g in torch.autograd.grad(f, outs, grad_outputs=seeds[0])]
         if not has_conv:
@@ -124,7 +165,7 @@ class Tape:
                 pass  # an op without a batching rule: fall through to one reverse pass per seed
         per_seed = [torch.autograd.grad(f, outs, grad_outputs=seeds[s], retain_graph=(s + 1 < S)) for s in range(S)]
         result = []
-        for i, tap in enumerate(self.taps):
+        for i, tap in enumerate(taps):
             gs = [ps[i].contiguous() for ps in per_seed]
             if tap.kind == "conv2d" and not stack:
                 result.append(gs)
@@ -133,10 +174,11 @@ class Tape:
         return result
 
     def release(self):
-        for t in self.taps:
+        for t in self.taps + self.norm_taps:
             t.a = None
             t.a_split = None
             t.out = None
-        sweep = getattr(self, "sweep", None)
-        if sweep:
-            sweep.release()
+        for attr in ("sweep", "norm_sweep"):
+            sweep = getattr(self, attr, None)
+            if sweep:
+                sweep.release()

@@ -2,7 +2,7 @@
 
 Only shapes matter: the configs use random-init weights and synthetic data.  ResNet-18 follows the
 CIFAR layout named in SURVEY.md §8 (3x3 stride-1 stem, no max-pool, BasicBlock x [2,2,2,2]); its
-BatchNorm affine parameters are frozen because the reference's KFAC path supports nn.Linear /
+BatchNorm affine parameters are frozen by default because the reference's KFAC path supports nn.Linear /
 nn.Conv2d only (docs/index.md:364-366; baselaplace.py:115-125 treats frozen params as non-Laplace).
 """
 from __future__ import annotations
@@ -33,7 +33,12 @@ class ResNet18(nn.Module):
     """``act`` defaults to ReLU (the benchmark model).  Tests that compare two *separately executed*
     forward/backward passes use a smooth activation: with ReLU, fp32 rounding differences between MIOpen
     solvers flip a handful of pre-activations that sit within 1e-6 of zero, which changes individual
-    gradients by O(1) and is a property of the host framework, not of the curvature kernels."""
+    gradients by O(1) and is a property of the host framework, not of the curvature kernels.
+
+    ``freeze_bn=True`` is needed for KFAC only (the reference has no Kronecker factors for normalisation parameters and
+    refuses them, as this backend does).  With ``freeze_bn=False`` the 9 600 BatchNorm weights and biases are Laplace
+    parameters like any other: ``jacobians`` / ``diag`` / ``full`` / the EF / the diagonal predictive serve them on the
+    device in eval mode (csrc/lk_norm.hip)."""
 
     def __init__(self, num_classes: int = 10, freeze_bn: bool = True, act=torch.relu):
         super().__init__()

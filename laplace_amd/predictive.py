@@ -197,14 +197,20 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
     """``(f_mu, f_var)`` under a diagonal posterior with variances ``post_var[P]``."""
     _fp32_only(backend)
     K = get_kernels()
-    f, tape, grad_fn = backend._forward(x)
-    if tape.uncovered:
-        raise NotImplementedError("fused diagonal predictive needs Linear/Conv2d-only models")
+    f, tape, grad_fn = backend._forward(x, norm=True)
+    if backend._unserved(tape):
+        tape.release()
+        raise NotImplementedError("fused diagonal predictive needs Linear / Conv2d / affine normalisation layers only")
     B, C = f.shape
     grads = grad_fn(_identity_seeds(f))
     post_var = post_var.detach().to(torch.float32).contiguous()
     fvar = torch.zeros(B, C, C, dtype=torch.float32, device=f.device)
-    for tap, g in zip(tape.taps, grads):
+    for tap, g in zip(backend._served_taps(tape), grads):
+        if tap.kind == "norm":  # the layer's [B, C, 2 Ch] Jacobian block against its slice of the posterior variance
+            Jl, n_w, n_b = backend._norm_block(tap, g)
+            var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])
+            fvar += K.diag_quadform_js(Jl, var.contiguous())
+            continue
         m = tap.module
         n_w = m.weight.numel()
         vw = post_var[tap.w_off:tap.w_off + n_w]

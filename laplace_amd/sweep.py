@@ -413,8 +413,11 @@ class SeedBatchedSweep:
         """If the activation's input is an eval-mode BatchNorm used only by it, its scale folds into the
         activation's VJP: returns (scale, node to push the cotangent to)."""
         if (isinstance(src, fx.Node) and src.op == "call_module" and len(src.users) == 1
-                and isinstance(self.modules[src.target], (nn.BatchNorm2d, nn.BatchNorm1d))):
+                and isinstance(self.modules[src.target], (nn.BatchNorm2d, nn.BatchNorm1d))
+                and src.target not in self.tap_names):
             return self._bn_scale(src.target, self.modules[src.target]), src.args[0]
+        # (a TAPPED BatchNorm must see ``act'(.) * g``, the cotangent of its own output, before its scale is applied:
+        # the activation hands it over unscaled and the BatchNorm rule of `backward` multiplies afterwards)
         return None, src
 
     # ---- reverse sweep -----------------------------------------------------------------------------------

@@ -151,6 +151,10 @@ class SplitSweep(SeedBatchedSweep):
 
     # ---- static eligibility ---------------------------------------------------------------------------------------
     def _split_eligible(self):
+        for name in sorted(self.tap_names):
+            if isinstance(self.modules.get(name), (nn.BatchNorm2d, nn.BatchNorm1d)):
+                # its weight / bias Jacobian reads the fp32 NCHW cotangent of the BatchNorm's output (lk_norm.hip, layout 0)
+                return f"{name}: tapped BatchNorm (its cotangent is delivered by the NCHW sweep)"
         if self.kernels is None or not hasattr(self.kernels(), "conv_nhwc_f16x2"):
             return "kernels without the split-fp16 convolution"
         n_conv = 0
