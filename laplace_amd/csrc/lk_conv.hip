@@ -1329,6 +1329,14 @@ struct WinPCfg {
   static_assert(WG_PER_CU * LDS <= 160 * 1024, "workgroups per CU");
 };
 
+// Width of the two chunk-index fields of a tile descriptor (`item` in conv_winp_f16x2_kernel: first chunk | end chunk <<
+// WINP_KC_BITS | (slab + 1) << 2 * WINP_KC_BITS).  The END chunk of an ordinary tile is KC = Ci / 16 itself and chunk ranges are
+// even, so the widest cotangent the form can take has KC = 254: Ci <= 4064.  lk_conv_winp_eligible refuses wider ones (they run
+// the generic fused kernel, which has no such field); launch_winp checks it again.
+constexpr int WINP_KC_BITS = 8, WINP_KC_MASK = (1 << WINP_KC_BITS) - 1;
+constexpr int WINP_MAX_CI = (WINP_KC_MASK & ~1) * 16;
+static_assert(WINP_MAX_CI == 4064 && 3 * WINP_KC_BITS <= 31, "tile descriptor: two chunk fields and the slab index in one int");
+
 struct WinPArgs {  // (a slim argument block: everything here stays in scalar registers for the whole launch)
   int M, Hi, Wi, Ci, Co, HW, n_tiles, nb_m, wt0, wtstep, stagger, halo_all, coloc;
   FastDiv div_hw, div_w, div_mask;
@@ -1398,14 +1406,14 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
   // (an item's chunk range and slab index travel as ONE word — first chunk | end chunk << 8 | (slab + 1) << 16 — : the kernel
   //  sits at the register limit, and values carried around the persistent loop are booked as vector registers)
   auto item = [&](int v, int& m0_, int& n0_, int& desc_) {
-    desc_ = KC << 8;
+    desc_ = KC << WINP_KC_BITS;
     if (p.split_S > 1 && v >= p.split_v0) {
       const int j = v - p.split_v0;
       if (j >= p.split_L * p.split_S) return false;
       // (uniform values, but integer division runs in the vector unit: back into scalar registers for the staging bases)
       const int tl = __builtin_amdgcn_readfirstlane(j / p.split_S), len = __builtin_amdgcn_readfirstlane(KC / p.split_S);
       const int sl = j - tl * p.split_S;
-      desc_ = (sl * len) | ((sl * len + len) << 8) | ((j + 1) << 16);
+      desc_ = (sl * len) | ((sl * len + len) << WINP_KC_BITS) | ((j + 1) << (2 * WINP_KC_BITS));
       return coords(p.split_v0 + tl, m0_, n0_);
     }
     return coords(v, m0_, n0_);
@@ -1857,9 +1865,9 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
   // prologue: the first tile's first window and first three taps
   setup_window(m0);
   setup_frag(m0);
-  stage_win(__builtin_amdgcn_readfirstlane(desc & 0xff), 0);
-  stage_b(__builtin_amdgcn_readfirstlane(desc & 0xff), 0, 0, n0);
-  stage_b(__builtin_amdgcn_readfirstlane(desc & 0xff), 1, 1, n0);  // (the request stream runs two steps ahead of the MFMAs)
+  stage_win(__builtin_amdgcn_readfirstlane(desc & WINP_KC_MASK), 0);
+  stage_b(__builtin_amdgcn_readfirstlane(desc & WINP_KC_MASK), 0, 0, n0);
+  stage_b(__builtin_amdgcn_readfirstlane(desc & WINP_KC_MASK), 1, 1, n0);  // (the request stream runs two steps ahead of the MFMAs)
   // the second workgroup of a CU starts half a tile late (the host passes the delay in units of 64 s_sleep cycles): from
   // then on one workgroup's epilogue runs beside the other's K loop
   if (blockIdx.x >= (unsigned)(G / 2))
@@ -1883,8 +1891,8 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
     const bool last_tile = !item(tile + G, next_m0, next_n0, next_desc);
     // (uniform by construction; said explicitly — carried around the persistent loop hipcc books them as divergent, and the
     //  staging bases and LDS buffer selects below live in scalar registers)
-    const int kc0 = __builtin_amdgcn_readfirstlane(desc & 0xff), part = __builtin_amdgcn_readfirstlane(desc >> 16) - 1;
-    kc1 = __builtin_amdgcn_readfirstlane((desc >> 8) & 0xff), next_kc0 = __builtin_amdgcn_readfirstlane(next_desc & 0xff);
+    const int kc0 = __builtin_amdgcn_readfirstlane(desc & WINP_KC_MASK), part = __builtin_amdgcn_readfirstlane(desc >> (2 * WINP_KC_BITS)) - 1;
+    kc1 = __builtin_amdgcn_readfirstlane((desc >> WINP_KC_BITS) & WINP_KC_MASK), next_kc0 = __builtin_amdgcn_readfirstlane(next_desc & WINP_KC_MASK);
     LK_WINP_STAMP(0)
     for (int kc = kc0; kc < kc1; kc += 2) {  // (chunk ranges are even in start and length)
       using I0 = std::integral_constant<int, 0>;
@@ -1919,7 +1927,7 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
     if (last_tile) break;
     tile += G;
     m0 = next_m0, n0 = next_n0, desc = next_desc;
-    if (!frag_const || (desc >> 16)) setup_frag(m0);
+    if (!frag_const || (desc >> (2 * WINP_KC_BITS))) setup_frag(m0);
   }
   if (p.amax_out) {
 #pragma unroll
@@ -2176,6 +2184,7 @@ static bool launch_winp(const ConvGeom& g, const void* Ah, const void* Al, const
   const int step = wt[1] - wt[0];
   for (int t = 0; t < 9; ++t)
     if (wt[t] != wt[0] + t * step) return false;
+  if (g.Ci > WINP_MAX_CI) return false;  // (the descriptor's chunk fields: the caller takes the generic kernel)
   WinPArgs p;
   const int64_t M = (int64_t)g.N * g.Hi * g.Wi;
   p.M = (int)M, p.Hi = g.Hi, p.Wi = g.Wi, p.Ci = g.Ci, p.Co = g.Co, p.HW = g.Hi * g.Wi;
@@ -2309,7 +2318,8 @@ static int conv_dispatch(const void* in_h, const void* in_l, const int* in_sexp,
 // Does a fused 3 x 3 / stride-1 launch of this shape qualify for the persistent window form (conv_winp_f16x2_kernel)?  The
 // caller then prepares chunk-major weights for it (lk_conv_nhwc_f16x2_vjp_wc).
 extern "C" int lk_conv_winp_eligible(int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t T, int mask_is_float) {
-  return T == 9 && Wi <= 47 && Hi * Wi >= 16 && Ci % 32 == 0 && Ci >= 32 && Co >= 64 && Co % 64 == 0 && N * Hi * Wi * Ci < (1ll << 30) &&
+  // (Ci <= WINP_MAX_CI = 4064: the 8-bit chunk fields of the kernel's tile descriptor, KC = Ci / 16 <= 254)
+  return T == 9 && Wi <= 47 && Hi * Wi >= 16 && Ci % 32 == 0 && Ci >= 32 && Ci <= lk::WINP_MAX_CI && Co >= 64 && Co % 64 == 0 && N * Hi * Wi * Ci < (1ll << 30) &&
                  N * Hi * Wi * Co < (1ll << 31) && N * Hi * Wi >= 512 && !mask_is_float
              ? 1
              : 0;

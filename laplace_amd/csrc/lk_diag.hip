@@ -140,6 +140,8 @@ extern "C" int lk_diag_ggn_linear_f32(const float* a, const float* g, int64_t B,
                                       float alpha, float* h_w, float* h_b, void* stream) {
   LK_REQUIRE(a && g && h_w && B >= 0 && Cc >= 1 && Di >= 1 && Do >= 1, "lk_diag_ggn_linear_f32: bad arguments");
   LK_REQUIRE(Do <= 65535 * 16, "lk_diag_ggn_linear_f32: Do too large");
+  // (B, Cc, Di travel as int; grid.x = ceil(Di / 16))
+  LK_REQUIRE(B < (1ll << 31) && Cc < (1ll << 31) && Di < (1ll << 31) - 16, "lk_diag_ggn_linear_f32: B, Cc, Di must be < 2^31");
   dim3 grid((unsigned)((Di + 15) / 16), (unsigned)((Do + 15) / 16));
   hipLaunchKernelGGL(diag_ggn_linear_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, g, (int)B, (int)Cc, (int)Di,
                      (int)Do, alpha, h_w, h_b);
@@ -151,6 +153,7 @@ extern "C" int lk_jac_linear_f32(const float* a, const float* g, int64_t B, int6
   LK_REQUIRE(a && g && Js && B >= 0 && Cc >= 1 && Di >= 1 && Do >= 1 && col0 >= 0 && col0 + Do * Di <= P,
              "lk_jac_linear_f32: bad arguments");
   LK_REQUIRE(B * Cc <= 65535, "lk_jac_linear_f32: B*C too large for grid.y (chunk the batch)");
+  LK_REQUIRE(Di < (1ll << 31) && Do < (1ll << 31), "lk_jac_linear_f32: Di, Do must be < 2^31");  // (they travel as int)
   if (B == 0) return LK_OK;
   int64_t bx = (Do * Di + 255) / 256;
   if (bx > 1024) bx = 1024;
@@ -164,6 +167,11 @@ extern "C" int lk_jac_conv_f32(const float* x_nchw, const float* g, int64_t B, i
                                float* Js, int64_t P, int64_t col0, int64_t bcol0, void* stream) {
   LK_REQUIRE(x_nchw && g && Js && B >= 0 && Cc >= 1 && Cin >= 1 && Do >= 1, "lk_jac_conv_f32: bad arguments");
   LK_REQUIRE(B * Cc <= 65535, "lk_jac_conv_f32: B*C too large for grid.z (chunk the batch)");
+  // grid.y = ceil(Do / 16) is a 16-bit extent too; the geometry travels as int (Dk = Cin * kh * kw is formed in int)
+  LK_REQUIRE(Do <= 65535 * 16, "lk_jac_conv_f32: Do too large for grid.y (Do <= %d)", 65535 * 16);
+  LK_REQUIRE(kh >= 1 && kw >= 1 && sh >= 1 && sw >= 1 && dh >= 1 && dw >= 1 && ph >= 0 && pw >= 0 && H >= 1 && W >= 1 &&
+                 H < (1ll << 24) && W < (1ll << 24) && Cin * kh * kw < (1ll << 31) - 16,
+             "lk_jac_conv_f32: bad geometry (kernel, stride, dilation >= 1; Cin*kh*kw < 2^31 - 16)");
   if (B == 0) return LK_OK;
   ConvGeom cg;
   cg.Cin = (int)Cin; cg.H = (int)H; cg.W = (int)W; cg.kh = kh; cg.kw = kw; cg.sh = sh; cg.sw = sw;
@@ -182,6 +190,7 @@ extern "C" int lk_jac_conv_f32(const float* x_nchw, const float* g, int64_t B, i
 extern "C" int lk_sq_colsum_f32(const float* Js, int64_t rows, int64_t P, int64_t col0, int64_t width, float alpha,
                                 float* h, void* stream) {
   LK_REQUIRE(Js && h && rows >= 0 && width >= 0 && col0 >= 0 && col0 + width <= P, "lk_sq_colsum_f32: bad arguments");
+  LK_REQUIRE(width < (1ll << 39), "lk_sq_colsum_f32: width too large for grid.x (width < 2^39)");
   if (width == 0) return LK_OK;
   hipLaunchKernelGGL(sq_colsum_kernel, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Js,
                      rows, P, col0, width, alpha, h);

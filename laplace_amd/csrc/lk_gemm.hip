@@ -126,6 +126,7 @@ extern "C" int lk_gemm_f32(const float* A, const float* B, const float* E, float
 extern "C" int lk_kron_pow_f32(const float* l1, int64_t n1, const float* l2, int64_t n2, const float* delta, float exponent,
                                int damping, float* lam, void* stream) {
   LK_REQUIRE(l1 && delta && lam && n1 >= 0 && (!l2 || n2 >= 0), "lk_kron_pow_f32: bad arguments");
+  LK_REQUIRE(n1 < (1ll << 31) && (!l2 || n2 < (1ll << 31)), "lk_kron_pow_f32: n1, n2 must be < 2^31");  // (they travel as int)
   const int64_t total = n1 * (l2 ? n2 : 1);
   if (total == 0) return LK_OK;
   int64_t blocks = (total + 255) / 256;

@@ -1308,6 +1308,8 @@ extern "C" int lk_nchw_to_nhwc_f32(const float* src, int64_t B, int64_t C, int64
   LK_REQUIRE(src && dst && B >= 0 && C > 0 && HW > 0, "lk_nchw_to_nhwc_f32: bad arguments");
   if (B == 0) return LK_OK;
   LK_REQUIRE(B < 65536, "lk_nchw_to_nhwc_f32: batch too large for grid.z");
+  // grid.y = ceil(C / 64) is a 16-bit extent as well; HW travels as int (grid.x = ceil(HW / 64))
+  LK_REQUIRE(C <= 65535 * 64 && HW < (1ll << 31) - 64, "lk_nchw_to_nhwc_f32: C too large for grid.y (C <= %d) or HW >= 2^31 - 64", 65535 * 64);
   dim3 grid((unsigned)((HW + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)B);
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, (int)C, (int)HW, dst);
   return check_launch("nchw_to_nhwc_kernel");
@@ -1315,6 +1317,7 @@ extern "C" int lk_nchw_to_nhwc_f32(const float* src, int64_t B, int64_t C, int64
 
 extern "C" int lk_symmetrize_f32(float* C, int64_t n, void* stream) {
   LK_REQUIRE(C && n >= 0, "lk_symmetrize_f32: bad arguments");
+  LK_REQUIRE(n <= 65535 * 64, "lk_symmetrize_f32: n too large for grid.y (n <= %d)", 65535 * 64);  // grid = (ceil(n / 64))^2
   if (n == 0) return LK_OK;
   const unsigned nb = (unsigned)((n + 63) / 64);
   hipLaunchKernelGGL(symmetrize_kernel, dim3(nb, nb), dim3(256), 0, (hipStream_t)stream, C, (int)n);
@@ -1324,6 +1327,7 @@ extern "C" int lk_symmetrize_f32(float* C, int64_t n, void* stream) {
 extern "C" int lk_permute_sym_f32(const float* src, int64_t Cin, int64_t KK, float* dst, int accumulate,
                                   void* stream) {
   LK_REQUIRE(src && dst && Cin > 0 && KK > 0 && src != dst, "lk_permute_sym_f32: bad arguments");
+  LK_REQUIRE(Cin < (1ll << 24) && KK < (1ll << 24) && Cin * KK < (1ll << 24), "lk_permute_sym_f32: Cin * KK must be < 2^24");
   const int64_t n = Cin * KK;
   const int64_t total = n * n;
   int64_t blocks = (total + 255) / 256;
@@ -1370,6 +1374,9 @@ extern "C" int lk_conv3x3_pixpair_plan(int64_t H, int64_t W, int64_t Cin, int64_
                                        int64_t* n_blocks) {
   LK_REQUIRE(H >= 1 && W >= 1 && Cin >= 64 && Cin % 64 == 0 && tile && n_tiles && n_blocks,
              "lk_conv3x3_pixpair_plan: needs Cin % 64 == 0");
+  // (before the count below walks the map: its cost is H * W, and a map beyond 2^31 elements is refused anyway)
+  LK_REQUIRE(H < (1ll << 31) && W < (1ll << 31) && Cin < (1ll << 31) && H * W < (1ll << 31) && H * W * Cin < (1ll << 31),
+             "lk_conv3x3_pixpair_plan: problem too large");
   int64_t nb = 0;
   for (int64_t y = 0; y < H; ++y)
     for (int64_t x = 0; x < W; ++x)

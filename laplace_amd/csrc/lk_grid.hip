@@ -80,14 +80,14 @@ __global__ __launch_bounds__(256) void quadform_linear_grid_kernel(const float* 
       if (n >= B) continue;
       const float* uc = u + ((int64_t)c * B + n) * Do;
       const float* Sg = S + ((size_t)nb * GS + gg) * Do;
-      float acc = 0.f;
+      float acc = 0.f, accb = 0.f;  // (the bias block in its own accumulator, as in quadform_linear_kernel)
       for (int o = 0; o < Do; ++o) acc += uc[o] * uc[o] * Sg[o];
       if (ub != nullptr) {
         const float d = deltas[g0 + gg];
         const float* bc = ub + ((int64_t)c * B + n) * Do;
-        for (int o = 0; o < Do; ++o) acc += bc[o] * bc[o] / (wb[o] + d);
+        for (int o = 0; o < Do; ++o) accb += bc[o] * bc[o] / (wb[o] + d);
       }
-      var[((int64_t)(g0 + gg) * B + n) * C + c] += acc;
+      var[((int64_t)(g0 + gg) * B + n) * C + c] += acc + accb;
     }
   }
 }
@@ -322,7 +322,7 @@ extern "C" int lk_quadform_linear_grid_f32(const float* u, const float* v, const
 }
 
 extern "C" size_t lk_quadform_shared_grid_workspace_bytes(int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t G) {
-  if (B < 0 || C < 1 || Do < 1 || Dk < 1 || G < 1) return 0;
+  if (B < 1 || C < 1 || Do < 1 || Dk < 1 || G < 1) return 0;  // (B == 0: nothing to do, and grid_split divides by B)
   const int64_t gl = G < GRID_GMAX ? G : GRID_GMAX;
   return (size_t)B * grid_split(B, Do, Dk) * gl * grid_class_tile(C) * sizeof(float);
 }

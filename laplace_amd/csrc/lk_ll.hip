@@ -331,6 +331,7 @@ __global__ __launch_bounds__(256) void jac_last_layer_kernel(const float* __rest
 
 extern "C" int lk_jac_last_layer_f32(const float* phi, int64_t B, int64_t C, int64_t D, int has_bias, float* Js, void* stream) {
   LK_REQUIRE(phi && Js && B >= 0 && C >= 1 && D >= 1, "lk_jac_last_layer_f32: bad arguments");
+  LK_REQUIRE(C < (1ll << 31) && D < (1ll << 31), "lk_jac_last_layer_f32: C, D must be < 2^31");  // (they travel as int)
   if (B == 0) return LK_OK;
   const int64_t P = C * D + (has_bias ? C : 0);
   const int64_t work = B * C * ((P + 3) / 4);
@@ -349,6 +350,8 @@ extern "C" int lk_dense_quadform_ll_f32(const float* phi, const float* Sigma, in
   (void)ws; (void)ws_bytes;
   LK_REQUIRE(phi && Sigma && fvar && B >= 0 && C >= 1 && D >= 1, "lk_dense_quadform_ll_f32: bad arguments");
   LK_REQUIRE(C * (C + 1) / 2 <= 65535, "lk_dense_quadform_ll_f32: too many class pairs");
+  // (D travels as int; grid.x = ceil(B / 128))
+  LK_REQUIRE(D < (1ll << 31) - 1 && B < (1ll << 38), "lk_dense_quadform_ll_f32: D must be < 2^31 - 1, B < 2^38");
   if (B == 0) return LK_OK;
   const int Dt = (int)(D + (has_bias ? 1 : 0));
   dim3 grid((unsigned)((B + 127) / 128), (unsigned)(C * (C + 1) / 2));

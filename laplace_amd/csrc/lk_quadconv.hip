@@ -542,7 +542,7 @@ static int qc_split(int64_t B, int64_t Do, int64_t Dk) {
 
 extern "C" size_t lk_quadform_shared_workspace_bytes(int64_t B, int64_t C, int64_t Do, int64_t Dk) {
   const int ct = qc_class_tile(C);
-  if (B < 0 || ct == 0 || Do < 1 || Dk < 1) return 0;
+  if (B < 1 || ct == 0 || Do < 1 || Dk < 1) return 0;  // (B == 0: nothing to do, and qc_split divides by B)
   return (size_t)B * qc_split(B, Do, Dk) * (ct * (ct + 1) / 2) * sizeof(float);
 }
 
@@ -725,7 +725,7 @@ extern "C" size_t lk_diag_ggn_shared_workspace_bytes(int64_t B, int64_t Do, int6
 extern "C" int lk_diag_ggn_shared_f32(const float* u, const float* v, int64_t B, int64_t S, int64_t Do, int64_t Dk,
                                       int64_t L, float alpha, float* h, void* ws, size_t ws_bytes, void* stream_) {
   LK_REQUIRE(u && v && h && B >= 0 && S >= 1 && Do >= 1 && Dk >= 1 && L >= 1, "lk_diag_ggn_shared_f32: bad arguments");
-  LK_REQUIRE(S * L * Do < (1ll << 29) && L * Dk < (1ll << 29) && Do * Dk < (1ll << 31),
+  LK_REQUIRE(S * L * Do < (1ll << 29) && L * Dk < (1ll << 29) && Do * Dk < (1ll << 31) && B < (1ll << 31),
              "lk_diag_ggn_shared_f32: sizes out of range");
   const int ct = qc_class_tile(S);
   if (ct == 0) {

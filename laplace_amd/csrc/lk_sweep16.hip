@@ -619,6 +619,9 @@ extern "C" int lk_unsplit_transpose_f32(const void* x_h, const void* x_l, const 
                                        int64_t C, float* out, void* stream) {
   LK_REQUIRE(x_h && x_l && sexp && out && S >= 0 && B >= 0 && L >= 0 && C >= 0 && S * B <= 65535,
              "lk_unsplit_transpose_f32: bad arguments (S * B <= 65535)");
+  // grid = (ceil(C / 32), ceil(L / 32), S * B): grid.y is a 16-bit extent like grid.z, and the kernel holds C, c0 + 31 in int
+  LK_REQUIRE(L <= 65535 * 32ll, "lk_unsplit_transpose_f32: L too large for grid.y (L <= %lld positions)", 65535 * 32ll);
+  LK_REQUIRE(C < (1ll << 31) - 32, "lk_unsplit_transpose_f32: C too large (C < 2^31 - 32 channels)");
   if (S * B == 0 || L == 0 || C == 0) return LK_OK;
   hipLaunchKernelGGL(unsplit_transpose_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((L + 31) / 32), (unsigned)(S * B)),
                      dim3(256), 0, (hipStream_t)stream, (const _Float16*)x_h, (const _Float16*)x_l, sexp, (int)S, (int)B,
