@@ -403,6 +403,20 @@ int lk_jac_conv_f32(const float* x_nchw, const float* g, int64_t B, int64_t Cc, 
 int lk_jac_norm_affine_f32(const float* g, const float* xhat, int64_t S, int64_t B, int64_t L, int64_t Ch, int layout,
                            float* Js, int64_t P, int64_t wcol0, int64_t bcol0, void* stream);
 
+/* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
+ * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
+ * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):
+ *   Js[n][c][col0 + o*Dkg + k] = sum_l g[c][n][o][l] * patch[n][l][grp(o)*Cig + ci][dy][dx]
+ *   Js[n][c][bcol0 + o]        = sum_l g[c][n][o][l]                                  (skipped when bcol0 < 0)
+ * Cig = Cin / groups, Dkg = Cig*kh*kw, k = (ci, dy, dx) as weight[o].flatten(), grp(o) = o / (Do / groups); groups must
+ * divide Cin and Do.  x_nchw: [B][Cin][H][W], g: [Cc][B][Do][OH*OW].  With groups = 1 this is lk_jac_conv_f32's contract.
+ * Depthwise layers (Cig = 1, kh*kw <= 49) run a streaming reduction with any B*Cc; every other shape runs the 16 x 16 tile
+ * scheme and needs B*Cc <= 65535 and groups * ceil(Do/groups/16) <= 65535.  Every other column of Js is left untouched.
+ * Deterministic (no atomics; one owner per output, fixed reduction tree). */
+int lk_jac_gconv_f32(const float* x_nchw, const float* g, int64_t B, int64_t Cc, int64_t Cin, int64_t H, int64_t W,
+                     int64_t Do, int64_t groups, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                     float* Js, int64_t P, int64_t col0, int64_t bcol0, void* stream);
+
 /* h[p] += alpha * sum_r Js[r][col0 + p]^2 for p < width (rows r = (sample, class)); the conv-layer
  * diagonal GGN / EF is the squared per-sample weight Jacobian summed over samples. */
 int lk_sq_colsum_f32(const float* Js, int64_t rows, int64_t P, int64_t col0, int64_t width, float alpha,

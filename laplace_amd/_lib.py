@@ -106,6 +106,11 @@ SIGNATURES = {
         _int,
         [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _i64, _i64, _vp],
     ),
+    "lk_jac_gconv_f32": (
+        _int,
+        [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _i64, _i64,
+         _vp],
+    ),
     "lk_sq_colsum_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
     "lk_jac_norm_affine_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _i64, _vp]),
     "lk_bn_act_fwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
@@ -1117,6 +1122,24 @@ class HipKernels:
             self.lib.lk_jac_conv_f32(_ptr(x), _ptr(g), B, Cc, Cin, H, W, Do, kh, kw, sh, sw, ph, pw, dh, dw, _ptr(Js), P,
                                      int(col0), int(bcol0), self._stream(x.device)),
             "lk_jac_conv_f32",
+        )
+
+    def jac_gconv(self, x, g, kernel_size, stride, padding, dilation, groups, Js, col0, bcol0=-1):
+        """the weight (and bias) Jacobian columns of a grouped convolution: ``x [B, Cin, H, W]``, ``g [S, B, Do, OH, OW]``,
+        ``Js [B, S, P]`` (csrc/lk_gconv.hip)"""
+        _check(x, "x"), _check(g, "g"), _check(Js, "Js")
+        B, Cin, H, W = x.shape
+        Cc, _, Do = g.shape[:3]
+        if g.shape[1] != B or Js.shape[:2] != (B, Cc):
+            raise LaplaceHipError("jac_gconv: x [B, Cin, H, W], g [S, B, Do, ...] and Js [B, S, P] do not match")
+        kh, kw = _pair(kernel_size)
+        sh, sw = _pair(stride)
+        ph, pw = _pair(padding)
+        dh, dw = _pair(dilation)
+        self._rc(
+            self.lib.lk_jac_gconv_f32(_ptr(x), _ptr(g), B, Cc, Cin, H, W, Do, int(groups), kh, kw, sh, sw, ph, pw, dh, dw,
+                                      _ptr(Js), Js.shape[-1], int(col0), int(bcol0), self._stream(x.device)),
+            "lk_jac_gconv_f32",
         )
 
     def jac_norm_affine(self, g, xhat, Ch, layout, Js, wcol0, bcol0=-1):

@@ -209,7 +209,7 @@ class _HipCurvatureMixin:
                     a.copy_(b)  # (casts)
             cur[0] = sig
         twin = cur[1]
-        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "generator"):
+        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "use_gconv_kernels", "gconv_block_bytes", "generator"):
             if k in self.__dict__:
                 setattr(twin, k, self.__dict__[k])
         return twin, dt
@@ -250,6 +250,7 @@ class _HipCurvatureMixin:
         ``norm``: the normalisation layers are tapped too (``grad_fn`` then returns ``tape.taps + tape.norm_taps``
         gradients, in that order) when :meth:`_norm_route` allows it."""
         tape = self._tape()
+        gconv = bool(norm and not self.last_layer and self._gconv_route(tape))  # (the callers that tap the extra layers)
         norm = bool(norm and not self.last_layer and self._norm_route(tape))
         if self.last_layer:
             # f = last_layer(phi): the gradient w.r.t. the head's output IS the seed -> no reverse pass
@@ -266,11 +267,11 @@ class _HipCurvatureMixin:
             B = phi.shape[0]
             f = f.detach().reshape(B, -1).contiguous()
             return f, tape, lambda seeds, stack=True: [seeds.contiguous()]
-        swept = self._forward_swept(x, tape, keep_tap_splits, norm)
+        swept = self._forward_swept(x, tape, keep_tap_splits, norm, gconv)
         if swept is not None:
             return swept
         try:
-            f = tape.forward(x, norm=norm)
+            f = tape.forward(x, norm=norm, gconv=gconv)
         except NormTapReused:
             tape.norm_off = True  # (a norm layer applied twice per forward: this model stays on the generic route)
             return self._forward(x, keep_tap_splits)
@@ -285,6 +286,9 @@ class _HipCurvatureMixin:
     #: ``False``: parameters of normalisation layers are not served by csrc/lk_norm.hip; a model that tracks one takes the
     #: reference's generic route, as it does when the active kernel object has no ``jac_norm_affine``
     use_norm_kernels = True
+    #: ``False``: weights of grouped convolutions are not served by csrc/lk_gconv.hip; a model that tracks one takes the
+    #: reference's generic route, as it does when the active kernel object has no ``jac_gconv``
+    use_gconv_kernels = True
     #: ``False`` forces the autograd tape (one reverse pass per seed).  (Path selectors are plain attributes — of the class
     #: for a process-wide default, of an object for one backend; nothing here reads the environment.)
     use_sweep = True
@@ -330,14 +334,15 @@ class _HipCurvatureMixin:
         fs.release()
         return f, phi
 
-    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, norm: bool = False):
+    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, norm: bool = False, gconv: bool = False):
         """Seed-batched reverse sweep (laplace_amd/sweep.py) when the model is fx-traceable and built from
         modules with a closed-form VJP; ``None`` -> caller uses the autograd tape.  ``norm``: the sweep that also taps the
-        normalisation layers, built and cached beside the Linear / Conv2d one (``tape.norm_sweep``)."""
+        normalisation layers, built and cached beside the Linear / Conv2d one (``tape.norm_sweep``); ``gconv``: the one that
+        taps the grouped convolutions (``tape.gconv_sweep``, ``tape.gconv_norm_sweep``)."""
         if not self.use_sweep or not torch.is_tensor(x) or not tape.taps:
             return None
-        slot = "norm_sweep" if norm else "sweep"
-        taps = tape.taps + tape.norm_taps if norm else tape.taps
+        slot = ("gconv_" if gconv else "") + ("norm_sweep" if norm else "sweep")
+        taps = tape.active_taps(norm, gconv)
         sweep = getattr(tape, slot, None)
         if sweep is None:
             try:
@@ -582,6 +587,11 @@ class _HipCurvatureMixin:
             xhat, Ch, layout = self._norm_xhat(tap)
             K.jac_norm_affine(g.contiguous(), xhat, Ch, layout, Js, tap.w_off, tap.b_off)
             return
+        if tap.kind == "gconv":
+            m = tap.module
+            K.jac_gconv(tap.a.to(torch.float32).contiguous(), g.contiguous(), m.kernel_size, m.stride, m.padding, m.dilation,
+                        m.groups, Js, tap.w_off, tap.b_off)
+            return
         a = tap.a.to(torch.float32)
         if tap.kind == "linear" and a.ndim == 2:
             K.jac_linear(a.contiguous(), g.contiguous(), Js, tap.w_off, tap.b_off)
@@ -617,12 +627,38 @@ class _HipCurvatureMixin:
                     and getattr(get_kernels(), "jac_norm_affine", None) is not None
                     and all(norm_servable(t.module) for t in tape.norm_taps))
 
+    def _gconv_route(self, tape) -> bool:
+        """Are the tracked grouped convolutions served by csrc/lk_gconv.hip?  Needs a kernel object with the entry point
+        (the stock emulation of the CPU test tier has none: such a model then takes the generic route)."""
+        return bool(tape.gconv_taps and self.use_gconv_kernels and getattr(get_kernels(), "jac_gconv", None) is not None)
+
     def _unserved(self, tape):
-        """tracked parameters that no device rule serves in this call (``tape.uncovered`` when the norm route is off)"""
-        return tape.unserved if self._norm_route(tape) else tape.uncovered
+        """tracked parameters that no device rule serves in this call (``tape.uncovered`` when the norm and grouped-
+        convolution routes are off)"""
+        return tape.unserved_by(self._norm_route(tape), self._gconv_route(tape))
 
     def _served_taps(self, tape):
-        return tape.taps + tape.norm_taps if self._norm_route(tape) and not self.last_layer else tape.taps
+        if self.last_layer:
+            return tape.taps
+        return tape.active_taps(self._norm_route(tape), self._gconv_route(tape))
+
+    #: bytes a grouped convolution's own Jacobian block ``[b, S, width]`` may take; larger minibatches are cut along the batch
+    gconv_block_bytes = 256 << 20
+
+    def _gconv_blocks(self, tap, g):
+        """yields ``(n0, Jl [b, S, width + n_b], width, n_b)`` over batch chunks of a grouped convolution's Jacobian block,
+        each within ``gconv_block_bytes`` and the tile path's ``b * S <= 65535``"""
+        m = tap.module
+        S, B = g.shape[0], g.shape[1]
+        width, n_b = m.weight.numel(), (m.out_channels if tap.has_bias else 0)
+        step = max(1, min(int(self.gconv_block_bytes) // (4 * S * (width + n_b)), 65535 // S, B))
+        a = tap.a.to(torch.float32)
+        for n0 in range(0, B, step):
+            b = min(step, B - n0)
+            Jl = torch.zeros(b, S, width + n_b, dtype=torch.float32, device=g.device)
+            get_kernels().jac_gconv(a[n0:n0 + b].contiguous(), g[:, n0:n0 + b].contiguous(), m.kernel_size, m.stride,
+                                    m.padding, m.dilation, m.groups, Jl, 0, width if n_b else -1)
+            yield n0, Jl, width, n_b
 
     @staticmethod
     def _norm_xhat(tap):
@@ -708,6 +744,13 @@ class _HipCurvatureMixin:
                     K.sq_colsum(Jl, 0, n_w, alpha, h[tap.w_off:tap.w_off + n_w])
                 if n_b:
                     K.sq_colsum(Jl, n_w, n_b, alpha, h[tap.b_off:tap.b_off + n_b])
+                continue
+            if tap.kind == "gconv":
+                # the layer's own block (a depthwise 3x3 layer has 9 columns per channel), its columns square-summed
+                for _, Jl, n_w, n_b in self._gconv_blocks(tap, g):
+                    K.sq_colsum(Jl, 0, n_w, alpha, h[tap.w_off:tap.w_off + n_w])
+                    if n_b:
+                        K.sq_colsum(Jl, n_w, n_b, alpha, h[tap.b_off:tap.b_off + n_b])
                 continue
             a = tap.a.to(torch.float32)
             m = tap.module
@@ -1449,6 +1492,7 @@ class KronAccumulator:
 
     def _add_batch(self, x, y):
         b = self.backend
+        b._tape().refuse_kfac()
         b._act_sink = self._pix_sink if (self.direct_stack and self.overlap and not self.defer_pix and getattr(self, "_pix_pending", None)
                                          and torch.is_tensor(x) and x.is_cuda) else None
         try:

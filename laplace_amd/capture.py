@@ -26,7 +26,7 @@ NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm)
 class Tap:
     name: str
     module: nn.Module
-    kind: str  # 'linear' | 'conv2d' | 'norm'
+    kind: str  # 'linear' | 'conv2d' | 'gconv' | 'norm'
     w_off: int  # column offset of the weight in the flattened parameter vector (a norm tap: -1 if absent / frozen)
     b_off: int  # column offset of the bias, -1 if the module has no (tracked) bias
     a: torch.Tensor | None = None  # module input (detached)
@@ -51,8 +51,6 @@ def norm_servable(m: nn.Module) -> bool:
 
 
 def _conv_checks(m: nn.Conv2d, name: str):
-    if m.groups != 1:
-        raise NotImplementedError(f"{name}: grouped convolutions are not supported by the KFAC path")
     if isinstance(m.padding, str):
         raise NotImplementedError(f"{name}: string padding ('{m.padding}') not supported")
     if m.padding_mode != "zeros":
@@ -77,6 +75,8 @@ class Tape:
                 continue
             if isinstance(mod, nn.Conv2d):
                 _conv_checks(mod, name)
+                if mod.groups != 1:
+                    continue  # (a tap list of its own, below)
             b_off = -1
             if mod.bias is not None and id(mod.bias) in offsets:
                 b_off = offsets[id(mod.bias)]
@@ -86,6 +86,14 @@ class Tape:
                                  offsets[id(mod.weight)], b_off))
         # tracked parameters that no supported module owns (norm layers, embeddings, lone biases ...)
         self.uncovered = [p for p in params if id(p) not in covered]
+        # grouped convolutions (groups > 1) with a tracked weight, in a list of their own: no KFAC rule exists for them, their
+        # Jacobian block comes from csrc/lk_gconv.hip.  Their parameters stay in `uncovered`, which keeps meaning "no
+        # Linear / dense Conv2d owns it" (what the KFAC accumulator, the Kron predictive and the batched grids refuse on).
+        self.gconv_taps: list[Tap] = []
+        for name, mod in model.named_modules():
+            if isinstance(mod, nn.Conv2d) and mod.groups != 1 and id(mod.weight) in offsets:
+                b_off = offsets[id(mod.bias)] if mod.bias is not None and id(mod.bias) in offsets else -1
+                self.gconv_taps.append(Tap(name, mod, "gconv", offsets[id(mod.weight)], b_off))
         # affine normalisation layers with a tracked weight and / or bias, in a list of their own: `taps` stays the list
         # of Linear / Conv2d layers that the KFAC accumulator, the Kron predictive and the last-layer shortcut walk
         self.norm_taps: list[Tap] = []
@@ -110,10 +118,31 @@ class Tape:
                 owned.update(id(p) for p in (t.module.weight, t.module.bias) if p is not None)
         return [p for p in self.uncovered if id(p) not in owned]
 
-    def forward(self, x, norm: bool = False):
-        """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph).  ``norm``: tap the norm layers too."""
+    def refuse_kfac(self):
+        """KFAC (the accumulator, ``kron``, the Kron predictive) has no rule for a grouped convolution: what the reference's
+        KFAC (curvlinops) does with ``groups > 1`` is not pinned by any golden here, so nothing is guessed"""
+        if self.gconv_taps:
+            t = self.gconv_taps[0]
+            raise NotImplementedError(f"{t.name}: KFAC has no rule for a grouped convolution (groups={t.module.groups}); "
+                                      "freeze the layer (requires_grad=False) or use hessian_structure 'diag' or 'full'")
+
+    def unserved_by(self, norm: bool, gconv: bool):
+        """``uncovered`` minus what the norm taps (``norm``) and the grouped-convolution taps (``gconv``) own"""
+        left = self.unserved if norm else self.uncovered
+        if gconv:
+            owned = {id(p) for t in self.gconv_taps for p in (t.module.weight, t.module.bias) if p is not None}
+            left = [p for p in left if id(p) not in owned]
+        return left
+
+    def active_taps(self, norm: bool = False, gconv: bool = False):
+        """the taps of one call, in the order in which ``grad_fn`` returns their gradients"""
+        return self.taps + (self.gconv_taps if gconv else []) + (self.norm_taps if norm else [])
+
+    def forward(self, x, norm: bool = False, gconv: bool = False):
+        """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph).  ``norm``: tap the norm layers too;
+        ``gconv``: and the grouped convolutions."""
         handles, seen = [], set()
-        self._active = self.taps + self.norm_taps if norm else self.taps
+        self._active = self.active_taps(norm, gconv)
         for tap in self._active:
             def hook(m, inp, out, tap=tap):
                 if id(m) in seen:
@@ -154,7 +183,7 @@ class Tape:
             raise RuntimeError("a tapped module's output does not require grad (frozen parameters upstream and "
                                "downstream?)")
         S = seeds.shape[0]
-        has_conv = any(t.kind == "conv2d" for t in taps)
+        has_conv = any(t.kind in ("conv2d", "gconv") for t in taps)
         if S == 1:
             return [g.unsqueeze(0).contiguous() for g in torch.autograd.grad(f, outs, grad_outputs=seeds[0])]
         if not has_conv:
@@ -167,18 +196,18 @@ class Tape:
         result = []
         for i, tap in enumerate(taps):
             gs = [ps[i].contiguous() for ps in per_seed]
-            if tap.kind == "conv2d" and not stack:
+            if tap.kind == "conv2d" and not stack:  # (dense convolutions only: a grouped one is always stacked)
                 result.append(gs)
             else:
                 result.append(torch.stack(gs))
         return result
 
     def release(self):
-        for t in self.taps + self.norm_taps:
+        for t in self.taps + self.gconv_taps + self.norm_taps:
             t.a = None
             t.a_split = None
             t.out = None
-        for attr in ("sweep", "norm_sweep"):
+        for attr in ("sweep", "norm_sweep", "gconv_sweep", "gconv_norm_sweep"):
             sweep = getattr(self, attr, None)
             if sweep:
                 sweep.release()

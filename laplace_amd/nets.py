@@ -75,3 +75,61 @@ def lenet5(num_classes: int = 10) -> nn.Sequential:
 def mlp_1_50_1() -> nn.Sequential:
     """Config c1 (examples/regression_example.py:17-21 of the reference)."""
     return nn.Sequential(nn.Linear(1, 50), nn.Tanh(), nn.Linear(50, 1))
+
+
+class InvertedResidual(nn.Module):
+    """MobileNetV2 block: 1x1 expansion (skipped at ``expand = 1``), depthwise 3x3, linear 1x1 projection; identity shortcut
+    when the shape is kept.  None of its convolutions has a bias."""
+
+    def __init__(self, cin: int, cout: int, stride: int, expand: int, act=nn.ReLU6):
+        super().__init__()
+        hidden = cin * expand
+        layers = []
+        if expand != 1:
+            layers += [nn.Conv2d(cin, hidden, 1, bias=False), nn.BatchNorm2d(hidden), act()]
+        layers += [nn.Conv2d(hidden, hidden, 3, stride, 1, groups=hidden, bias=False), nn.BatchNorm2d(hidden), act(),
+                   nn.Conv2d(hidden, cout, 1, bias=False), nn.BatchNorm2d(cout)]
+        self.block = nn.Sequential(*layers)
+        self.use_res = stride == 1 and cin == cout
+
+    def forward(self, x):
+        return x + self.block(x) if self.use_res else self.block(x)
+
+
+class MobileNetV2Small(nn.Module):
+    """A small MobileNetV2-style network for 3 x 32 x 32 inputs (3x3 stride-1 stem, nine inverted residuals, 1x1 head
+    convolution, pool, linear): the workload of the grouped-convolution route (csrc/lk_gconv.hip).  Its depthwise layers
+    have no Kronecker factors here (``kron`` refuses them by name); ``jacobians`` / ``diag`` / ``full`` / the EF / the
+    diagonal predictive serve every parameter, BatchNorm included, on the device in eval mode.
+
+    ``width`` scales every channel count (multiples of 8 are kept); ``act`` is the activation module's class - tests that
+    compare two separately executed passes use a smooth one, as with :class:`ResNet18`."""
+
+    #: (expansion, output channels, blocks, stride of the first block)
+    SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 2, 2), (6, 64, 2, 2), (6, 96, 1, 1), (6, 160, 1, 1))
+
+    def __init__(self, num_classes: int = 10, width: float = 1.0, freeze_bn: bool = False, act=nn.ReLU6):
+        super().__init__()
+
+        def ch(c):
+            return max(8, int(c * width + 4) // 8 * 8)
+
+        cin = ch(32)
+        self.stem = nn.Sequential(nn.Conv2d(3, cin, 3, 1, 1, bias=False), nn.BatchNorm2d(cin), act())
+        blocks = []
+        for t, c, n, s in self.SETTINGS:
+            for i in range(n):
+                blocks.append(InvertedResidual(cin, ch(c), s if i == 0 else 1, t, act))
+                cin = ch(c)
+        self.layers = nn.Sequential(*blocks)
+        self.head = nn.Sequential(nn.Conv2d(cin, ch(320), 1, bias=False), nn.BatchNorm2d(ch(320)), act())
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(ch(320), num_classes)
+        if freeze_bn:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.weight.requires_grad_(False)
+                    m.bias.requires_grad_(False)
+
+    def forward(self, x):
+        return self.fc(torch.flatten(self.pool(self.head(self.layers(self.stem(x)))), 1))

@@ -112,6 +112,7 @@ def _shared_quadform(K, call, u, v, fvar, weight_sharing_only: bool):
 def _kron_sweep(backend, x):
     """forward pass + one seed-batched reverse sweep: ``(f, tape, per-tap output gradients)``"""
     _fp32_only(backend)
+    backend._tape().refuse_kfac()
     f, tape, grad_fn = backend._forward(x, keep_tap_splits=True)  # the eigenbasis rotations re-use the split inputs
     if tape.uncovered:
         raise NotImplementedError("fused Kron predictive needs Linear/Conv2d-only models")
@@ -210,6 +211,11 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
             Jl, n_w, n_b = backend._norm_block(tap, g)
             var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])
             fvar += K.diag_quadform_js(Jl, var.contiguous())
+            continue
+        if tap.kind == "gconv":  # likewise, in batch chunks of a bounded block
+            for n0, Jl, n_w, n_b in backend._gconv_blocks(tap, g):
+                var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])
+                fvar[n0:n0 + Jl.shape[0]] += K.diag_quadform_js(Jl, var.contiguous())
             continue
         m = tap.module
         n_w = m.weight.numel()

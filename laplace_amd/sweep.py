@@ -83,7 +83,8 @@ class SeedBatchedSweep:
                                       nn.Sigmoid, nn.Identity, nn.Dropout, nn.Flatten, nn.AdaptiveAvgPool2d,
                                       nn.MaxPool2d, nn.AvgPool2d, nn.Sequential)):
                     raise SweepUnsupported(f"no VJP rule for module {type(m).__name__} ({node.target})")
-                if isinstance(m, nn.Conv2d) and (m.groups != 1 or isinstance(m.padding, str) or m.padding_mode != "zeros"):
+                # (grouped convolutions: forward is the module itself, backward-data `_conv_input_grad`, which passes `groups`)
+                if isinstance(m, nn.Conv2d) and (isinstance(m.padding, str) or m.padding_mode != "zeros"):
                     raise SweepUnsupported(f"{node.target}: unsupported convolution variant")
             elif node.op == "call_function":
                 if node.target not in (self._ELEMENTWISE_FN | self._GENERIC_ACT_FN | self._POOL_FN

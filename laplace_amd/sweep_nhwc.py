@@ -164,6 +164,8 @@ class SplitSweep(SeedBatchedSweep):
                 if isinstance(m, nn.Conv2d):
                     src = node.args[0]
                     first = isinstance(src, fx.Node) and src.op == "placeholder"
+                    if m.groups != 1:
+                        return f"{node.target}: grouped convolution (foreign to the NHWC kernels; the NCHW sweep serves it)"
                     if not cv.supported(m) and not (first and node.target in self.tap_names and m.out_channels % 8 == 0):
                         return f"{node.target}: convolution outside the implicit-GEMM kernel's coverage"
                     n_conv += 1
