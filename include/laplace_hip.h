@@ -458,7 +458,16 @@ int lk_ll_ggn_full_f32(const float* phi, const float* probs, int64_t B, int64_t 
  * (laplace/utils/utils.py:193-228, laplace/utils/matrix.py:123-150):
  *   reads the UPPER triangle of A[n][n]; writes ascending eigenvalues w[n] clamped at >= 0 (when
  *   clamp != 0) and eigenvectors as the COLUMNS of Q[n][n] (row-major), NaNs zeroed.
- *   info (device int32[2]): info[0] = 0 converged / 1 sweeps ran out; info[1] = sweeps executed.
+ *   info (device int32[2]): info[0] = 0 converged / 1 sweeps ran out, or A is outside the supported range (below);
+ *   info[1] = sweeps executed.
+ * Supported magnitudes: every symmetric fp32 matrix whose spectrum fp32 can hold.  The solve runs on A * 2^-e (e = the
+ *   binary exponent of max |a_ij|, exact) and scales the eigenvalues back, so its thresholds and its split-fp16 products
+ *   see the same numbers at every scale: the accuracy relative to lambda_max that holds for an O(1) matrix holds for
+ *   max |a_ij| from 2^-126 (the smallest normal float) up to max_i sum_j |a_ij| < 3e38 (the row sum bounds lambda_max);
+ *   tests/test_gpu_eigensolver.py holds it to 5e-6 from 2^-100 to 2^100.  Outside of that -- a max row sum of 3e38 or
+ *   more, or a non-zero matrix with only denormal entries -- the call sets info[0] = 1 and writes w = 0: it reports,
+ *   it does not guess.  NaN and +-inf entries (|a_ij| > 3e38) are read as 0.  Eigenvalues below 2^-126 come out as
+ *   denormals (absolute accuracy kept, relative accuracy lost).
  * A is not modified.  Fully asynchronous on `stream`.
  * ------------------------------------------------------------------------------------------- */
 size_t lk_syevj_workspace_bytes(int64_t n);

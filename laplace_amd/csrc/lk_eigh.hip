@@ -18,6 +18,14 @@
 //   clamped, and V's columns gathered.
 // Zero padding is exact: padded rows/columns never rotate (their off-diagonals are exactly 0).
 //
+// Magnitude: the solve runs on A * 2^-e, e = the binary exponent of max |a_ij| (a pass of its own before the load; a
+// power of two is exact, so the result is the one of the unscaled solve wherever that one was sound), and the eigenvalues
+// are multiplied back on the way out.  Nothing inside therefore depends on the scale of the input: the fp32 product
+// a_pp * a_qq of the rotation test (inf above 2^64, 0 below 2^-75), the squared norm of the power iteration and the
+// exponent range of the split-fp16 tile scale all see a matrix whose largest entry is in [1/2, 1).  The pivot loop --
+// the latency chain of the solver -- is untouched.  A matrix whose spectrum cannot be written in fp32 (max row sum
+// >= 3e38, or max |a_ij| a denormal) is reported through info[0], not guessed.
+//
 // Many matrices (one decomposition = 43 factors for ResNet-18): every launch of the three kernels serves a ROUND --
 // the current round-robin step of every matrix that is still iterating, each at its own position of its own sweep
 // (`EigRound`: per slot the matrix' descriptor, its step and the first workgroup of its share of the grid).  One
@@ -53,7 +61,17 @@ struct EigCtrl {             // lives in the workspace
   int converged;             // set when a sweep performed none
   int sweeps;                // completed sweeps
   float bound;               // max_i sum_j |a_ij| >= lambda_max: fixes the power-of-two scale of the split-fp16 tile products
+  float amax;                // max |a_ij| of the INPUT (finite entries of the upper triangle); scale, bound: of A 2^-e
 };
+
+// e with amax = m 2^e, m in [1/2, 1); 0 for the zero matrix
+__device__ __forceinline__ int eig_input_exp(const EigCtrl* ctrl) {
+  int e = 0;
+  if (ctrl->amax > 0.f) (void)frexpf(ctrl->amax, &e);
+  return e;
+}
+// what eig_init_kernel reads for A[r][c] of the UPLO="U" input: non-finite entries count as 0
+__device__ __forceinline__ float eig_guarded(float v) { return (!(v == v) || fabsf(v) > 3.0e38f) ? 0.f : v; }
 
 struct EigDesc {             // one matrix: where its buffers are (lives in its workspace, written once per solve)
   float* Aw;
@@ -100,16 +118,30 @@ __device__ __forceinline__ int pivot_index(int local, int I, int J) {  // local 
   return (local < EB ? I * EB : J * EB - EB) + local;
 }
 
+// ctrl->amax = max |a_ij| over the finite entries of the upper triangle (the max is order-independent)
+__global__ __launch_bounds__(256) void eig_absmax_kernel(const float* __restrict__ A, int n, EigCtrl* ctrl) {
+  const int64_t total = (int64_t)n * n;
+  float mx = 0.f;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int r = (int)(idx / n), c = (int)(idx - (int64_t)r * n);
+    if (r <= c) mx = fmaxf(mx, fabsf(eig_guarded(A[idx])));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(reinterpret_cast<int*>(&ctrl->amax), __float_as_int(mx));
+}
+
 __global__ __launch_bounds__(256) void eig_init_kernel(const float* __restrict__ A, int n, int np,
                                                        float* __restrict__ Aw, float* __restrict__ A0,
                                                        float* __restrict__ V, EigCtrl* ctrl) {
   const int64_t total = (int64_t)np * np;
+  const int e = eig_input_exp(ctrl);
   float mx = 0.f;
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
     const int r = (int)(idx / np), c = (int)(idx - (int64_t)r * np);
     float v = 0.f;
     if (r < n && c < n) v = (r <= c) ? A[(int64_t)r * n + c] : A[(int64_t)c * n + r];  // UPLO="U"
-    if (!(v == v) || fabsf(v) > 3.0e38f) v = 0.f;                                       // NaN / inf guard
+    v = ldexpf(eig_guarded(v), -e);                                                     // NaN / inf guard; A 2^-e (exact)
     Aw[idx] = v;
     A0[idx] = v;
     V[idx] = (r == c) ? 1.f : 0.f;
@@ -597,20 +629,25 @@ __global__ __launch_bounds__(256) void eig_gather_kernel(const float* __restrict
                                                          float* __restrict__ w, float* __restrict__ Q,
                                                          const EigCtrl* ctrl, int32_t* info) {
   const int64_t total = (int64_t)n * n;
+  // the solve ran on A 2^-e: the eigenvalues go back by 2^e.  Out of range = what cannot be written in fp32: lambda_max
+  // <= bound 2^e beyond the largest float (tested with room to spare, as the guards above), or an input so small that
+  // the spectrum would come out in a few denormal bits
+  const int e = eig_input_exp(ctrl);
+  const bool out_of_range = !(ldexpf(ctrl->bound, e) < 3.0e38f) || (ctrl->amax > 0.f && ctrl->amax < 1.17549435e-38f);
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
     const int r = (int)(idx / n), k = (int)(idx - (int64_t)r * n);
     float v = V[(int64_t)r * np + perm[k]];
     if (!(v == v)) v = 0.f;
     Q[idx] = v;
     if (r == 0) {
-      float l = d[perm[k]];
+      float l = out_of_range ? 0.f : ldexpf(d[perm[k]], e);
       if (!(l == l)) l = 0.f;
       if (clamp && l < 0.f) l = 0.f;
       w[k] = l;
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && info != nullptr) {
-    info[0] = ctrl->converged ? 0 : 1;
+    info[0] = (ctrl->converged && !out_of_range) ? 0 : 1;
     info[1] = ctrl->sweeps;  // sweeps actually executed (diagnostic)
   }
 }
@@ -783,6 +820,9 @@ static int eig_enqueue_init(const EigJob& j, hipStream_t stream) {
   EigDesc d;
   d.Aw = j.Aw, d.V = j.V, d.Rws = j.Rws, d.Dws = j.Dws, d.rotated = j.rotated, d.ctrl = j.ctrl, d.np = p.np, d.nb = p.nb;
   hipLaunchKernelGGL(eig_desc_kernel, dim3(1), dim3(1), 0, stream, d, j.desc);
+  int64_t ablocks = (j.n * j.n + 255) / 256;
+  if (ablocks > 4096) ablocks = 4096;
+  hipLaunchKernelGGL(eig_absmax_kernel, dim3((unsigned)ablocks), dim3(256), 0, stream, j.A, (int)j.n, j.ctrl);
   int64_t blocks = ((int64_t)p.np * p.np + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(eig_init_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, j.A, (int)j.n, p.np, j.Aw, j.A0, j.V,

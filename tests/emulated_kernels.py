@@ -488,11 +488,30 @@ class EmulatedKernels:
 
     # eigensolver
     def syevj(self, A, clamp=True, max_sweeps=0):
+        """LAPACK for the eigenpairs, plus the parts of lk_syevj_f32's contract that are not arithmetic: the upper
+        triangle only, non-finite entries read as 0, and the status word -- info[0] = 1 when the sweeps ran out or the
+        matrix is outside the supported magnitude range (include/laplace_hip.h), info[1] = sweeps executed.  The sweep
+        count is modelled, not computed: a matrix with no off-diagonal entry above the solver's convergence floor
+        (1e-6 lambda_max) converges in its first sweep, any other needs a sweep that rotates and one that finds nothing
+        left."""
         Au = torch.triu(A) + torch.triu(A, 1).T
+        fp32 = A.dtype == torch.float32
+        Au = torch.where(torch.isfinite(Au) & ((Au.abs() <= 3.0e38) | (not fp32)), Au, torch.zeros_like(Au))
+        n = Au.shape[0]
+        info = torch.zeros(2, dtype=torch.int32)
+        amax = float(Au.abs().max()) if n else 0.0
+        if fp32 and n and (float(Au.double().abs().sum(1).max()) >= 3.0e38 or 0.0 < amax < 2.0 ** -126):
+            info[0] = 1  # out of range: reported, the outputs are finite placeholders
+            return torch.zeros(n, dtype=A.dtype), torch.eye(n, dtype=A.dtype), info
         w, Q = torch.linalg.eigh(Au)
+        scale = max(float(w.abs().max()), float(Au.diagonal().abs().max())) if n else 0.0
+        off = float((Au - torch.diag(Au.diagonal())).abs().max()) if n else 0.0
+        need = 1 if off <= 1e-6 * scale else 2
+        done = need if max_sweeps <= 0 else min(need, int(max_sweeps))
+        info[0], info[1] = (0 if done >= need else 1), done
         if clamp:
             w = w.clamp(min=0.0)
-        return torch.nan_to_num(w), torch.nan_to_num(Q), torch.zeros(2, dtype=torch.int32)
+        return torch.nan_to_num(w), torch.nan_to_num(Q), info
 
     pixgram_max_hw = 25  # larger than the product's 16 so that the 5x5 test fixture exercises the pixel-pair path
 
