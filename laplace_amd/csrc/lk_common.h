@@ -63,6 +63,13 @@ __device__ __forceinline__ int fdiv(int n, const FastDiv& f) {
   return (int)(((uint64_t)(uint32_t)n * f.M) >> (32 + f.s));
 }
 
+// XCD-aware work order: consecutive block ids run on different XCDs (id % 8); block `bid` of `nblk` gets the index that gives
+// every XCD a contiguous range of the work items, so that the blocks sharing an L2 are neighbours in whatever the kernel orders
+__device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
+  const int q = nblk / 8, r = nblk % 8, x = bid % 8, j = bid / 8;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
+}
+
 }  // namespace lk
 
 #define LK_REQUIRE(cond, ...)            \

@@ -30,6 +30,7 @@
 // (or 256 x 64) output tile; the epilogue un-scales, optionally accumulates into `out`, and folds max|out| into a
 // device word (what the next producer needs to choose ITS scale).
 #include "lk_common.h"
+#include "lk_split16.h"
 
 #include <map>
 #include <mutex>
@@ -38,30 +39,10 @@
 
 namespace lk {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// ---- power-of-two scaling -------------------------------------------------------------------------------------------
-// exponent s such that amax * 2^s lies in [2^14, 2^15)  (clamped so that 2^s and every scaled element stay finite)
-__device__ __forceinline__ int scale_exp_for(float amax) {
-  int be = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-  if (be == 0) be = 1;  // zero / subnormal tensors: largest scale that is safe for anything below 2^-126
-  int s = 14 - (be - 127);
-  return s > 120 ? 120 : s;
-}
-__device__ __forceinline__ float exp2i(int s) {  // 2^s, -126 <= s <= 127
-  return __uint_as_float((unsigned)(127 + s) << 23);
-}
-__device__ __forceinline__ void split2(float x, float sc, _Float16& h, _Float16& l) {
-  // the scaled value is made opaque first: h and the residual must come from the SAME fp32 value (hipcc otherwise fuses
-  // the residual into fp16(x * sc - h') with h' rounded from the exact product, see lk_sweep16.hip)
-  float xs = x * sc;
-  asm volatile("" : "+v"(xs));
-  h = (_Float16)xs;
-  l = (_Float16)(xs - (float)h);
-}
+// (power-of-two scaling and the two-piece split: lk_split16.h)
 
 // maximum of a 256-thread workgroup into the result word: ONE atomic per workgroup (same-address atomics serialise in L2 at
 // ~5-10 ns each: one per wave of a 2048-workgroup launch was a 40-80 us floor under every measurement, whatever its size)
@@ -378,14 +359,11 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
   constexpr int BM = CFG::BM, BN = CFG::BN, BK = CFG::BK, Q = CFG::Q, TM = CFG::TM, TN = CFG::TN, NT = CFG::NT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware tile order: consecutive block ids run on different XCDs (id % 8); give every XCD a contiguous range of
-  // (n-tile major, m-tile minor) tiles so that the blocks sharing an L2 share one weight panel and neighbouring pixels
+  // XCD-aware tile order (xcd_tile_order, lk_common.h): every XCD gets a contiguous range of (n-tile major, m-tile minor)
+  // tiles so that the blocks sharing an L2 share one weight panel and neighbouring pixels
   const int nblk = gridDim.x;
   int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, x = bid % 8, j = bid / 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-  }
+  bid = xcd_tile_order(bid, nblk);
   const int M = g.N * g.Hc * g.Wc;
   const int KC = g.Ci / BK;
   const int tile = bid;
@@ -439,23 +417,13 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
   // The scale words (and, for the fused epilogue, the bound they combine to) are read HERE, at the top: left where they
   // are used — behind the K loop — they were a chain of dependent global loads at the end of every tile.
   const int sexp_a = a_sexp[0], sexp_w = w_sexp[0];
-  const float inv_a = exp2i(-sexp_a < -126 ? -126 : -sexp_a), inv_w = exp2i(-sexp_w < -126 ? -126 : -sexp_w);
-  int so = 0;
-  float sc_out = 1.f, inv2 = 0.f;
+  const float inv_a = exp2i_neg(sexp_a), inv_w = exp2i_neg(sexp_w);
+  VjpScale vs = {0, 1.f, 0.f};
   static_assert(FUSE || !FWD, "the forward epilogue uses the fused epilogue's staging");
   if constexpr (FUSE && !FWD) {
     // scale of the result from the guaranteed bound (every thread computes the same few flops; one writes the word)
-    float bound = fz.in_amax ? __uint_as_float(fz.in_amax[0]) : exp2i(15 - sexp_a < -126 ? -126 : (15 - sexp_a > 127 ? 127 : 15 - sexp_a));
-    bound *= fz.w_l1[0];
-    if (fz.add_h) {
-      const int s2 = fz.add_sexp[0];
-      bound += exp2i(15 - s2 < -126 ? -126 : (15 - s2 > 127 ? 127 : 15 - s2));
-      inv2 = exp2i(-s2 < -126 ? -126 : -s2);
-    }
-    if (fz.mask && fz.mask_float && fz.mult_amax) bound *= __uint_as_float(fz.mult_amax[0]);
-    if (fz.scale) bound *= __uint_as_float(fz.scale_amax[0]);
-    so = scale_exp_for(bound);
-    sc_out = exp2i(so);
+    const float bound = (fz.in_amax ? __uint_as_float(fz.in_amax[0]) : bound_of_sexp(sexp_a)) * fz.w_l1[0];
+    vs = vjp_bound_scale<false>(bound, fz.add_h, fz.add_sexp, fz.mask, fz.mask_float, fz.mult_amax, fz.scale, fz.scale_amax);
   }
 
   // Taps that reach no row of this tile are dropped from the K loop (position-major tiles of small maps: a corner pixel
@@ -655,7 +623,6 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
         for (int r = 0; r < 16; ++r)
           img[(a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PITCH + b * 32 + lr] = acc[a][b][r];
     __syncthreads();  // the slots are zero before anybody's maximum arrives
-    auto clampe = [](int e) { return e < -126 ? -126 : (e > 127 ? 127 : e); };
     const float s_amax = __uint_as_float(fz.fwd_scale_amax[0]), t_amax = __uint_as_float(fz.fwd_shift_amax[0]);
     const float x_mul = fz.w_l1[0];
     int c_n = -1, c_so = 0;
@@ -672,12 +639,12 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
       if (ok) {
         if (n != c_n) {  // (a tile of a large map lies in one or two images)
           const int sa = a_sexp[per_img ? n : 0];
-          c_inv = exp2i(clampe(-sa));
+          c_inv = exp2i_sat(-sa);
           float bx = __uint_as_float(fz.in_amax[n < fz.fwd_in_namax ? n : fz.fwd_in_namax - 1]) * x_mul;
           c_bound = __fmaf_rn(bx, s_amax, t_amax);
           if (fz.fwd_addend) c_bound += fz.fwd_addend_bound[n < fz.fwd_addend_nbound ? n : fz.fwd_addend_nbound - 1];
           c_so = scale_exp_for(c_bound);
-          c_sc = exp2i(clampe(c_so));
+          c_sc = exp2i_sat(c_so);
           c_n = n;
         }
         const f32x4 p0 = *reinterpret_cast<const f32x4*>(img + row * PITCH + c8 * 8);
@@ -711,11 +678,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           rmax = max(rmax, __float_as_uint(v[j]) & 0x7fffffffu);
-          float xs = v[j] * c_sc;
-          asm volatile("" : "+v"(xs));  // h and the residual from the SAME fp32 value (see split2)
-          const _Float16 hh = (_Float16)xs;
-          h[j] = hh;
-          l[j] = (_Float16)(xs - (float)hh);
+          split2_at(v[j] * c_sc, h, l, j);
         }
         if (fz.out_h) {
           *reinterpret_cast<f16x8*>(fz.out_h + e) = h;
@@ -745,7 +708,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
     return;
   }
   if constexpr (FUSE) {
-    if (blockIdx.x == 0 && tid == 0) fz.out_sexp[0] = so;
+    if (blockIdx.x == 0 && tid == 0) fz.out_sexp[0] = vs.so;
     // the wave's 64 x 64 (32 x 32, ...) block goes through LDS: MFMA layout (lane = channel, registers = pixels) ->
     // lane = 8 consecutive channels of one pixel, i.e. 16-byte loads of the addend / mask and 16-byte stores of each plane
     static_assert(CFG::EPI_LDS == CFG::WM * CFG::WN * ROWS_W * PITCH * 4 && CFG::EPI_LDS <= 80 * 1024, "staging image: two workgroups per CU");
@@ -774,57 +737,29 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
       const f32x4 p1 = *reinterpret_cast<const f32x4*>(img + row * PITCH + c8 * 8 + 4);
       float v[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
       const int64_t e = e_[it];
-      if (fz.add_h) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += ((float)h2_[it][j] + (float)l2_[it][j]) * inv2;
-      }
+      if (fz.add_h) vjp_add8(v, h2_[it], l2_[it], vs.inv2);
       float mult[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) mult[j] = sc_out;
+      for (int j = 0; j < 8; ++j) mult[j] = vs.sc_out;
       if (fz.mask) {
-        if (fz.mask_float) {
-          const int64_t em = (int64_t)mask_row(pix_[it]) * g.Co + col0;
-          const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)fz.mask + em);
-          const f32x4 b = *reinterpret_cast<const f32x4*>((const float*)fz.mask + em + 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) mult[j] *= a[j], mult[4 + j] *= b[j];
-        } else {
-          const uint2 u = mk_[it];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (!((u.x >> (8 * j)) & 0xffu)) mult[j] = 0.f;
-            if (!((u.y >> (8 * j)) & 0xffu)) mult[4 + j] = 0.f;
-          }
-        }
+        if (fz.mask_float) vjp_mult8_times(mult, (const float*)fz.mask + ((int64_t)mask_row(pix_[it]) * g.Co + col0));
+        else vjp_mult8_mask(mult, mk_[it]);
       }
-      if (fz.scale) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(fz.scale + col0), b = *reinterpret_cast<const f32x4*>(fz.scale + col0 + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mult[j] *= a[j], mult[4 + j] *= b[j];
-      }
+      if (fz.scale) vjp_mult8_times(mult, fz.scale + col0);
       f16x8 h, l;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float xs = v[j] * mult[j];
-        asm volatile("" : "+v"(xs));  // h and the residual from the SAME fp32 value (see split2)
-        const _Float16 hh = (_Float16)xs;
-        h[j] = hh;
-        l[j] = (_Float16)(xs - (float)hh);
-        vmax = max(vmax, __float_as_uint(xs) & 0x7fffffffu);
-      }
+      vjp_chunk8(v, mult, vmax, h, l);
       *reinterpret_cast<f16x8*>(fz.out_h + e) = h;
       *reinterpret_cast<f16x8*>(fz.out_l + e) = l;
     }
     // max|o| = max|o 2^so| * 2^-so (exact: a power of two), kept as the bit pattern of a non-negative float
-    if (amax_out) conv_block_max<NT / 64>(vmax, exp2i(-so < -126 ? -126 : -so), amax_out, smem);
+    if (amax_out) conv_block_max<NT / 64>(vmax, exp2i_neg(vs.so), amax_out, smem);
     return;
   }
   // A operand with one scale per image (the forward's activations, lk_split_images_f16x2 / lk_bn_act_fwd_nhwc_f16x2): GEMM
   // rows never mix images, so the accumulators are un-scaled row by row here (the K loop does not know about it)
   const bool per_img = g.a_nsexp > 1;
   auto image_inv = [&](int n) {
-    const int s = a_sexp[n];
-    return exp2i(-s < -126 ? -126 : -s);
+    return exp2i_neg(a_sexp[n]);
   };
   if (g.out_nchw) {
     // position-contiguous output [n][co][pixel] (what the predictive's quadratic-form kernel reads): a lane owns one
@@ -848,7 +783,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
           const int ns = per_img ? n : 0;
           if (ns != pl_ns) {
             const int sa = a_sexp[ns];
-            float bound = fz.in_amax ? __uint_as_float(fz.in_amax[ns]) : exp2i(15 - sa < -126 ? -126 : (15 - sa > 127 ? 127 : 15 - sa));
+            float bound = fz.in_amax ? __uint_as_float(fz.in_amax[ns]) : bound_of_sexp(sa);
             pl_so = scale_exp_for(bound * pl_l1);
             pl_sc = exp2i(pl_so) * inv_w;
             pl_ns = ns;
@@ -862,13 +797,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
             const int col = tile_n * BN + (wn * TN + b) * 32 + lr;
             f16x4 h4, l4;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float xs = acc[a][b][4 * q + j] * inv_an * pl_sc;
-              asm volatile("" : "+v"(xs));  // h and the residual from the SAME fp32 value (see split2)
-              const _Float16 hh = (_Float16)xs;
-              h4[j] = hh;
-              l4[j] = (_Float16)(xs - (float)hh);
-            }
+            for (int j = 0; j < 4; ++j) split2_at(acc[a][b][4 * q + j] * inv_an * pl_sc, h4, l4, j);
             if (col == 0 && pix == 0 && (per_img || n == 0) && col < g.Co) fz.out_sexp[ns] = pl_so;
             if (pl_pair && pair_ok) {
               // lh == 0 keeps h4 and receives the partner's h4; lh == 1 keeps l4 and receives the partner's l4
@@ -986,10 +915,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nblk = gridDim.x;
   int bid = blockIdx.x;
-  {  // XCD-contiguous tile ranges (see conv_f16x2_kernel)
-    const int q = nblk / 8, r = nblk % 8, x = bid % 8, j = bid / 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-  }
+  bid = xcd_tile_order(bid, nblk);  // XCD-contiguous tile ranges (see conv_f16x2_kernel)
   const int M = g.N * g.Hc * g.Wc;  // rows of ONE class
   const int KC = g.Ci / BK;
   const int nb_mc = nb_m * g.ncls;
@@ -1036,28 +962,16 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
   }
   const int64_t w_tap = (int64_t)g.Co * g.Ci;
 
-  auto clampe = [](int e) { return e < -126 ? -126 : (e > 127 ? 127 : e); };
   const int sexp_a = s1.a_sexp[0], sexp_w = s1.w_sexp[0];
-  const float inv = exp2i(clampe(-sexp_a)) * exp2i(clampe(-sexp_w));
-  float ratio = 1.f, inv2 = 0.f;
-  int so;
-  {
-    float bound = (s1.in_amax ? __uint_as_float(s1.in_amax[0]) : exp2i(clampe(15 - sexp_a))) * s1.w_l1[0];
-    if (g.second) {
-      const int sa2 = s2.a_sexp[0], sw2 = s2.w_sexp[0];
-      bound += (s2.in_amax ? __uint_as_float(s2.in_amax[0]) : exp2i(clampe(15 - sa2))) * s2.w_l1[0];
-      ratio = exp2i(clampe((sexp_a + sexp_w) - (sa2 + sw2)));
-    }
-    if (fz.add_h) {
-      const int sadd = fz.add_sexp[0];
-      bound += exp2i(clampe(15 - sadd));
-      inv2 = exp2i(clampe(-sadd));
-    }
-    if (fz.mask && fz.mask_float && fz.mult_amax) bound *= __uint_as_float(fz.mult_amax[0]);
-    if (fz.scale) bound *= __uint_as_float(fz.scale_amax[0]);
-    so = scale_exp_for(bound);
+  const float inv = exp2i_sat(-sexp_a) * exp2i_sat(-sexp_w);
+  float ratio = 1.f;
+  float bound = (s1.in_amax ? __uint_as_float(s1.in_amax[0]) : exp2i_sat(15 - sexp_a)) * s1.w_l1[0];
+  if (g.second) {
+    const int sa2 = s2.a_sexp[0], sw2 = s2.w_sexp[0];
+    bound += (s2.in_amax ? __uint_as_float(s2.in_amax[0]) : exp2i_sat(15 - sa2)) * s2.w_l1[0];
+    ratio = exp2i_sat((sexp_a + sexp_w) - (sa2 + sw2));
   }
-  const float sc_out = exp2i(so);
+  const VjpScale vs = vjp_bound_scale<true>(bound, fz.add_h, fz.add_sexp, fz.mask, fz.mask_float, fz.mult_amax, fz.scale, fz.scale_amax);
 
   // taps of this class that reach a row of this tile (uniform over the workgroup), the second source's first
   unsigned long long tap_list = 0;
@@ -1220,7 +1134,7 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
   }
 
   unsigned vmax = 0;
-  if (blockIdx.x == 0 && tid == 0) fz.out_sexp[0] = so;
+  if (blockIdx.x == 0 && tid == 0) fz.out_sexp[0] = vs.so;
   static_assert(CFG::EPI_LDS == CFG::WM * CFG::WN * ROWS_W * PITCH * 4 && CFG::EPI_LDS <= 80 * 1024, "staging image: two workgroups per CU");
 #pragma unroll
   for (int it = 0; it < NIT; ++it) prefetch(it);
@@ -1243,48 +1157,21 @@ __global__ __launch_bounds__(CFG::NT) __attribute__((amdgpu_waves_per_eu(CFG::WP
     const f32x4 p1 = *reinterpret_cast<const f32x4*>(img + row * PITCH + c8 * 8 + 4);
     float v[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
     const int64_t e = e_[it];
-    if (fz.add_h) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += ((float)h2_[it][j] + (float)l2_[it][j]) * inv2;
-    }
+    if (fz.add_h) vjp_add8(v, h2_[it], l2_[it], vs.inv2);
     float mult[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) mult[j] = sc_out;
+    for (int j = 0; j < 8; ++j) mult[j] = vs.sc_out;
     if (fz.mask) {
-      if (fz.mask_float) {
-        const int64_t em = (int64_t)mask_row(pix_[it]) * g.Co + col0;
-        const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)fz.mask + em);
-        const f32x4 b = *reinterpret_cast<const f32x4*>((const float*)fz.mask + em + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mult[j] *= a[j], mult[4 + j] *= b[j];
-      } else {
-        const uint2 u = mk_[it];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!((u.x >> (8 * j)) & 0xffu)) mult[j] = 0.f;
-          if (!((u.y >> (8 * j)) & 0xffu)) mult[4 + j] = 0.f;
-        }
-      }
+      if (fz.mask_float) vjp_mult8_times(mult, (const float*)fz.mask + ((int64_t)mask_row(pix_[it]) * g.Co + col0));
+      else vjp_mult8_mask(mult, mk_[it]);
     }
-    if (fz.scale) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(fz.scale + col0), b = *reinterpret_cast<const f32x4*>(fz.scale + col0 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mult[j] *= a[j], mult[4 + j] *= b[j];
-    }
+    if (fz.scale) vjp_mult8_times(mult, fz.scale + col0);
     f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float xs = v[j] * mult[j];
-      asm volatile("" : "+v"(xs));
-      const _Float16 hh = (_Float16)xs;
-      h[j] = hh;
-      l[j] = (_Float16)(xs - (float)hh);
-      vmax = max(vmax, __float_as_uint(xs) & 0x7fffffffu);
-    }
+    vjp_chunk8(v, mult, vmax, h, l);
     *reinterpret_cast<f16x8*>(fz.out_h + e) = h;
     *reinterpret_cast<f16x8*>(fz.out_l + e) = l;
   }
-  if (amax_out) conv_block_max<NT / 64>(vmax, exp2i(-so < -126 ? -126 : -so), amax_out, smem);
+  if (amax_out) conv_block_max<NT / 64>(vmax, exp2i_neg(vs.so), amax_out, smem);
 }
 
 
@@ -1377,10 +1264,7 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
   // 321 us on the c4 launch).  With several 64-channel column tiles per pixel tile the same order puts all the readers of
   // one window into one L2 at the same moment and LOSES (256 channels: 264 -> 314 us, 512: 289 -> 385): they stay spread.
   int tile = blockIdx.x;
-  if (p.Co == 64) {
-    const int q = G / 8, r = G % 8, x = tile % 8, j = tile / 8;
-    tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-  }
+  if (p.Co == 64) tile = xcd_tile_order(tile, G);
   // tile index -> (first pixel, first output channel); false behind the last tile of this workgroup's walk.  Plain order:
   // the column tiles of a pixel tile are consecutive indices, i.e. run at the same time on DIFFERENT XCDs (index % 8), each
   // XCD always on the same column(s): its weight slice stays hot in its L2, every window is fetched by Co / 64 L2s.
@@ -1435,19 +1319,10 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
 
   // ---- scales (see conv_f16x2_kernel): the result's scale from the guaranteed bound
   const int sexp_a = p.a_sexp[0], sexp_w = p.w_sexp[0];
-  const float inv = exp2i(-sexp_a < -126 ? -126 : -sexp_a) * exp2i(-sexp_w < -126 ? -126 : -sexp_w);
-  float inv2 = 0.f;
-  float bound = p.in_amax ? __uint_as_float(p.in_amax[0]) : exp2i(15 - sexp_a < -126 ? -126 : (15 - sexp_a > 127 ? 127 : 15 - sexp_a));
-  bound *= p.w_l1[0];
-  if (p.add_h) {
-    const int s2 = p.add_sexp[0];
-    bound += exp2i(15 - s2 < -126 ? -126 : (15 - s2 > 127 ? 127 : 15 - s2));
-    inv2 = exp2i(-s2 < -126 ? -126 : -s2);
-  }
-  if (p.scale) bound *= __uint_as_float(p.scale_amax[0]);
-  const int so = scale_exp_for(bound);
-  const float sc_out = exp2i(so);
-  if (blockIdx.x == 0 && tid == 0) p.out_sexp[0] = so;
+  const float inv = exp2i_neg(sexp_a) * exp2i_neg(sexp_w);
+  const VjpScale vs = vjp_bound_scale<false>((p.in_amax ? __uint_as_float(p.in_amax[0]) : bound_of_sexp(sexp_a)) * p.w_l1[0], p.add_h,
+                                             p.add_sexp, false, 0, nullptr, p.scale, p.scale_amax);
+  if (blockIdx.x == 0 && tid == 0) p.out_sexp[0] = vs.so;
 
   // ---- window staging: wave-instruction i = it * NW + wave covers slots [64 i, 64 i + 64) of [plane][pixel][2].
   //      Addresses are (scalar base) + (32-bit lane offset): the lane offsets are the only registers the staging keeps.
@@ -1746,14 +1621,10 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
   auto epilogue = [&](int m0_t, int n0_t) {
     epi_request(m0_t, n0_t, NH, NS);
     const int mrow0 = m0_t + wave * 64 + e_row;
-    float mult[8];
+    float mult[8];  // (the byte mask is not folded in here: vjp_chunk8<true> applies it as a select)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) mult[j] = sc_out;
-    if (p.scale) {
-      const f32x4 s0 = *reinterpret_cast<const f32x4*>(p.scale + n0_t + e_c0), s1 = *reinterpret_cast<const f32x4*>(p.scale + n0_t + e_c0 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mult[j] *= s0[j], mult[4 + j] *= s1[j];
-    }
+    for (int j = 0; j < 8; ++j) mult[j] = vs.sc_out;
+    if (p.scale) vjp_mult8_times(mult, p.scale + n0_t + e_c0);
 #pragma unroll
     for (int sl = 0; sl < NS; ++sl) {
       const int a = sl >> 2, q = sl & 3;
@@ -1768,21 +1639,9 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
       const int m = mrow0 + sl * 8;
       if (m >= M) continue;
       float v[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
-      if (p.add_h) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += ((float)e_h2[sl][j] + (float)e_l2[sl][j]) * inv2;
-      }
       f16x8 h, l;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const bool keep = ((j < 4 ? e_mk[sl].x >> (8 * j) : e_mk[sl].y >> (8 * (j - 4))) & 0xffu) != 0;
-        float xs = keep ? v[j] * mult[j] : 0.f;
-        asm volatile("" : "+v"(xs));  // h and the residual from the SAME fp32 value (see split2)
-        const _Float16 hh = (_Float16)xs;
-        h[j] = hh;
-        l[j] = (_Float16)(xs - (float)hh);
-        vmax = max(vmax, __float_as_uint(xs) & 0x7fffffffu);
-      }
+      if (p.add_h) vjp_add8(v, e_h2[sl], e_l2[sl], vs.inv2);
+      vjp_chunk8<true>(v, mult, vmax, h, l, e_mk[sl]);
       // Before this wave's FIRST store: everything it has requested so far has landed (the operands above are in
       // registers, and the next tile's first weights were requested a whole epilogue ago) — said explicitly, because
       // the next tile's first step then does not wait on vmcnt at all: the stores below would be in that count, and a
@@ -1932,8 +1791,7 @@ void conv_winp_f16x2_kernel(const WinPArgs p) {
   if (p.amax_out) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) vmax = max(vmax, (unsigned)__shfl_xor((int)vmax, off, 64));
-    const int back = -so < -126 ? -126 : -so;
-    if (lane == 0 && vmax) atomicMax(p.amax_out, __float_as_uint(__uint_as_float(vmax) * exp2i(back)));
+    if (lane == 0 && vmax) atomicMax(p.amax_out, __float_as_uint(__uint_as_float(vmax) * exp2i_neg(vs.so)));
   }
 #ifdef LK_WINP_TRACE
   if (tid == 0 && blockIdx.x < 1024) {
@@ -2072,19 +1930,21 @@ static int launch_conv(const ConvGeom& g, const void* Ah, const void* Al, const 
   const int64_t M = (int64_t)g.N * g.Hc * g.Wc;
   const int nb_m = (int)((M + CFG::BM - 1) / CFG::BM), nb_n = (g.Co + CFG::BN - 1) / CFG::BN;
   const size_t lds = (size_t)CFG::NBUF * CFG::STAGE;
+  // one instantiation: raise its dynamic-LDS limit once, launch, check (`attr_set`: the call site's static flag)
+  auto launch = [&](auto kernel, bool& attr_set, size_t bytes, const ConvVjp& z, const char* what) {
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(nb_m * nb_n)), dim3(CFG::NT), bytes, stream, g, (const _Float16*)Ah, (const _Float16*)Al,
+                       (const _Float16*)Wh, (const _Float16*)Wl, a_sexp, w_sexp, (const _Float16*)zero16, out, accumulate, amax_out, nb_m, z);
+    return check_launch(what);
+  };
   if (fz && fz->fwd_y) {  // forward epilogue (BatchNorm / add / ReLU): the staging image + BM + 1 words for the images' maxima
     if constexpr (CFG::FUSABLE) {
       const size_t need = (size_t)CFG::EPI_LDS + 4 * (CFG::BM + 1);
-      const size_t lds_w = lds > need ? lds : (need + 15) / 16 * 16;
       static bool attr_set_w = false;
-      if (!attr_set_w) {
-        (void)hipFuncSetAttribute((const void*)conv_f16x2_kernel<CFG, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w);
-        attr_set_w = true;
-      }
-      hipLaunchKernelGGL((conv_f16x2_kernel<CFG, true, true>), dim3((unsigned)(nb_m * nb_n)), dim3(CFG::NT), lds_w, stream, g,
-                         (const _Float16*)Ah, (const _Float16*)Al, (const _Float16*)Wh, (const _Float16*)Wl, a_sexp, w_sexp,
-                         (const _Float16*)zero16, out, accumulate, amax_out, nb_m, *fz);
-      return check_launch("conv_f16x2_kernel(bn_act)");
+      return launch(conv_f16x2_kernel<CFG, true, true>, attr_set_w, lds > need ? lds : (need + 15) / 16 * 16, *fz, "conv_f16x2_kernel(bn_act)");
     } else {
       set_error("lk_conv_bn_act_nhwc_f16x2: this tile shape has no fused epilogue");
       return LK_EINVAL;
@@ -2092,30 +1952,15 @@ static int launch_conv(const ConvGeom& g, const void* Ah, const void* Al, const 
   }
   if (fz) {
     if constexpr (CFG::FUSABLE) {
-      const size_t lds_f = lds > (size_t)CFG::EPI_LDS ? lds : (size_t)CFG::EPI_LDS;
       static bool attr_set_f = false;
-      if (!attr_set_f) {
-        (void)hipFuncSetAttribute((const void*)conv_f16x2_kernel<CFG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
-        attr_set_f = true;
-      }
-      hipLaunchKernelGGL((conv_f16x2_kernel<CFG, true>), dim3((unsigned)(nb_m * nb_n)), dim3(CFG::NT), lds_f, stream, g,
-                         (const _Float16*)Ah, (const _Float16*)Al, (const _Float16*)Wh, (const _Float16*)Wl, a_sexp, w_sexp,
-                         (const _Float16*)zero16, out, accumulate, amax_out, nb_m, *fz);
-      return check_launch("conv_f16x2_kernel(vjp)");
+      return launch(conv_f16x2_kernel<CFG, true>, attr_set_f, lds > (size_t)CFG::EPI_LDS ? lds : (size_t)CFG::EPI_LDS, *fz, "conv_f16x2_kernel(vjp)");
     } else {
       set_error("lk_conv_nhwc_f16x2_vjp: this tile shape has no fused epilogue");
       return LK_EINVAL;
     }
   }
   static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_f16x2_kernel<CFG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_f16x2_kernel<CFG, false>), dim3((unsigned)(nb_m * nb_n)), dim3(CFG::NT), lds, stream, g, (const _Float16*)Ah,
-                     (const _Float16*)Al, (const _Float16*)Wh, (const _Float16*)Wl, a_sexp, w_sexp, (const _Float16*)zero16,
-                     out, accumulate, amax_out, nb_m, plain);
-  return check_launch("conv_f16x2_kernel");
+  return launch(conv_f16x2_kernel<CFG, false>, attr_set, lds, plain, "conv_f16x2_kernel");
 }
 
 static int cu_count() {

@@ -38,18 +38,10 @@
 #include <vector>
 
 #include "lk_common.h"
+#include "lk_split16.h"
 
 namespace lk {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// x = h + l (+ <= 2^-22 |x|, 2^-25 absolute), both fp16.  The value is made opaque first: h and the residual must come
-// from the SAME fp32 value (hipcc otherwise fuses the residual into fp16(x - h') with h' rounded from an exact product)
-__device__ __forceinline__ void eig_split2(float x, _Float16& h, _Float16& l) {
-  asm volatile("" : "+v"(x));
-  h = (_Float16)x;
-  l = (_Float16)(x - (float)h);
-}
 
 constexpr int EB = 32;       // index block
 constexpr int EP = 64;       // pivot size (two blocks)
@@ -381,7 +373,7 @@ __global__ __launch_bounds__(256) void eig_pivot_kernel(EigRound rd, float tol_r
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       _Float16 hh, ll;
-      eig_split2(R[k0 + e][j] * 16384.f, hh, ll);
+      split2_scaled(R[k0 + e][j] * 16384.f, hh, ll);
       h[e] = hh, l[e] = ll;
     }
     *reinterpret_cast<f16x4*>(Rout + j * EP + k0) = h;
@@ -484,10 +476,10 @@ __device__ __forceinline__ void eig_stage_block(EigTileLds& L, const float* __re
     const float4 v = vv[e];
     f16x4 h, l;
     _Float16 hh, ll;
-    eig_split2(v.x * sc, hh, ll), h[0] = hh, l[0] = ll;
-    eig_split2(v.y * sc, hh, ll), h[1] = hh, l[1] = ll;
-    eig_split2(v.z * sc, hh, ll), h[2] = hh, l[2] = ll;
-    eig_split2(v.w * sc, hh, ll), h[3] = hh, l[3] = ll;
+    split2_scaled(v.x * sc, hh, ll), h[0] = hh, l[0] = ll;
+    split2_scaled(v.y * sc, hh, ll), h[1] = hh, l[1] = ll;
+    split2_scaled(v.z * sc, hh, ll), h[2] = hh, l[2] = ll;
+    split2_scaled(v.w * sc, hh, ll), h[3] = hh, l[3] = ll;
     *reinterpret_cast<f16x4*>(&L.op.a[0][r * EHP + c0]) = h;
     *reinterpret_cast<f16x4*>(&L.op.a[1][r * EHP + c0]) = l;
   }
@@ -576,7 +568,7 @@ __global__ __launch_bounds__(256) void eig_update_kernel(EigRound rd) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       _Float16 hh, ll;
-      eig_split2(t[4 * g + e] * (1.f / 16384.f), hh, ll);
+      split2_scaled(t[4 * g + e] * (1.f / 16384.f), hh, ll);
       h[e] = hh, l[e] = ll;
     }
     const int off = (wn * 32 + lr) * EHP + wm * 32 + 8 * g + 4 * lh;

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "lk_common.h"
+#include "lk_split16.h"
 
 namespace lk {
 
@@ -220,15 +221,7 @@ struct NtbCfg {
   static constexpr int PANEL_F = 3 * PIECE / 4;            // panel size in floats (the LDS arena is float-typed)
 };
 
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xffff0000u;
-  const float r1 = x - __uint_as_float(h);
-  m = __float_as_uint(r1) & 0xffff0000u;
-  l = __float_as_uint(r1 - __uint_as_float(m));  // at most 8 significant bits are left: exact in bf16
-}
-__device__ __forceinline__ unsigned pack_hi16(unsigned lo_elem, unsigned hi_elem) {
-  return (lo_elem >> 16) | (hi_elem & 0xffff0000u);
-}
+// (split3 / pack_hi16: lk_split16.h)
 
 template <int VEC, int CFG>
 __device__ __forceinline__ void store_panel_ntb(float* panel, int tid, const float (&st)[Cfg<CFG>::EPT]) {

@@ -14,6 +14,7 @@
 
 #include "lk_common.h"
 #include "lk_quadtile.h"
+#include "lk_split16.h"
 
 namespace lk {
 
@@ -23,16 +24,6 @@ namespace lk {
 // measured equal to the bf16 form: the kernel was never bound by its matrix pipe.  Removed in round 5.)
 typedef _Float16 qf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 qf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int qc_scale_exp(float amax) {  // amax * 2^s in [2^14, 2^15)
-  int be = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-  if (be == 0) be = 1;
-  const int s = 14 - (be - 127);
-  return s > 120 ? 120 : s;
-}
-__device__ __forceinline__ float qc_exp2i(int s) {
-  s = s < -126 ? -126 : (s > 127 ? 127 : s);
-  return __uint_as_float((unsigned)(127 + s) << 23);
-}
 // grid = B * split workgroups of 4 waves; workgroup (n, sp) walks the super-tiles (32 rows o) x (128 columns i)
 // t = sp, sp + split, ...; wave w owns columns [32 w, 32 w + 32) of the super-tile for all CT outputs.
 // ARITH: 0 = fp32 MFMA (any L), 1 = three-piece bf16 (six MFMAs)
@@ -198,7 +189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
   const _Float16* __restrict__ vhn = vh + (size_t)n * Dk * L;
   const _Float16* __restrict__ vln = vl + (size_t)n * Dk * L;
   const int su = u_sexp[0], sv = v_sexp[n < v_nsexp ? n : v_nsexp - 1];
-  const float un_u = qc_exp2i(-su), un_v = qc_exp2i(-sv);
+  const float un_u = exp2i_sat(-su), un_v = exp2i_sat(-sv);
   const float dlt = delta[0];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
   // the eigenvalues behind the ring (host: w_in_lds when they fit): read in every tile's epilogue — from memory those loads

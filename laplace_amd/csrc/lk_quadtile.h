@@ -3,6 +3,7 @@
 #pragma once
 
 #include "lk_common.h"
+#include "lk_split16.h"
 
 namespace lk {
 
@@ -98,13 +99,7 @@ __device__ __forceinline__ void qc_tile_gemm(const QcOperands& t, int C, int Do,
 // lane's own 8 positions of column icol, split in registers.  The pipeline runs across tiles: during a tile's last
 // chunk the first chunk of the NEXT tile (other rows / columns, or the next sample) is fetched; loads are issued raw
 // from a clamped address and zeroed where they are consumed.
-__device__ __forceinline__ void qc_split3(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xffff0000u;
-  const float r1 = x - __uint_as_float(h);
-  m = __float_as_uint(r1) & 0xffff0000u;
-  l = __float_as_uint(r1 - __uint_as_float(m));  // at most 8 significant bits are left: exact in bf16
-}
-__device__ __forceinline__ unsigned qc_pack(unsigned even, unsigned odd) { return (even >> 16) | (odd & 0xffff0000u); }
+// (split3 / pack_hi16: lk_split16.h)
 
 template <int CT>
 struct QcStage {  // raw operands in flight: this thread's float4 slots of the A chunk, this lane's 8 positions of B
@@ -156,11 +151,11 @@ __device__ __forceinline__ void qc_tile_gemm_b6(const QcOperands& cur, const QcO
         const f32x4 x = ok ? st.ra[j] : f32x4{0.f, 0.f, 0.f, 0.f};
         unsigned h[4], m[4], l[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) qc_split3(x[q], h[q], m[q], l[q]);
+        for (int q = 0; q < 4; ++q) split3(x[q], h[q], m[q], l[q]);
         char* dst = wr + (((c0 + 2 * j) * 32 + o) * 16 + k4) * 2;
-        *reinterpret_cast<u32x2*>(dst) = u32x2{qc_pack(h[0], h[1]), qc_pack(h[2], h[3])};
-        *reinterpret_cast<u32x2*>(dst + PIECE) = u32x2{qc_pack(m[0], m[1]), qc_pack(m[2], m[3])};
-        *reinterpret_cast<u32x2*>(dst + 2 * PIECE) = u32x2{qc_pack(l[0], l[1]), qc_pack(l[2], l[3])};
+        *reinterpret_cast<u32x2*>(dst) = u32x2{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3])};
+        *reinterpret_cast<u32x2*>(dst + PIECE) = u32x2{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
+        *reinterpret_cast<u32x2*>(dst + 2 * PIECE) = u32x2{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
       }
     // this lane's B operand: positions l0 + 8 hi .. + 7 of column icol, as three bf16x8
     u32x4 bp[3];
@@ -170,13 +165,13 @@ __device__ __forceinline__ void qc_tile_gemm_b6(const QcOperands& cur, const QcO
       const f32x4 x = ok ? st.rb[hh] : f32x4{0.f, 0.f, 0.f, 0.f};
       unsigned h[4], m[4], l[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) qc_split3(x[q], h[q], m[q], l[q]);
-      bp[0][2 * hh] = qc_pack(h[0], h[1]);
-      bp[0][2 * hh + 1] = qc_pack(h[2], h[3]);
-      bp[1][2 * hh] = qc_pack(m[0], m[1]);
-      bp[1][2 * hh + 1] = qc_pack(m[2], m[3]);
-      bp[2][2 * hh] = qc_pack(l[0], l[1]);
-      bp[2][2 * hh + 1] = qc_pack(l[2], l[3]);
+      for (int q = 0; q < 4; ++q) split3(x[q], h[q], m[q], l[q]);
+      bp[0][2 * hh] = pack_hi16(h[0], h[1]);
+      bp[0][2 * hh + 1] = pack_hi16(h[2], h[3]);
+      bp[1][2 * hh] = pack_hi16(m[0], m[1]);
+      bp[1][2 * hh + 1] = pack_hi16(m[2], m[3]);
+      bp[2][2 * hh] = pack_hi16(l[0], l[1]);
+      bp[2][2 * hh + 1] = pack_hi16(l[2], l[3]);
     }
     bf16x8 b[3];
 #pragma unroll

@@ -5,23 +5,11 @@
 // G = sum_{n,l,c} g g^T (laplace/curvature/curvlinops.py:87-100).  Stock autograd runs one
 // activation / BatchNorm backward kernel per seed and layer; here all seeds of a layer go through one pass.
 #include "lk_common.h"
+#include "lk_split16.h"
 
 namespace lk {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int scale_exp_for16(float amax) {  // as in lk_conv.hip: amax * 2^s in [2^14, 2^15)
-  int be = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-  if (be == 0) be = 1;
-  int s = 14 - (be - 127);
-  return s > 120 ? 120 : s;
-}
-__device__ __forceinline__ float exp2i16(int s) {
-  s = s < -126 ? -126 : (s > 127 ? 127 : s);
-  return __uint_as_float((unsigned)(127 + s) << 23);
-}
 
 // ---- element-wise VJP, NHWC, split output -------------------------------------------------------------------------------
 //   out[s][e] = (g[s][e] + g2[s][e]) * M[e] * scale[e % C]        e < per = B*H*W*C, all S seeds in one pass
@@ -35,41 +23,22 @@ __global__ __launch_bounds__(256) void vjp_nhwc_split_kernel(
     const _Float16* __restrict__ g2l, const int* __restrict__ g2_sexp, const void* __restrict__ m,
     const unsigned* __restrict__ m_amax, const float* __restrict__ scale, const unsigned* __restrict__ scale_amax, int C,
     int S, int64_t per8, _Float16* __restrict__ oh, _Float16* __restrict__ ol, int* __restrict__ out_sexp) {
-  float bound = 0.f, inv2 = 0.f;
+  // (the result's scale clamped as exp2i_sat does: what this kernel has always computed)
+  float bound = 0.f;
   if (g) bound += __uint_as_float(g_amax[0]);
-  if (g2h) {
-    const int s2 = g2_sexp[0];
-    bound += exp2i16(15 - s2);  // max|g2| * 2^s2 < 2^15
-    inv2 = exp2i16(-s2);
-  }
-  if (m && MFLOAT && m_amax) bound *= __uint_as_float(m_amax[0]);
-  if (scale) bound *= __uint_as_float(scale_amax[0]);
-  const int so = scale_exp_for16(bound);
-  if (blockIdx.x == 0 && threadIdx.x == 0) out_sexp[0] = so;
-  const float sc_out = exp2i16(so);
+  const VjpScale vs = vjp_bound_scale<true>(bound, g2h != nullptr, g2_sexp, m != nullptr, MFLOAT, m_amax, scale != nullptr, scale_amax);
+  const float sc_out = exp2i_sat(vs.so);
+  if (blockIdx.x == 0 && threadIdx.x == 0) out_sexp[0] = vs.so;
   const int64_t e8 = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e8 >= per8) return;
   float mult[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) mult[j] = sc_out;
   if (m) {
-    if (MFLOAT) {
-      const float4 a = reinterpret_cast<const float4*>(m)[2 * e8], b = reinterpret_cast<const float4*>(m)[2 * e8 + 1];
-      mult[0] *= a.x, mult[1] *= a.y, mult[2] *= a.z, mult[3] *= a.w, mult[4] *= b.x, mult[5] *= b.y, mult[6] *= b.z, mult[7] *= b.w;
-    } else {
-      const uint2 u = reinterpret_cast<const uint2*>(m)[e8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (!((u.x >> (8 * j)) & 0xffu)) mult[j] = 0.f;
-        if (!((u.y >> (8 * j)) & 0xffu)) mult[4 + j] = 0.f;
-      }
-    }
+    if (MFLOAT) vjp_mult8_times(mult, reinterpret_cast<const float*>(m) + 8 * e8);
+    else vjp_mult8_mask(mult, reinterpret_cast<const uint2*>(m)[e8]);
   }
-  if (scale) {
-    const int c0 = (int)((e8 * 8) % C);
-    const float4 a = *reinterpret_cast<const float4*>(scale + c0), b = *reinterpret_cast<const float4*>(scale + c0 + 4);
-    mult[0] *= a.x, mult[1] *= a.y, mult[2] *= a.z, mult[3] *= a.w, mult[4] *= b.x, mult[5] *= b.y, mult[6] *= b.z, mult[7] *= b.w;
-  }
+  if (scale) vjp_mult8_times(mult, scale + (int)((e8 * 8) % C));
 #pragma unroll 2
   for (int s = 0; s < S; ++s) {
     const int64_t i8 = (int64_t)s * per8 + e8;
@@ -81,23 +50,10 @@ __global__ __launch_bounds__(256) void vjp_nhwc_split_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    if (g2h) {
-      const f16x8 h2 = reinterpret_cast<const f16x8*>(g2h)[i8], l2 = reinterpret_cast<const f16x8*>(g2l)[i8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += ((float)h2[j] + (float)l2[j]) * inv2;
-    }
+    if (g2h) vjp_add8(v, reinterpret_cast<const f16x8*>(g2h)[i8], reinterpret_cast<const f16x8*>(g2l)[i8], vs.inv2);
     f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      // The product is made opaque before it is split.  Left to itself hipcc forms the stored h from the fp32-rounded
-      // product but the residual from a fused fp16(v * mult - h') with h' = fp16 of the EXACT product (v_fma_mix); the
-      // two h differ at rounding ties and the pair then misses the value by a whole fp16 ulp.
-      float xs = v[j] * mult[j];
-      asm volatile("" : "+v"(xs));
-      const _Float16 hh = (_Float16)xs;
-      h[j] = hh;
-      l[j] = (_Float16)(xs - (float)hh);
-    }
+    unsigned vmax = 0;  // (not measured here: whoever consumes the planes starts from the guaranteed bound)
+    vjp_chunk8(v, mult, vmax, h, l);
     reinterpret_cast<f16x8*>(oh)[i8] = h;
     reinterpret_cast<f16x8*>(ol)[i8] = l;
   }
@@ -130,12 +86,12 @@ __global__ __launch_bounds__(256) void bn_act_fwd_nhwc_kernel(
   float bound = bx * __uint_as_float(scale_amax[0]) + __uint_as_float(shift_amax[0]);
   if (addend) bound += addend_bound[n < addend_nbound ? n : addend_nbound - 1];
   if (act == 2) bound = 1.f;
-  const int so = scale_exp_for16(bound);
+  const int so = scale_exp_for(bound);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     y_sexp[n] = so;
     y_bound[n] = bound;
   }
-  const float sc_out = exp2i16(so);
+  const float sc_out = exp2i_sat(so);
   unsigned vmax = 0;
   // a workgroup walks BN_ACT_IT x 256 float8s of its image (the header's dependent loads and the atomic below are paid once
   // per 8192 elements: one atomic per 2048 elements — 4096 per launch into the 128 words of a minibatch, i.e. four cache
@@ -171,13 +127,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_nhwc_kernel(
     if (yh) {
       f16x8 h, l;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float xs = v[j] * sc_out;
-        asm volatile("" : "+v"(xs));  // see vjp_nhwc_split_kernel: split an opaque value
-        const _Float16 hh = (_Float16)xs;
-        h[j] = hh;
-        l[j] = (_Float16)(xs - (float)hh);
-      }
+      for (int j = 0; j < 8; ++j) split2_at(v[j] * sc_out, h, l, j);
       reinterpret_cast<f16x8*>(yh)[e8] = h;
       reinterpret_cast<f16x8*>(yl)[e8] = l;
     }
@@ -204,7 +154,7 @@ __global__ __launch_bounds__(256) void unsplit_transpose_kernel(const _Float16* 
   __shared__ float tile[32][33];
   const int n = blockIdx.z, s = n / B, b = n - s * B;
   const int c0 = blockIdx.x * 32, l0 = blockIdx.y * 32;
-  const float inv = exp2i16(-sexp[0]);
+  const float inv = exp2i_sat(-sexp[0]);
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
     const int l = l0 + i, c = c0 + tx;
@@ -281,8 +231,7 @@ __global__ __launch_bounds__(256) void gram16_kernel(const _Float16* __restrict_
     // contiguous range of the table so that the sharing happens inside one L2
     const int nblk = gridDim.x;
     int bid = blockIdx.x;
-    const int q = nblk / 8, r = nblk % 8, x = bid % 8, j = bid / 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
+    bid = xcd_tile_order(bid, nblk);
     colA = tp.tiles[3 * bid], colB = tp.tiles[3 * bid + 1], out_off = tp.tiles[3 * bid + 2];
   } else {
     int p = blockIdx.x;
@@ -445,7 +394,7 @@ __global__ __launch_bounds__(256) void gram16_kernel(const _Float16* __restrict_
     __syncthreads();
     float tscale = 0.f;
     if constexpr (TNP) {
-      const float inv = exp2i16(-tp.sexp[0]);
+      const float inv = exp2i_sat(-tp.sexp[0]);
       tscale = tp.alpha * inv * inv;
     }
 #pragma unroll
@@ -463,7 +412,7 @@ __global__ __launch_bounds__(256) void gram16_kernel(const _Float16* __restrict_
   if (!wave_active) return;
   float tscale = 0.f;
   if constexpr (TNP) {
-    const float inv = exp2i16(-tp.sexp[0]);
+    const float inv = exp2i_sat(-tp.sexp[0]);
     tscale = tp.alpha * inv * inv;
   }
 #pragma unroll
@@ -507,7 +456,7 @@ __global__ __launch_bounds__(256) void gram16_reduce_kernel(const float* __restr
     float t = red[0][el];
 #pragma unroll
     for (int k = 1; k < 8; ++k) t += red[k][el];
-    const float inv = exp2i16(-sexp[0]);
+    const float inv = exp2i_sat(-sexp[0]);
     Gm[(int64_t)(bi * NB + row) * C + bj * NB + col] += alpha * (t * inv) * inv;
   }
 }
@@ -554,7 +503,7 @@ __global__ __launch_bounds__(256) void gram16_reduce4_kernel(const float* __rest
     float4 t = red[0][q];
 #pragma unroll
     for (int k = 1; k < 4; ++k) t.x += red[k][q].x, t.y += red[k][q].y, t.z += red[k][q].z, t.w += red[k][q].w;
-    const float inv = exp2i16(-sexp[0]);
+    const float inv = exp2i_sat(-sexp[0]);
     const float f = alpha * inv * inv;
     float4* dst = reinterpret_cast<float4*>(Gm + (int64_t)(bi * NB + row) * C + bj * NB + col);
     float4 o = *dst;
@@ -737,8 +686,7 @@ __global__ __launch_bounds__(512) void pixpair13_kernel(const Pix13Args p) {
   int q;
   {  // neighbouring pixels share panels: every XCD (block id % 8) takes a contiguous range of pixels
     const int nblk = gridDim.x, bid = blockIdx.x;
-    const int qq = nblk / 8, r = nblk % 8, x = bid % 8, j = bid / 8;
-    q = (x < r ? x * (qq + 1) : r * (qq + 1) + (x - r) * qq) + j;
+    q = xcd_tile_order(bid, nblk);
   }
   // shift h: (dy, dx) = (0, 0 .. 2), (1, -2 .. 2), (2, -2 .. 2) — lk_gram.hip's kHalfDy / kHalfDx
   auto panel_col = [&](int h) {  // first column of the panel of pixel q + shift h (scalar arithmetic: h is uniform)
@@ -827,7 +775,7 @@ __global__ __launch_bounds__(512) void pixpair13_kernel(const Pix13Args p) {
   }
 
   // blocks[slot][row][col] += alpha 2^(-2 sexp) acc: the block is this wave's alone (one workgroup per pixel, one wave per tile)
-  const float inv = exp2i16(-p.sexp[0]);
+  const float inv = exp2i_sat(-p.sexp[0]);
   const float tscale = p.alpha * inv * inv;
   const int lr = lane & 31, lh = lane >> 5;
   // (the old values of FOUR blocks — then three — are requested together: one round trip of memory latency per batch, not per block)
