@@ -20,7 +20,7 @@ stock PyTorch-ROCm kernels — this is host-side plumbing, not a replacement for
 from __future__ import annotations
 
 import operator
-from typing import Any
+from typing import Any, NamedTuple
 
 import torch
 import torch.fx as fx
@@ -32,18 +32,121 @@ class SweepUnsupported(RuntimeError):
     pass
 
 
+# canonical node kinds ("placeholder" / "output" nodes carry their fx op as kind)
+CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM = (
+    "conv", "linear", "batch-norm", "activation", "identity", "reshape", "adaptive-avg-pool", "avg-pool", "max-pool",
+    "mean", "add", "size", "getitem")
+
+
+class Rule(NamedTuple):
+    """What the sweeps know about one traced node, decided once at construction (:func:`classify`)."""
+
+    kind: str
+    src: tuple = ()  # input node(s), where the cotangent goes: one, two for ADD (either may be a constant)
+    fn: Any = None  # evaluates the node: ``fn(*args, **kwargs)`` on the forward values of ``call``
+    call: tuple = ((), {})  # ``(args, kwargs)`` of ``fn`` as fx arguments (nodes and constants)
+    what: str = ""  # the operation as messages name it
+    flavour: str | None = None  # ACT: "relu" | "tanh" | "sigmoid" | "generic"
+    mod: nn.Module | None = None  # CONV / LINEAR / BN: the module
+    args: tuple = ()  # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written
+
+
+# any other element-wise activation: its per-sample derivative is taken ONCE from autograd on the [B, ...]
+# forward value (1/S of the sweep's work) and then applied to all seeds by the same fused kernel
+_GENERIC_ACT_MODULES = (nn.GELU, nn.SiLU, nn.LeakyReLU, nn.ELU, nn.Softplus, nn.Hardtanh, nn.ReLU6, nn.Mish,
+                        nn.Hardswish, nn.Hardsigmoid, nn.SELU, nn.CELU, nn.Softsign, nn.LogSigmoid)
+_GENERIC_ACT_FN = (F.gelu, F.silu, F.leaky_relu, F.elu, F.softplus, F.hardtanh, F.relu6, F.mish, F.hardswish,
+                   F.hardsigmoid, F.selu, F.celu, F.softsign, F.logsigmoid)
+
+# the three spellings of an operation -> (kind, activation flavour); adding an operation starts here
+_MODULE_KINDS = (
+    ((nn.Conv2d,), CONV, None), ((nn.Linear,), LINEAR, None), ((nn.BatchNorm2d, nn.BatchNorm1d), BN, None),
+    ((nn.ReLU,), ACT, "relu"), ((nn.Tanh,), ACT, "tanh"), ((nn.Sigmoid,), ACT, "sigmoid"),
+    (_GENERIC_ACT_MODULES, ACT, "generic"), ((nn.Identity, nn.Dropout), IDENTITY, None), ((nn.Flatten,), RESHAPE, None),
+    ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None))
+_FUNCTION_KINDS = {
+    torch.relu: (ACT, "relu"), F.relu: (ACT, "relu"), torch.tanh: (ACT, "tanh"), F.tanh: (ACT, "tanh"),
+    torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
+    operator.add: (ADD, None), torch.add: (ADD, None), operator.iadd: (ADD, None), torch.flatten: (RESHAPE, None),
+    F.adaptive_avg_pool2d: (GPOOL, None), F.avg_pool2d: (AVGPOOL, None), F.max_pool2d: (MAXPOOL, None),
+    torch.mean: (MEAN, None), operator.getitem: (GETITEM, None)}
+_METHOD_KINDS = {
+    "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
+    "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
+    "size": (SIZE, None)}
+_POOL_PARAMS = {  # names and defaults of the functional form; the modules carry attributes of the same names
+    MAXPOOL: (("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices"), (None, None, 0, 1, False, False)),
+    AVGPOOL: (("kernel_size", "stride", "padding", "ceil_mode", "count_include_pad", "divisor_override"),
+              (None, None, 0, False, True, None))}
+
+
+def _bind(node, names, defaults):
+    """positional / keyword arguments of a functional call -> dict (input excluded)"""
+    vals = dict(zip(names, defaults))
+    for n, a in zip(names, node.args[1:]):
+        vals[n] = a
+    for k, v in node.kwargs.items():
+        if k in vals:
+            vals[k] = v
+    if any(isinstance(v, fx.Node) for v in vals.values()):
+        raise SweepUnsupported("data-dependent pooling arguments")
+    return vals
+
+
+def classify(node: fx.Node, modules: dict) -> Rule:
+    """The :class:`Rule` of a traced node — the one place that tells ``call_module`` / ``call_function`` / ``call_method``
+    apart; whatever has no VJP rule is refused here, so that neither sweep meets it half-way."""
+    if node.op in ("placeholder", "output"):
+        return Rule(node.op)
+    if node.op == "get_attr":
+        raise SweepUnsupported("graph reads attributes directly")
+    m, args, kwargs = None, node.args, dict(node.kwargs)
+    if node.op == "call_module":
+        m = fn = modules[node.target]
+        hit, what = next(((k, fl) for types, k, fl in _MODULE_KINDS if isinstance(m, types)), None), type(m).__name__
+        if isinstance(m, nn.Sequential):
+            raise SweepUnsupported("nested Sequential was not inlined by the tracer")
+        if hit is None:
+            raise SweepUnsupported(f"no VJP rule for module {what} ({node.target})")
+        # (grouped convolutions: forward is the module itself, backward-data `_conv_input_grad`, which passes `groups`)
+        if isinstance(m, nn.Conv2d) and (isinstance(m.padding, str) or m.padding_mode != "zeros"):
+            raise SweepUnsupported(f"{node.target}: unsupported convolution variant")
+    elif node.op == "call_function":
+        fn, hit, what = node.target, _FUNCTION_KINDS.get(node.target), getattr(node.target, "__name__", node.target)
+        if hit is None:
+            raise SweepUnsupported(f"no VJP rule for function {what}")
+    else:
+        hit, what = _METHOD_KINDS.get(node.target), f"method {node.target}"
+        if hit is None:
+            raise SweepUnsupported(f"no VJP rule for method {node.target}")
+        fn = getattr(torch.Tensor, node.target)
+    kind, flavour = hit
+    src, static = tuple(args[:1]), ()
+    if kind == ADD:
+        if kwargs.get("alpha", 1) != 1:
+            raise SweepUnsupported("add with alpha")
+        src, fn = tuple(args[:2]), operator.add if fn is operator.iadd else fn  # (`+=` must not write into a kept tensor)
+    elif flavour == "generic":
+        kwargs.pop("inplace", None)  # (the derivative is taken by autograd on a leaf)
+    elif kind in _POOL_PARAMS:
+        names, defaults = _POOL_PARAMS[kind]
+        p = {n: getattr(m, n) for n in names} if m is not None else _bind(node, names, defaults)
+        if p.pop("return_indices", False):
+            raise SweepUnsupported("max_pool2d(return_indices=True)")
+        if kind == MAXPOOL:  # always evaluated with indices: they are what its VJP scatters by
+            fn, args, kwargs = F.max_pool2d, (args[0], *p.values(), True), {}
+        else:
+            static = tuple(p.values())
+    elif kind == GPOOL:
+        static = (m.output_size if m is not None else kwargs.get("output_size", args[1] if len(args) > 1 else None),)
+    elif kind == MEAN:
+        static = (kwargs.get("dim", args[1] if len(args) > 1 else None),
+                  kwargs.get("keepdim", args[2] if len(args) > 2 else False))
+    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN) else None, static)
+
+
 class SeedBatchedSweep:
     """Forward + seed-batched reverse sweep over an fx-traced module."""
-
-    _ELEMENTWISE_FN = {torch.relu, F.relu, torch.tanh, F.tanh, torch.sigmoid, F.sigmoid}
-    # any other element-wise activation: its per-sample derivative is taken ONCE from autograd on the [B, ...]
-    # forward value (1/S of the sweep's work) and then applied to all seeds by the same fused kernel
-    _GENERIC_ACT_MODULES = (nn.GELU, nn.SiLU, nn.LeakyReLU, nn.ELU, nn.Softplus, nn.Hardtanh, nn.ReLU6, nn.Mish,
-                            nn.Hardswish, nn.Hardsigmoid, nn.SELU, nn.CELU, nn.Softsign, nn.LogSigmoid)
-    _GENERIC_ACT_FN = {F.gelu, F.silu, F.leaky_relu, F.elu, F.softplus, F.hardtanh, F.relu6, F.mish, F.hardswish,
-                       F.hardsigmoid, F.selu, F.celu, F.softsign, F.logsigmoid}
-
-    _POOL_FN = {F.max_pool2d, F.avg_pool2d, F.adaptive_avg_pool2d}
 
     @staticmethod
     def _with_derivative(fn, inp):
@@ -67,40 +170,15 @@ class SeedBatchedSweep:
             raise SweepUnsupported(f"torch.fx cannot trace the model: {e}") from e
         self.modules = dict(self.gm.named_modules())
         self.tap_names = set(tap_modules)
-        self._check_graph()
-
-    # ---- static checks -------------------------------------------------------------------------------
-    def _check_graph(self):
-        n_inputs = 0
-        for node in self.gm.graph.nodes:
-            if node.op == "placeholder":
-                n_inputs += 1
-            elif node.op == "call_module":
-                m = self.modules[node.target]
-                if isinstance(m, self._GENERIC_ACT_MODULES):
-                    continue
-                if not isinstance(m, (nn.Conv2d, nn.Linear, nn.BatchNorm2d, nn.BatchNorm1d, nn.ReLU, nn.Tanh,
-                                      nn.Sigmoid, nn.Identity, nn.Dropout, nn.Flatten, nn.AdaptiveAvgPool2d,
-                                      nn.MaxPool2d, nn.AvgPool2d, nn.Sequential)):
-                    raise SweepUnsupported(f"no VJP rule for module {type(m).__name__} ({node.target})")
-                # (grouped convolutions: forward is the module itself, backward-data `_conv_input_grad`, which passes `groups`)
-                if isinstance(m, nn.Conv2d) and (isinstance(m.padding, str) or m.padding_mode != "zeros"):
-                    raise SweepUnsupported(f"{node.target}: unsupported convolution variant")
-            elif node.op == "call_function":
-                if node.target not in (self._ELEMENTWISE_FN | self._GENERIC_ACT_FN | self._POOL_FN
-                                       | {operator.add, torch.add, torch.flatten, operator.iadd, operator.getitem,
-                                          torch.mean}):
-                    raise SweepUnsupported(f"no VJP rule for function {getattr(node.target, '__name__', node.target)}")
-                if node.target in (operator.add, torch.add, operator.iadd) and node.kwargs.get("alpha", 1) != 1:
-                    raise SweepUnsupported("add with alpha")  # (checked here: backward() must not fail half-way)
-            elif node.op == "call_method":
-                if node.target not in ("view", "reshape", "flatten", "relu", "tanh", "sigmoid", "contiguous", "size",
-                                       "mean"):
-                    raise SweepUnsupported(f"no VJP rule for method {node.target}")
-            elif node.op == "get_attr":
-                raise SweepUnsupported("graph reads attributes directly")
-        if n_inputs != 1:
+        #: node -> :class:`Rule`, in graph order (the graph does not change after tracing)
+        self.rule: dict[fx.Node, Rule] = {node: classify(node, self.modules) for node in self.gm.graph.nodes}
+        if sum(r.kind == "placeholder" for r in self.rule.values()) != 1:
             raise SweepUnsupported("models with one tensor input only")
+        self.out_node = next(reversed(self.rule)).args[0]
+        if not isinstance(self.out_node, fx.Node):
+            raise SweepUnsupported("model must return a single tensor")
+        # the modules whose VJP rules assume eval mode
+        self._mode_mods = [m for m in self.gm.modules() if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d, nn.Dropout))]
 
     # ---- forward ---------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -108,127 +186,73 @@ class SeedBatchedSweep:
         """Returns ``f``; fills ``self.saved`` (per node: what the VJP needs) and ``self.taps[name]['a']``.
         ``need_vjp=False``: inference only (the feature pass of the last-layer flavours) — nothing is kept for a
         reverse sweep, only the tapped inputs."""
-        mode_mods = self.__dict__.get("_mode_mods")
-        if mode_mods is None:  # (the modules whose VJP rules assume eval mode; the graph does not change after tracing)
-            mode_mods = self._mode_mods = [m for m in self.gm.modules() if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d, nn.Dropout))]
-        if self.gm.training or any(m.training for m in mode_mods):
+        if self.gm.training or any(m.training for m in self._mode_mods):
             raise SweepUnsupported("model must be in eval mode (BatchNorm / Dropout VJPs assume it)")
         env: dict[fx.Node, Any] = {}
         self.saved: dict[fx.Node, Any] = {}
         self.taps: dict[str, dict] = {}
-        self.out_node = None
         fused_relu: dict[fx.Node, tuple] = {}  # ReLU node -> (output, mask) already produced by the BatchNorm kernel
         self.max_act_numel = 1  # largest per-sample activation: bounds the memory of a seed-batched cotangent
-        for node in self.gm.graph.nodes:
+        for node, r in self.rule.items():
             if node in fused_relu:
                 env[node], keep = fused_relu.pop(node)
                 if keep is not None:
                     self.saved[node] = keep
                 continue
-            if node.op == "placeholder":
+            kind = r.kind
+            if kind == "placeholder":
                 env[node] = x
-            elif node.op == "output":
-                self.out_node = node.args[0]
-                if not isinstance(self.out_node, fx.Node):
-                    raise SweepUnsupported("model must return a single tensor")
-            elif node.op == "call_module":
-                m = self.modules[node.target]
-                inp = env[node.args[0]]
-                if isinstance(m, nn.MaxPool2d):
-                    out, idx = F.max_pool2d(inp, m.kernel_size, m.stride, m.padding, m.dilation, m.ceil_mode, True)
-                    self.saved[node] = (idx, inp.shape)
-                elif isinstance(m, self._GENERIC_ACT_MODULES):
-                    out, self.saved[node] = self._with_derivative(m, inp) if need_vjp else (m(inp), None)
-                elif (isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)) and self.kernels is not None and inp.dim() >= 2
-                      and inp.dtype == torch.float32 and m.running_var is not None):
-                    # eval-mode BatchNorm = per-channel affine map: one fused launch, with the ReLU that follows it
-                    # (and the mask its VJP needs) when the BatchNorm output has no other consumer
-                    scale, shift = self._bn_scale(node.target, m), self._bn_shift(node.target, m)
-                    nxt = next(iter(node.users)) if len(node.users) == 1 else None
-                    addend, add_node = None, None
-                    if nxt is not None and self._is_plain_add(nxt):
-                        # residual join `bn(..) + other`: folded in when the other branch is already available
-                        other = nxt.args[1] if nxt.args[0] is node else nxt.args[0]
-                        if isinstance(other, fx.Node) and other in env and torch.is_tensor(env[other]) \
-                                and env[other].shape == inp.shape and env[other].dtype == inp.dtype:
-                            addend, add_node = env[other], nxt
-                            nxt = next(iter(add_node.users)) if len(add_node.users) == 1 else None
-                    relu = nxt is not None and self._is_plain_relu(nxt) and nxt.args[0] is (add_node or node)
-                    self._group_out_node = nxt if relu else (add_node or node)  # (whose users read this launch's output)
-                    out, mask = self._run_bn_act(node, inp, scale, shift, relu, addend, need_vjp)
-                    if add_node is not None:
-                        fused_relu[add_node] = (out, None)  # (the add node itself keeps nothing for its VJP)
-                    if relu:
-                        fused_relu[nxt] = (out, mask)
-                else:
-                    out = self._run_conv(node, m, inp) if isinstance(m, nn.Conv2d) else m(inp)
-                    if isinstance(m, (nn.ReLU,)):
-                        self.saved[node] = (out > 0) if need_vjp else None
-                    elif isinstance(m, (nn.Tanh, nn.Sigmoid)):
-                        self.saved[node] = out
-                    elif isinstance(m, (nn.AdaptiveAvgPool2d, nn.AvgPool2d, nn.Flatten)):
-                        self.saved[node] = inp.shape
-                    elif isinstance(m, nn.Conv2d):
-                        self.saved[node] = inp.shape
-                if node.target in self.tap_names:
-                    if node.target in self.taps:
-                        raise SweepUnsupported(f"{node.target}: module is applied more than once per forward")
-                    self.taps[node.target] = {"a": inp, "node": node}
-                env[node] = out
-            elif node.op == "call_function":
-                args = list(fx.node.map_arg(node.args, lambda n: env[n]))
-                kwargs = dict(fx.node.map_arg(node.kwargs, lambda n: env[n]))
-                if node.target is operator.getitem and torch.is_tensor(args[0]):
-                    raise SweepUnsupported("tensor indexing")
-                if node.target is F.max_pool2d:
-                    p = self._bind(node, ("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices"),
-                                   (None, None, 0, 1, False, False))
-                    if p["return_indices"]:
-                        raise SweepUnsupported("max_pool2d(return_indices=True)")
-                    out, idx = F.max_pool2d(args[0], p["kernel_size"], p["stride"], p["padding"], p["dilation"],
-                                            p["ceil_mode"], True)
-                    self.saved[node] = (idx, args[0].shape)
-                    env[node] = out
-                    continue
-                if node.target in (F.avg_pool2d, F.adaptive_avg_pool2d):
-                    self.saved[node] = args[0].shape
-                if node.target is torch.mean:
-                    dim = kwargs.get("dim", args[1] if len(args) > 1 else None)
-                    self.saved[node] = (args[0].shape, bool(kwargs.get("keepdim", args[2] if len(args) > 2 else False)),
-                                        self._mean_dims(dim, args[0].dim()))
-                if node.target is operator.iadd:
-                    out = args[0] + args[1]
-                elif node.target in self._GENERIC_ACT_FN:
-                    kwargs.pop("inplace", None)
-                    if need_vjp:
-                        out, self.saved[node] = self._with_derivative(lambda t: node.target(t, *args[1:], **kwargs), args[0])
-                    else:
-                        out = node.target(*args, **kwargs)
-                else:
-                    out = node.target(*args, **kwargs)
-                if node.target in (torch.relu, F.relu):
-                    self.saved[node] = (out > 0) if need_vjp else None
-                elif node.target in (torch.tanh, F.tanh, torch.sigmoid, F.sigmoid):
-                    self.saved[node] = out
-                elif node.target is torch.flatten:
-                    self.saved[node] = args[0].shape
-                env[node] = out
-            elif node.op == "call_method":
-                self_t = env[node.args[0]]
-                args = list(fx.node.map_arg(node.args[1:], lambda n: env[n]))
-                kwargs = dict(fx.node.map_arg(node.kwargs, lambda n: env[n]))
-                out = getattr(self_t, node.target)(*args, **kwargs)
-                if node.target == "mean":
-                    dim = kwargs.get("dim", args[0] if args else None)
-                    self.saved[node] = (self_t.shape, bool(kwargs.get("keepdim", args[1] if len(args) > 1 else False)),
-                                        self._mean_dims(dim, self_t.dim()))
-                if node.target == "relu":
-                    self.saved[node] = (out > 0) if need_vjp else None
-                elif node.target in ("tanh", "sigmoid"):
-                    self.saved[node] = out
-                elif node.target in ("view", "reshape", "flatten"):
-                    self.saved[node] = self_t.shape
-                env[node] = out
+                continue
+            if kind == "output":
+                continue
+            args, kwargs = fx.node.map_arg(r.call, env.__getitem__)
+            inp, keep = args[0], None  # (keep: what the node's VJP needs)
+            if (kind == BN and self.kernels is not None and inp.dim() >= 2 and inp.dtype == torch.float32
+                    and r.mod.running_var is not None):
+                # eval-mode BatchNorm = per-channel affine map: one fused launch, with the ReLU that follows it
+                # (and the mask its VJP needs) when the BatchNorm output has no other consumer
+                scale, shift = self._bn_scale(node.target, r.mod), self._bn_shift(node.target, r.mod)
+                nxt = next(iter(node.users)) if len(node.users) == 1 else None
+                addend, add_node = None, None
+                if nxt is not None and self.rule[nxt].kind == ADD and all(isinstance(a, fx.Node) for a in nxt.args):
+                    # residual join `bn(..) + other`: folded in when the other branch is already available
+                    other = nxt.args[1] if nxt.args[0] is node else nxt.args[0]
+                    if other in env and torch.is_tensor(env[other]) \
+                            and env[other].shape == inp.shape and env[other].dtype == inp.dtype:
+                        addend, add_node = env[other], nxt
+                        nxt = next(iter(add_node.users)) if len(add_node.users) == 1 else None
+                relu = nxt is not None and self.rule[nxt].flavour == "relu" and nxt.args[0] is (add_node or node)
+                self._group_out_node = nxt if relu else (add_node or node)  # (whose users read this launch's output)
+                out, mask = self._run_bn_act(node, inp, scale, shift, relu, addend, need_vjp)
+                if add_node is not None:
+                    fused_relu[add_node] = (out, None)  # (the add node itself keeps nothing for its VJP)
+                if relu:
+                    fused_relu[nxt] = (out, mask)
+            elif kind == CONV:
+                out, keep = self._run_conv(node, r.mod, inp), inp.shape
+            elif kind == MAXPOOL:
+                out, idx = r.fn(*args)
+                keep = (idx, inp.shape)
+            elif r.flavour == "generic" and need_vjp:
+                out, keep = self._with_derivative(lambda t: r.fn(t, *args[1:], **kwargs), inp)
+            elif kind == GETITEM and torch.is_tensor(inp):
+                raise SweepUnsupported("tensor indexing")
+            else:
+                out = r.fn(*args, **kwargs)
+                if kind == ACT and need_vjp:  # (tanh / sigmoid: the derivative is a function of the value)
+                    keep = (out > 0) if r.flavour == "relu" else out
+                elif kind in (RESHAPE, GPOOL, AVGPOOL):
+                    keep = inp.shape
+                elif kind == MEAN:
+                    dim, keepdim = fx.node.map_arg(r.args, env.__getitem__)
+                    keep = (inp.shape, bool(keepdim), self._mean_dims(dim, inp.dim()))
+            if keep is not None:
+                self.saved[node] = keep
+            if r.mod is not None and node.target in self.tap_names:
+                if node.target in self.taps:
+                    raise SweepUnsupported(f"{node.target}: module is applied more than once per forward")
+                self.taps[node.target] = {"a": inp, "node": node}
+            env[node] = out
         if not need_vjp:
             self.saved = {}
         nb = max(int(x.shape[0]), 1)
@@ -251,24 +275,11 @@ class SeedBatchedSweep:
                                              None if addend is None else addend.contiguous(), want_mask=want_mask)
 
     @staticmethod
-    def _bind(node, names, defaults):
-        """positional / keyword arguments of a functional call -> dict (input excluded)"""
-        vals = dict(zip(names, defaults))
-        for n, a in zip(names, node.args[1:]):
-            vals[n] = a
-        for k, v in node.kwargs.items():
-            if k in vals:
-                vals[k] = v
-        if any(isinstance(v, fx.Node) for v in vals.values()):
-            raise SweepUnsupported("data-dependent pooling arguments")
-        return vals
-
-    @staticmethod
     def _pair2(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
     @staticmethod
-    def _avgpool_vjp(g, in_shape, kernel, stride, padding, SB, ceil_mode=False, count_include_pad=True,
+    def _avgpool_vjp(g, in_shape, SB, kernel, stride, padding, ceil_mode=False, count_include_pad=True,
                      divisor_override=None):
         """VJP of ``avg_pool2d`` for the whole seed batch: non-overlapping, unpadded windows that tile the input are an
         upsampling; every other geometry (padding, overlap, ragged edges, ceil_mode) goes through the pooling
@@ -350,13 +361,6 @@ class SeedBatchedSweep:
             self._bn_cache[name] = hit
         return hit[1]
 
-    def _is_activation(self, node) -> bool:
-        if node.op == "call_module":
-            return isinstance(self.modules[node.target], (nn.ReLU, nn.Tanh, nn.Sigmoid) + self._GENERIC_ACT_MODULES)
-        if node.op == "call_function":
-            return node.target in self._ELEMENTWISE_FN or node.target in self._GENERIC_ACT_FN
-        return node.op == "call_method" and node.target in ("relu", "tanh", "sigmoid")
-
     def _bn_shift(self, name: str, m) -> torch.Tensor:
         """beta - running_mean * scale (cached like the scale)"""
         key = (m.running_mean._version, m.running_var._version, None if m.weight is None else m.weight._version,
@@ -369,18 +373,6 @@ class SeedBatchedSweep:
             hit = (key, shift)
             self._bn_cache[name + "/shift"] = hit
         return hit[1]
-
-    @staticmethod
-    def _is_plain_add(node) -> bool:
-        return (node.op == "call_function" and node.target in (operator.add, torch.add, operator.iadd) and len(node.args) == 2
-                and all(isinstance(a, fx.Node) for a in node.args) and node.kwargs.get("alpha", 1) == 1)
-
-    def _is_plain_relu(self, node) -> bool:
-        if node.op == "call_module":
-            return isinstance(self.modules[node.target], nn.ReLU)
-        if node.op == "call_function":
-            return node.target in (torch.relu, F.relu)
-        return node.op == "call_method" and node.target == "relu"
 
     def _scale_mask(self, g, S, mult, scale, g2=None):
         """``(g[s] + g2[s]) * mult * scale[channel]`` for all seeds (``g``: [S*B, C, ...], ``mult``: [B, C, ...])."""
@@ -399,27 +391,31 @@ class SeedBatchedSweep:
             out = out * scale.reshape((1, -1) + (1,) * (g.dim() - 2))
         return out
 
-    @classmethod
-    def _act_mult(cls, kind, saved):
-        """per-sample derivative of the activation from what the forward kept (ReLU: the mask itself)"""
-        if isinstance(kind, cls._GENERIC_ACT_MODULES) or (callable(kind) and kind in cls._GENERIC_ACT_FN):
-            return saved  # the derivative itself
-        if kind in (torch.relu, F.relu, "relu") or isinstance(kind, nn.ReLU):
-            return saved
-        if kind in (torch.tanh, F.tanh, "tanh") or isinstance(kind, nn.Tanh):
+    @staticmethod
+    def _act_mult(flavour, saved):
+        """per-sample derivative of the activation from what the forward kept (ReLU: the mask; generic: the derivative)"""
+        if flavour == "tanh":
             return 1 - saved * saved
-        return saved * (1 - saved)  # sigmoid
+        if flavour == "sigmoid":
+            return saved * (1 - saved)
+        return saved
 
     def _fold_bn(self, src):
         """If the activation's input is an eval-mode BatchNorm used only by it, its scale folds into the
         activation's VJP: returns (scale, node to push the cotangent to)."""
-        if (isinstance(src, fx.Node) and src.op == "call_module" and len(src.users) == 1
-                and isinstance(self.modules[src.target], (nn.BatchNorm2d, nn.BatchNorm1d))
-                and src.target not in self.tap_names):
-            return self._bn_scale(src.target, self.modules[src.target]), src.args[0]
+        r = self.rule.get(src)
+        if r is not None and r.kind == BN and len(src.users) == 1 and src.target not in self.tap_names:
+            return self._bn_scale(src.target, r.mod), r.src[0]
         # (a TAPPED BatchNorm must see ``act'(.) * g``, the cotangent of its own output, before its scale is applied:
         # the activation hands it over unscaled and the BatchNorm rule of `backward` multiplies afterwards)
         return None, src
+
+    def _defers_scale_to(self, src, cot) -> bool:
+        """may the BatchNorm reading ``src`` leave its scale to it (`backward`, ``defer_bn_scale``)?  A tapped convolution
+        that feeds only this BatchNorm and has no cotangent yet."""
+        r = self.rule.get(src)
+        return (r is not None and r.kind == CONV and len(src.users) == 1 and src.target in self.tap_names
+                and src not in cot)
 
     # ---- reverse sweep -----------------------------------------------------------------------------------
     @torch.no_grad()
@@ -449,95 +445,57 @@ class SeedBatchedSweep:
                 return
             cot.setdefault(n, []).append(g)
 
-        for node in reversed(list(self.gm.graph.nodes)):
-            if node not in cot or node.op in ("placeholder", "output"):
+        for node, r in reversed(self.rule.items()):
+            if node not in cot:
                 continue
             parts, g2 = cot.pop(node), None
             g = parts[0]
             if len(parts) > 1:
-                if self._is_activation(node):
+                if r.kind == ACT:
                     g2 = parts[1] if len(parts) == 2 else sum(parts[2:], parts[1])
                 else:
                     g = sum(parts[1:], parts[0])
-            if node.op == "call_module":
-                m = self.modules[node.target]
-                if node.target in self.tap_names:
-                    grads[node.target] = g.reshape(S, B, *g.shape[1:])
-                    if node in pending_scale:
-                        self.grad_scale[node.target] = pending_scale[node]
-                    if on_tap is not None:
-                        on_tap(node.target, grads[node.target])
-                    remaining.discard(node.target)
-                    if not remaining:
-                        break  # nothing upstream of the first tapped module is needed
-                src = node.args[0]
-                if isinstance(m, nn.Conv2d):
-                    in_shape = (S * B,) + tuple(self.saved[node][1:])
-                    push(src, self._conv_input_grad(in_shape, m, g, self._scaled_weight(node.target, m, pending_scale.get(node))))
-                elif isinstance(m, nn.Linear):
-                    push(src, g @ m.weight)
-                elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
-                    scale = self._bn_scale(node.target, m)
-                    if (defer_bn_scale and isinstance(src, fx.Node) and src.op == "call_module" and len(src.users) == 1
-                            and isinstance(self.modules[src.target], nn.Conv2d) and src.target in self.tap_names
-                            and src not in cot):
-                        pending_scale[src] = scale  # the conv sees the unscaled cotangent (see the docstring)
-                        push(src, g)
-                    else:
-                        push(src, self._scale_mask(g, S, None, scale))
-                elif isinstance(m, (nn.ReLU, nn.Tanh, nn.Sigmoid) + self._GENERIC_ACT_MODULES):
-                    scale, dst = self._fold_bn(src)
-                    push(dst, self._scale_mask(g, S, self._act_mult(m, self.saved[node]), scale, g2))
-                elif isinstance(m, (nn.Identity, nn.Dropout)):
+            kind, m, src = r.kind, r.mod, r.src[0]
+            if m is not None and node.target in self.tap_names:
+                grads[node.target] = g.reshape(S, B, *g.shape[1:])
+                if node in pending_scale:
+                    self.grad_scale[node.target] = pending_scale[node]
+                if on_tap is not None:
+                    on_tap(node.target, grads[node.target])
+                remaining.discard(node.target)
+                if not remaining:
+                    break  # nothing upstream of the first tapped module is needed
+            if kind == CONV:
+                in_shape = (S * B,) + tuple(self.saved[node][1:])
+                push(src, self._conv_input_grad(in_shape, m, g, self._scaled_weight(node.target, m, pending_scale.get(node))))
+            elif kind == LINEAR:
+                push(src, g @ m.weight)
+            elif kind == BN:
+                scale = self._bn_scale(node.target, m)
+                if defer_bn_scale and self._defers_scale_to(src, cot):
+                    pending_scale[src] = scale  # the conv sees the unscaled cotangent (see the docstring)
                     push(src, g)
-                elif isinstance(m, nn.Flatten):
-                    push(src, g.reshape((S * B,) + tuple(self.saved[node][1:])))
-                elif isinstance(m, nn.AdaptiveAvgPool2d):
-                    push(src, self._adaptive_avgpool_vjp(g, self.saved[node], S * B))
-                elif isinstance(m, nn.AvgPool2d):
-                    push(src, self._avgpool_vjp(g, self.saved[node], m.kernel_size, m.stride, m.padding, S * B,
-                                                m.ceil_mode, m.count_include_pad, m.divisor_override))
-                elif isinstance(m, nn.MaxPool2d):
-                    idx, shp = self.saved[node]
-                    push(src, self._maxpool_vjp(g, idx, shp, S, B))
-                elif isinstance(m, nn.Sequential):
-                    raise SweepUnsupported("nested Sequential was not inlined by the tracer")
-            elif node.op == "call_function":
-                t = node.target
-                if t in (operator.add, torch.add, operator.iadd):
-                    if node.kwargs.get("alpha", 1) != 1:
-                        raise SweepUnsupported("add with alpha")
-                    for a in node.args[:2]:
-                        push(a, g)
-                elif t in self._ELEMENTWISE_FN or t in self._GENERIC_ACT_FN:
-                    scale, dst = self._fold_bn(node.args[0])
-                    push(dst, self._scale_mask(g, S, self._act_mult(t, self.saved[node]), scale, g2))
-                elif t is torch.flatten:
-                    push(node.args[0], g.reshape((S * B,) + tuple(self.saved[node][1:])))
-                elif t is F.max_pool2d:
-                    idx, shp = self.saved[node]
-                    push(node.args[0], self._maxpool_vjp(g, idx, shp, S, B))
-                elif t is F.avg_pool2d:
-                    p = self._bind(node, ("kernel_size", "stride", "padding", "ceil_mode", "count_include_pad",
-                                          "divisor_override"), (None, None, 0, False, True, None))
-                    push(node.args[0], self._avgpool_vjp(g, self.saved[node], p["kernel_size"], p["stride"], p["padding"],
-                                                         S * B, p["ceil_mode"], p["count_include_pad"],
-                                                         p["divisor_override"]))
-                elif t is F.adaptive_avg_pool2d:
-                    push(node.args[0], self._adaptive_avgpool_vjp(g, self.saved[node], S * B))
-                elif t is torch.mean:
-                    push(node.args[0], self._mean_vjp(g, self.saved[node], S * B))
-            elif node.op == "call_method":
-                t = node.target
-                if t in ("relu", "tanh", "sigmoid"):
-                    scale, dst = self._fold_bn(node.args[0])
-                    push(dst, self._scale_mask(g, S, self._act_mult(t, self.saved[node]), scale, g2))
-                elif t in ("view", "reshape", "flatten"):
-                    push(node.args[0], g.reshape((S * B,) + tuple(self.saved[node][1:])))
-                elif t == "contiguous":
-                    push(node.args[0], g)
-                elif t == "mean":
-                    push(node.args[0], self._mean_vjp(g, self.saved[node], S * B))
+                else:
+                    push(src, self._scale_mask(g, S, None, scale))
+            elif kind == ACT:
+                scale, dst = self._fold_bn(src)
+                push(dst, self._scale_mask(g, S, self._act_mult(r.flavour, self.saved[node]), scale, g2))
+            elif kind == IDENTITY:
+                push(src, g)
+            elif kind == RESHAPE:
+                push(src, g.reshape((S * B,) + tuple(self.saved[node][1:])))
+            elif kind == GPOOL:
+                push(src, self._adaptive_avgpool_vjp(g, self.saved[node], S * B))
+            elif kind == AVGPOOL:
+                push(src, self._avgpool_vjp(g, self.saved[node], S * B, *r.args))
+            elif kind == MAXPOOL:
+                idx, shp = self.saved[node]
+                push(src, self._maxpool_vjp(g, idx, shp, S, B))
+            elif kind == MEAN:
+                push(src, self._mean_vjp(g, self.saved[node], S * B))
+            elif kind == ADD:
+                for a in r.src:
+                    push(a, g)
         if remaining:
             raise SweepUnsupported(f"no cotangent reached {sorted(remaining)}")
         return grads

@@ -18,19 +18,22 @@ are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
 
-import operator
-import os
-
 import weakref
 
 import torch
 import torch.fx as fx
-import torch.nn.functional as F
 from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
-from laplace_amd.sweep import SeedBatchedSweep, SweepUnsupported
+from laplace_amd.sweep import (ACT, ADD, AVGPOOL, BN, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, RESHAPE, SIZE,
+                               SeedBatchedSweep, SweepUnsupported)
+
+# node kinds by what the NHWC walk does with them
+_LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
+_PASS_THROUGH = {ACT, IDENTITY, ADD}  # shape-preserving: the cotangent keeps the representation it arrives in
+_FEATURE = {CONV, BN, GPOOL}  # produce / consume NHWC feature maps
+_NO_RULE = {MAXPOOL, AVGPOOL, MEAN, SIZE, GETITEM}  # a graph with one of these runs through the NCHW sweep
 
 
 class _F32:
@@ -137,18 +140,6 @@ class SplitSweep(SeedBatchedSweep):
     #: residue class and branch) instead of the strided fused launch
     fuse_strided = True
 
-    def _consumes_lazily(self, node) -> bool:
-        """nodes whose rule hands all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)"""
-        if node.op == "call_module":
-            m = self.modules[node.target]
-            return isinstance(m, (nn.Conv2d, nn.BatchNorm2d, nn.ReLU, nn.Tanh, nn.Sigmoid, nn.Identity, nn.Dropout)
-                              + self._GENERIC_ACT_MODULES)
-        if node.op == "call_function":
-            return node.target in self._ELEMENTWISE_FN or node.target in self._GENERIC_ACT_FN
-        if node.op == "call_method":
-            return node.target in ("relu", "tanh", "sigmoid", "contiguous")
-        return False
-
     # ---- static eligibility ---------------------------------------------------------------------------------------
     def _split_eligible(self):
         for name in sorted(self.tap_names):
@@ -158,26 +149,18 @@ class SplitSweep(SeedBatchedSweep):
         if self.kernels is None or not hasattr(self.kernels(), "conv_nhwc_f16x2"):
             return "kernels without the split-fp16 convolution"
         n_conv = 0
-        for node in self.gm.graph.nodes:
-            if node.op == "call_module":
-                m = self.modules[node.target]
-                if isinstance(m, nn.Conv2d):
-                    src = node.args[0]
-                    first = isinstance(src, fx.Node) and src.op == "placeholder"
-                    if m.groups != 1:
-                        return f"{node.target}: grouped convolution (foreign to the NHWC kernels; the NCHW sweep serves it)"
-                    if not cv.supported(m) and not (first and node.target in self.tap_names and m.out_channels % 8 == 0):
-                        return f"{node.target}: convolution outside the implicit-GEMM kernel's coverage"
-                    n_conv += 1
-                elif isinstance(m, (nn.MaxPool2d, nn.AvgPool2d, nn.BatchNorm1d)):
-                    return f"{node.target}: {type(m).__name__} has no NHWC rule"
-                elif isinstance(m, nn.AdaptiveAvgPool2d) and tuple(self._pair2(m.output_size)) != (1, 1):
-                    return f"{node.target}: adaptive pooling to more than one cell"
-            elif node.op == "call_function":
-                if node.target in (F.max_pool2d, F.avg_pool2d, torch.mean, operator.getitem):
-                    return f"{getattr(node.target, '__name__', node.target)} has no NHWC rule"
-            elif node.op == "call_method" and node.target in ("mean", "size"):
-                return f"method {node.target} has no NHWC rule"
+        for node, r in self.rule.items():
+            if r.kind == CONV:
+                m, first = r.mod, r.src[0].op == "placeholder"
+                if m.groups != 1:
+                    return f"{node.target}: grouped convolution (foreign to the NHWC kernels; the NCHW sweep serves it)"
+                if not cv.supported(m) and not (first and node.target in self.tap_names and m.out_channels % 8 == 0):
+                    return f"{node.target}: convolution outside the implicit-GEMM kernel's coverage"
+                n_conv += 1
+            elif r.kind in _NO_RULE or isinstance(r.mod, nn.BatchNorm1d):
+                return (f"{node.target}: " if node.op == "call_module" else "") + f"{r.what} has no NHWC rule"
+            elif r.kind == GPOOL and tuple(self._pair2(r.args[0])) != (1, 1):
+                return f"{node.target if node.op == 'call_module' else node.name}: adaptive pooling to more than one cell"
         if not n_conv:
             return "no convolution in the graph"
         return self._region_check()
@@ -185,61 +168,31 @@ class SplitSweep(SeedBatchedSweep):
     # The reverse sweep must not fail half-way (`on_tap` has already added G factors by then): every structural
     # condition `backward` would raise on is checked here, on the graph alone, so that such a model runs through the
     # parent class's NCHW sweep from the start.
-    def _is_reshape(self, node) -> bool:
-        if node.op == "call_module":
-            return isinstance(self.modules[node.target], nn.Flatten)
-        if node.op == "call_function":
-            return node.target is torch.flatten
-        return node.op == "call_method" and node.target in ("view", "reshape", "flatten")
-
-    def _is_global_pool(self, node) -> bool:
-        if node.op == "call_module":
-            return isinstance(self.modules[node.target], nn.AdaptiveAvgPool2d)
-        return node.op == "call_function" and node.target is F.adaptive_avg_pool2d
-
-    def _is_feature_op(self, node) -> bool:
-        """produces / consumes NHWC feature maps"""
-        if node.op == "call_module" and isinstance(self.modules[node.target], (nn.Conv2d, nn.BatchNorm2d)):
-            return True
-        return self._is_global_pool(node)
-
-    def _passes_through(self, node) -> bool:
-        """shape-preserving nodes: the cotangent keeps the representation it arrives in"""
-        if node.op == "call_module":
-            return isinstance(self.modules[node.target], (nn.ReLU, nn.Tanh, nn.Sigmoid, nn.Identity, nn.Dropout)
-                              + self._GENERIC_ACT_MODULES)
-        if node.op == "call_function":
-            return (node.target in self._ELEMENTWISE_FN or node.target in self._GENERIC_ACT_FN
-                    or node.target in (operator.add, torch.add, operator.iadd))
-        return node.op == "call_method" and node.target in ("relu", "tanh", "sigmoid", "contiguous")
-
     def _walk(self, start, downstream: bool):
-        """nodes reachable from ``start`` through shape-preserving nodes (users if ``downstream`` else inputs)"""
+        """kinds of the nodes reachable from ``start`` through shape-preserving nodes (users if ``downstream`` else inputs)"""
         seen, todo, out = set(), [start], []
         while todo:
             n = todo.pop()
-            nxt = list(n.users) if downstream else [a for a in n.all_input_nodes]
-            for m in nxt:
+            for m in (n.users if downstream else n.all_input_nodes):
                 if m in seen:
                     continue
                 seen.add(m)
-                out.append(m)
-                if self._passes_through(m):
+                kind = self.rule[m].kind
+                out.append(kind)
+                if kind in _PASS_THROUGH:
                     todo.append(m)
         return out
 
     def _region_check(self):
-        for node in self.gm.graph.nodes:
-            if self._is_reshape(node) and any(self._is_feature_op(u) for u in self._walk(node, True)):
+        for node, r in self.rule.items():
+            if r.kind == RESHAPE and any(k in _FEATURE for k in self._walk(node, True)):
                 return f"{node.name}: view / reshape / flatten whose result is used as a feature map"
-            if self._is_global_pool(node):
+            if r.kind == GPOOL:
                 users = list(node.users)
-                if len(users) != 1 or not self._is_reshape(users[0]):
+                if len(users) != 1 or self.rule[users[0]].kind != RESHAPE:
                     return f"{node.name}: pooled tensor with a consumer other than one flatten"
-            if node.op == "call_module" and isinstance(self.modules[node.target], nn.Linear):
-                if any(self._is_feature_op(a) and not self._is_global_pool(a) or a.op == "placeholder"
-                       for a in self._walk(node, False)):
-                    return f"{node.target}: Linear layer applied to a feature map"
+            if r.kind == LINEAR and any(k in (CONV, BN, "placeholder") for k in self._walk(node, False)):
+                return f"{node.target}: Linear layer applied to a feature map"
         return None
 
     # ---- forward: own convolution + fused BatchNorm/add/activation kernels on NHWC -----------------------------------
@@ -342,10 +295,9 @@ class SplitSweep(SeedBatchedSweep):
                 and len(node.users) == 1):
             return False
         nxt = next(iter(node.users))
-        if not (nxt.op == "call_module" and len(nxt.args) == 1 and nxt.args[0] is node and not nxt.kwargs):
-            return False
-        bn = self.modules.get(nxt.target)
-        return isinstance(bn, nn.BatchNorm2d) and bn.running_var is not None and nxt.target not in self.tap_names
+        bn = self.rule[nxt].mod
+        return (isinstance(bn, nn.BatchNorm2d) and len(nxt.args) == 1 and nxt.args[0] is node and not nxt.kwargs
+                and bn.running_var is not None and nxt.target not in self.tap_names)
 
     def _run_bn_act(self, node, inp, scale, shift, relu, addend, want_mask):
         K = self.kernels()
@@ -417,12 +369,12 @@ class SplitSweep(SeedBatchedSweep):
             self._amax_cache[key] = hit
         return hit[1]
 
-    def _nhwc_mult(self, node, kind):
+    def _nhwc_mult(self, node, flavour):
         """per-sample multiplier of an activation as an NHWC tensor (+ its max| | word for generic derivatives)"""
         hit = self._mult_cache.get(node)
         if hit is None:
             saved = self.saved[node]
-            mult = self._act_mult(kind, saved)
+            mult = self._act_mult(flavour, saved)
             if mult.dim() != 4:
                 raise SweepUnsupported("activation on a non-feature-map tensor inside the NHWC region")
             amax = None
@@ -430,8 +382,7 @@ class SplitSweep(SeedBatchedSweep):
                 mult = mult.permute(0, 2, 3, 1).contiguous().view(torch.uint8)
             else:
                 mult = mult.to(torch.float32).permute(0, 2, 3, 1).contiguous()
-                generic = isinstance(kind, self._GENERIC_ACT_MODULES) or (callable(kind) and kind in self._GENERIC_ACT_FN)
-                if generic:  # tanh' and sigmoid' are bounded by 1; anything else is measured
+                if flavour == "generic":  # tanh' and sigmoid' are bounded by 1; anything else is measured
                     amax = self.kernels().absmax(mult)
             hit = (mult, amax)
             self._mult_cache[node] = hit
@@ -526,13 +477,7 @@ class SplitSweep(SeedBatchedSweep):
             t = t4_nchw_like.permute(0, 2, 3, 1).contiguous()
             return _F32(t, K.absmax(t))
 
-        def is4(node):
-            shp = self.saved.get(node)
-            return shp is not None
-
-        for node in reversed(list(self.gm.graph.nodes)):
-            if node.op in ("placeholder", "output"):
-                continue
+        for node, r in reversed(self.rule.items()):
             if node in deferred and node not in cot:
                 # nothing else reached this node: the deferred branches produce the cotangent on their own
                 fns = deferred.pop(node)
@@ -543,7 +488,8 @@ class SplitSweep(SeedBatchedSweep):
             if node not in cot:
                 continue
             parts = cot.pop(node)
-            if node in deferred or not self._consumes_lazily(node):
+            kind, m, src = r.kind, r.mod, r.src[0]
+            if node in deferred or kind not in _LAZY:
                 parts = _materialize(parts)
             if node in deferred:
                 f32p = [p for p in parts if isinstance(p, _F32)]
@@ -556,117 +502,108 @@ class SplitSweep(SeedBatchedSweep):
                     for fn in fns[1:]:
                         fn(part)
                     parts.append(part)
-            flat = all(torch.is_tensor(p) for p in parts)  # still in the head (Linear / flatten) region
-            if node.op == "call_module":
-                m = self.modules[node.target]
-                src = node.args[0]
-                if isinstance(m, nn.Conv2d):
-                    g = self._to_split(parts, S)
-                    if node.target in self.tap_names:
-                        grads[node.target] = g
-                        if node in pending_scale:
-                            self.grad_scale[node.target] = pending_scale[node]
-                        if on_tap is not None:
-                            on_tap(node.target, g)
-                        remaining.discard(node.target)
-                        if not remaining:
-                            break
-                    if not (isinstance(src, fx.Node) and src.op != "placeholder"):
-                        continue
-                    prep = self._prep.get(node.target)
-                    if prep is None:
-                        prep = self._prep[node.target] = cv.PreparedConv(m)
-                    in_shape = self.saved[node]  # [B, Cin, Hin, Win]
-                    hw = (int(in_shape[2]), int(in_shape[3]))
-                    cscale = pending_scale.get(node)
-                    sparse = any(not p[4] for p in cv.backward_plan(m, *hw))
+            if kind == CONV:
+                g = self._to_split(parts, S)
+                if node.target in self.tap_names:
+                    grads[node.target] = g
+                    if node in pending_scale:
+                        self.grad_scale[node.target] = pending_scale[node]
+                    if on_tap is not None:
+                        on_tap(node.target, g)
+                    remaining.discard(node.target)
+                    if not remaining:
+                        break
+                if src.op == "placeholder":
+                    continue
+                prep = self._prep.get(node.target)
+                if prep is None:
+                    prep = self._prep[node.target] = cv.PreparedConv(m)
+                in_shape = self.saved[node]  # [B, Cin, Hin, Win]
+                hw = (int(in_shape[2]), int(in_shape[3]))
+                cscale = pending_scale.get(node)
+                sparse = any(not p[4] for p in cv.backward_plan(m, *hw))
 
-                    def run(into, g=g, prep=prep, hw=hw, cscale=cscale):
-                        if into is None:
-                            w = new_word()
-                            out = cv.conv_backward_data(prep, g, hw, cscale=cscale, amax_out=w)
-                            return _F32(out, w)
-                        cv.conv_backward_data(prep, g, hw, cscale=cscale, out=into.t, accumulate=True, amax_out=into.amax)
-                        return into
+                def run(into, g=g, prep=prep, hw=hw, cscale=cscale):
+                    if into is None:
+                        w = new_word()
+                        out = cv.conv_backward_data(prep, g, hw, cscale=cscale, amax_out=w)
+                        return _F32(out, w)
+                    cv.conv_backward_data(prep, g, hw, cscale=cscale, out=into.t, accumulate=True, amax_out=into.amax)
+                    return into
 
-                    if (self.fuse_vjp and self.fuse_strided and cv.strided_fused_ok(m, hw) and src not in deferred
-                            and hasattr(K, "conv_nhwc_f16x2_vjp_strided")
-                            and all(isinstance(p, (_LazyStrided, SplitTensor)) for p in cot.get(src, []))):
-                        # (the consumer of the cotangent decides: alone or with the block's other strided branch in one
-                        # fused launch, or — something else joined — class by class into an fp32 tensor)
-                        push(src, _LazyStrided(run, (prep, g, cscale), hw))
-                        continue
-                    if src in cot:
-                        cot[src] = _materialize(cot[src])
-                    existing = [p for p in cot.get(src, []) if isinstance(p, _F32)]
-                    if existing:
-                        run(existing[0])
-                    elif sparse and len(src.users) > 1:
-                        deferred.setdefault(src, []).append(run)  # wait for the dense branch, then add into it
-                    elif self.fuse_vjp and cv.fused_backward_ok(m) and hasattr(K, "conv_nhwc_f16x2_vjp"):
-                        def run_fused(g=g, prep=prep, hw=hw, cscale=cscale, **kw):
-                            return cv.conv_backward_data_vjp(prep, g, hw, cscale=cscale, **kw)
+                if (self.fuse_vjp and self.fuse_strided and cv.strided_fused_ok(m, hw) and src not in deferred
+                        and hasattr(K, "conv_nhwc_f16x2_vjp_strided")
+                        and all(isinstance(p, (_LazyStrided, SplitTensor)) for p in cot.get(src, []))):
+                    # (the consumer of the cotangent decides: alone or with the block's other strided branch in one
+                    # fused launch, or — something else joined — class by class into an fp32 tensor)
+                    push(src, _LazyStrided(run, (prep, g, cscale), hw))
+                    continue
+                if src in cot:
+                    cot[src] = _materialize(cot[src])
+                existing = [p for p in cot.get(src, []) if isinstance(p, _F32)]
+                if existing:
+                    run(existing[0])
+                elif sparse and len(src.users) > 1:
+                    deferred.setdefault(src, []).append(run)  # wait for the dense branch, then add into it
+                elif self.fuse_vjp and cv.fused_backward_ok(m) and hasattr(K, "conv_nhwc_f16x2_vjp"):
+                    def run_fused(g=g, prep=prep, hw=hw, cscale=cscale, **kw):
+                        return cv.conv_backward_data_vjp(prep, g, hw, cscale=cscale, **kw)
 
-                        push(src, _LazyConv(lambda run=run: run(None), run_fused))
-                    else:
-                        push(src, run(None))
-                elif isinstance(m, nn.Linear):
+                    push(src, _LazyConv(lambda run=run: run(None), run_fused))
+                else:
+                    push(src, run(None))
+            elif kind == LINEAR:
+                g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
+                if not torch.is_tensor(g):
+                    raise SweepUnsupported("Linear layer inside the NHWC region")
+                if node.target in self.tap_names:
+                    grads[node.target] = g.reshape(S, B, *g.shape[1:])
+                    if on_tap is not None:
+                        on_tap(node.target, grads[node.target])
+                    remaining.discard(node.target)
+                    if not remaining:
+                        break
+                push(src, g @ m.weight)
+            elif kind == BN:
+                scale = self._bn_scale(node.target, m)
+                if (defer_bn_scale and self._defers_scale_to(src, cot) and len(parts) == 1
+                        and isinstance(parts[0], SplitTensor)):
+                    pending_scale[src] = scale
+                    push(src, parts[0])
+                else:
+                    push(src, self._to_split(parts, S, scale=scale, scale_amax=self._amax_of(node.target, scale)))
+            elif kind == ACT:
+                scale, dst = self._fold_bn(src)
+                if all(torch.is_tensor(p) for p in parts):
+                    # activation in the head region (MLP head after the flatten): parent-class math on plain tensors
                     g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                    if not torch.is_tensor(g):
-                        raise SweepUnsupported("Linear layer inside the NHWC region")
-                    if node.target in self.tap_names:
-                        grads[node.target] = g.reshape(S, B, *g.shape[1:])
-                        if on_tap is not None:
-                            on_tap(node.target, grads[node.target])
-                        remaining.discard(node.target)
-                        if not remaining:
-                            break
-                    push(src, g @ m.weight)
-                elif isinstance(m, nn.BatchNorm2d):
-                    scale = self._bn_scale(node.target, m)
-                    if (defer_bn_scale and isinstance(src, fx.Node) and src.op == "call_module" and len(src.users) == 1
-                            and isinstance(self.modules[src.target], nn.Conv2d) and src.target in self.tap_names
-                            and src not in cot and len(parts) == 1 and isinstance(parts[0], SplitTensor)):
-                        pending_scale[src] = scale
-                        push(src, parts[0])
-                    else:
-                        push(src, self._to_split(parts, S, scale=scale, scale_amax=self._amax_of(node.target, scale)))
-                elif isinstance(m, (nn.ReLU, nn.Tanh, nn.Sigmoid) + self._GENERIC_ACT_MODULES):
-                    self._activation(node, m, src, parts, S, push, flat)
-                elif isinstance(m, (nn.Identity, nn.Dropout)):
+                    push(dst, self._scale_mask(g, S, self._act_mult(r.flavour, self.saved[node]), scale))
+                else:
+                    mult, mult_amax = self._nhwc_mult(node, r.flavour)
+                    scale_amax = None if scale is None else self._amax_of(src.target, scale)
+                    push(dst, self._to_split(parts, S, mult=mult, mult_amax=mult_amax, scale=scale, scale_amax=scale_amax))
+            elif kind == IDENTITY:
+                for p in parts:
+                    push(src, p)
+            elif kind == ADD:
+                for a in r.src:
                     for p in parts:
-                        push(src, p)
-                elif isinstance(m, nn.Flatten):
-                    self._unflatten(node, src, parts, SB, push, feature_f32)
-                elif isinstance(m, nn.AdaptiveAvgPool2d):
-                    self._global_pool(node, src, parts, SB, push, K)
-                else:
-                    raise SweepUnsupported(f"no NHWC rule for {type(m).__name__}")
-            elif node.op == "call_function":
-                t = node.target
-                if t in (operator.add, torch.add, operator.iadd):
-                    for a in node.args[:2]:
-                        for p in parts:
-                            push(a, p)
-                elif t in self._ELEMENTWISE_FN or t in self._GENERIC_ACT_FN:
-                    self._activation(node, t, node.args[0], parts, S, push, flat)
-                elif t is torch.flatten:
-                    self._unflatten(node, node.args[0], parts, SB, push, feature_f32)
-                elif t is F.adaptive_avg_pool2d:
-                    self._global_pool(node, node.args[0], parts, SB, push, K)
-                else:
-                    raise SweepUnsupported(f"no NHWC rule for {getattr(t, '__name__', t)}")
-            elif node.op == "call_method":
-                t = node.target
-                if t in ("relu", "tanh", "sigmoid"):
-                    self._activation(node, t, node.args[0], parts, S, push, flat)
-                elif t in ("view", "reshape", "flatten"):
-                    self._unflatten(node, node.args[0], parts, SB, push, feature_f32)
-                elif t == "contiguous":
-                    for p in parts:
-                        push(node.args[0], p)
-                else:
-                    raise SweepUnsupported(f"no NHWC rule for method {t}")
+                        push(a, p)
+            elif kind == RESHAPE:
+                g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
+                if not torch.is_tensor(g):
+                    raise SweepUnsupported("reshape inside the NHWC region")
+                g = g.reshape((SB,) + tuple(self.saved[node])[1:])
+                push(src, feature_f32(g) if g.dim() == 4 else g)
+            elif kind == GPOOL:
+                shp, p = self.saved[node], parts[0]  # [B, C, H, W]
+                if len(parts) != 1 or not isinstance(p, _F32):
+                    raise SweepUnsupported("global average pooling expects one fp32 cotangent")
+                H, W = int(shp[-2]), int(shp[-1])
+                t = (p.t / (H * W)).expand(SB, H, W, p.t.shape[-1]).contiguous()
+                push(src, _F32(t, K.absmax(t)))
+            else:
+                raise SweepUnsupported(f"no NHWC rule for {r.what}")
         self._new_word = None
         if remaining:
             raise SweepUnsupported(f"no cotangent reached {sorted(remaining)}")
@@ -676,34 +613,3 @@ class SplitSweep(SeedBatchedSweep):
                 if isinstance(g, SplitTensor):
                     grads[name] = g.float().reshape(S, B, *g.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
         return grads
-
-    # ---- node rules ---------------------------------------------------------------------------------------------------
-    def _activation(self, node, kind, src, parts, S, push, flat):
-        if flat:  # activation in the head region (MLP head after the flatten): parent-class math on plain tensors
-            g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-            scale, dst = self._fold_bn(src)
-            push(dst, self._scale_mask(g, S, self._act_mult(kind, self.saved[node]), scale))
-            return
-        mult, mult_amax = self._nhwc_mult(node, kind)
-        scale, dst = self._fold_bn(src)
-        scale_amax = None
-        if scale is not None:
-            scale_amax = self._amax_of(src.target, scale)
-        push(dst, self._to_split(parts, S, mult=mult, mult_amax=mult_amax, scale=scale, scale_amax=scale_amax))
-
-    def _unflatten(self, node, src, parts, SB, push, feature_f32):
-        g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-        if not torch.is_tensor(g):
-            raise SweepUnsupported("reshape inside the NHWC region")
-        shp = tuple(self.saved[node])
-        g = g.reshape((SB,) + shp[1:])
-        push(src, feature_f32(g) if g.dim() == 4 else g)
-
-    def _global_pool(self, node, src, parts, SB, push, K):
-        shp = self.saved[node]  # [B, C, H, W]
-        p = parts[0]
-        if len(parts) != 1 or not isinstance(p, _F32):
-            raise SweepUnsupported("global average pooling expects one fp32 cotangent")
-        H, W = int(shp[-2]), int(shp[-1])
-        t = (p.t / (H * W)).expand(SB, H, W, p.t.shape[-1]).contiguous()
-        push(src, _F32(t, K.absmax(t)))
