@@ -619,6 +619,23 @@ size_t lk_quadform_shared_grid_workspace_bytes(int64_t B, int64_t C, int64_t Do,
 int lk_quadform_shared_grid_f32(const float* u, const float* v, const float* w0, const float* w1, const float* deltas,
                                 int64_t G, int mode, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L,
                                 int seed_major, float* var, void* ws, size_t ws_bytes, void* stream);
+/* Which instantiation of the weight-sharing kernels a shape launches (pure host function, no device call: the launchers
+ * above decide with the same helpers).  `form`: LK_QF_*; `C`: outputs (seeds S for LK_QF_DIAG_GGN); `aligned16`: u and v
+ * are 16-byte aligned (ignored by LK_QF_PLANES, which requires it; for LK_QF_GRID the answer is that of one block of
+ * outputs — every block launches the same CT, the alignment is that of the block's first output).  Returns
+ *   CT | flags << 4 | split << 8      CT: outputs held in accumulators, split: workgroups per sample (LK_QF_DIAG_GGN: nsplit,
+ *                                     workgroups per tile)
+ *   flags, LK_QF_PLANES: 1 = two workgroups per CU (OCC = 2), 2 = SUB (one-chunk tiles), 4 = eigenvalues in LDS
+ *   flags, other forms:  1 = ARITH 1 (three-piece bf16 products; 0: v_mfma_f32_32x32x2_f32)
+ * or a negative value for a shape the form does not serve (B, C, Do, Dk or L < 1, more than 10 outputs outside LK_QF_GRID,
+ * LK_QF_PLANES with L % 16 or Do % 32, an unknown form). */
+#define LK_QF_KRON 0           /* lk_kron_quadform_shared_f32 */
+#define LK_QF_KRON_SEEDMAJOR 1 /* lk_kron_quadform_shared_seedmajor_f32 */
+#define LK_QF_DIAG 2           /* lk_diag_quadform_shared_f32 */
+#define LK_QF_PLANES 3         /* lk_kron_quadform_shared_planes_f16x2 */
+#define LK_QF_DIAG_GGN 4       /* lk_diag_ggn_shared_f32 */
+#define LK_QF_GRID 5           /* lk_quadform_shared_grid_f32, all three modes, either layout of u */
+int lk_quadform_shared_variant(int form, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L, int aligned16);
 /* Probit link + NLL: loss_sum[g] += sum_n -log(max(softmax(kappa f_mu[n])[labels[n]], 1e-30)),
  * kappa_c = 1 / sqrt(1 + pi/8 var[g][n][c]) (baselaplace.py:649-651); f_mu [B][C], labels int64 [B], loss_sum double [G]. */
 int lk_probit_nll_grid_f32(const float* f_mu, const float* var, const int64_t* labels, int64_t G, int64_t B, int64_t C,

@@ -142,6 +142,7 @@ SIGNATURES = {
     "lk_quadform_shared_grid_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "lk_quadform_shared_grid_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz,
                                            _vp]),
+    "lk_quadform_shared_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _int]),
     "lk_probit_nll_grid_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
 }
 
@@ -1505,6 +1506,24 @@ class HipKernels:
                                  int(bool(seed_major)), _ptr(var), _ptr(ws), ws.numel(), self._stream(u.device))),
                  "lk_quadform_shared_grid_f32")
         return var
+
+    #: ``form`` of :meth:`quadform_shared_variant` (LK_QF_* of include/laplace_hip.h)
+    QF_KRON, QF_KRON_SEEDMAJOR, QF_DIAG, QF_PLANES, QF_DIAG_GGN, QF_GRID = range(6)
+
+    def quadform_shared_variant(self, form, B, C, Do, Dk, L, aligned16=True):
+        """lk_quadform_shared_variant: the instantiation of the weight-sharing kernels the shape launches (host only, no
+        device call), or ``None`` for a shape the form does not serve.  ``ct`` and ``split`` always; the planes form adds
+        ``occ``, ``sub``, ``w_in_lds``, the others ``arith``."""
+        r = int(self.lib.lk_quadform_shared_variant(int(form), int(B), int(C), int(Do), int(Dk), int(L), int(bool(aligned16))))
+        if r < 0:
+            return None
+        out = {"ct": r & 15, "split": r >> 8}
+        flags = (r >> 4) & 15
+        if form == self.QF_PLANES:
+            out.update(occ=2 if flags & 1 else 1, sub=bool(flags & 2), w_in_lds=bool(flags & 4))
+        else:
+            out["arith"] = flags & 1
+        return out
 
     def probit_nll_grid(self, f_mu, var, y, loss_sum):
         """``loss_sum [G] (float64) +=`` the probit-link NLL of the batch at every grid point; ``f_mu [B, C]``,

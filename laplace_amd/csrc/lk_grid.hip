@@ -260,17 +260,7 @@ __global__ __launch_bounds__(256) void probit_nll_grid_kernel(const float* __res
 
 using namespace lk;
 
-static bool grid_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// output block of one launch of the weight-sharing grid kernel
-static int grid_class_tile(int64_t C) { return C <= 1 ? 1 : C <= 2 ? 2 : C <= 5 ? 5 : 10; }
-
-static int grid_split(int64_t B, int64_t Do, int64_t Dk) {
-  const int64_t ntiles = ((Do + 31) / 32) * ((Dk + 127) / 128);
-  int64_t want = (2048 + B - 1) / B;
-  if (want < 1) want = 1;
-  return (int)(want < ntiles ? want : ntiles);
-}
+// (grid_class_tile, grid_split, qc_arith: lk_quadtile.h — the rules the variant query reports)
 
 extern "C" int lk_quadform_linear_grid_f32(const float* u, const float* v, const float* w0, const float* w1,
                                            const float* deltas, int64_t G, int mode, int64_t B, int64_t C, int64_t Do,
@@ -356,7 +346,7 @@ extern "C" int lk_quadform_shared_grid_f32(const float* u, const float* v, const
   for (int64_t c0 = 0; c0 < C; c0 += ct) {
     const int cl = (int)(C - c0 < ct ? C - c0 : ct);
     const float* uc = u + (size_t)c0 * ucs;
-    const bool v4 = (L % 4 == 0) && grid_aligned16(uc) && grid_aligned16(v);
+    const bool v4 = qc_arith(L, qc_aligned16(uc) && qc_aligned16(v)) == 1;
     for (int64_t g0 = 0; g0 < G; g0 += GRID_GMAX) {
       const int gl = (int)(G - g0 < GRID_GMAX ? G - g0 : GRID_GMAX);
       const float* dg = deltas + g0;

@@ -511,26 +511,7 @@ __global__ __launch_bounds__(256) void diag_ggn_shared_reduce_kernel(const float
 
 using namespace lk;
 
-static int qc_b6_enabled() { return 1; }
-static bool qc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-static int qc_class_tile(int64_t C) {
-  static const int tiles[] = {1, 2, 3, 4, 5, 6, 8, 10};  // 12 outputs would spill accumulators
-  for (int t : tiles)
-    if (C <= t) return t;
-  return 0;
-}
-
-static int qc_split(int64_t B, int64_t Do, int64_t Dk) {
-  const int64_t ntiles = ((Do + 31) / 32) * ((Dk + 127) / 128);
-  int64_t want = (2048 + B - 1) / B;
-#ifdef LK_QC_MIN_SPLIT
-  if (want < LK_QC_MIN_SPLIT) want = LK_QC_MIN_SPLIT;
-#endif
-  if (want < 1) want = 1;
-  return (int)(want < ntiles ? want : ntiles);
-}
-
+// (qc_class_tile, qc_split, dg_split, qc_arith, qp_variant: lk_quadtile.h — the rules the variant query reports)
 extern "C" size_t lk_quadform_shared_workspace_bytes(int64_t B, int64_t C, int64_t Do, int64_t Dk) {
   const int ct = qc_class_tile(C);
   if (B < 1 || ct == 0 || Do < 1 || Dk < 1) return 0;  // (B == 0: nothing to do, and qc_split divides by B)
@@ -557,7 +538,7 @@ static int launch_quadform_conv(const float* u, const float* v, const float* w0,
   const int split = qc_split(B, Do, Dk);
   float* partial = static_cast<float*>(ws);
   const dim3 grid((unsigned)(B * split));
-  const bool v4 = (L % 4 == 0) && qc_aligned16(u) && qc_aligned16(v) && qc_b6_enabled();
+  const bool v4 = qc_arith(L, qc_aligned16(u) && qc_aligned16(v)) == 1;
 #define LK_QC_CASE(CT)                                                                                              \
   case CT:                                                                                                          \
     if (v4)                                                                                                         \
@@ -636,11 +617,12 @@ extern "C" int lk_kron_quadform_shared_planes_f16x2(const void* u_h, const void*
     return LK_EWORKSPACE;
   }
   hipStream_t stream = (hipStream_t)stream_;
-  const int split = qc_split(B, Do, Dk);
+  const QpVariant qp = qp_variant(B, C, Do, Dk, L);
+  const int split = qp.split;
   float* partial = static_cast<float*>(ws);
   const dim3 grid((unsigned)(B * split));
   const size_t w_bytes = (size_t)(Do + Dk) * sizeof(float);
-  const int w_in_lds = w_bytes <= 40960 ? 1 : 0;  // (the eigenvalues behind the ring: ResNet-18's widest layer needs 20 KB)
+  const int w_in_lds = qp.w_in_lds;
 #define LK_QP_LAUNCH(CT, OCC, SUB)                                                                                          \
   {                                                                                                                         \
     static bool attr_set = false;                                                                                           \
@@ -665,13 +647,7 @@ extern "C" int lk_kron_quadform_shared_planes_f16x2(const void* u_h, const void*
   // deeper ring covered); ten outputs spill 17 registers outside the chunk loop.  Measured on the c4 layers, ms per launch
   // (profiles/r06_quad_layers.log): 64 channels 0.42 -> 0.34, 128: 0.49 -> 0.38, 256: 0.65 -> 0.48, 512: 1.37 -> 1.10; a
   // predictive call 10.5 -> 8.8 ms of quadratic forms.  One per CU only where the eigenvalues do not fit beside two rings.
-  const bool occ2 = w_bytes <= 24576;
-  // one-chunk tiles (4 x 4 maps): the sub-tile form with two-wide pair sums (see the kernel; -DLK_QC_NO_SUB: development build)
-#ifdef LK_QC_NO_SUB
-  const bool sub = false;
-#else
-  const bool sub = occ2 && w_in_lds && L == 16;
-#endif
+  const bool occ2 = qp.occ == 2, sub = qp.sub != 0;
   switch (ct) {
     LK_QP_CASE(1)
     LK_QP_CASE(2)
@@ -701,13 +677,6 @@ extern "C" int lk_diag_quadform_shared_f32(const float* u, const float* v, const
                                  "lk_diag_quadform_shared_f32");
 }
 
-static int dg_split(int64_t B, int64_t Do, int64_t Dk) {
-  const int64_t ntiles = ((Do + 31) / 32) * ((Dk + 127) / 128);
-  int64_t want = (1024 + ntiles - 1) / ntiles;
-  if (want < 1) want = 1;
-  return (int)(want < B ? want : (B < 1 ? 1 : B));
-}
-
 extern "C" size_t lk_diag_ggn_shared_workspace_bytes(int64_t B, int64_t Do, int64_t Dk) {
   if (B < 0 || Do < 1 || Dk < 1) return 0;
   return (size_t)dg_split(B, Do, Dk) * Do * Dk * sizeof(float);
@@ -730,11 +699,11 @@ extern "C" int lk_diag_ggn_shared_f32(const float* u, const float* v, int64_t B,
   }
   hipStream_t stream = (hipStream_t)stream_;
   const int nsplit = dg_split(B, Do, Dk);
-  const int64_t ntiles = ((Do + 31) / 32) * ((Dk + 127) / 128);
+  const int64_t ntiles = qc_ntiles(Do, Dk);
   LK_REQUIRE(ntiles * nsplit < (1ll << 31), "lk_diag_ggn_shared_f32: grid too large");
   float* partial = static_cast<float*>(ws);
   const dim3 grid((unsigned)(ntiles * nsplit));
-  const bool v4 = (L % 4 == 0) && qc_aligned16(u) && qc_aligned16(v) && qc_b6_enabled();
+  const bool v4 = qc_arith(L, qc_aligned16(u) && qc_aligned16(v)) == 1;
 #define LK_DG_CASE(CT)                                                                                               \
   case CT:                                                                                                           \
     if (v4)                                                                                                          \
@@ -759,4 +728,33 @@ extern "C" int lk_diag_ggn_shared_f32(const float* u, const float* v, int64_t B,
   hipLaunchKernelGGL(diag_ggn_shared_reduce_kernel, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, stream, partial,
                      width, nsplit, alpha, h);
   return check_launch("lk_diag_ggn_shared_f32");
+}
+
+// Which instantiation a shape launches (include/laplace_hip.h): CT | flags << 4 | split << 8, negative = not served.
+extern "C" int lk_quadform_shared_variant(int form, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L, int aligned16) {
+  if (B < 1 || C < 1 || Do < 1 || Dk < 1 || L < 1) return -1;
+  int ct, flags, split;
+  switch (form) {
+    case LK_QF_KRON:
+    case LK_QF_KRON_SEEDMAJOR:
+    case LK_QF_DIAG:
+      ct = qc_class_tile(C), flags = qc_arith(L, aligned16 != 0), split = qc_split(B, Do, Dk);
+      break;
+    case LK_QF_PLANES: {
+      if (L % 16 != 0 || Do % 32 != 0) return -1;
+      const QpVariant qp = qp_variant(B, C, Do, Dk, L);
+      ct = qp.ct, flags = (qp.occ == 2 ? 1 : 0) | (qp.sub ? 2 : 0) | (qp.w_in_lds ? 4 : 0), split = qp.split;
+      break;
+    }
+    case LK_QF_DIAG_GGN:
+      ct = qc_class_tile(C), flags = qc_arith(L, aligned16 != 0), split = dg_split(B, Do, Dk);
+      break;
+    case LK_QF_GRID:
+      ct = grid_class_tile(C), flags = qc_arith(L, aligned16 != 0), split = grid_split(B, Do, Dk);
+      break;
+    default:
+      return -1;
+  }
+  if (ct == 0) return -1;
+  return ct | flags << 4 | split << 8;
 }

@@ -212,4 +212,72 @@ __device__ __forceinline__ void qc_tile_gemm_b6(const QcOperands& cur, const QcO
   __syncthreads();
 }
 
+// ---- host side: which instantiation a shape launches ------------------------------------------------------------------
+// The ONE copy of the selection rules: the launchers of lk_quadconv.hip / lk_grid.hip and lk_quadform_shared_variant (the
+// query the tests read) all go through these.
+inline int64_t qc_ntiles(int64_t Do, int64_t Dk) { return ((Do + 31) / 32) * ((Dk + 127) / 128); }
+
+inline int qc_class_tile(int64_t C) {
+  static const int tiles[] = {1, 2, 3, 4, 5, 6, 8, 10};  // 12 outputs would spill accumulators
+  for (int t : tiles)
+    if (C <= t) return t;
+  return 0;
+}
+
+// workgroups per sample of the quadratic-form kernels (fp32 operands and planes)
+inline int qc_split(int64_t B, int64_t Do, int64_t Dk) {
+  const int64_t ntiles = qc_ntiles(Do, Dk);
+  int64_t want = (2048 + B - 1) / B;
+#ifdef LK_QC_MIN_SPLIT
+  if (want < LK_QC_MIN_SPLIT) want = LK_QC_MIN_SPLIT;
+#endif
+  if (want < 1) want = 1;
+  return (int)(want < ntiles ? want : ntiles);
+}
+
+// workgroups per tile of diag_ggn_shared_kernel (each walks the samples sp, sp + nsplit, ...)
+inline int dg_split(int64_t B, int64_t Do, int64_t Dk) {
+  const int64_t ntiles = qc_ntiles(Do, Dk);
+  int64_t want = (1024 + ntiles - 1) / ntiles;
+  if (want < 1) want = 1;
+  return (int)(want < B ? want : (B < 1 ? 1 : B));
+}
+
+// output block of one launch of the weight-sharing grid kernel, and its workgroups per sample
+inline int grid_class_tile(int64_t C) { return C <= 1 ? 1 : C <= 2 ? 2 : C <= 5 ? 5 : 10; }
+
+inline int grid_split(int64_t B, int64_t Do, int64_t Dk) {
+  const int64_t ntiles = qc_ntiles(Do, Dk);
+  int64_t want = (2048 + B - 1) / B;
+  if (want < 1) want = 1;
+  return (int)(want < ntiles ? want : ntiles);
+}
+
+inline bool qc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ARITH of the fp32-operand kernels: 1 (three-piece bf16, positions read four at a time) needs whole float4s
+inline int qc_arith(int64_t L, bool aligned16) { return (L % 4 == 0) && aligned16 ? 1 : 0; }
+
+// quadform_conv_planes_kernel<CT, OCC, SUB>, the eigenvalues in LDS or not, workgroups per sample
+struct QpVariant {
+  int ct, occ, sub, w_in_lds, split;
+};
+
+inline QpVariant qp_variant(int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L) {
+  QpVariant q;
+  q.ct = qc_class_tile(C);
+  const size_t w_bytes = (size_t)(Do + Dk) * sizeof(float);
+  q.w_in_lds = w_bytes <= 40960 ? 1 : 0;  // (the eigenvalues behind the ring: ResNet-18's widest layer needs 20 KB)
+  // two workgroups per CU only where the eigenvalues fit beside two rings (see lk_kron_quadform_shared_planes_f16x2)
+  q.occ = w_bytes <= 24576 ? 2 : 1;
+  // one-chunk tiles (4 x 4 maps): the sub-tile form with two-wide pair sums (see the kernel; -DLK_QC_NO_SUB: development build)
+#ifdef LK_QC_NO_SUB
+  q.sub = 0;
+#else
+  q.sub = q.occ == 2 && q.w_in_lds && L == 16 ? 1 : 0;
+#endif
+  q.split = qc_split(B, Do, Dk);
+  return q;
+}
+
 }  // namespace lk

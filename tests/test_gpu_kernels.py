@@ -482,7 +482,8 @@ def test_quadform_shared(K, B, C, Do, Dk, L):
                                         (7, 1, 96, 200, 33), (1, 3, 16, 16, 4)])
 def test_diag_ggn_shared(K, B, S, Do, Dk, L):
     """exact GGN diagonal of a weight-sharing layer: sum over (sample, seed) of the squared per-sample Jacobian,
-    accumulated on top of what h already holds; ragged tiles, one and many samples per workgroup"""
+    accumulated on top of what h already holds; ragged tiles, one sample per workgroup (several samples per workgroup,
+    B > nsplit, and every seed count on both tile products: tests/test_gpu_quadform_instances.py)"""
     u, v = rnd(B, S, Do, L, seed=1), rnd(B, Dk, L, seed=2)
     base = rnd(Do * Dk, seed=3)
     f32 = lambda t: t.float().to(DEV).contiguous()
