@@ -636,6 +636,27 @@ int lk_quadform_shared_grid_f32(const float* u, const float* v, const float* w0,
 #define LK_QF_DIAG_GGN 4       /* lk_diag_ggn_shared_f32 */
 #define LK_QF_GRID 5           /* lk_quadform_shared_grid_f32, all three modes, either layout of u */
 int lk_quadform_shared_variant(int form, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L, int aligned16);
+/* Which kernel, tile, epilogue and grid a launch of the split-fp16 convolution takes (pure host function except for the
+ * device's CU count, 256 without a device: conv_dispatch and the launchers decide with the same helpers of csrc/lk_conv.hip).
+ * `entry`: LK_CONV_*; the arguments are those of the entry point (the three dense entry points ignore Hc, Wc, out_step, oh0, ow0,
+ * LK_CONV_VJP also in_mul); `have_wc`: chunk-major weights are handed over (lk_conv_nhwc_f16x2_vjp_wc); `mask_is_float`: the
+ * multiplier is fp32.  Fills out[16]:
+ *   [0] kernel: 0 generic (conv_f16x2_kernel), 1 / 2 persistent window form on 256 / 512 pixels, 3 strided
+ *   [1] BM  [2] BN  [3] epilogue: 0 plain, 1 split planes, 2 VJP, 3 forward (BatchNorm / add / ReLU)
+ *   [4] position-major rows  [5] dense grid  [6] workgroups  [7] pixel tiles nb_m  [8] column tiles nb_n
+ *   [9] co-located columns  [10] split_S (1: no split tail)  [11] split_L  [12] workgroups per CU (window form)
+ *   [13] tiles walked  [14] position-contiguous output  [15] residue classes (strided form)
+ * and returns 0, or a negative value for a shape the entry point refuses or launches nothing for. */
+#define LK_CONV_PLAIN 0  /* lk_conv_nhwc_f16x2 */
+#define LK_CONV_PLANES 1 /* lk_conv_nhwc_f16x2_planes */
+#define LK_CONV_BN_ACT 2 /* lk_conv_bn_act_nhwc_f16x2 */
+#define LK_CONV_VJP 3    /* lk_conv_nhwc_f16x2_vjp, lk_conv_nhwc_f16x2_vjp_wc */
+int lk_conv_launch_variant(int entry, int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t Hc, int64_t Wc,
+                           int64_t in_mul, int64_t Ho, int64_t Wo, int64_t out_step, int64_t oh0, int64_t ow0, int64_t T,
+                           const int* taps, int64_t in_nsexp, int have_wc, int mask_is_float, int config, int* out);
+/* the same for lk_conv_nhwc_f16x2_vjp_strided (`taps`: T x 6 ints as there) */
+int lk_conv_strided_launch_variant(int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t Ho, int64_t Wo, int64_t os,
+                                   int64_t T, const int* taps, int two_sources, int* out);
 /* Probit link + NLL: loss_sum[g] += sum_n -log(max(softmax(kappa f_mu[n])[labels[n]], 1e-30)),
  * kappa_c = 1 / sqrt(1 + pi/8 var[g][n][c]) (baselaplace.py:649-651); f_mu [B][C], labels int64 [B], loss_sum double [G]. */
 int lk_probit_nll_grid_f32(const float* f_mu, const float* var, const int64_t* labels, int64_t G, int64_t B, int64_t C,

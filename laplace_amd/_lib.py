@@ -143,6 +143,9 @@ SIGNATURES = {
     "lk_quadform_shared_grid_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz,
                                            _vp]),
     "lk_quadform_shared_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _int]),
+    "lk_conv_launch_variant": (_int, [_int] + [_i64] * 14 + [ctypes.POINTER(ctypes.c_int), _i64, _int, _int, _int,
+                                      ctypes.POINTER(ctypes.c_int)]),
+    "lk_conv_strided_launch_variant": (_int, [_i64] * 9 + [ctypes.POINTER(ctypes.c_int), _int, ctypes.POINTER(ctypes.c_int)]),
     "lk_probit_nll_grid_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
 }
 
@@ -632,6 +635,41 @@ class HipKernels:
 
     #: ``False``: fused 64-channel launches stay on the generic kernel (see :meth:`conv_winp_eligible`)
     use_winp = True
+
+    #: ``entry`` of :meth:`conv_launch_variant` (LK_CONV_* of include/laplace_hip.h)
+    CONV_PLAIN, CONV_PLANES, CONV_BN_ACT, CONV_VJP = range(4)
+    _CONV_KERNELS = ("generic", "window-256", "window-512", "strided")
+    _CONV_EPILOGUES = ("plain", "planes", "vjp", "forward")
+
+    @classmethod
+    def _conv_variant(cls, rc, o):
+        if rc < 0:
+            return None
+        return {"kernel": cls._CONV_KERNELS[o[0]], "bm": o[1], "bn": o[2], "epilogue": cls._CONV_EPILOGUES[o[3]], "pmajor": bool(o[4]),
+                "dense": bool(o[5]), "grid": o[6], "nb_m": o[7], "nb_n": o[8], "coloc": o[9], "split_S": o[10], "split_L": o[11],
+                "wg_per_cu": o[12], "n_tiles": o[13], "out_nchw": bool(o[14]), "ncls": o[15]}
+
+    def conv_launch_variant(self, entry, N, Hi, Wi, Ci, Co, Ho, Wo, taps, Hc=None, Wc=None, in_mul=1, out_step=1, oh0=0, ow0=0,
+                            in_nsexp=1, have_wc=False, mask_is_float=False, config=None):
+        """lk_conv_launch_variant: kernel, tile, epilogue, row order and grid the launch takes (host only; ``grid`` and what follows
+        from it depend on the device's CU count, 256 without a device), or ``None`` for a refused shape.  ``taps``: rows
+        ``(dh, dw, weight slice)``; ``config``: as the launch would carry it (default: ``conv_config``)."""
+        flat = (ctypes.c_int * max(3 * len(taps), 1))(*[int(v) for t in taps for v in t])
+        out = (ctypes.c_int * 16)()
+        cfg = self.conv_config if config is None else config
+        rc = self.lib.lk_conv_launch_variant(int(entry), int(N), int(Hi), int(Wi), int(Ci), int(Co), int(Ho if Hc is None else Hc),
+                                             int(Wo if Wc is None else Wc), int(in_mul), int(Ho), int(Wo), int(out_step), int(oh0),
+                                             int(ow0), len(taps), flat, int(in_nsexp), int(bool(have_wc)), int(bool(mask_is_float)),
+                                             int(cfg), out)
+        return self._conv_variant(rc, out)
+
+    def conv_strided_launch_variant(self, N, Hi, Wi, Ci, Co, Ho, Wo, os, taps, two_sources=False):
+        """lk_conv_strided_launch_variant: the same for lk_conv_nhwc_f16x2_vjp_strided (``taps``: rows of six)"""
+        flat = (ctypes.c_int * max(6 * len(taps), 1))(*[int(v) for t in taps for v in t])
+        out = (ctypes.c_int * 16)()
+        rc = self.lib.lk_conv_strided_launch_variant(int(N), int(Hi), int(Wi), int(Ci), int(Co), int(Ho), int(Wo), int(os), len(taps),
+                                                     flat, int(bool(two_sources)), out)
+        return self._conv_variant(rc, out)
 
     def conv_winp_eligible(self, N, Hi, Wi, Ci, Co, T, mask_is_float=False) -> bool:
         """does a fused 3 x 3 / stride-1 launch of this shape run the persistent window form (lk_conv_nhwc_f16x2_vjp_wc)?  The

@@ -1973,9 +1973,6 @@ static int cu_count() {
   return n;
 }
 
-// persistent window form (fused VJP epilogue only): one workgroup per CU walks through the pixel tiles.  The taps are put
-// into raster order here (the sum over taps is commutative); their weight slices must then form an arithmetic sequence
-// (forward: 0, 1, ..; backward-data: 8, 7, ..) — returns false (caller takes another kernel) otherwise.
 // default number of column tiles of a pixel tile that share an XCD in the persistent window form (measured per shape:
 // profiles/r05_winp_coloc.md); config bits 28-29 of a launch override it
 static int coloc_default(int Ci, int Co) {
@@ -2015,27 +2012,122 @@ static WinpScratch* winp_scratch(hipStream_t stream, size_t slab_bytes, int n_ar
   return &w;
 }
 
-template <typename CFG>
-static bool launch_winp(const ConvGeom& g, const void* Ah, const void* Al, const void* Wh /* chunk-major */, const void* Wl, const int* a_sexp,
-                        const int* w_sexp, unsigned* amax_out, hipStream_t stream, const ConvVjp* fz, int* rc, int config) {
+// ---- launch selection ----------------------------------------------------------------------------------------------------
+// The ONE copy of the rules that decide what a launch runs: conv_dispatch / launch_winp / lk_conv_nhwc_f16x2_vjp_strided and the
+// queries lk_conv_launch_variant / lk_conv_strided_launch_variant (what the tests prove their coverage with) all call these.
+// Pure host code, except for the CU count (256 without a device).
+
+// tile shapes of conv_f16x2_kernel, by the index of config bits 12..14 (BM, BN)
+static const int kConvTile[6][2] = {{0, 0}, {64, 64}, {128, 64}, {64, 128}, {128, 128}, {256, 64}};
+
+// small maps: rows ordered (pixel, image) so that border taps drop out of whole tiles (config bit 15 turns it off; bits 16-17
+// lift the limit from 64 pixels to 256 / 1024 / 4096)
+static int conv_pmajor_rule(int64_t N, int64_t Hc, int64_t Wc, int config) {
+  return (Hc * Wc <= (64 << (2 * ((config >> 16) & 3))) && N >= 64 && !(config & 16) && !(config & 32768)) ? 1 : 0;
+}
+
+// tile shape of the generic kernel (index into kConvTile): explicit (config bits 12..14; the tests walk through them) or
+// by occupancy (measured on the c4 layer shapes, profiles/r02_conv_tile_sweep.json): the big tile (2 workgroups per CU =
+// 512 slots) when it fills the chip and its last round is not mostly idle; otherwise the half tile (3 per CU) if that
+// gives >= 512 tiles; otherwise 64 x 64 (the forward of the deep, small-map layers at batch 128 has only 64-128 big
+// tiles).  A pure function of the shapes: the same launch always takes the same tile.
+static int conv_tile_rule(int64_t M, int64_t Co, int config) {
+  const int explicit_tile = (config >> 12) & 7;
+  if (explicit_tile >= 1 && explicit_tile <= 5) return explicit_tile;
+  auto tiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((Co + bn - 1) / bn); };
+  const bool narrow = Co <= 64;
+  const int64_t tb = narrow ? tiles(256, 64) : tiles(128, 128);
+  const int64_t rounds = (tb + 511) / 512;
+  const bool big_ok = tb >= 512 && tb * 100 >= rounds * 512 * 74;
+  if (!big_ok) {
+    const int64_t tm = narrow ? tiles(128, 64) : tiles(64, 128);
+    if (tm >= 512) return narrow ? 2 : 3;
+    return 1;
+  }
+  return narrow ? 5 : 4;
+}
+
+// persistent window form: the taps are put into raster order (the sum over taps is commutative); their weight slices must
+// then form an arithmetic sequence (forward: 0, 1, ..; backward-data: 8, 7, ..) — false (another kernel) otherwise
+static bool winp_tap_sequence(const int* dh, const int* dw, const int* wts, int* wt0, int* step) {
   int wt[9];
   for (int t = 0; t < 9; ++t) wt[t] = -1;
   for (int t = 0; t < 9; ++t) {
-    if (g.dh[t] < -1 || g.dh[t] > 1 || g.dw[t] < -1 || g.dw[t] > 1) return false;
-    const int c = (g.dh[t] + 1) * 3 + g.dw[t] + 1;
+    if (dh[t] < -1 || dh[t] > 1 || dw[t] < -1 || dw[t] > 1) return false;
+    const int c = (dh[t] + 1) * 3 + dw[t] + 1;
     if (wt[c] >= 0) return false;
-    wt[c] = g.wt[t];
+    wt[c] = wts[t];
   }
-  const int step = wt[1] - wt[0];
+  *step = wt[1] - wt[0];
   for (int t = 0; t < 9; ++t)
-    if (wt[t] != wt[0] + t * step) return false;
-  if (g.Ci > WINP_MAX_CI) return false;  // (the descriptor's chunk fields: the caller takes the generic kernel)
+    if (wt[t] != wt[0] + t * *step) return false;
+  *wt0 = wt[0];
+  return true;
+}
+
+// does this launch run the persistent window form?  Fused VJP launches whose caller also handed over chunk-major weights
+// (config bit 27 switches it off) of an eligible shape (lk_conv_winp_eligible) on a dense stride-1 grid with a 3 x 3 tap
+// table in sequence.  Returns the pixel tile, 256 or 512 (config bit 26), or 0.
+static int winp_route(bool vjp_epilogue, bool have_wc, int config, int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t T,
+                      bool mask_is_float, int64_t in_mul, int64_t Hc, int64_t Wc, bool dense, const int* dh, const int* dw,
+                      const int* wts, int* wt0, int* step) {
+  if (!vjp_epilogue || !have_wc || (config & 134217728) || !lk_conv_winp_eligible(N, Hi, Wi, Ci, Co, T, mask_is_float) ||
+      in_mul != 1 || Hc != Hi || Wc != Wi || !dense)
+    return 0;
+  if (!winp_tap_sequence(dh, dw, wts, wt0, step)) return 0;
+  if (Ci > WINP_MAX_CI) return 0;  // (the descriptor's chunk fields: the generic kernel has no such field)
+  return (config & 67108864) ? 512 : 256;
+}
+
+// grid, co-location and split tail of a window-form launch
+struct WinpPlan {
+  int nb_m, n_tiles, wg_per_cu, grid, coloc, split_S, split_L, split_v0;
+};
+static WinpPlan winp_plan(int BM, int cfg_wg_per_cu, int64_t M, int Ci, int Co, int config, int cus) {
+  WinpPlan w;
+  w.nb_m = (int)((M + BM - 1) / BM);
+  w.n_tiles = w.nb_m * (Co / 64);
+  w.wg_per_cu = (config & 524288) ? 1 : cfg_wg_per_cu;  // (development: bit 19 = one workgroup per CU)
+  w.grid = w.n_tiles < w.wg_per_cu * cus ? w.n_tiles : w.wg_per_cu * cus;  // two workgroups per CU
+  w.coloc = 1;
+  {
+    // columns of a pixel tile that share an XCD (see `coords` in the kernel): config bits 28-29 = log2, 0 = the default
+    const int nb_n = Co / 64;
+    int c = 1 << ((config >> 28) & 3);
+    if (c == 1) c = coloc_default(Ci, Co);
+    if (c > 1 && c <= nb_n && nb_n % c == 0 && nb_n / c <= 8 && 8 % (nb_n / c) == 0 && w.grid % 8 == 0 && (w.grid / 8) % c == 0) w.coloc = c;
+  }
+  // split tail (see `item` in the kernel; config bit 25 switches it ON — measured 15 - 30 us slower per c4 launch than leaving
+  // the last round ragged: the slab round trip costs what the balance gains, profiles/r06_winp_study.md): the leftover tiles of the last round in S slices
+  // each — S the largest divisor of the chunk count with L * S <= grid and an even number (>= 2) of chunks per slice
+  w.split_S = 1, w.split_L = 0, w.split_v0 = 0;
+  {
+    const int KC = Ci / 16, L = w.n_tiles % w.grid;
+    int holes = 0;
+    if (w.coloc > 1) holes = w.nb_m % (8 / ((Co / 64) / w.coloc));  // (`coords` with co-located columns: index space = tiles only then)
+    if (L > 0 && w.n_tiles > w.grid && !holes && (config & 33554432)) {
+      int S = 1;
+      for (int d = 2; d <= 8 && d <= KC && d * L <= w.grid; d += 2)  // (even: the combine reads slabs in pairs)
+        if (KC % d == 0 && (KC / d) % 2 == 0) S = d;
+      if (S > 1) w.split_S = S, w.split_L = L, w.split_v0 = w.n_tiles - L;
+    }
+  }
+  return w;
+}
+
+// tile shape of the strided form
+static int strided_tile_rule(int64_t Co) { return Co <= 64 ? 5 : 4; }
+
+template <typename CFG>
+static int launch_winp(const ConvGeom& g, const void* Ah, const void* Al, const void* Wh /* chunk-major */, const void* Wl, const int* a_sexp,
+                       const int* w_sexp, unsigned* amax_out, hipStream_t stream, const ConvVjp* fz, int config, int wt0, int wtstep) {
   WinPArgs p;
   const int64_t M = (int64_t)g.N * g.Hi * g.Wi;
+  const WinpPlan w = winp_plan(CFG::BM, CFG::WG_PER_CU, M, g.Ci, g.Co, config, cu_count());
   p.M = (int)M, p.Hi = g.Hi, p.Wi = g.Wi, p.Ci = g.Ci, p.Co = g.Co, p.HW = g.Hi * g.Wi;
-  p.nb_m = (int)((M + CFG::BM - 1) / CFG::BM);
-  p.n_tiles = p.nb_m * (g.Co / 64);
-  p.wt0 = wt[0], p.wtstep = step;
+  p.nb_m = w.nb_m;
+  p.n_tiles = w.n_tiles;
+  p.wt0 = wt0, p.wtstep = wtstep;
   p.div_hw = g.div_hw, p.div_w = g.div_w, p.div_mask = fz->div_mask;
   p.Ah = (const _Float16*)Ah, p.Al = (const _Float16*)Al, p.Wh = (const _Float16*)Wh, p.Wl = (const _Float16*)Wl;
   p.a_sexp = a_sexp, p.w_sexp = w_sexp, p.add_sexp = fz->add_sexp;
@@ -2050,7 +2142,7 @@ static bool launch_winp(const ConvGeom& g, const void* Ah, const void* Al, const
   p.stagger = 0;
   if ((config >> 20) & 31) p.stagger = ((config >> 20) & 31) - 1;  // (development: bits 20-24 = delay + 1)
   p.halo_all = (config >> 30) & 1;  // (development: stage the whole PP-pixel window as round 4 did)
-  p.coloc = 1;
+  p.coloc = w.coloc;
   p.out_h = fz->out_h, p.out_l = fz->out_l, p.out_sexp = fz->out_sexp;
   p.amax_out = amax_out;
   static bool attr_set = false;
@@ -2058,37 +2150,14 @@ static bool launch_winp(const ConvGeom& g, const void* Ah, const void* Al, const
     (void)hipFuncSetAttribute((const void*)conv_winp_f16x2_kernel<CFG>, hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS);
     attr_set = true;
   }
-  const int wg_per_cu = (config & 524288) ? 1 : CFG::WG_PER_CU;  // (development: bit 19 = one workgroup per CU)
-  if (wg_per_cu == 1) p.stagger = 0;
-  const int grid = p.n_tiles < wg_per_cu * cu_count() ? p.n_tiles : wg_per_cu * cu_count();  // two workgroups per CU
-  {
-    // columns of a pixel tile that share an XCD (see `coords` in the kernel): config bits 28-29 = log2, 0 = the default below
-    const int nb_n = g.Co / 64;
-    int c = 1 << ((config >> 28) & 3);
-    if (c == 1) c = coloc_default(g.Ci, g.Co);
-    if (c > 1 && c <= nb_n && nb_n % c == 0 && nb_n / c <= 8 && 8 % (nb_n / c) == 0 && grid % 8 == 0 && (grid / 8) % c == 0) p.coloc = c;
-  }
-  // split tail (see `item` in the kernel; config bit 25 switches it ON — measured 15 - 30 us slower per c4 launch than leaving
-  // the last round ragged: the slab round trip costs what the balance gains, profiles/r06_winp_study.md): the leftover tiles of the last round in S slices
-  // each — S the largest divisor of the chunk count with L * S <= grid and an even number (>= 2) of chunks per slice
+  if (w.wg_per_cu == 1) p.stagger = 0;
   p.split_S = 1, p.split_L = 0, p.split_v0 = 0, p.slabs = nullptr, p.arrivals = nullptr;
-  {
-    const int KC = g.Ci / 16, L = p.n_tiles % grid;
-    int holes = 0;
-    if (p.coloc > 1) holes = p.nb_m % (8 / ((g.Co / 64) / p.coloc));  // (`coords` with co-located columns: index space = tiles only then)
-    if (L > 0 && p.n_tiles > grid && !holes && (config & 33554432)) {
-      int S = 1;
-      for (int d = 2; d <= 8 && d <= KC && d * L <= grid; d += 2)  // (even: the combine reads slabs in pairs)
-        if (KC % d == 0 && (KC / d) % 2 == 0) S = d;
-      if (S > 1) {
-        WinpScratch* w = winp_scratch(stream, (size_t)cu_count() * wg_per_cu * 16 * CFG::NT * sizeof(float) * 4, cu_count() * wg_per_cu);
-        if (w) p.split_S = S, p.split_L = L, p.split_v0 = p.n_tiles - L, p.slabs = w->slabs, p.arrivals = w->arrivals;
-      }
-    }
+  if (w.split_S > 1) {  // (without its slabs the launch leaves the last round ragged)
+    WinpScratch* sc = winp_scratch(stream, (size_t)cu_count() * w.wg_per_cu * 16 * CFG::NT * sizeof(float) * 4, cu_count() * w.wg_per_cu);
+    if (sc) p.split_S = w.split_S, p.split_L = w.split_L, p.split_v0 = w.split_v0, p.slabs = sc->slabs, p.arrivals = sc->arrivals;
   }
-  hipLaunchKernelGGL((conv_winp_f16x2_kernel<CFG>), dim3((unsigned)grid), dim3(CFG::NT), CFG::LDS, stream, p);
-  *rc = check_launch("conv_winp_f16x2_kernel");
-  return true;
+  hipLaunchKernelGGL((conv_winp_f16x2_kernel<CFG>), dim3((unsigned)w.grid), dim3(CFG::NT), CFG::LDS, stream, p);
+  return check_launch("conv_winp_f16x2_kernel");
 }
 
 // One launch of the implicit GEMM.  `taps`: T x {dh, dw, weight slice}.
@@ -2110,52 +2179,28 @@ static int conv_dispatch(const void* in_h, const void* in_l, const int* in_sexp,
   for (int t = 0; t < 9; ++t) g.dh[t] = g.dw[t] = g.wt[t] = 0;
   for (int t = 0; t < T; ++t) g.dh[t] = taps[3 * t], g.dw[t] = taps[3 * t + 1], g.wt[t] = taps[3 * t + 2];
   g.div_hw = make_fastdiv((int)(Hc * Wc)), g.div_w = make_fastdiv((int)Wc), g.div_n = make_fastdiv((int)N);
-  // small maps: rows ordered (pixel, image) so that border taps drop out of whole tiles (config bit 15 turns it off)
-  g.pmajor = (Hc * Wc <= (64 << (2 * ((config >> 16) & 3))) && N >= 64 && !(config & 16) && !(config & 32768)) ? 1 : 0;
+  g.pmajor = conv_pmajor_rule(N, Hc, Wc, config);
   g.dense = out_step == 1 && oh0 == 0 && ow0 == 0 && Hc == Ho && Wc == Wo;
   g.out_nchw = (config & 16) ? 1 : 0;
   g.out_planes = (fz && fz->out_h && (config & 16)) ? 1 : 0;  // (fused launches never carry bit 4: conv_vjp_impl clears it)
   LK_REQUIRE(!g.out_nchw || (g.dense && (Ho * Wo) % 4 == 0 && !accumulate),
              "lk_conv_nhwc_f16x2: position-contiguous output needs a dense grid with Ho*Wo % 4 == 0 and no accumulate");
   hipStream_t st = (hipStream_t)stream;
-  // persistent window form (fused launches with 64 output channels whose caller also handed over chunk-major weights;
-  // config bit 27 switches it off): see conv_winp_f16x2_kernel
-  if (fz && !g.out_planes && !fz->fwd_y && fz->wc_h && !(config & 134217728) && lk_conv_winp_eligible(N, Hi, Wi, Ci, Co, T, fz->mask && fz->mask_float) &&
-      in_mul == 1 && Hc == Hi && Wc == Wi && g.dense) {
-    int rc = LK_OK;
-    if ((config & 67108864) && launch_winp<WinPCfg<512>>(g, in_h, in_l, fz->wc_h, fz->wc_l, in_sexp, w_sexp, amax_out, st, fz, &rc, config)) return rc;
-    if (launch_winp<WinPCfg<256>>(g, in_h, in_l, fz->wc_h, fz->wc_l, in_sexp, w_sexp, amax_out, st, fz, &rc, config)) return rc;
+  // persistent window form: see winp_route, conv_winp_f16x2_kernel
+  {
+    int wt0 = 0, step = 0;
+    const int win = winp_route(fz && !g.out_planes && !fz->fwd_y, fz && fz->wc_h, config, N, Hi, Wi, Ci, Co, T, fz && fz->mask && fz->mask_float,
+                               in_mul, Hc, Wc, g.dense, g.dh, g.dw, g.wt, &wt0, &step);
+    if (win == 512) return launch_winp<WinPCfg<512>>(g, in_h, in_l, fz->wc_h, fz->wc_l, in_sexp, w_sexp, amax_out, st, fz, config, wt0, step);
+    if (win == 256) return launch_winp<WinPCfg<256>>(g, in_h, in_l, fz->wc_h, fz->wc_l, in_sexp, w_sexp, amax_out, st, fz, config, wt0, step);
   }
 #define LK_CONV_GO(...) return launch_conv<ConvCfg<__VA_ARGS__>>(g, in_h, in_l, w_h, w_l, in_sexp, w_sexp, zero16, out, accumulate, amax_out, st, fz)
-  switch ((config >> 12) & 7) {  // explicit tile shape (bits 12..14; the tests walk through them); 0: chosen below
+  switch (conv_tile_rule(N * Hc * Wc, Co, config)) {  // (the template arguments of kConvTile's rows)
     case 1: LK_CONV_GO(64, 64, 32, 2, 2, 2, 4);
     case 2: LK_CONV_GO(128, 64, 32, 2, 2, 2, 3);
     case 3: LK_CONV_GO(64, 128, 32, 2, 2, 2, 3);
     case 4: LK_CONV_GO(128, 128, 32, 2, 2);
-    case 5: LK_CONV_GO(256, 64, 32, 4, 1);
-    default: break;
-  }
-  {
-    // Tile shape by occupancy (measured on the c4 layer shapes, profiles/r02_conv_tile_sweep.json): the big tile
-    // (2 workgroups per CU = 512 slots) when it fills the chip and its last round is not mostly idle; otherwise the
-    // half tile (3 per CU) if that gives >= 512 tiles; otherwise 64 x 64 (the forward of the deep, small-map layers at
-    // batch 128 has only 64-128 big tiles).  A pure function of the shapes: the same launch always takes the same tile.
-    const int64_t M = N * Hc * Wc;
-    auto tiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((Co + bn - 1) / bn); };
-    const bool narrow = Co <= 64;
-    const int64_t tb = narrow ? tiles(256, 64) : tiles(128, 128);
-    const int64_t rounds = (tb + 511) / 512;
-    const bool big_ok = tb >= 512 && tb * 100 >= rounds * 512 * 74;
-    if (!big_ok) {
-      const int64_t tm = narrow ? tiles(128, 64) : tiles(64, 128);
-      if (tm >= 512) {
-        if (narrow) LK_CONV_GO(128, 64, 32, 2, 2, 2, 3);
-        LK_CONV_GO(64, 128, 32, 2, 2, 2, 3);
-      }
-      LK_CONV_GO(64, 64, 32, 2, 2, 2, 4);
-    }
-    if (narrow) LK_CONV_GO(256, 64, 32, 4, 1);
-    LK_CONV_GO(128, 128, 32, 2, 2);
+    default: LK_CONV_GO(256, 64, 32, 4, 1);
   }
 #undef LK_CONV_GO
 }
@@ -2168,6 +2213,53 @@ extern "C" int lk_conv_winp_eligible(int64_t N, int64_t Hi, int64_t Wi, int64_t 
                  N * Hi * Wi * Co < (1ll << 31) && N * Hi * Wi >= 512 && !mask_is_float
              ? 1
              : 0;
+}
+
+// Which kernel, tile, epilogue and grid a launch of the entry points above takes: what conv_dispatch decides, from the same
+// helpers, without a launch (include/laplace_hip.h).  `entry`: LK_CONV_PLAIN / _PLANES / _BN_ACT / _VJP; the three dense entry
+// points ignore Hc, Wc, out_step, oh0, ow0 (their grid is the output tensor) and _VJP also in_mul (1).
+extern "C" int lk_conv_launch_variant(int entry, int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t Hc, int64_t Wc,
+                                      int64_t in_mul, int64_t Ho, int64_t Wo, int64_t out_step, int64_t oh0, int64_t ow0, int64_t T,
+                                      const int* taps, int64_t in_nsexp, int have_wc, int mask_is_float, int config, int* out) {
+  if (!out || !taps || entry < 0 || entry > 3) return -1;
+  if (entry != 0) Hc = Ho, Wc = Wo, out_step = 1, oh0 = 0, ow0 = 0;
+  if (entry == 3) in_mul = 1;
+  config = entry == 1 ? (config | 16) : (entry == 0 ? config : (config & ~16));
+  // the shapes the entry points refuse
+  if (!(T >= 1 && T <= 9 && Ci >= 32 && Ci % 32 == 0 && Co >= 1 && N >= 1)) return -1;
+  if (Hi < 1 || Wi < 1 || Hc < 0 || Wc < 0 || Ho < 1 || Wo < 1 || in_mul < 1 || out_step < 1) return -1;
+  if (!(N * Hc * Wc < (1ll << 31) && N * Hi * Wi * Ci < (1ll << 40))) return -1;
+  if (!(in_nsexp == 1 || (in_nsexp == N && entry != 3))) return -1;
+  if (entry == 1 && (Ho * Wo) % 16 != 0) return -1;
+  if ((entry == 2 || entry == 3) && Co % 8 != 0) return -1;
+  if (entry == 2 && !(N * Ho * Wo * Co < (1ll << 40))) return -1;
+  const bool dense = out_step == 1 && oh0 == 0 && ow0 == 0 && Hc == Ho && Wc == Wo;
+  if ((config & 16) && !(dense && (Ho * Wo) % 4 == 0)) return -1;
+  if (Hc == 0 || Wc == 0) return -1;  // (nothing is launched)
+  int dh[9] = {0}, dw[9] = {0}, wt[9] = {0};
+  for (int t = 0; t < T; ++t) dh[t] = taps[3 * t], dw[t] = taps[3 * t + 1], wt[t] = taps[3 * t + 2];
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  out[3] = entry == 0 ? 0 : entry == 1 ? 1 : entry == 3 ? 2 : 3;  // epilogue: plain / planes / VJP / forward
+  out[4] = conv_pmajor_rule(N, Hc, Wc, config), out[5] = dense ? 1 : 0;
+  out[9] = 1, out[10] = 1;
+  out[14] = (config & 16) ? 1 : 0;
+  int wt0 = 0, step = 0;
+  const int win = winp_route(entry == 3, have_wc != 0, config, N, Hi, Wi, Ci, Co, T, mask_is_float != 0, in_mul, Hc, Wc, dense, dh, dw,
+                             wt, &wt0, &step);
+  if (win) {
+    const WinpPlan w = win == 512 ? winp_plan(512, WinPCfg<512>::WG_PER_CU, N * Hi * Wi, (int)Ci, (int)Co, config, cu_count())
+                                  : winp_plan(256, WinPCfg<256>::WG_PER_CU, N * Hi * Wi, (int)Ci, (int)Co, config, cu_count());
+    out[0] = win == 512 ? 2 : 1, out[1] = win, out[2] = 64;
+    out[4] = 0;  // (the window form walks (image, pixel) rows)
+    out[6] = w.grid, out[7] = w.nb_m, out[8] = (int)(Co / 64), out[9] = w.coloc, out[10] = w.split_S, out[11] = w.split_L;
+    out[12] = w.wg_per_cu, out[13] = w.n_tiles;
+    return 0;
+  }
+  const int tile = conv_tile_rule(N * Hc * Wc, Co, config);
+  const int bm = kConvTile[tile][0], bn = kConvTile[tile][1];
+  const int nb_m = (int)((N * Hc * Wc + bm - 1) / bm), nb_n = (int)((Co + bn - 1) / bn);
+  out[0] = 0, out[1] = bm, out[2] = bn, out[6] = nb_m * nb_n, out[7] = nb_m, out[8] = nb_n, out[13] = nb_m * nb_n;
+  return 0;
 }
 
 extern "C" int lk_conv_nhwc_f16x2(const void* in_h, const void* in_l, const int* in_sexp, int64_t in_nsexp, int64_t N, int64_t Hi,
@@ -2378,6 +2470,32 @@ extern "C" int lk_conv_nhwc_f16x2_vjp_strided(
   fz.out_h = (_Float16*)out_h, fz.out_l = (_Float16*)out_l, fz.out_sexp = out_sexp;
   fz.wc_h = fz.wc_l = nullptr;
   hipStream_t st = (hipStream_t)stream;
-  if (Co <= 64) return launch_strided<ConvCfg<256, 64, 32, 4, 1>>(g, s1, s2, zero16, (unsigned*)out_amax, st, fz);
+  if (strided_tile_rule(Co) == 5) return launch_strided<ConvCfg<256, 64, 32, 4, 1>>(g, s1, s2, zero16, (unsigned*)out_amax, st, fz);
   return launch_strided<ConvCfg<128, 128, 32, 2, 2>>(g, s1, s2, zero16, (unsigned*)out_amax, st, fz);
+}
+
+// lk_conv_launch_variant for lk_conv_nhwc_f16x2_vjp_strided: `taps` as there (T x 6 ints; their classes are counted)
+extern "C" int lk_conv_strided_launch_variant(int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t Ho, int64_t Wo, int64_t os,
+                                              int64_t T, const int* taps, int two_sources, int* out) {
+  if (!out || !taps) return -1;
+  if (!(os >= 1 && os <= 2 && Ho % os == 0 && Wo % os == 0 && Hi == Ho / os && Wi == Wo / os)) return -1;
+  if (!(T >= 1 && T <= 12 && Ci >= 32 && Ci % 32 == 0 && Co >= 8 && Co % 8 == 0 && N >= 1 && Hi >= 1 && Wi >= 1)) return -1;
+  if (!(N * Ho * Wo < (1ll << 31) && N * Ho * Wo * Co < (1ll << 40) && N * Hi * Wi * Ci < (1ll << 40))) return -1;
+  bool cls[2][2] = {{false, false}, {false, false}};
+  for (int t = 0; t < T; ++t) {
+    const int* p = taps + 6 * t;
+    if (!(p[3] == 0 || (p[3] == 1 && two_sources)) || p[4] < 0 || p[4] >= os || p[5] < 0 || p[5] >= os) return -1;
+    cls[p[4]][p[5]] = true;
+  }
+  int ncls = 0;
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) ncls += cls[a][b] ? 1 : 0;
+  if (ncls != os * os) return -1;
+  const int tile = strided_tile_rule(Co);
+  const int bm = kConvTile[tile][0], bn = kConvTile[tile][1];
+  const int nb_m = (int)((N * Hi * Wi + bm - 1) / bm), nb_n = (int)((Co + bn - 1) / bn);
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  out[0] = 3, out[1] = bm, out[2] = bn, out[3] = 2, out[5] = os == 1 ? 1 : 0, out[6] = nb_m * ncls * nb_n, out[7] = nb_m, out[8] = nb_n;
+  out[9] = 1, out[10] = 1, out[13] = out[6], out[15] = ncls;
+  return 0;
 }

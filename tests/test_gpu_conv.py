@@ -1,7 +1,7 @@
 """The split-fp16 implicit-GEMM convolution (csrc/lk_conv.hip, laplace_amd/conv.py) against fp64 convolutions of the
 same operands: backward-data on the ten convolution shapes of ResNet-18 (config c4: 3x3 stride 1 and 2, 1x1 stride 2,
 64...512 channels, 32x32...4x4 maps), the forward form, the residual accumulate mode, and the split itself.
-Tolerance: 1e-4 of the largest element (BASELINE.json); the measured errors are ~1e-6.  -m gpu only."""
+Tolerance: 1e-5 of the largest element (BASELINE.json asks for 1e-4); the measured errors are ~1e-6.  -m gpu only."""
 import pytest
 import torch
 import torch.nn.functional as F
