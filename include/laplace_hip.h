@@ -403,6 +403,38 @@ int lk_jac_conv_f32(const float* x_nchw, const float* g, int64_t B, int64_t Cc, 
 int lk_jac_norm_affine_f32(const float* g, const float* xhat, int64_t S, int64_t B, int64_t L, int64_t Ch, int layout,
                            float* Js, int64_t P, int64_t wcol0, int64_t bcol0, void* stream);
 
+/* Forward and input VJP of the per-sample normalisation layers (nn.GroupNorm, nn.LayerNorm) for the seed-batched reverse
+ * sweep; they replace the reverse passes through these layers of laplace/curvature/curvlinops.py:87-100 (the KFAC backward)
+ * and of the jacrev materialisation of CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129 (one stock
+ * autograd pass per seed).  Geometry as lk_jac_norm_affine_f32: layout 0 is [B][Ch][L], layout 1 is [B][L][Ch]; a statistics
+ * row is (n, group) with N = (Ch / G) * L elements.  nn.GroupNorm(G, Ch) is either layout with that G; nn.LayerNorm is
+ * layout 1 with B = product of the leading dims, L = 1, Ch = prod(normalized_shape), G = 1.
+ *
+ * lk_norm_fwd_f32: biased variance by the mean-shifted two-pass form, rstd = 1 / sqrt(var + eps), xhat = (x - mu) * rstd,
+ *   y = w[ch] * xhat + b[ch]; w and b may be null (no affine).  rstd is [B * G].  Always a lane group per statistics row: in
+ *   layout 1 with L > 1 and Ch / G not a multiple of 4 it reads 4 bytes per lane (DESIGN.md has the measured cost).
+ * lk_norm_vjp_f32: g is [S][B].. in the layout of xhat (ONE xhat and rstd per sample for all seeds):
+ *   t = w * g;  m1 = mean_row(t);  m2 = mean_row(t * xhat);  dx = rstd * (t - m1 - xhat * m2)
+ *   w may be null.  amax, when given, receives max|dx| as the bit pattern of a non-negative float through atomicMax (as
+ *   amax_out of lk_conv_nhwc_f16x2); the caller zeroes it.  dx must not overlap g.  Deterministic: one owner per element,
+ *   fixed reduction trees, plain stores.
+ * Contract of both: layout 0 or 1; G >= 1 divides Ch; 1 <= S < 2^31, 0 <= B < 2^31, 1 <= L, Ch < 2^30, N < 2^31; B == 0
+ * returns LK_OK.
+ * lk_norm_sweep_variant (host only): the kernel and path lk_norm_vjp_f32 takes for a shape; `aligned`: g, xhat and dx are
+ * 16-byte aligned.  Returns
+ *   kernel | vec << 1 | two-pass << 2 | seed-split << 3 | lanes << 4 | groups << 16
+ *   kernel: LK_NORMVJP_ROW (a lane group per statistics row) or LK_NORMVJP_TILE (layout 1 with narrow groups: a workgroup owns
+ *   `groups` adjacent groups of a sample); vec: 16-byte loads; two-pass: the row does not stay on chip, g is read twice;
+ *   seed-split: the seeds are split over grid.y; lanes: per row (ROW) or across the channel vectors (TILE)
+ * or a negative value for a shape the entry point refuses. */
+#define LK_NORMVJP_ROW 0
+#define LK_NORMVJP_TILE 1
+int lk_norm_fwd_f32(const float* x, const float* w, const float* b, int64_t B, int64_t L, int64_t Ch, int64_t G, int layout,
+                    float eps, float* y, float* xhat, float* rstd, void* stream);
+int lk_norm_vjp_f32(const float* g, const float* xhat, const float* rstd, const float* w, int64_t S, int64_t B, int64_t L,
+                    int64_t Ch, int64_t G, int layout, float* dx, unsigned* amax, void* stream);
+int lk_norm_sweep_variant(int64_t S, int64_t B, int64_t L, int64_t Ch, int64_t G, int layout, int aligned);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

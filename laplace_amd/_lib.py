@@ -113,6 +113,9 @@ SIGNATURES = {
     ),
     "lk_sq_colsum_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
     "lk_jac_norm_affine_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _i64, _vp]),
+    "lk_norm_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp]),
+    "lk_norm_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "lk_norm_sweep_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
     "lk_bn_act_fwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_vjp_scale_mask_f32": (_int, [_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_ll_ggn_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1197,6 +1200,67 @@ class HipKernels:
                                             int(wcol0), int(bcol0), self._stream(g.device)),
             "lk_jac_norm_affine_f32",
         )
+
+    @staticmethod
+    def _norm_geometry(x, B, G, layout, what):
+        """``(L, Ch)`` of a per-sample normalisation over ``x`` = ``[B, Ch, L..]`` (layout 0) / ``[B, L.., Ch]`` (layout 1)"""
+        if x.dim() < 2 or x.shape[0] != B:
+            raise LaplaceHipError(f"{what}: expected [B, Ch, ...] / [B, ..., Ch]")
+        Ch = int(x.shape[1] if layout == 0 else x.shape[-1])
+        L = x.numel() // max(B * Ch, 1) if x.numel() else 1
+        if G < 1 or Ch % G or layout not in (0, 1):
+            raise LaplaceHipError(f"{what}: G must divide the {Ch} channels; layout is 0 or 1")
+        return max(L, 1), Ch
+
+    def norm_forward(self, x, w, b, G, layout, eps):
+        """``(y, xhat, rstd)`` of a per-sample normalisation (csrc/lk_normvjp.hip): statistics over the rows ``(n, group)`` of
+        ``x`` = ``[B, Ch, L..]`` (``layout`` 0) or ``[B, L.., Ch]`` (``layout`` 1), ``y = w[ch] * xhat + b[ch]`` (``w``, ``b``
+        may be None), ``rstd`` ``[B, G]``.  nn.LayerNorm: ``x`` reshaped to ``[rows, D]``, layout 1, ``G = 1``."""
+        _check(x, "x")
+        B = x.shape[0]
+        L, Ch = self._norm_geometry(x, B, int(G), int(layout), "norm_forward")
+        for t, name in ((w, "w"), (b, "b")):
+            if t is not None:
+                _check(t, name)
+                if t.numel() != Ch:
+                    raise LaplaceHipError(f"norm_forward: {name} must have {Ch} elements")
+        y, xhat = torch.empty_like(x), torch.empty_like(x)
+        rstd = torch.empty(B, int(G), dtype=torch.float32, device=x.device)
+        self._rc(self.lib.lk_norm_fwd_f32(_ptr(x), _ptr(w), _ptr(b), B, L, Ch, int(G), int(layout), float(eps), _ptr(y),
+                                          _ptr(xhat), _ptr(rstd), self._stream(x.device)), "lk_norm_fwd_f32")
+        return y, xhat, rstd
+
+    def norm_vjp(self, g, xhat, rstd, w, S, G, layout, amax=None):
+        """``dx`` of a per-sample normalisation for the ``S`` seeds stacked in ``g`` (``[S*B, ...]`` in the layout of ``xhat``
+        ``[B, ...]``): ``t = w * g``, ``dx = rstd * (t - mean_row(t) - xhat * mean_row(t * xhat))``.  ``amax``: zeroed device
+        word that receives the bit pattern of max|dx|."""
+        _check(g, "g"), _check(xhat, "xhat"), _check(rstd, "rstd")
+        B = xhat.shape[0]
+        L, Ch = self._norm_geometry(xhat, B, int(G), int(layout), "norm_vjp")
+        if g.numel() != int(S) * xhat.numel() or rstd.numel() != B * int(G):
+            raise LaplaceHipError("norm_vjp: g [S*B, ...], xhat [B, ...] and rstd [B, G] do not match")
+        if w is not None:
+            _check(w, "w")
+            if w.numel() != Ch:
+                raise LaplaceHipError(f"norm_vjp: w must have {Ch} elements")
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("norm_vjp: amax is one 32-bit device word")
+        dx = torch.empty_like(g)
+        self._rc(self.lib.lk_norm_vjp_f32(_ptr(g), _ptr(xhat), _ptr(rstd), _ptr(w), int(S), B, L, Ch, int(G), int(layout),
+                                          _ptr(dx), _ptr(amax), self._stream(g.device)), "lk_norm_vjp_f32")
+        return dx
+
+    #: ``kernel`` of :meth:`norm_sweep_variant` (LK_NORMVJP_* of include/laplace_hip.h)
+    NORMVJP_ROW, NORMVJP_TILE = 0, 1
+
+    def norm_sweep_variant(self, S, B, L, Ch, G, layout, aligned=True):
+        """lk_norm_sweep_variant: the kernel and path ``lk_norm_vjp_f32`` takes for a shape (host only, no device call), or
+        ``None`` for a shape it refuses."""
+        r = int(self.lib.lk_norm_sweep_variant(int(S), int(B), int(L), int(Ch), int(G), int(layout), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"kernel": r & 1, "vec": bool(r & 2), "two_pass": bool(r & 4), "seed_split": bool(r & 8), "lanes": (r >> 4) & 0xFFF,
+                "groups": r >> 16, "layout": int(layout)}
 
     def sq_colsum(self, Js, col0, width, alpha, h):
         _check(Js, "Js"), _check(h, "h")

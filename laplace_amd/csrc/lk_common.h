@@ -70,6 +70,22 @@ __device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
 
+// ---- launch shapes of the row-streaming kernels (lk_norm.hip, lk_normvjp.hip) ----
+static inline int pow2_ceil(int64_t v, int cap) {
+  int p = 1;
+  while (p < v && p < cap) p <<= 1;
+  return p;
+}
+
+// seeds per grid.y slice: all of them unless the rows alone leave the device short of waves
+static inline int seeds_per_slice(int64_t S, int64_t waves) {
+  const int64_t want = 2048;  // 256 CUs x 8 waves
+  int64_t slices = waves >= want ? 1 : (want + waves - 1) / (waves > 0 ? waves : 1);
+  if (slices > S) slices = S;
+  if (slices > 65535) slices = 65535;
+  return (int)((S + slices - 1) / slices);
+}
+
 }  // namespace lk
 
 #define LK_REQUIRE(cond, ...)            \

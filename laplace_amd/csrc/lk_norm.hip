@@ -171,21 +171,6 @@ __global__ __launch_bounds__(256) void jac_norm_cl_kernel(const float* __restric
   }
 }
 
-static inline int pow2_ceil(int64_t v, int cap) {
-  int p = 1;
-  while (p < v && p < cap) p <<= 1;
-  return p;
-}
-
-// seeds per grid.y slice: all of them unless the rows alone leave the device short of waves
-static inline int seeds_per_slice(int64_t S, int64_t waves) {
-  const int64_t want = 2048;  // 256 CUs x 8 waves
-  int64_t slices = waves >= want ? 1 : (want + waves - 1) / (waves > 0 ? waves : 1);
-  if (slices > S) slices = S;
-  if (slices > 65535) slices = 65535;
-  return (int)((S + slices - 1) / slices);
-}
-
 }  // namespace lk
 
 using namespace lk;

@@ -11,17 +11,29 @@ import torch
 from torch import nn
 
 
+NORM_LAYERS = (nn.BatchNorm2d, nn.GroupNorm)
+
+
+def norm_layer(norm: str, channels: int) -> nn.Module:
+    """``"bn"``: ``BatchNorm2d``; ``"gn"``: ``GroupNorm(32, channels)`` (the usual BatchNorm-free ResNet of Bayesian deep learning)"""
+    if norm == "bn":
+        return nn.BatchNorm2d(channels)
+    if norm == "gn":
+        return nn.GroupNorm(32, channels)
+    raise ValueError(f"norm must be 'bn' or 'gn', got {norm!r}")
+
+
 class BasicBlock(nn.Module):
-    def __init__(self, cin: int, cout: int, stride: int, act=torch.relu):
+    def __init__(self, cin: int, cout: int, stride: int, act=torch.relu, norm: str = "bn"):
         super().__init__()
         self.act = act
         self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(cout)
+        self.bn1 = norm_layer(norm, cout)
         self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(cout)
+        self.bn2 = norm_layer(norm, cout)
         self.downsample = None
         if stride != 1 or cin != cout:
-            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), norm_layer(norm, cout))
 
     def forward(self, x):
         out = self.act(self.bn1(self.conv1(x)))
@@ -38,23 +50,26 @@ class ResNet18(nn.Module):
     ``freeze_bn=True`` is needed for KFAC only (the reference has no Kronecker factors for normalisation parameters and
     refuses them, as this backend does).  With ``freeze_bn=False`` the 9 600 BatchNorm weights and biases are Laplace
     parameters like any other: ``jacobians`` / ``diag`` / ``full`` / the EF / the diagonal predictive serve them on the
-    device in eval mode (csrc/lk_norm.hip)."""
+    device in eval mode (csrc/lk_norm.hip).
 
-    def __init__(self, num_classes: int = 10, freeze_bn: bool = True, act=torch.relu):
+    ``norm="gn"`` puts ``GroupNorm(32, C)`` wherever a BatchNorm is (same attribute names; ``freeze_bn`` freezes its affine
+    parameters alike).  Its reverse sweep goes through csrc/lk_normvjp.hip."""
+
+    def __init__(self, num_classes: int = 10, freeze_bn: bool = True, act=torch.relu, norm: str = "bn"):
         super().__init__()
         self.act = act
         self.conv1 = nn.Conv2d(3, 64, 3, 1, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(64)
+        self.bn1 = norm_layer(norm, 64)
         blocks, cin = [], 64
         for cout, stride in ((64, 1), (64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1)):
-            blocks.append(BasicBlock(cin, cout, stride, act))
+            blocks.append(BasicBlock(cin, cout, stride, act, norm))
             cin = cout
         self.layers = nn.Sequential(*blocks)
         self.pool = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(512, num_classes)
         if freeze_bn:
             for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
+                if isinstance(m, NORM_LAYERS):
                     m.weight.requires_grad_(False)
                     m.bias.requires_grad_(False)
 

@@ -9,7 +9,9 @@ element-wise kernels per step.  This module is the "fused host-side extraction" 
 * the forward is executed node by node on the ``B`` samples, keeping only what a vector-Jacobian
   product needs (ReLU masks, pooling indices, BatchNorm-eval scales, ...);
 * the reverse sweep pushes a cotangent of batch ``S*B`` (seed-major) through closed-form VJP rules:
-  one MIOpen backward-data call per conv for *all* seeds, one element-wise kernel per activation.
+  one MIOpen backward-data call per conv for *all* seeds, one element-wise kernel per activation, one row-reduction kernel
+  per GroupNorm / LayerNorm (csrc/lk_normvjp.hip: these normalise with per-sample statistics, so their VJP is a reduction per
+  statistics row that reuses one ``xhat`` / ``rstd`` per sample for all seeds).
 
 It produces exactly what :class:`laplace_amd.capture.Tape` produces (layer inputs ``a`` and output
 gradients ``g`` per tapped module), so everything downstream is unchanged.  Unsupported graphs
@@ -33,9 +35,9 @@ class SweepUnsupported(RuntimeError):
 
 
 # canonical node kinds ("placeholder" / "output" nodes carry their fx op as kind)
-CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM = (
+CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM, NORM = (
     "conv", "linear", "batch-norm", "activation", "identity", "reshape", "adaptive-avg-pool", "avg-pool", "max-pool",
-    "mean", "add", "size", "getitem")
+    "mean", "add", "size", "getitem", "per-sample-norm")
 
 
 class Rule(NamedTuple):
@@ -47,7 +49,7 @@ class Rule(NamedTuple):
     call: tuple = ((), {})  # ``(args, kwargs)`` of ``fn`` as fx arguments (nodes and constants)
     what: str = ""  # the operation as messages name it
     flavour: str | None = None  # ACT: "relu" | "tanh" | "sigmoid" | "generic"
-    mod: nn.Module | None = None  # CONV / LINEAR / BN: the module
+    mod: nn.Module | None = None  # CONV / LINEAR / BN / NORM: the module
     args: tuple = ()  # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written
 
 
@@ -61,6 +63,8 @@ _GENERIC_ACT_FN = (F.gelu, F.silu, F.leaky_relu, F.elu, F.softplus, F.hardtanh, 
 # the three spellings of an operation -> (kind, activation flavour); adding an operation starts here
 _MODULE_KINDS = (
     ((nn.Conv2d,), CONV, None), ((nn.Linear,), LINEAR, None), ((nn.BatchNorm2d, nn.BatchNorm1d), BN, None),
+    # (normalisation with per-sample statistics; the functional spellings read their weights through `get_attr` and stay refused)
+    ((nn.GroupNorm, nn.LayerNorm), NORM, None),
     ((nn.ReLU,), ACT, "relu"), ((nn.Tanh,), ACT, "tanh"), ((nn.Sigmoid,), ACT, "sigmoid"),
     (_GENERIC_ACT_MODULES, ACT, "generic"), ((nn.Identity, nn.Dropout), IDENTITY, None), ((nn.Flatten,), RESHAPE, None),
     ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None))
@@ -142,7 +146,61 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == MEAN:
         static = (kwargs.get("dim", args[1] if len(args) > 1 else None),
                   kwargs.get("keepdim", args[2] if len(args) > 2 else False))
-    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN) else None, static)
+    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
+
+
+def norm_geometry(m, inp):
+    """``(view, G, layout)`` of a per-sample normalisation layer on ``inp`` in the convention of csrc/lk_normvjp.hip:
+    nn.GroupNorm is ``[B, Ch, L]`` (layout 0) with its own ``G``; nn.LayerNorm is ``[rows, 1, D]`` (layout 1, ``L = 1``) with
+    ``rows`` the product of the leading dims, ``D = prod(normalized_shape)`` and ``G = 1`` (as ``backend._norm_xhat``)."""
+    if isinstance(m, nn.GroupNorm):
+        if inp.dim() < 2 or inp.shape[1] != m.num_channels:
+            raise SweepUnsupported(f"GroupNorm({m.num_groups}, {m.num_channels}) on an input of shape {tuple(inp.shape)}")
+        return (inp.shape[0], m.num_channels, max(inp.numel() // max(inp.shape[0] * m.num_channels, 1), 1)), m.num_groups, 0
+    D = 1
+    for d in m.normalized_shape:
+        D *= int(d)
+    if tuple(inp.shape[inp.dim() - len(m.normalized_shape):]) != tuple(m.normalized_shape):
+        raise SweepUnsupported(f"LayerNorm({tuple(m.normalized_shape)}) on an input of shape {tuple(inp.shape)}")
+    return (inp.numel() // D, 1, D), 1, 1
+
+
+def _norm_rows(t, G, layout):
+    """``[.., B, Ch, L]`` / ``[.., B, L, Ch]`` -> the statistics rows ``[.., B, G, Ch / G, L]`` / ``[.., B, L, G, Ch / G]``,
+    the dims a row reduces over, and the shape the affine vectors broadcast in"""
+    if layout == 0:
+        Ch, L = t.shape[-2], t.shape[-1]
+        return t.reshape(*t.shape[:-2], G, Ch // G, L), (-2, -1), (G, Ch // G, 1)
+    L, Ch = t.shape[-2], t.shape[-1]
+    return t.reshape(*t.shape[:-2], L, G, Ch // G), (-3, -1), (1, G, Ch // G)
+
+
+def norm_forward_math(x, w, b, G, layout, eps):
+    """``(y, xhat, rstd)`` of csrc/lk_normvjp.hip's forward in plain torch (any dtype): ``x`` is ``[B, Ch, L]`` (layout 0) or
+    ``[B, L, Ch]`` (layout 1); mean-shifted biased variance, ``rstd`` ``[B, G]``."""
+    xr, dims, wshape = _norm_rows(x, G, layout)
+    mu = xr.mean(dims, keepdim=True)
+    d = xr - mu
+    rstd = 1.0 / torch.sqrt((d * d).mean(dims, keepdim=True) + eps)
+    xhat = d * rstd
+    # (``y`` never shares storage with ``xhat``: an in-place op behind the layer - ReLU(inplace=True), ``out += identity`` -
+    # writes into ``y``, and ``xhat`` is kept for the VJP)
+    y = xhat * w.detach().reshape(wshape) if w is not None else xhat.clone()
+    if b is not None:
+        y = y + b.detach().reshape(wshape)
+    return y.reshape(x.shape), xhat.reshape(x.shape), rstd.reshape(x.shape[0], G)
+
+
+def norm_vjp_math(g, xhat, rstd, w, S, G, layout):
+    """``dx = rstd * (t - mean_row(t) - xhat * mean_row(t * xhat))``, ``t = w * g``, for the ``S`` seeds stacked in ``g``
+    (``[S*B, ..]`` in the layout of ``xhat`` ``[B, ..]``) - the formula of lk_norm_vjp_f32 in plain torch"""
+    xr, dims, wshape = _norm_rows(xhat, G, layout)
+    t, _, _ = _norm_rows(g.reshape(S, *xhat.shape), G, layout)
+    if w is not None:
+        t = t * w.detach().reshape(wshape)
+    rs = rstd.reshape(rstd.shape[0], G, 1, 1) if layout == 0 else rstd.reshape(rstd.shape[0], 1, G, 1)
+    dx = rs * (t - t.mean(dims, keepdim=True) - xr * (t * xr).mean(dims, keepdim=True))
+    return dx.reshape(g.shape)
 
 
 class SeedBatchedSweep:
@@ -230,6 +288,9 @@ class SeedBatchedSweep:
                     fused_relu[nxt] = (out, mask)
             elif kind == CONV:
                 out, keep = self._run_conv(node, r.mod, inp), inp.shape
+            elif kind == NORM:
+                out, keep = self._run_norm(node, r.mod, inp)
+                keep = keep if need_vjp else None
             elif kind == MAXPOOL:
                 out, idx = r.fn(*args)
                 keep = (idx, inp.shape)
@@ -273,6 +334,38 @@ class SeedBatchedSweep:
     def _run_bn_act(self, node, inp, scale, shift, relu, addend, want_mask):
         return self.kernels().bn_act_forward(inp.contiguous(), scale, shift, relu,
                                              None if addend is None else addend.contiguous(), want_mask=want_mask)
+
+    def _norm_kernels(self, t):
+        """the kernel object when it serves per-sample normalisation of ``t`` (fp32 and an object with the entry points; the
+        stock emulation has none), else ``None``: plain torch math with the same formula"""
+        K = self.kernels() if self.kernels is not None else None
+        return K if K is not None and hasattr(K, "norm_forward") and t.dtype == torch.float32 else None
+
+    def _run_norm(self, node, m, inp):
+        """GroupNorm / LayerNorm forward -> ``(out, (xhat, rstd, G, layout))``: what the VJP needs is one normalised input
+        and one ``rstd`` per statistics row, shared by all seeds (csrc/lk_normvjp.hip)"""
+        view, G, layout = norm_geometry(m, inp)
+        x = inp.contiguous().reshape(view)
+        K = self._norm_kernels(x)
+        w = None if m.weight is None else m.weight.detach().reshape(-1)
+        b = None if m.bias is None else m.bias.detach().reshape(-1)
+        if K is not None:
+            y, xhat, rstd = K.norm_forward(x, None if w is None else w.contiguous(), None if b is None else b.contiguous(),
+                                           G, layout, m.eps)
+        else:
+            y, xhat, rstd = norm_forward_math(x, w, b, G, layout, m.eps)
+        return y.reshape(inp.shape), (xhat, rstd, G, layout)
+
+    def _norm_vjp(self, m, saved, g, S):
+        """input cotangent of a GroupNorm / LayerNorm for all seeds: ONE launch of lk_norm_vjp_f32 (or the same formula in
+        torch); ``g`` is ``[S*B, ...]``"""
+        xhat, rstd, G, layout = saved
+        K = self._norm_kernels(g)
+        w = None if m.weight is None else m.weight.detach().reshape(-1)
+        gv = g.contiguous().reshape(S * xhat.shape[0], *xhat.shape[1:])  # (the seeds stacked over the view the forward took)
+        if K is not None and xhat.dtype == torch.float32:
+            return K.norm_vjp(gv, xhat, rstd, None if w is None else w.contiguous(), S, G, layout).reshape(g.shape)
+        return norm_vjp_math(gv, xhat, rstd, w, S, G, layout).reshape(g.shape)
 
     @staticmethod
     def _pair2(v):
@@ -477,6 +570,8 @@ class SeedBatchedSweep:
                     push(src, g)
                 else:
                     push(src, self._scale_mask(g, S, None, scale))
+            elif kind == NORM:
+                push(src, self._norm_vjp(m, self.saved[node], g, S))
             elif kind == ACT:
                 scale, dst = self._fold_bn(src)
                 push(dst, self._scale_mask(g, S, self._act_mult(r.flavour, self.saved[node]), scale, g2))

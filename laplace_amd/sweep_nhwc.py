@@ -26,13 +26,14 @@ from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
-from laplace_amd.sweep import (ACT, ADD, AVGPOOL, BN, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, RESHAPE, SIZE,
+from laplace_amd.sweep import (ACT, ADD, AVGPOOL, BN, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, NORM, RESHAPE, SIZE,
                                SeedBatchedSweep, SweepUnsupported)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
 _PASS_THROUGH = {ACT, IDENTITY, ADD}  # shape-preserving: the cotangent keeps the representation it arrives in
-_FEATURE = {CONV, BN, GPOOL}  # produce / consume NHWC feature maps
+GN_MAP = "group-norm on a feature map"  # what `_walk` reports for an nn.GroupNorm node (NORM covers nn.LayerNorm in the head too)
+_FEATURE = {CONV, BN, GPOOL, GN_MAP}  # produce / consume NHWC feature maps
 _NO_RULE = {MAXPOOL, AVGPOOL, MEAN, SIZE, GETITEM}  # a graph with one of these runs through the NCHW sweep
 
 
@@ -146,6 +147,8 @@ class SplitSweep(SeedBatchedSweep):
             if isinstance(self.modules.get(name), (nn.BatchNorm2d, nn.BatchNorm1d)):
                 # its weight / bias Jacobian reads the fp32 NCHW cotangent of the BatchNorm's output (lk_norm.hip, layout 0)
                 return f"{name}: tapped BatchNorm (its cotangent is delivered by the NCHW sweep)"
+            if isinstance(self.modules.get(name), (nn.GroupNorm, nn.LayerNorm)):
+                return f"{name}: tapped {type(self.modules[name]).__name__} (its cotangent is delivered by the NCHW sweep)"
         if self.kernels is None or not hasattr(self.kernels(), "conv_nhwc_f16x2"):
             return "kernels without the split-fp16 convolution"
         n_conv = 0
@@ -159,6 +162,14 @@ class SplitSweep(SeedBatchedSweep):
                 n_conv += 1
             elif r.kind in _NO_RULE or isinstance(r.mod, nn.BatchNorm1d):
                 return (f"{node.target}: " if node.op == "call_module" else "") + f"{r.what} has no NHWC rule"
+            elif r.kind == NORM:
+                on_map = any(k in (CONV, BN, GN_MAP, "placeholder") for k in self._walk(node, False))
+                if isinstance(r.mod, nn.LayerNorm) and on_map:
+                    return f"{node.target}: LayerNorm applied to a feature map (the NHWC kernels normalise per channel group)"
+                if isinstance(r.mod, nn.GroupNorm) and not on_map:
+                    return f"{node.target}: GroupNorm outside the feature maps"
+                if isinstance(r.mod, nn.GroupNorm) and not all(hasattr(self.kernels(), f) for f in ("norm_forward", "norm_vjp")):
+                    return f"{node.target}: kernels without the per-sample normalisation entry points"
             elif r.kind == GPOOL and tuple(self._pair2(r.args[0])) != (1, 1):
                 return f"{node.target if node.op == 'call_module' else node.name}: adaptive pooling to more than one cell"
         if not n_conv:
@@ -178,7 +189,7 @@ class SplitSweep(SeedBatchedSweep):
                     continue
                 seen.add(m)
                 kind = self.rule[m].kind
-                out.append(kind)
+                out.append(GN_MAP if kind == NORM and isinstance(self.rule[m].mod, nn.GroupNorm) else kind)
                 if kind in _PASS_THROUGH:
                     todo.append(m)
         return out
@@ -191,7 +202,7 @@ class SplitSweep(SeedBatchedSweep):
                 users = list(node.users)
                 if len(users) != 1 or self.rule[users[0]].kind != RESHAPE:
                     return f"{node.name}: pooled tensor with a consumer other than one flatten"
-            if r.kind == LINEAR and any(k in (CONV, BN, "placeholder") for k in self._walk(node, False)):
+            if r.kind == LINEAR and any(k in (CONV, BN, GN_MAP, "placeholder") for k in self._walk(node, False)):
                 return f"{node.target}: Linear layer applied to a feature map"
         return None
 
@@ -281,6 +292,23 @@ class SplitSweep(SeedBatchedSweep):
             Ho, Wo = (xs.shape[1] + 2 * ph - KH) // s_ + 1, (xs.shape[2] + 2 * pw - KW) // s_ + 1
             return _PendingConv(prep, xs, (xs.shape[0], m.out_channels, Ho, Wo), run)
         return run()
+
+    def _run_norm(self, node, m, inp):
+        """GroupNorm on a feature map: layout 1 of lk_norm_fwd_f32 on the NHWC memory of the convolution output; returns the
+        NCHW-logical view over NHWC memory, as `_run_bn_act` does.  Nothing is registered in ``_aux``: the next convolution
+        measures and splits its input itself (`_split_input`).  A LayerNorm of the head region runs the parent's math."""
+        if not (self.split_ok and isinstance(m, nn.GroupNorm)):
+            return super()._run_norm(node, m, inp)
+        # (also with ``nhwc_forward = False``: the reverse sweep is NHWC either way)
+        if not (torch.is_tensor(inp) and inp.dim() == 4 and inp.dtype == torch.float32 and inp.shape[0] > 0):
+            raise SweepUnsupported(f"{node.target}: GroupNorm of the NHWC sweep expects a non-empty fp32 feature map")
+        if inp.shape[1] != m.num_channels:
+            raise SweepUnsupported(f"{node.target}: GroupNorm({m.num_groups}, {m.num_channels}) on {tuple(inp.shape)}")
+        xh = inp.permute(0, 2, 3, 1).contiguous()  # (a view when inp is already NHWC in memory)
+        w = None if m.weight is None else m.weight.detach().to(torch.float32).contiguous()
+        b = None if m.bias is None else m.bias.detach().to(torch.float32).contiguous()
+        y, xhat, rstd = self.kernels().norm_forward(xh, w, b, m.num_groups, 1, m.eps)
+        return y.permute(0, 3, 1, 2), (xhat, rstd, m.num_groups, 1)
 
     #: ``False``: a convolution and the BatchNorm / add / ReLU behind it stay two launches
     fuse_conv_bn = True
@@ -572,6 +600,19 @@ class SplitSweep(SeedBatchedSweep):
                     push(src, parts[0])
                 else:
                     push(src, self._to_split(parts, S, scale=scale, scale_amax=self._amax_of(node.target, scale)))
+            elif kind == NORM:
+                if all(torch.is_tensor(p) for p in parts):
+                    # LayerNorm in the head region (plain tensors after the flatten): parent-class math
+                    g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
+                    push(src, self._norm_vjp(m, self.saved[node], g, S))
+                else:
+                    # the parts as ONE fp32 NHWC tensor (the VJP reads fp32; a kernel that reads split planes is out of scope)
+                    ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
+                    g = ts[0] if len(ts) == 1 else sum(ts[1:], ts[0])
+                    xhat, rstd, G, _ = self.saved[node]
+                    w = None if m.weight is None else m.weight.detach().to(torch.float32).contiguous()
+                    word = new_word()
+                    push(src, _F32(K.norm_vjp(g.contiguous(), xhat, rstd, w, S, G, 1, amax=word), word))
             elif kind == ACT:
                 scale, dst = self._fold_bn(src)
                 if all(torch.is_tensor(p) for p in parts):
