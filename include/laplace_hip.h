@@ -435,6 +435,41 @@ int lk_norm_vjp_f32(const float* g, const float* xhat, const float* rstd, const 
                     int64_t Ch, int64_t G, int layout, float* dx, unsigned* amax, void* stream);
 int lk_norm_sweep_variant(int64_t S, int64_t B, int64_t L, int64_t Ch, int64_t G, int layout, int aligned);
 
+/* Max and average pooling (nn.MaxPool2d / nn.AvgPool2d, ceil_mode false, no dilation) on fp32 NHWC feature maps for the NHWC
+ * reverse sweep; they replace, there, max_pool2d(return_indices=True) / avg_pool2d and the seed-expanded scatter_add_ of the
+ * NCHW sweep (the reverse passes of laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through a pooling layer).
+ * OH = (H + 2 ph - kh) / sh + 1, OW likewise; the window of (oh, ow) starts at (oh * sh - ph, ow * sw - pw).
+ *
+ * lk_pool_fwd_nhwc_f32: x [B][H][W][C] -> y [B][OH][OW][C].
+ *   LK_POOL_MAX: the maximum over the window's in-image taps (padding takes no part); arg [B][OH][OW][C], one byte each, is
+ *     the window-local tap code dy * kw + dx of the FIRST maximum in row-major scan order (strict >, torch's tie rule).
+ *   LK_POOL_AVG: (sum of the in-image taps) / div with div = divisor_override when it is > 0, else kh * kw when
+ *     count_include_pad is set, else the number of in-image taps; arg must be null.
+ * lk_pool_vjp_nhwc_f32: g [S][B][OH][OW][C] -> dx [S][B][H][W][C], ONE arg for all seeds.  Gather form: the owner of a dx
+ *   element walks the windows that cover its pixel in fixed (oh, ow) order and adds g where the window's code names the pixel
+ *   (max) or g / div(window) (average).  Plain stores, no atomics on data: deterministic.  amax, when given, receives max|dx|
+ *   as the bit pattern of a non-negative float through atomicMax (as lk_norm_vjp_f32); the caller zeroes it.  dx must not
+ *   overlap g.  Minimal traffic: 4 S B C (OH OW + H W) + B C OH OW bytes.
+ * Contract of both: kind 0 or 1; 1 <= kh, kw <= 8; 1 <= sh, sw < 32768; 0 <= ph <= kh / 2, 0 <= pw <= kw / 2; OH, OW >= 1;
+ * 1 <= H, W < 32768; 1 <= C < 2^30; 1 <= S, 0 <= B, S * B < 2^31; S * B * C * max(H * W, OH * OW) < 2^40; arg non-null exactly
+ * for LK_POOL_MAX.  B == 0 returns LK_OK.
+ * lk_pool_variant (host only): the path lk_pool_vjp_nhwc_f32 takes for a shape; `aligned`: g and dx are 16-byte and arg is
+ * 4-byte aligned.  Returns
+ *   vec | summing << 1 | seed-split << 2 | seeds per pass << 4 | seeds per grid.y slice (capped at 65535) << 12
+ *   vec: 16-byte loads of g, 4-byte loads of arg (C % 4 == 0 and aligned); summing: two windows may share a pixel (otherwise
+ *   SELECTION: kh <= sh and kw <= sw, dx is a copy or a zero); seed-split: the seeds are split over grid.y; seeds per pass:
+ *   how many seeds' loads a lane has in flight
+ * or a negative value for a shape the entry point refuses. */
+#define LK_POOL_MAX 0
+#define LK_POOL_AVG 1
+int lk_pool_fwd_nhwc_f32(int kind, const float* x, int64_t B, int64_t H, int64_t W, int64_t C, int kh, int kw, int sh, int sw,
+                         int ph, int pw, int count_include_pad, int divisor_override, float* y, uint8_t* arg, void* stream);
+int lk_pool_vjp_nhwc_f32(int kind, const float* g, const uint8_t* arg, int64_t S, int64_t B, int64_t H, int64_t W, int64_t C,
+                         int kh, int kw, int sh, int sw, int ph, int pw, int count_include_pad, int divisor_override, float* dx,
+                         unsigned* amax, void* stream);
+int lk_pool_variant(int kind, int64_t S, int64_t B, int64_t H, int64_t W, int64_t C, int kh, int kw, int sh, int sw, int ph,
+                    int pw, int aligned);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

@@ -116,6 +116,9 @@ SIGNATURES = {
     "lk_norm_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp]),
     "lk_norm_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_norm_sweep_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
+    "lk_pool_fwd_nhwc_f32": (_int, [_int, _vp, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
+    "lk_pool_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
+    "lk_pool_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64] + [_int] * 7),
     "lk_bn_act_fwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_vjp_scale_mask_f32": (_int, [_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_ll_ggn_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1261,6 +1264,79 @@ class HipKernels:
             return None
         return {"kernel": r & 1, "vec": bool(r & 2), "two_pass": bool(r & 4), "seed_split": bool(r & 8), "lanes": (r >> 4) & 0xFFF,
                 "groups": r >> 16, "layout": int(layout)}
+
+    #: ``kind`` of the pooling entry points (LK_POOL_* of include/laplace_hip.h)
+    POOL_MAX, POOL_AVG = 0, 1
+
+    @staticmethod
+    def _pool_geometry(kind, kernel, stride, padding, what):
+        """``(kh, kw, sh, sw, ph, pw)`` as ints (``stride`` None / empty: the kernel size, as torch)"""
+        if kind not in (0, 1):
+            raise LaplaceHipError(f"{what}: kind is POOL_MAX (0) or POOL_AVG (1)")
+        kh, kw = _pair(kernel)
+        sh, sw = (kh, kw) if stride is None or stride == [] or stride == () else _pair(stride)
+        ph, pw = _pair(padding)
+        return kh, kw, sh, sw, ph, pw
+
+    def pool_forward(self, x_nhwc, kind, kernel, stride, padding, count_include_pad=True, divisor_override=None):
+        """``(y, arg)`` of a max / average pooling over the fp32 NHWC map ``x_nhwc`` ``[B, H, W, C]`` (csrc/lk_pool.hip,
+        ``ceil_mode`` false): ``y`` ``[B, OH, OW, C]``; ``arg`` (max only, else None) uint8 ``[B, OH, OW, C]``, the window-local tap
+        code ``dy * kw + dx`` of the first maximum in row-major order (torch's tie rule)."""
+        _check(x_nhwc, "x_nhwc")
+        if x_nhwc.dim() != 4:
+            raise LaplaceHipError("pool_forward: expected an NHWC map [B, H, W, C]")
+        kh, kw, sh, sw, ph, pw = self._pool_geometry(kind, kernel, stride, padding, "pool_forward")
+        B, H, W, C = x_nhwc.shape
+        if min(kh, kw, sh, sw) < 1 or H + 2 * ph < kh or W + 2 * pw < kw:
+            raise LaplaceHipError(f"pool_forward: window ({kh}, {kw}) / stride ({sh}, {sw}) / padding ({ph}, {pw}) leaves no "
+                                  f"output on a {H} x {W} map")
+        OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+        y = torch.empty(B, OH, OW, C, dtype=torch.float32, device=x_nhwc.device)
+        arg = torch.empty(B, OH, OW, C, dtype=torch.uint8, device=x_nhwc.device) if kind == self.POOL_MAX else None
+        self._rc(self.lib.lk_pool_fwd_nhwc_f32(int(kind), _ptr(x_nhwc), B, H, W, C, kh, kw, sh, sw, ph, pw,
+                                               int(bool(count_include_pad)), int(divisor_override or 0), _ptr(y), _ptr(arg),
+                                               self._stream(x_nhwc.device)), "lk_pool_fwd_nhwc_f32")
+        return y, arg
+
+    def pool_vjp(self, g, arg, S, in_hw, kind, kernel, stride, padding, count_include_pad=True, divisor_override=None,
+                 amax=None):
+        """``dx`` ``[S*B, H, W, C]`` of a pooling layer for the ``S`` seeds stacked in ``g`` ``[S*B, OH, OW, C]``; ``in_hw`` =
+        ``(H, W)``; ``arg`` ``[B, OH, OW, C]`` from :meth:`pool_forward` (None for the average), shared by all seeds.  ``amax``:
+        zeroed device word that receives the bit pattern of max|dx|."""
+        _check(g, "g")
+        kh, kw, sh, sw, ph, pw = self._pool_geometry(kind, kernel, stride, padding, "pool_vjp")
+        S, (H, W) = int(S), (int(in_hw[0]), int(in_hw[1]))
+        if g.dim() != 4 or S < 1 or g.shape[0] % S:
+            raise LaplaceHipError("pool_vjp: g must be [S*B, OH, OW, C]")
+        B, C = g.shape[0] // S, g.shape[3]
+        if min(kh, kw, sh, sw) < 1 or H + 2 * ph < kh or W + 2 * pw < kw \
+                or tuple(g.shape[1:3]) != ((H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1):
+            raise LaplaceHipError(f"pool_vjp: g {tuple(g.shape)} is not the pooled {H} x {W} map of window ({kh}, {kw}), stride "
+                                  f"({sh}, {sw}), padding ({ph}, {pw})")
+        if kind == self.POOL_MAX:
+            _check(arg, "arg", torch.uint8)
+            if tuple(arg.shape) != (B, *g.shape[1:]):
+                raise LaplaceHipError("pool_vjp: arg must be [B, OH, OW, C]")
+        elif arg is not None:
+            raise LaplaceHipError("pool_vjp: the average takes no arg")
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("pool_vjp: amax is one 32-bit device word")
+        dx = torch.empty(S * B, H, W, C, dtype=torch.float32, device=g.device)
+        self._rc(self.lib.lk_pool_vjp_nhwc_f32(int(kind), _ptr(g), _ptr(arg), S, B, H, W, C, kh, kw, sh, sw, ph, pw,
+                                               int(bool(count_include_pad)), int(divisor_override or 0), _ptr(dx), _ptr(amax),
+                                               self._stream(g.device)), "lk_pool_vjp_nhwc_f32")
+        return dx
+
+    def pool_variant(self, kind, S, B, H, W, C, kernel, stride, padding, aligned=True):
+        """lk_pool_variant: the path ``lk_pool_vjp_nhwc_f32`` takes for a shape (host only, no device call), or ``None`` for a
+        shape it refuses."""
+        kh, kw, sh, sw, ph, pw = self._pool_geometry(kind, kernel, stride, padding, "pool_variant")
+        r = int(self.lib.lk_pool_variant(int(kind), int(S), int(B), int(H), int(W), int(C), kh, kw, sh, sw, ph, pw,
+                                         int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "summing": bool(r & 2), "seed_split": bool(r & 4), "seeds_per_pass": (r >> 4) & 0xFF,
+                "seeds_per_slice": r >> 12}
 
     def sq_colsum(self, Js, col0, width, alpha, h):
         _check(Js, "Js"), _check(h, "h")

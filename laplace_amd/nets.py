@@ -53,13 +53,20 @@ class ResNet18(nn.Module):
     device in eval mode (csrc/lk_norm.hip).
 
     ``norm="gn"`` puts ``GroupNorm(32, C)`` wherever a BatchNorm is (same attribute names; ``freeze_bn`` freezes its affine
-    parameters alike).  Its reverse sweep goes through csrc/lk_normvjp.hip."""
+    parameters alike).  Its reverse sweep goes through csrc/lk_normvjp.hip.
 
-    def __init__(self, num_classes: int = 10, freeze_bn: bool = True, act=torch.relu, norm: str = "bn"):
+    ``stem="imagenet"`` is the torchvision stem - a 7 x 7 stride-2 convolution, norm, activation, ``MaxPool2d(3, 2, 1)`` - in
+    front of the same blocks (the pool runs through csrc/lk_pool.hip); the default ``"cifar"`` is the 3 x 3 stride-1 stem
+    without a pool."""
+
+    def __init__(self, num_classes: int = 10, freeze_bn: bool = True, act=torch.relu, norm: str = "bn", stem: str = "cifar"):
         super().__init__()
+        if stem not in ("cifar", "imagenet"):
+            raise ValueError(f"stem must be 'cifar' or 'imagenet', got {stem!r}")
         self.act = act
-        self.conv1 = nn.Conv2d(3, 64, 3, 1, 1, bias=False)
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False) if stem == "imagenet" else nn.Conv2d(3, 64, 3, 1, 1, bias=False)
         self.bn1 = norm_layer(norm, 64)
+        self.maxpool = nn.MaxPool2d(3, 2, 1) if stem == "imagenet" else None
         blocks, cin = [], 64
         for cout, stride in ((64, 1), (64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1)):
             blocks.append(BasicBlock(cin, cout, stride, act, norm))
@@ -75,6 +82,8 @@ class ResNet18(nn.Module):
 
     def forward(self, x):
         x = self.act(self.bn1(self.conv1(x)))
+        if self.maxpool is not None:
+            x = self.maxpool(x)
         x = self.layers(x)
         return self.fc(torch.flatten(self.pool(x), 1))
 

@@ -291,9 +291,9 @@ class SeedBatchedSweep:
             elif kind == NORM:
                 out, keep = self._run_norm(node, r.mod, inp)
                 keep = keep if need_vjp else None
-            elif kind == MAXPOOL:
-                out, idx = r.fn(*args)
-                keep = (idx, inp.shape)
+            elif kind in (MAXPOOL, AVGPOOL):
+                out, keep = self._run_pool(node, r, args, kwargs)
+                keep = keep if need_vjp else None
             elif r.flavour == "generic" and need_vjp:
                 out, keep = self._with_derivative(lambda t: r.fn(t, *args[1:], **kwargs), inp)
             elif kind == GETITEM and torch.is_tensor(inp):
@@ -302,7 +302,7 @@ class SeedBatchedSweep:
                 out = r.fn(*args, **kwargs)
                 if kind == ACT and need_vjp:  # (tanh / sigmoid: the derivative is a function of the value)
                     keep = (out > 0) if r.flavour == "relu" else out
-                elif kind in (RESHAPE, GPOOL, AVGPOOL):
+                elif kind in (RESHAPE, GPOOL):
                     keep = inp.shape
                 elif kind == MEAN:
                     dim, keepdim = fx.node.map_arg(r.args, env.__getitem__)
@@ -334,6 +334,28 @@ class SeedBatchedSweep:
     def _run_bn_act(self, node, inp, scale, shift, relu, addend, want_mask):
         return self.kernels().bn_act_forward(inp.contiguous(), scale, shift, relu,
                                              None if addend is None else addend.contiguous(), want_mask=want_mask)
+
+    def _run_pool(self, node, r, args, kwargs):
+        """max / average pooling forward -> ``(out, keep)``: a max pool is evaluated with indices (`classify`), which are what
+        its VJP scatters by; the average's VJP needs the input's shape only"""
+        if r.kind == MAXPOOL:
+            out, idx = r.fn(*args)
+            return out, (idx, args[0].shape)
+        return r.fn(*args, **kwargs), args[0].shape
+
+    @staticmethod
+    def pool_params(r) -> dict:
+        """the static arguments of a MAXPOOL / AVGPOOL rule by name (``stride``: the window when none is given, as torch)"""
+        if r.kind == MAXPOOL:  # (`classify` made the call positional: input, the five parameters, return_indices)
+            p = dict(zip(_POOL_PARAMS[MAXPOOL][0][:5], r.call[0][1:6]))
+        else:
+            p = dict(zip(_POOL_PARAMS[AVGPOOL][0], r.args))
+        pair = SeedBatchedSweep._pair2
+        k = tuple(int(v) for v in pair(p["kernel_size"]))
+        st = k if p["stride"] in (None, [], ()) else tuple(int(v) for v in pair(p["stride"]))
+        return {"kernel": k, "stride": st, "padding": tuple(int(v) for v in pair(p["padding"])),
+                "dilation": tuple(int(v) for v in pair(p.get("dilation", 1))), "ceil_mode": bool(p["ceil_mode"]),
+                "count_include_pad": bool(p.get("count_include_pad", True)), "divisor_override": p.get("divisor_override")}
 
     def _norm_kernels(self, t):
         """the kernel object when it serves per-sample normalisation of ``t`` (fp32 and an object with the entry points; the

@@ -13,8 +13,9 @@ laplace/curvature/curvlinops.py:87-100):
   the main branch's result instead of materialising its three-quarters-zero cotangent;
 * the G factor of a convolution layer is the Gram of the split tensor itself (``lk_gram_tn_f16x2``).
 
-Graphs with nodes this path has no rule for (pooling other than the global average, convolutions whose channel counts
-are not multiples of 32, ...) run through the parent class unchanged.
+Max and average pooling run on the fp32 NHWC maps (csrc/lk_pool.hip: one byte of window-local argmax per output element for
+all seeds, a gather-form VJP).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive
+pooling to several cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
 
@@ -33,8 +34,10 @@ from laplace_amd.sweep import (ACT, ADD, AVGPOOL, BN, CONV, GETITEM, GPOOL, IDEN
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
 _PASS_THROUGH = {ACT, IDENTITY, ADD}  # shape-preserving: the cotangent keeps the representation it arrives in
 GN_MAP = "group-norm on a feature map"  # what `_walk` reports for an nn.GroupNorm node (NORM covers nn.LayerNorm in the head too)
-_FEATURE = {CONV, BN, GPOOL, GN_MAP}  # produce / consume NHWC feature maps
-_NO_RULE = {MAXPOOL, AVGPOOL, MEAN, SIZE, GETITEM}  # a graph with one of these runs through the NCHW sweep
+_POOL = {MAXPOOL, AVGPOOL}  # spatial pooling: fp32 NHWC in, fp32 NHWC out (lk_pool.hip)
+_FEATURE = {CONV, BN, GPOOL, GN_MAP} | _POOL  # produce / consume NHWC feature maps
+_MAP_SOURCES = {CONV, BN, GN_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
+_NO_RULE = {MEAN, SIZE, GETITEM}  # a graph with one of these runs through the NCHW sweep
 
 
 class _F32:
@@ -160,10 +163,14 @@ class SplitSweep(SeedBatchedSweep):
                 if not cv.supported(m) and not (first and node.target in self.tap_names and m.out_channels % 8 == 0):
                     return f"{node.target}: convolution outside the implicit-GEMM kernel's coverage"
                 n_conv += 1
-            elif r.kind in _NO_RULE or isinstance(r.mod, nn.BatchNorm1d):
+            elif r.kind in _NO_RULE or isinstance(r.mod, nn.BatchNorm1d) or (r.kind in _POOL and not self.nhwc_pool):
                 return (f"{node.target}: " if node.op == "call_module" else "") + f"{r.what} has no NHWC rule"
+            elif r.kind in _POOL:
+                why = self._pool_refusal(node, r)
+                if why is not None:
+                    return f"{node.target if node.op == 'call_module' else node.name}: {why}"
             elif r.kind == NORM:
-                on_map = any(k in (CONV, BN, GN_MAP, "placeholder") for k in self._walk(node, False))
+                on_map = any(k in _MAP_SOURCES for k in self._walk(node, False))
                 if isinstance(r.mod, nn.LayerNorm) and on_map:
                     return f"{node.target}: LayerNorm applied to a feature map (the NHWC kernels normalise per channel group)"
                 if isinstance(r.mod, nn.GroupNorm) and not on_map:
@@ -175,6 +182,26 @@ class SplitSweep(SeedBatchedSweep):
         if not n_conv:
             return "no convolution in the graph"
         return self._region_check()
+
+    #: ``False``: a model with max / average pooling runs through the NCHW sweep, as it did before lk_pool.hip
+    nhwc_pool = True
+
+    def _pool_refusal(self, node, r):
+        """why this MAXPOOL / AVGPOOL node keeps the model off the NHWC walk (None: lk_pool.hip serves it)"""
+        p = self.pool_params(r)
+        if not any(k in _MAP_SOURCES for k in self._walk(node, False)):
+            return f"{r.what} outside the feature maps"
+        if p["dilation"] != (1, 1):
+            return f"dilated pooling (dilation {p['dilation']}; the NHWC kernels take none)"
+        if p["ceil_mode"]:
+            return "pooling with ceil_mode=True (the NHWC kernels take ceil_mode=False only)"
+        (kh, kw), (sh, sw), (ph, pw) = p["kernel"], p["stride"], p["padding"]
+        if not (1 <= kh <= 8 and 1 <= kw <= 8 and sh >= 1 and sw >= 1 and 0 <= ph <= kh // 2 and 0 <= pw <= kw // 2):
+            return (f"pooling window {(kh, kw)} / stride {(sh, sw)} / padding {(ph, pw)} outside the NHWC kernels' contract "
+                    "(1 <= window <= 8, stride >= 1, padding <= window / 2)")
+        if not all(hasattr(self.kernels(), f) for f in ("pool_forward", "pool_vjp", "POOL_MAX", "POOL_AVG")):
+            return "kernels without the pooling entry points"
+        return None
 
     # The reverse sweep must not fail half-way (`on_tap` has already added G factors by then): every structural
     # condition `backward` would raise on is checked here, on the graph alone, so that such a model runs through the
@@ -202,7 +229,7 @@ class SplitSweep(SeedBatchedSweep):
                 users = list(node.users)
                 if len(users) != 1 or self.rule[users[0]].kind != RESHAPE:
                     return f"{node.name}: pooled tensor with a consumer other than one flatten"
-            if r.kind == LINEAR and any(k in (CONV, BN, GN_MAP, "placeholder") for k in self._walk(node, False)):
+            if r.kind == LINEAR and any(k in _MAP_SOURCES for k in self._walk(node, False)):
                 return f"{node.target}: Linear layer applied to a feature map"
         return None
 
@@ -309,6 +336,30 @@ class SplitSweep(SeedBatchedSweep):
         b = None if m.bias is None else m.bias.detach().to(torch.float32).contiguous()
         y, xhat, rstd = self.kernels().norm_forward(xh, w, b, m.num_groups, 1, m.eps)
         return y.permute(0, 3, 1, 2), (xhat, rstd, m.num_groups, 1)
+
+    def _run_pool(self, node, r, args, kwargs):
+        """max / average pooling on a feature map: lk_pool_fwd_nhwc_f32 on the NHWC memory of the input; returns the NCHW-logical
+        view over NHWC memory, as `_run_norm` does, and keeps ``(arg, in_shape)`` (max: one byte of window-local argmax per
+        output element, shared by all seeds) or ``in_shape`` (average).  Pooling cannot raise a map's maximum, so the output
+        inherits the input's per-image ``"bound"`` words; no ``"split"`` is registered: the next convolution splits its input
+        itself (`_split_input`)."""
+        if not self.split_ok:
+            return super()._run_pool(node, r, args, kwargs)
+        # (also with ``nhwc_forward = False``: the reverse sweep is NHWC either way)
+        inp = args[0]
+        if not (torch.is_tensor(inp) and inp.dim() == 4 and inp.dtype == torch.float32):
+            raise SweepUnsupported(f"{node.name}: pooling of the NHWC sweep expects an fp32 feature map")
+        K, p = self.kernels(), self.pool_params(r)
+        is_max = r.kind == MAXPOOL
+        xh = inp.permute(0, 2, 3, 1).contiguous()  # (a view when inp is already NHWC in memory)
+        y, arg = K.pool_forward(xh, K.POOL_MAX if is_max else K.POOL_AVG, p["kernel"], p["stride"], p["padding"],
+                                p["count_include_pad"], p["divisor_override"])
+        out = y.permute(0, 3, 1, 2)
+        aux = self._aux_get(inp)
+        # (an average with a divisor of its own may exceed the map's maximum: it inherits nothing)
+        if aux is not None and aux.get("bound") is not None and (is_max or p["divisor_override"] is None):
+            self._aux_put(out, {"split": None, "bound": aux["bound"]})
+        return out, ((arg, inp.shape) if is_max else inp.shape)
 
     #: ``False``: a convolution and the BatchNorm / add / ReLU behind it stay two launches
     fuse_conv_bn = True
@@ -613,6 +664,17 @@ class SplitSweep(SeedBatchedSweep):
                     w = None if m.weight is None else m.weight.detach().to(torch.float32).contiguous()
                     word = new_word()
                     push(src, _F32(K.norm_vjp(g.contiguous(), xhat, rstd, w, S, G, 1, amax=word), word))
+            elif kind in _POOL:
+                # the parts as ONE fp32 NHWC tensor, as the NORM rule (a pool that reads split planes is out of scope)
+                ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
+                g = ts[0] if len(ts) == 1 else sum(ts[1:], ts[0])
+                pp, keep = self.pool_params(r), self.saved[node]
+                arg, shp = keep if kind == MAXPOOL else (None, keep)  # [B, C, H, W]
+                word = new_word()
+                dx = K.pool_vjp(g.contiguous(), arg, S, (int(shp[2]), int(shp[3])), K.POOL_MAX if kind == MAXPOOL else K.POOL_AVG,
+                                pp["kernel"], pp["stride"], pp["padding"], pp["count_include_pad"], pp["divisor_override"],
+                                amax=word)
+                push(src, _F32(dx, word))
             elif kind == ACT:
                 scale, dst = self._fold_bn(src)
                 if all(torch.is_tensor(p) for p in parts):
