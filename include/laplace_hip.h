@@ -470,6 +470,39 @@ int lk_pool_vjp_nhwc_f32(int kind, const float* g, const uint8_t* arg, int64_t S
 int lk_pool_variant(int kind, int64_t S, int64_t B, int64_t H, int64_t W, int64_t C, int kh, int kw, int sh, int sw, int ph,
                     int pw, int aligned);
 
+/* Depthwise convolution (nn.Conv2d with groups == in_channels == out_channels, no dilation, zero padding) on NHWC feature
+ * maps for the NHWC reverse sweep; they replace, there, the module's own forward and convolution_backward with `groups` of the
+ * NCHW sweep (the reverse pass through a depthwise layer of laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129).
+ * OH = (H + 2 ph - kh) / sh + 1, OW likewise.  Weights are tap-major fp32: w_tap[kh kw][C], w_tap[dy kw + dx][c] =
+ * weight[c, 0, dy, dx].
+ *
+ * lk_dwconv_fwd_nhwc_f32: x [B][H][W][C] -> y [B][OH][OW][C],
+ *   y = bias[c] + sum over the in-image taps, in fixed (dy, dx) order, of w_tap[dy kw + dx][c] * x[n, oh sh - ph + dy, ow sw - pw + dx, c];
+ *   bias may be null.
+ * lk_dwconv_bwd_nhwc_f16x2: the cotangent g [S][B][OH][OW][C] as the two fp16 planes g_h, g_l of a ONE-scale split tensor,
+ *   g = (float(h) + float(l)) * 2^-sexp[0] (sexp: one device int) -> dx [S][B][H][W][C] fp32,
+ *   dx[s,n,h,w,c] = sum over (dy, dx) in fixed row-major order with (h + ph - dy) % sh == 0, (w + pw - dx) % sw == 0 and
+ *   oh = (h + ph - dy) / sh in [0, OH), ow likewise, of w_tap[dy kw + dx][c] * g[s,n,oh,ow,c].
+ *   Gather form: every dx element has one owner, plain stores, deterministic; a pixel no window reaches receives 0.  amax, when
+ *   given, receives max|dx| as the bit pattern of a non-negative float through atomicMax (as lk_pool_vjp_nhwc_f32); the caller
+ *   zeroes it.  dx must not overlap g.  Minimal traffic: 4 S B C (OH OW + H W) + 4 kh kw C bytes.
+ * Contract of both: 1 <= kh, kw and kh * kw <= 25; 1 <= sh, sw <= 8; 0 <= ph < kh, 0 <= pw < kw; OH, OW >= 1; 1 <= H, W < 32768;
+ * 1 <= C < 2^30; 1 <= S, 0 <= B, S * B < 2^31; S * B * C * max(H * W, OH * OW) < 2^40.  B == 0 returns LK_OK.
+ * lk_dwconv_variant (host only): the path lk_dwconv_bwd_nhwc_f16x2 takes for a shape; `aligned`: g_h and g_l are 8-byte, w_tap
+ * and dx 16-byte aligned.  Returns
+ *   vec | strided << 1 | seed-split << 2 | tap class << 3 | seeds per pass << 4 | seeds per grid.y slice (capped at 65535) << 12
+ *   vec: 8-byte loads of the planes, 16-byte loads of w_tap and stores of dx (C % 4 == 0 and aligned); strided: sh > 1 or
+ *   sw > 1, the divisibility test is live; seed-split: the seeds are split over grid.y; tap class: 0 for <= 9 taps, 1 for
+ *   <= 25; seeds per pass: how many seeds' loads a lane has in flight
+ * or a negative value for a shape the entry point refuses. */
+int lk_dwconv_fwd_nhwc_f32(const float* x, const float* w_tap, const float* bias, int64_t B, int64_t H, int64_t W, int64_t C,
+                           int kh, int kw, int sh, int sw, int ph, int pw, float* y, void* stream);
+int lk_dwconv_bwd_nhwc_f16x2(const void* g_h, const void* g_l, const int* sexp, const float* w_tap, int64_t S, int64_t B,
+                             int64_t H, int64_t W, int64_t C, int kh, int kw, int sh, int sw, int ph, int pw, float* dx,
+                             unsigned* amax, void* stream);
+int lk_dwconv_variant(int64_t S, int64_t B, int64_t H, int64_t W, int64_t C, int kh, int kw, int sh, int sw, int ph, int pw,
+                      int aligned);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

@@ -119,6 +119,9 @@ SIGNATURES = {
     "lk_pool_fwd_nhwc_f32": (_int, [_int, _vp, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64] + [_int] * 7),
+    "lk_dwconv_fwd_nhwc_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp]),
+    "lk_dwconv_bwd_nhwc_f16x2": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp, _vp]),
+    "lk_dwconv_variant": (_int, [_i64, _i64, _i64, _i64, _i64] + [_int] * 7),
     "lk_bn_act_fwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_vjp_scale_mask_f32": (_int, [_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_ll_ggn_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1337,6 +1340,65 @@ class HipKernels:
             return None
         return {"vec": bool(r & 1), "summing": bool(r & 2), "seed_split": bool(r & 4), "seeds_per_pass": (r >> 4) & 0xFF,
                 "seeds_per_slice": r >> 12}
+
+    @staticmethod
+    def _dwconv_geometry(x_hw, kernel, stride, padding, what):
+        """``(kh, kw, sh, sw, ph, pw, OH, OW)`` as ints, or an error when the window leaves no output on the map"""
+        (H, W), (kh, kw), (sh, sw), (ph, pw) = x_hw, _pair(kernel), _pair(stride), _pair(padding)
+        if min(kh, kw, sh, sw) < 1 or H + 2 * ph < kh or W + 2 * pw < kw:
+            raise LaplaceHipError(f"{what}: window ({kh}, {kw}) / stride ({sh}, {sw}) / padding ({ph}, {pw}) leaves no output "
+                                  f"on a {H} x {W} map")
+        return kh, kw, sh, sw, ph, pw, (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+
+    def dwconv_forward(self, x_nhwc, w_tap, bias, kernel, stride, padding):
+        """``y`` ``[B, OH, OW, C]`` of a depthwise convolution over the fp32 NHWC map ``x_nhwc`` ``[B, H, W, C]`` (csrc/lk_dwconv.hip);
+        ``w_tap`` ``[kh * kw, C]`` fp32 with ``w_tap[dy * kw + dx, c] = weight[c, 0, dy, dx]``; ``bias`` ``[C]`` or None."""
+        _check(x_nhwc, "x_nhwc"), _check(w_tap, "w_tap")
+        if x_nhwc.dim() != 4:
+            raise LaplaceHipError("dwconv_forward: expected an NHWC map [B, H, W, C]")
+        B, H, W, C = x_nhwc.shape
+        kh, kw, sh, sw, ph, pw, OH, OW = self._dwconv_geometry((H, W), kernel, stride, padding, "dwconv_forward")
+        if tuple(w_tap.shape) != (kh * kw, C):
+            raise LaplaceHipError(f"dwconv_forward: w_tap {tuple(w_tap.shape)} is not [kh * kw, C] = [{kh * kw}, {C}]")
+        if bias is not None and tuple(_check(bias, "bias").shape) != (C,):
+            raise LaplaceHipError("dwconv_forward: bias must be [C]")
+        y = torch.empty(B, OH, OW, C, dtype=torch.float32, device=x_nhwc.device)
+        self._rc(self.lib.lk_dwconv_fwd_nhwc_f32(_ptr(x_nhwc), _ptr(w_tap), _ptr(bias), B, H, W, C, kh, kw, sh, sw, ph, pw, _ptr(y),
+                                                 self._stream(x_nhwc.device)), "lk_dwconv_fwd_nhwc_f32")
+        return y
+
+    def dwconv_backward(self, g: "SplitTensor", w_tap, S, in_hw, kernel, stride, padding, amax=None):
+        """``dx`` ``[S*B, H, W, C]`` (fp32) of a depthwise convolution for the ``S`` seeds stacked in the one-scale split cotangent
+        ``g`` ``[S*B, OH, OW, C]``; ``in_hw`` = ``(H, W)``.  ``amax``: zeroed device word that receives the bit pattern of max|dx|."""
+        _one_scale(g, "dwconv_backward")
+        _check(g.planes, "g.planes", torch.float16), _check(g.sexp, "g.sexp", torch.int32), _check(w_tap, "w_tap")
+        S, (H, W) = int(S), (int(in_hw[0]), int(in_hw[1]))
+        if g.chunked or g.planes.dim() != 5 or S < 1 or g.planes.shape[1] % S:
+            raise LaplaceHipError("dwconv_backward: g must be a split tensor [S*B, OH, OW, C]")
+        B, C = g.planes.shape[1] // S, g.planes.shape[4]
+        kh, kw, sh, sw, ph, pw, OH, OW = self._dwconv_geometry((H, W), kernel, stride, padding, "dwconv_backward")
+        if tuple(g.planes.shape[2:4]) != (OH, OW):
+            raise LaplaceHipError(f"dwconv_backward: g {tuple(g.shape)} is not the output of window ({kh}, {kw}), stride "
+                                  f"({sh}, {sw}), padding ({ph}, {pw}) on a {H} x {W} map")
+        if tuple(w_tap.shape) != (kh * kw, C):
+            raise LaplaceHipError(f"dwconv_backward: w_tap {tuple(w_tap.shape)} is not [kh * kw, C] = [{kh * kw}, {C}]")
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("dwconv_backward: amax is one 32-bit device word")
+        dx = torch.empty(S * B, H, W, C, dtype=torch.float32, device=g.planes.device)
+        self._rc(self.lib.lk_dwconv_bwd_nhwc_f16x2(_ptr(g.planes[0]), _ptr(g.planes[1]), _ptr(g.sexp), _ptr(w_tap), S, B, H, W, C,
+                                                   kh, kw, sh, sw, ph, pw, _ptr(dx), _ptr(amax), self._stream(dx.device)),
+                 "lk_dwconv_bwd_nhwc_f16x2")
+        return dx
+
+    def dwconv_variant(self, S, B, H, W, C, kernel, stride, padding, aligned=True):
+        """lk_dwconv_variant: the path ``lk_dwconv_bwd_nhwc_f16x2`` takes for a shape (host only, no device call), or ``None`` for
+        a shape it refuses."""
+        (kh, kw), (sh, sw), (ph, pw) = _pair(kernel), _pair(stride), _pair(padding)
+        r = int(self.lib.lk_dwconv_variant(int(S), int(B), int(H), int(W), int(C), kh, kw, sh, sw, ph, pw, int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "strided": bool(r & 2), "seed_split": bool(r & 4), "tap_class": (r >> 3) & 1,
+                "seeds_per_pass": (r >> 4) & 0xFF, "seeds_per_slice": r >> 12}
 
     def sq_colsum(self, Js, col0, width, alpha, h):
         _check(Js, "Js"), _check(h, "h")

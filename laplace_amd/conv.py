@@ -31,6 +31,69 @@ def forward_supported(m: nn.Conv2d) -> bool:
     return _geometry_ok(m) and (m.in_channels % 32 == 0 or m.in_channels < 32) and m.out_channels % 8 == 0
 
 
+def depthwise_refusal(m: nn.Conv2d):
+    """why the depthwise kernels (csrc/lk_dwconv.hip) do not take the grouped convolution ``m``, or None: the contract of
+    lk_dwconv_fwd_nhwc_f32 / lk_dwconv_bwd_nhwc_f16x2 as a predicate on the module"""
+    (kh, kw), (sh, sw) = m.kernel_size, m.stride
+    if m.groups != m.in_channels:
+        return f"narrow groups ({m.in_channels // m.groups} input channels per group)"
+    if m.out_channels != m.in_channels:
+        return f"channel multiplier {m.out_channels // m.in_channels}"
+    if isinstance(m.padding, str) or m.padding_mode != "zeros":
+        return "padding other than zeros"
+    if tuple(m.dilation) != (1, 1):
+        return f"dilation {tuple(m.dilation)}"
+    if kh * kw > 25:
+        return f"window {kh} x {kw}: kh kw > 25"
+    if not (1 <= sh <= 8 and 1 <= sw <= 8):
+        return f"stride {(sh, sw)} above 8"
+    if not (0 <= m.padding[0] < kh and 0 <= m.padding[1] < kw):
+        return f"padding {tuple(m.padding)} not below the window {(kh, kw)}"
+    return None
+
+
+def depthwise_supported(m) -> bool:
+    """what the depthwise kernels cover: ``groups == in_channels == out_channels``, undilated, zero padding below the window,
+    at most 25 taps, strides up to 8"""
+    return isinstance(m, nn.Conv2d) and m.groups > 1 and depthwise_refusal(m) is None
+
+
+class PreparedDepthwise:
+    """Tap-major fp32 copy ``w_tap [kh * kw, C]`` of a depthwise weight (``w_tap[dy * kw + dx, c] = weight[c, 0, dy, dx]``: a
+    lane's four channels of a tap are one 16-byte load) and the words of the forward bound; rebuilt when the weight changes."""
+
+    def __init__(self, m: nn.Conv2d):
+        self.m = m
+        self._w = None  # (key, w_tap, l1)
+        self._b = None  # (key, max|bias|)
+
+    @property
+    def w_tap(self) -> torch.Tensor:
+        w = self.m.weight
+        key = (w._version, w.data_ptr())
+        if self._w is None or self._w[0] != key:
+            wt = w.detach().to(torch.float32).reshape(w.shape[0], -1).t().contiguous()
+            # max|y_n| <= max|x_n| * max_c sum_taps |w[c]| + max|bias| (a per-layer constant: preparation, not the hot path)
+            self._w = (key, wt, wt.abs().sum(0).max().reshape(1).contiguous())
+        return self._w[1]
+
+    @property
+    def bias(self):
+        b = self.m.bias
+        return None if b is None else b.detach().to(torch.float32).contiguous()
+
+    def forward_l1(self):
+        """(l1, max|bias| or None): device words with ``max|y_n| <= max|x_n| * l1 + max|bias|``"""
+        self.w_tap
+        b = self.m.bias
+        if b is None:
+            return self._w[2], None
+        key = (b._version, b.data_ptr())
+        if self._b is None or self._b[0] != key:
+            self._b = (key, b.detach().abs().float().max().reshape(1).contiguous())
+        return self._w[2], self._b[1]
+
+
 class PreparedConv:
     """Split, tap-major copies of a conv weight for the two GEMM forms; rebuilt when the weight (or the per-output-channel
     scale folded into it, e.g. a deferred BatchNorm scale) changes."""

@@ -157,3 +157,46 @@ class MobileNetV2Small(nn.Module):
 
     def forward(self, x):
         return self.fc(torch.flatten(self.pool(self.head(self.layers(self.stem(x)))), 1))
+
+
+class MobileNetV1(nn.Module):
+    """A MobileNetV1-style network for 3 x 32 x 32 inputs: 3x3 stride-1 stem, thirteen depthwise-separable blocks (depthwise
+    3x3, BatchNorm, activation, pointwise 1x1, BatchNorm, activation), pool, linear.  Every channel count is a multiple of 32
+    (``ch(c) = max(32, int(c * width + 16) // 32 * 32)``), so the pointwise layers match the split-fp16 MFMA kernels and the
+    depthwise layers can run through csrc/lk_dwconv.hip (``SplitSweep.nhwc_depthwise = True``): the workload of the depthwise route of the
+    NHWC sweep.  No convolution
+    has a bias.
+
+    ``freeze_depthwise=True`` takes the depthwise weights out of the Laplace parameters: the supported way to run ``kron``, which
+    has no rule for a grouped layer.  ``act`` is the activation module's class, as with :class:`MobileNetV2Small`."""
+
+    #: (output channels, stride) of the separable blocks
+    SETTINGS = ((64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1), (512, 1), (512, 1), (512, 1), (512, 1),
+                (1024, 2), (1024, 1))
+
+    def __init__(self, num_classes: int = 10, width: float = 1.0, freeze_bn: bool = True, freeze_depthwise: bool = False,
+                 act=nn.ReLU):
+        super().__init__()
+
+        def ch(c):
+            return max(32, int(c * width + 16) // 32 * 32)
+
+        cin = ch(32)
+        self.stem = nn.Sequential(nn.Conv2d(3, cin, 3, 1, 1, bias=False), nn.BatchNorm2d(cin), act())
+        blocks = []
+        for c, s in self.SETTINGS:
+            blocks.append(nn.Sequential(nn.Conv2d(cin, cin, 3, s, 1, groups=cin, bias=False), nn.BatchNorm2d(cin), act(),
+                                        nn.Conv2d(cin, ch(c), 1, bias=False), nn.BatchNorm2d(ch(c)), act()))
+            cin = ch(c)
+        self.layers = nn.Sequential(*blocks)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+        for m in self.modules():
+            if freeze_bn and isinstance(m, nn.BatchNorm2d):
+                m.weight.requires_grad_(False)
+                m.bias.requires_grad_(False)
+            if freeze_depthwise and isinstance(m, nn.Conv2d) and m.groups != 1:
+                m.weight.requires_grad_(False)
+
+    def forward(self, x):
+        return self.fc(torch.flatten(self.pool(self.layers(self.stem(x))), 1))

@@ -14,8 +14,10 @@ laplace/curvature/curvlinops.py:87-100):
 * the G factor of a convolution layer is the Gram of the split tensor itself (``lk_gram_tn_f16x2``).
 
 Max and average pooling run on the fp32 NHWC maps (csrc/lk_pool.hip: one byte of window-local argmax per output element for
-all seeds, a gather-form VJP).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive
-pooling to several cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
+all seeds, a gather-form VJP), and - with ``nhwc_depthwise = True`` - depthwise convolutions on their own streaming kernels
+(csrc/lk_dwconv.hip: an fp32 forward, a gather-form backward-data that reads the split cotangent and writes fp32 for all seeds in
+one launch).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
+cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
 
@@ -159,7 +161,10 @@ class SplitSweep(SeedBatchedSweep):
             if r.kind == CONV:
                 m, first = r.mod, r.src[0].op == "placeholder"
                 if m.groups != 1:
-                    return f"{node.target}: grouped convolution (foreign to the NHWC kernels; the NCHW sweep serves it)"
+                    why = self._depthwise_refusal(node, m)
+                    if why is not None:
+                        return f"{node.target}: grouped convolution ({why}; the NCHW sweep serves it)"
+                    continue  # (served by lk_dwconv.hip; a graph still needs a dense convolution)
                 if not cv.supported(m) and not (first and node.target in self.tap_names and m.out_channels % 8 == 0):
                     return f"{node.target}: convolution outside the implicit-GEMM kernel's coverage"
                 n_conv += 1
@@ -185,6 +190,32 @@ class SplitSweep(SeedBatchedSweep):
 
     #: ``False``: a model with max / average pooling runs through the NCHW sweep, as it did before lk_pool.hip
     nhwc_pool = True
+    #: ``True``: depthwise convolutions run on csrc/lk_dwconv.hip and their model stays on the NHWC walk.  ``False`` (the default):
+    #: such a model runs through the NCHW sweep, as it did before lk_dwconv.hip.  Off by default because the route has to lose on
+    #: neither line of tools/dwconv_bench.py and lost on one: on MobileNetV1 at minibatch 128 it halves `kron` with the depthwise
+    #: weights frozen, but `diag` with them tracked came out 0.3 % slower, in every round (profiles/dwconv_bench.json)
+    nhwc_depthwise = False
+
+    def _depthwise_refusal(self, node, m):
+        """why this grouped convolution keeps the model off the NHWC walk (None: lk_dwconv.hip serves it)"""
+        if not self.nhwc_depthwise:
+            return "foreign to the NHWC kernels"
+        why = cv.depthwise_refusal(m)
+        if why is not None:
+            return f"{why}: outside the depthwise kernels' contract"
+        if not any(k in _MAP_SOURCES for k in self._walk(node, False)):
+            return "depthwise convolution outside the feature maps"
+        if not all(hasattr(self.kernels(), f) for f in ("dwconv_forward", "dwconv_backward")):
+            return "kernels without the depthwise entry points"
+        return None
+
+    def _is_depthwise(self, m) -> bool:
+        return self.split_ok and isinstance(m, nn.Conv2d) and m.groups != 1
+
+    def _defers_scale_to(self, src, cot) -> bool:
+        # (the depthwise backward-data takes no folded BatchNorm scale)
+        r = self.rule.get(src)
+        return not (r is not None and self._is_depthwise(r.mod)) and super()._defers_scale_to(src, cot)
 
     def _pool_refusal(self, node, r):
         """why this MAXPOOL / AVGPOOL node keeps the model off the NHWC walk (None: lk_pool.hip serves it)"""
@@ -291,7 +322,29 @@ class SplitSweep(SeedBatchedSweep):
             xh = xp
         return K.split_images_f16x2(xh)  # one scale per image (lk_split_images_f16x2)
 
+    def _run_depthwise(self, node, m, inp):
+        """depthwise convolution on a feature map: lk_dwconv_fwd_nhwc_f32 on the NHWC memory of the input; returns the
+        NCHW-logical view over NHWC memory, as `_run_pool` does.  Where the input carries per-image ``"bound"`` words the output
+        registers the guaranteed bound ``max|x_n| * l1 + max|bias|``, as a dense convolution does, and the BatchNorm launch behind
+        it needs no pass over the map."""
+        # (also with ``nhwc_forward = False``: the reverse sweep is NHWC either way)
+        if not (torch.is_tensor(inp) and inp.dim() == 4 and inp.dtype == torch.float32):
+            raise SweepUnsupported(f"{node.target}: depthwise convolution of the NHWC sweep expects an fp32 feature map")
+        prep = self._prep.get(node.target)
+        if prep is None:
+            prep = self._prep[node.target] = cv.PreparedDepthwise(m)
+        xh = inp.permute(0, 2, 3, 1).contiguous()  # (a view when inp is already NHWC in memory)
+        y = self.kernels().dwconv_forward(xh, prep.w_tap, prep.bias, m.kernel_size, m.stride, m.padding)
+        out = y.permute(0, 3, 1, 2)
+        aux = self._aux_get(inp)
+        if aux is not None and aux.get("bound") is not None:
+            l1, bmax = prep.forward_l1()
+            self._aux_put(out, {"in_amax": aux["bound"], "mul": l1, "add": bmax})
+        return out
+
     def _run_conv(self, node, m, inp):
+        if self._is_depthwise(m):
+            return self._run_depthwise(node, m, inp)
         if not (self._use_nhwc_forward(inp) and cv.forward_supported(m)):
             return m(inp)
         prep = self._prep.get(node.target)
@@ -593,6 +646,15 @@ class SplitSweep(SeedBatchedSweep):
                     if not remaining:
                         break
                 if src.op == "placeholder":
+                    continue
+                if self._is_depthwise(m):
+                    # one launch for all seeds into fp32 (lk_dwconv_bwd_nhwc_f16x2): no lazy part, no fused epilogue
+                    prep = self._prep.get(node.target)
+                    if prep is None:
+                        prep = self._prep[node.target] = cv.PreparedDepthwise(m)
+                    in_shape, word = self.saved[node], new_word()  # [B, C, Hin, Win]
+                    push(src, _F32(K.dwconv_backward(g, prep.w_tap, S, (int(in_shape[2]), int(in_shape[3])), m.kernel_size,
+                                                     m.stride, m.padding, amax=word), word))
                     continue
                 prep = self._prep.get(node.target)
                 if prep is None:
