@@ -88,6 +88,29 @@ int lk_sq_err_sum_f32(const float* f, const float* y, int64_t numel, float scale
  * ------------------------------------------------------------------------------------------- */
 size_t lk_gram_workspace_bytes(int64_t n, int64_t K);
 size_t lk_gram_nt_workspace_bytes(int64_t nb_total, int64_t n, int64_t L);
+/* Which instantiation of the Gram engine, which split of K and which reduction a launch takes (pure host function, no device:
+ * the launchers decide with the same helpers of csrc/lk_gram.hip).  `entry`: LK_GRAM_*; (n, K, L) per entry:
+ *   LK_GRAM_TN            n, K of lk_gram_tn_f32
+ *   LK_GRAM_NT            n, K = nseg * nb images, L positions of lk_gram_nt_f32 / lk_gram_nt_seg_f32
+ *   LK_GRAM_CONV          n = Cin * kh * kw, K = B * OH * OW of lk_gram_conv_nhwc_f32
+ *   LK_GRAM_XCORR_FULL    n = Cin, K = B * H * W: the full-grid launch of lk_conv3x3_shiftcorr_f32 (13 shifts)
+ *   LK_GRAM_XCORR_STRIPS  n = Cin, K = B * max(H, W): its launch of the four boundary strips and four corners (25 shifts)
+ * `vec4_ok`: what of the 16-byte-load rule the arguments do not show — every operand pointer 16-byte aligned, for _TN
+ * ldx % 4 == 0, for _CONV Cin % 4 == 0 (n % 4 for _TN, L % 4 for _NT and Cin % 4 for _XCORR_* are applied here).  `flags`: as
+ * for the launch.  Fills out[12]:
+ *   [0] loader: 0 TN, 1 NT, 2 CONV, 3 XCORR, 5 NTB (NT on split-bf16 products)   [1] VEC: 4 or 1 floats per load
+ *   [2] tile configuration: 0 SMALL (64), 1 BIG (128), 2 WIDE (192)   [3] T   [4] BK rows per chunk
+ *   [5] tile pairs (workgroups per split)   [6] chunks   [7] splits of K   [8] chunks per split
+ *   [9] epilogue: 0 slabs + reduce, 1 direct into C, 2 persistent slabs   [10] two-level slab reduction   [11] rows per
+ *   workgroup of the reduction (4 or 64)
+ * and returns 0, or a negative value for what the entry point refuses or launches nothing for (n < 1, K < 0; _XCORR_*: K < 1).
+ * The pixel-pair form reports its tile through lk_conv3x3_pixpair_plan (64: the 64-tile with 16-row chunks, 128: BIG). */
+#define LK_GRAM_TN 0
+#define LK_GRAM_NT 1
+#define LK_GRAM_CONV 2
+#define LK_GRAM_XCORR_FULL 3
+#define LK_GRAM_XCORR_STRIPS 4
+int lk_gram_launch_variant(int entry, int64_t n, int64_t K, int64_t L, int vec4_ok, unsigned flags, int* out);
 /* C += alpha * sum of the persistent slabs (LK_GRAM_SLABS_PERSIST) of an n x n product; L_nt = L of the _nt launches
  * that filled them (0 for _tn / _conv); `slabs` is modified.  flags: LK_GRAM_UPPER_ONLY as for the launches. */
 int lk_gram_slabs_reduce_f32(float* slabs, size_t slabs_bytes, int64_t n, int64_t L_nt, float alpha, float* C,

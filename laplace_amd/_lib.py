@@ -46,6 +46,7 @@ SIGNATURES = {
     "lk_sq_err_sum_f32": (_int, [_vp, _vp, _i64, _f32, _vp, _vp, _vp]),
     "lk_gram_workspace_bytes": (_sz, [_i64, _i64]),
     "lk_gram_nt_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "lk_gram_launch_variant": (_int, [_int, _i64, _i64, _i64, _int, _u32, _vp]),
     "lk_gram_slabs_reduce_f32": (_int, [_vp, _sz, _i64, _i64, _f32, _vp, _u32, _vp]),
     "lk_gram_tn_f32": (_int, [_vp, _i64, _i64, _i64, _f32, _vp, _u32, _vp, _sz, _vp]),
     "lk_gram_nt_f32": (_int, [_vp, _i64, _i64, _i64, _f32, _vp, _u32, _vp, _sz, _vp]),
@@ -373,6 +374,25 @@ class HipKernels:
             "lk_gram_tn_f32",
         )
         return out
+
+    #: ``entry`` of :meth:`gram_launch_variant` (LK_GRAM_* of include/laplace_hip.h)
+    GRAM_TN, GRAM_NT, GRAM_CONV, GRAM_XCORR_FULL, GRAM_XCORR_STRIPS = range(5)
+    GRAM_UPPER_ONLY, GRAM_SLABS_PERSIST = 1, 2
+    _GRAM_MODES = {0: "TN", 1: "NT", 2: "CONV", 3: "XCORR", 5: "NTB"}
+    _GRAM_CFGS = ("SMALL", "BIG", "WIDE")
+    _GRAM_EPILOGUES = ("slabs", "direct", "persist")
+
+    def gram_launch_variant(self, entry, n, K, L=0, vec4_ok=True, flags=0):
+        """lk_gram_launch_variant: loader, VEC, tile configuration, split of K, epilogue and reduction a launch of the fp32 Gram
+        engine takes (host only, no device), or ``None`` for what the entry point refuses or launches nothing for.  ``vec4_ok``:
+        what of the 16-byte-load rule the arguments do not show (pointer alignment; TN: ``ldx % 4 == 0``; CONV: ``Cin % 4 == 0``)."""
+        o = (ctypes.c_int * 12)()
+        rc = self.lib.lk_gram_launch_variant(int(entry), int(n), int(K), int(L), int(bool(vec4_ok)), int(flags), o)
+        if rc < 0:
+            return None
+        return {"mode": self._GRAM_MODES[o[0]], "vec": o[1], "cfg": self._GRAM_CFGS[o[2]], "T": o[3], "BK": o[4], "npairs": o[5],
+                "nchunks": o[6], "nsplit": o[7], "chunks_per_split": o[8], "epilogue": self._GRAM_EPILOGUES[o[9]],
+                "two_level": bool(o[10]), "rpw": o[11]}
 
     def gram_nt_slab_bytes(self, nb_total, n, L) -> int:
         return int(self.lib.lk_gram_nt_workspace_bytes(int(nb_total), int(n), int(L)))

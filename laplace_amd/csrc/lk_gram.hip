@@ -713,6 +713,21 @@ static GramPlan make_plan_rect(int64_t nA, int64_t nB, int64_t K) {
 static int reduce_slabs(const GramPlan& p, float* slabs, int nslabs, float alpha, float* C, int n, unsigned flags,
                         hipStream_t stream);
 
+// The launch rules outside the plan.  The launchers and lk_gram_launch_variant (what the tests prove their coverage with) all
+// decide with these and with make_plan / make_plan_rect.
+// 16-byte loads: the contiguous extent (TN: n, NT: L, CONV / XCORR: Cin) is a multiple of four floats and the operand allows it
+static bool vec4_rule(int64_t extent, bool operand_ok) { return extent % 4 == 0 && operand_ok; }
+// one split + upper-only accumulation: the kernel adds into C itself (no slab round trip)
+static bool direct_rule(const GramPlan& p, unsigned flags) {
+  return !(flags & LK_GRAM_SLABS_PERSIST) && p.nsplit == 1 && (flags & LK_GRAM_UPPER_ONLY);
+}
+// two-level slab reduction keeps every thread's serial chain short
+static bool two_level_rule(int nslabs) { return nslabs > 32; }
+// NT: rows per chunk (a chunk never straddles images: L is padded to a multiple of it)
+static int nt_chunk_rows(int64_t n, int64_t L) { return cfg_bk(make_plan(n, 1, L).cfg); }
+// NT: fp32 products from split-bf16 MFMAs (MODE_NTB) whenever the positions can be read four at a time
+static int nt_mode_rule(bool vec4, int BK) { return (vec4 && BK % 16 == 0) ? MODE_NTB : MODE_NT; }
+
 // Kernels whose dynamic LDS exceeds the 64 KB default need the limit raised once per function.
 static bool allow_big_lds(const void* fn, size_t bytes) {
   if (bytes <= 64 * 1024) return true;
@@ -735,9 +750,8 @@ static int launch_gram(const GramGeom& g, bool vec4, float alpha, float* C, unsi
   }
   float* slabs = static_cast<float*>(ws);
   dim3 grid(p.npairs, p.nsplit), block(256);
-  // one split + upper-only accumulation: the kernel adds into C itself (no slab round trip)
   const bool persist = (flags & LK_GRAM_SLABS_PERSIST) != 0;
-  float* Cdirect = (!persist && p.nsplit == 1 && (flags & LK_GRAM_UPPER_ONLY)) ? C : nullptr;
+  float* Cdirect = direct_rule(p, flags) ? C : nullptr;
   GramGeom gp = g;
   gp.slab_accumulate = persist ? 1 : 0;
   const size_t lds = cfg_lds_bytes(p.cfg, !(p.cfg == CFG_SMALL), MODE == MODE_NTB);
@@ -769,7 +783,7 @@ static int reduce_slabs(const GramPlan& p, float* slabs, int nslabs, float alpha
                         hipStream_t stream) {
   int stride = 1;
   const int64_t slab_elems = (int64_t)p.npairs * p.T * p.T;
-  if (nslabs > 32) {  // two-level reduction keeps every thread's serial chain short
+  if (two_level_rule(nslabs)) {
     const int SG = 32;
     const int groups = (nslabs + SG - 1) / SG;
     int64_t bx = (slab_elems / 4 + 255) / 256;
@@ -826,7 +840,7 @@ static int launch_xcorr(const float* x, int64_t B, int H, int W, int Cin, const 
     return LK_EWORKSPACE;
   }
   float* slabs = static_cast<float*>(ws);
-  const bool vec4 = (Cin % 4 == 0) && aligned16(x);
+  const bool vec4 = vec4_rule(Cin, aligned16(x));
   dim3 grid(p.npairs, p.nsplit, nreg), block(256);
   const size_t lds = cfg_lds_bytes(p.cfg, true);
 #define LK_LAUNCH(V, S)                                                                                            \
@@ -850,7 +864,7 @@ static int launch_xcorr(const float* x, int64_t B, int H, int W, int Cin, const 
   if (rc) return rc;
   int nslabs = p.nslabs, stride = 1;
   const int64_t slab_elems = (int64_t)p.npairs * p.T * p.T;
-  if (nslabs > 32) {
+  if (two_level_rule(nslabs)) {
     const int SG = 32;
     const int groups = (nslabs + SG - 1) / SG;
     int64_t bx = (slab_elems / 4 + 255) / 256;
@@ -1222,9 +1236,51 @@ extern "C" size_t lk_gram_workspace_bytes(int64_t n, int64_t K) {
 
 extern "C" size_t lk_gram_nt_workspace_bytes(int64_t nb_total, int64_t n, int64_t L) {
   if (n <= 0 || L <= 0) return 0;
-  const int BK = cfg_bk(make_plan(n, 1, L).cfg);
+  const int BK = nt_chunk_rows(n, L);
   const int64_t Lp = (L + BK - 1) / BK * BK;
   return make_plan(n, nb_total < 1 ? Lp : nb_total * Lp, L).ws_bytes;
+}
+
+// Which instantiation, split and reduction a launch of the Gram entry points takes: what launch_gram / launch_xcorr decide, from
+// the same helpers, without a launch and without a device (include/laplace_hip.h).
+extern "C" int lk_gram_launch_variant(int entry, int64_t n, int64_t K, int64_t L, int vec4_ok, unsigned flags, int* out) {
+  if (!out || entry < LK_GRAM_TN || entry > LK_GRAM_XCORR_STRIPS) return -1;
+  if (n < 1 || K < 0 || n >= (1 << 30)) return -1;  // (n = 0 is accepted by the entry points and launches nothing)
+  GramPlan p;
+  int mode;
+  bool vec4;
+  unsigned fl = flags;
+  if (entry == LK_GRAM_TN) {  // lk_gram_tn_f32
+    p = make_plan(n, K);
+    mode = MODE_TN;
+    vec4 = vec4_rule(n, vec4_ok != 0);
+  } else if (entry == LK_GRAM_NT) {  // lk_gram_nt_f32 / lk_gram_nt_seg_f32: K images of L positions
+    if (L < 1 || L >= (1 << 30)) return -1;
+    const int BK = nt_chunk_rows(n, L);
+    const int64_t Lp = (L + BK - 1) / BK * BK;
+    p = make_plan(n, K * Lp, L);
+    vec4 = vec4_rule(L, vec4_ok != 0);
+    mode = nt_mode_rule(vec4, BK);
+  } else if (entry == LK_GRAM_CONV) {  // lk_gram_conv_nhwc_f32: K = B * OH * OW
+    if (K >= (1ll << 31) - 64) return -1;
+    p = make_plan(n, K);
+    mode = MODE_CONV;
+    vec4 = vec4_ok != 0;  // (Cin is not among the arguments: the caller applies Cin % 4 == 0)
+  } else {  // the two launches of lk_conv3x3_shiftcorr_f32: n = Cin, K = rows of the longest region
+    if (K < 1 || K >= (1ll << 31) - 64 || 25 * n >= (1 << 24)) return -1;
+    p = make_plan_rect(n, (entry == LK_GRAM_XCORR_FULL ? 13 : 25) * n, K);
+    mode = MODE_XCORR;
+    vec4 = vec4_rule(n, vec4_ok != 0);
+    fl = 0;  // (always slabs + reduce, no mirror)
+  }
+  const bool persist = (fl & LK_GRAM_SLABS_PERSIST) != 0;
+  const bool direct = direct_rule(p, fl);
+  out[0] = mode, out[1] = vec4 ? 4 : 1, out[2] = p.cfg, out[3] = p.T, out[4] = p.BK, out[5] = p.npairs;
+  out[6] = p.nchunks, out[7] = p.nsplit, out[8] = p.chunks_per_split;
+  out[9] = persist ? 2 : (direct ? 1 : 0);
+  out[10] = (!direct && two_level_rule(p.nslabs)) ? 1 : 0;
+  out[11] = p.rpw;
+  return 0;
 }
 
 extern "C" int lk_gram_slabs_reduce_f32(float* slabs, size_t slabs_bytes, int64_t n, int64_t L_nt, float alpha, float* C,
@@ -1243,7 +1299,7 @@ extern "C" int lk_gram_tn_f32(const float* X, int64_t K, int64_t n, int64_t ldx,
   LK_REQUIRE(n < (1 << 30), "lk_gram_tn_f32: n too large");
   GramGeom g{};
   g.x = X; g.K = K; g.n = (int)n; g.ldx = ldx;
-  const bool vec4 = (n % 4 == 0) && (ldx % 4 == 0) && aligned16(X);
+  const bool vec4 = vec4_rule(n, ldx % 4 == 0 && aligned16(X));
   return launch_gram<MODE_TN>(g, vec4, alpha, C, flags, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -1252,22 +1308,22 @@ extern "C" int lk_gram_nt_seg_f32(const float* const* segs, int64_t nseg, int64_
   LK_REQUIRE(segs && C && nseg >= 1 && nseg <= MAX_SEG && nb >= 0 && n >= 0 && L >= 1,
              "lk_gram_nt_seg_f32: bad arguments (at most 16 segments)");
   LK_REQUIRE(n < (1 << 30) && L < (1 << 30), "lk_gram_nt_seg_f32: dims too large");
-  const int BK = cfg_bk(make_plan(n, 1, L).cfg);
+  const int BK = nt_chunk_rows(n, L);
   GramGeom g{};
   g.n = (int)n; g.L = (int)L;
   g.Lp = (int)((L + BK - 1) / BK * BK);
   g.seg_nb = (int)(nb > 0 ? nb : 1);
   g.nseg = (int)nseg;
   g.K = nseg * nb * g.Lp;
-  bool vec4 = (L % 4 == 0);
+  bool all_aligned = true;
   for (int i = 0; i < nseg; ++i) {
     LK_REQUIRE(segs[i] != nullptr, "lk_gram_nt_seg_f32: null segment");
     g.seg[i] = segs[i];
-    vec4 = vec4 && aligned16(segs[i]);
+    all_aligned = all_aligned && aligned16(segs[i]);
   }
+  const bool vec4 = vec4_rule(L, all_aligned);
   g.x = segs[0];
-  // fp32 products from split-bf16 MFMAs (MODE_NTB) whenever the positions can be read four at a time
-  if (vec4 && BK % 16 == 0) return launch_gram<MODE_NTB>(g, vec4, alpha, C, flags, ws, ws_bytes, (hipStream_t)stream);
+  if (nt_mode_rule(vec4, BK) == MODE_NTB) return launch_gram<MODE_NTB>(g, vec4, alpha, C, flags, ws, ws_bytes, (hipStream_t)stream);
   return launch_gram<MODE_NT>(g, vec4, alpha, C, flags, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -1293,7 +1349,7 @@ extern "C" int lk_gram_conv_nhwc_f32(const float* x, int64_t B, int64_t H, int64
   LK_REQUIRE(g.K < (1ll << 31) - 64, "lk_gram_conv_nhwc_f32: B*OH*OW must be < 2^31");
   g.div_ohw = make_fastdiv((int)(OH * OW));
   g.div_ow = make_fastdiv((int)OW);
-  const bool vec4 = (Cin % 4 == 0) && aligned16(x);
+  const bool vec4 = vec4_rule(Cin, aligned16(x));
   return launch_gram<MODE_CONV>(g, vec4, alpha, C, flags, ws, ws_bytes, (hipStream_t)stream);
 }
 

@@ -496,6 +496,26 @@ for _name, _acc, _ref in WINP_EDGES:
     VALUE_PROBES.append((f"winp {_name} +", "lk_conv_winp_eligible", {**WINP_BASE, **_acc}))
     VALUE_PROBES.append((f"winp {_name} -", "lk_conv_winp_eligible", {**WINP_BASE, **_ref}))
 
+# lk_gram_launch_variant(entry, n, K, L, vec4_ok, flags, out): 0 for a launch the entry point makes, negative for what it refuses
+# or launches nothing for (host only: make_plan and the launch rules, no device)
+GRAM_VARIANT_BASE = dict(entry=0, n=8, K=16, L=4, vec4_ok=1, flags=0)
+GRAM_VARIANT_EDGES = [
+    ("entry <= 4", {"entry": 4}, {"entry": 5}),
+    ("entry >= 0", {"entry": 0}, {"entry": -1}),
+    ("n >= 1", {"n": 1}, {"n": 0}),
+    ("n < 2^30", {"n": 1 << 20}, {"n": 1 << 30}),
+    ("K >= 0", {"K": 0}, {"K": -1}),
+    ("NT: L >= 1", {"entry": 1, "L": 1}, {"entry": 1, "L": 0}),
+    ("NT: L < 2^30", {"entry": 1, "L": (1 << 30) - 1, "K": 1}, {"entry": 1, "L": 1 << 30, "K": 1}),
+    ("CONV: K < 2^31 - 64", {"entry": 2, "K": (1 << 31) - 65}, {"entry": 2, "K": (1 << 31) - 64}),
+    ("XCORR: K >= 1", {"entry": 3, "K": 1}, {"entry": 3, "K": 0}),
+    ("XCORR: 25 Cin < 2^24", {"entry": 4, "n": 671088}, {"entry": 4, "n": 671089}),
+    ("out", {}, {"out": None}),
+]
+for _name, _acc, _ref in GRAM_VARIANT_EDGES:
+    VALUE_PROBES.append((f"gramvar {_name} +", "lk_gram_launch_variant", {**GRAM_VARIANT_BASE, **_acc}))
+    VALUE_PROBES.append((f"gramvar {_name} -", "lk_gram_launch_variant", {**GRAM_VARIANT_BASE, **_ref}))
+
 # *_workspace_bytes at 0, 1 and the largest extent the entry point accepts: monotone, no wrap to a small number
 WORKSPACE_LADDERS = {
     "lk_loss_workspace_bytes": [dict(B=0), dict(B=1), dict(B=(1 << 31) - 1)],
@@ -742,6 +762,13 @@ def test_winp_eligibility_edges(probes, name):
     in nothing else, so a dropped condition shows as a 1 where a 0 is expected)"""
     assert probes["values"][f"winp {name} +"] == 1, f"{name}: the last accepted shape is not eligible"
     assert probes["values"][f"winp {name} -"] == 0, f"{name}: the first refused shape is eligible"
+
+
+@pytest.mark.parametrize("name", [e[0] for e in GRAM_VARIANT_EDGES])
+def test_gram_launch_variant_edges(probes, name):
+    """lk_gram_launch_variant answers (0) on the last shape the entry point launches and refuses (negative) the first it does not"""
+    assert probes["values"][f"gramvar {name} +"] == 0, f"{name}: the last accepted shape is refused"
+    assert probes["values"][f"gramvar {name} -"] < 0, f"{name}: the first refused shape is answered"
 
 
 @pytest.mark.parametrize("fn", sorted(WORKSPACE_LADDERS))
