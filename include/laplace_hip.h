@@ -426,6 +426,34 @@ int lk_jac_conv_f32(const float* x_nchw, const float* g, int64_t B, int64_t Cc, 
 int lk_jac_norm_affine_f32(const float* g, const float* xhat, int64_t S, int64_t B, int64_t L, int64_t Ch, int layout,
                            float* Js, int64_t P, int64_t wcol0, int64_t bcol0, void* stream);
 
+/* The same Jacobian for a norm layer tapped on the NHWC split-fp16 reverse sweep, read where that sweep leaves the cotangent
+ * of the layer's output (replaces the same norm-parameter columns of CurvatureInterface.jacobians,
+ * laplace/curvature/curvature.py:88-129, and of GGNInterface.diag / EFInterface.diag, curvature.py:413-433, 494-505):
+ *   g:  [S][B][L][Ch] as the two fp16 planes g_h, g_l of a ONE-scale split tensor, g = (float(h) + float(l)) * 2^-sexp[0]
+ *       (sexp: one device int);
+ *   x:  [B][L][Ch] fp32, ONE copy for all seeds; mu, rstd: [Ch], given together or both null;
+ *   xhat = (x - mu[ch]) * rstd[ch], formed in registers (no activation-sized xhat tensor exists); x itself when both are null;
+ *   Js[n][s][wcol0 + ch] = sum_l g * xhat      (skipped when wcol0 < 0)
+ *   Js[n][s][bcol0 + ch] = sum_l g             (skipped when bcol0 < 0)
+ * fp32 accumulation, the power-of-two scale applied once at the store.  Every other column of Js is left untouched.
+ * Deterministic: no atomics, one owner per output, a fixed reduction tree (xor-shuffles inside a wave, then LDS), plain stores.
+ * Few (sample, channel tile) pairs: the seeds are split over grid.y; L is never split.
+ * Minimal traffic: 4 S B L Ch + 4 B L Ch + 8 B S Ch bytes.
+ * Contract: g_h, g_l, sexp, x, Js non-null; 1 <= S, 0 <= B, S * B < 2^31; 1 <= L < 2^30; 1 <= Ch < 2^30; S * B * L * Ch < 2^40;
+ * B * (channel tiles per sample) < 2^31; column ranges inside P and not overlapping.  B == 0, or both offsets negative, returns
+ * LK_OK.
+ * lk_normtap_variant (host only): the path a shape takes; `affine`: mu and rstd are given; `aligned`: g_h, g_l, x, mu and rstd
+ * are 16-byte aligned.  Returns
+ *   vector class | seed-split << 2 | affine << 3 | seeds per pass << 4 | log2(lane rows per workgroup) << 8 |
+ *   seeds per grid.y slice (capped at 255) << 12 | channel tiles per sample (capped at 2047) << 20
+ *   vector class: 0 one channel per lane, 1 four (8-byte plane loads; Ch % 4 == 0 and aligned), 2 eight (16-byte plane loads;
+ *   Ch % 8 == 0 and aligned); seeds per pass: how many seeds' plane loads a lane has in flight
+ * or a negative value for a shape the entry point refuses. */
+int lk_jac_norm_affine_nhwc_f16x2(const void* g_h, const void* g_l, const int* sexp, const float* x, const float* mu,
+                                  const float* rstd, int64_t S, int64_t B, int64_t L, int64_t Ch, float* Js, int64_t P,
+                                  int64_t wcol0, int64_t bcol0, void* stream);
+int lk_normtap_variant(int64_t S, int64_t B, int64_t L, int64_t Ch, int affine, int aligned);
+
 /* Forward and input VJP of the per-sample normalisation layers (nn.GroupNorm, nn.LayerNorm) for the seed-batched reverse
  * sweep; they replace the reverse passes through these layers of laplace/curvature/curvlinops.py:87-100 (the KFAC backward)
  * and of the jacrev materialisation of CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129 (one stock

@@ -123,6 +123,8 @@ SIGNATURES = {
     "lk_dwconv_fwd_nhwc_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp]),
     "lk_dwconv_bwd_nhwc_f16x2": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp, _vp]),
     "lk_dwconv_variant": (_int, [_i64, _i64, _i64, _i64, _i64] + [_int] * 7),
+    "lk_jac_norm_affine_nhwc_f16x2": (_int, [_vp] * 6 + [_i64] * 4 + [_vp, _i64, _i64, _i64, _vp]),
+    "lk_normtap_variant": (_int, [_i64, _i64, _i64, _i64, _int, _int]),
     "lk_bn_act_fwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_vjp_scale_mask_f32": (_int, [_vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_ll_ggn_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1226,6 +1228,42 @@ class HipKernels:
                                             int(wcol0), int(bcol0), self._stream(g.device)),
             "lk_jac_norm_affine_f32",
         )
+
+    def jac_norm_affine_nhwc(self, g: "SplitTensor", x, mu, rstd, S, Js, wcol0, bcol0=-1):
+        """the same columns from the NHWC sweep's own cotangent (csrc/lk_normtap.hip): ``g`` the one-scale split tensor
+        ``[S*B, .., Ch]``, ``x`` ``[B, .., Ch]`` fp32, ``xhat = (x - mu) * rstd`` formed in registers (``mu``, ``rstd`` ``[Ch]``, or
+        both ``None``: ``x`` is ``xhat``)."""
+        _one_scale(g, "jac_norm_affine_nhwc")
+        if g.chunked:
+            raise LaplaceHipError("jac_norm_affine_nhwc: a chunk-major split tensor is an operand of the weight-sharing "
+                                  "predictive; this kernel reads position-major planes [S*B, .., Ch]")
+        _check(g.planes, "g.planes", torch.float16), _check(g.sexp, "g.sexp", torch.int32), _check(x, "x"), _check(Js, "Js")
+        S = int(S)
+        if x.dim() < 2 or g.planes.dim() != x.dim() + 1 or S < 1 or g.planes.shape[1] != S * x.shape[0] \
+                or tuple(g.planes.shape[2:]) != tuple(x.shape[1:]) or Js.dim() != 3 or tuple(Js.shape[:2]) != (x.shape[0], S):
+            raise LaplaceHipError("jac_norm_affine_nhwc: g [S*B, .., Ch], x [B, .., Ch] and Js [B, S, P] do not match")
+        B, Ch = x.shape[0], x.shape[-1]
+        if (mu is None) != (rstd is None):
+            raise LaplaceHipError("jac_norm_affine_nhwc: mu and rstd are given together or not at all")
+        for name, t in (("mu", mu), ("rstd", rstd)):
+            if t is not None and tuple(_check(t, name).shape) != (Ch,):
+                raise LaplaceHipError(f"jac_norm_affine_nhwc: {name} must be [Ch]")
+        L = x.numel() // max(B * Ch, 1)
+        self._rc(
+            self.lib.lk_jac_norm_affine_nhwc_f16x2(_ptr(g.planes[0]), _ptr(g.planes[1]), _ptr(g.sexp), _ptr(x), _ptr(mu), _ptr(rstd),
+                                                   S, B, max(L, 1), Ch, _ptr(Js), Js.shape[-1], int(wcol0), int(bcol0),
+                                                   self._stream(x.device)),
+            "lk_jac_norm_affine_nhwc_f16x2",
+        )
+
+    def normtap_variant(self, S, B, L, Ch, affine=True, aligned=True):
+        """lk_normtap_variant: the path ``lk_jac_norm_affine_nhwc_f16x2`` takes for a shape (host only, no device call), or
+        ``None`` for a shape it refuses."""
+        r = int(self.lib.lk_normtap_variant(int(S), int(B), int(L), int(Ch), int(bool(affine)), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": (1, 4, 8)[r & 3], "seed_split": bool(r & 4), "affine": bool(r & 8), "seeds_per_pass": (r >> 4) & 0xF,
+                "lane_rows": 1 << ((r >> 8) & 0xF), "seeds_per_slice": (r >> 12) & 0xFF, "channel_tiles": r >> 20}
 
     @staticmethod
     def _norm_geometry(x, B, G, layout, what):

@@ -38,7 +38,7 @@ from torch import nn
 from laplace_amd._lib import SplitTensor, get_kernels, is_channels_last, keep_layout
 from laplace_amd.capture import NormTapReused, Tape, norm_servable
 from laplace_amd.sweep import SeedBatchedSweep, SweepUnsupported
-from laplace_amd.sweep_nhwc import SplitSweep
+from laplace_amd.sweep_nhwc import NhwcNormGrad, SplitSweep
 from laplace_amd.kron import HipKron
 from laplace_amd.refapi import EFInterface, GGNInterface
 
@@ -209,7 +209,8 @@ class _HipCurvatureMixin:
                     a.copy_(b)  # (casts)
             cur[0] = sig
         twin = cur[1]
-        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "use_gconv_kernels", "gconv_block_bytes", "generator"):
+        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "nhwc_norm_taps", "use_gconv_kernels", "gconv_block_bytes",
+                  "generator"):
             if k in self.__dict__:
                 setattr(twin, k, self.__dict__[k])
         return twin, dt
@@ -286,6 +287,10 @@ class _HipCurvatureMixin:
     #: ``False``: parameters of normalisation layers are not served by csrc/lk_norm.hip; a model that tracks one takes the
     #: reference's generic route, as it does when the active kernel object has no ``jac_norm_affine``
     use_norm_kernels = True
+    #: ``True``: a model with tracked eval-mode BatchNorm2d / feature-map GroupNorm parameters stays on the NHWC split-fp16 sweep
+    #: (`SplitSweep.nhwc_norm_taps`, csrc/lk_normtap.hip); ``False`` (the default): it runs through the NCHW sweep.  Read when the
+    #: sweep is built
+    nhwc_norm_taps = False
     #: ``False``: weights of grouped convolutions are not served by csrc/lk_gconv.hip; a model that tracks one takes the
     #: reference's generic route, as it does when the active kernel object has no ``jac_gconv``
     use_gconv_kernels = True
@@ -347,8 +352,11 @@ class _HipCurvatureMixin:
         if sweep is None:
             try:
                 # NHWC split-fp16 sweep (own convolution kernels) where the graph allows it, else the NCHW sweep
-                cls = SplitSweep if self.use_split_sweep else SeedBatchedSweep
-                sweep = cls(self._model, {t.name: t.module for t in taps}, kernels=get_kernels)
+                if self.use_split_sweep:
+                    sweep = SplitSweep(self._model, {t.name: t.module for t in taps}, kernels=get_kernels,
+                                       nhwc_norm_taps=self.nhwc_norm_taps)
+                else:
+                    sweep = SeedBatchedSweep(self._model, {t.name: t.module for t in taps}, kernels=get_kernels)
             except SweepUnsupported as e:
                 sweep = False
                 tape.sweep_reason = str(e)
@@ -393,7 +401,11 @@ class _HipCurvatureMixin:
             for s0 in range(0, S, chunk):
                 grads = sweep.backward(seeds[s0:s0 + chunk].contiguous(), on_tap=on_tap, defer_bn_scale=defer_bn_scale)
                 if on_tap is None:
-                    parts.append([grads[t.name] for t in taps])
+                    # (split tensors of different scales do not concatenate: a norm tap of the NHWC sweep leaves a chunk in the
+                    # [S, B, C, H, W] fp32 form of the NCHW sweep)
+                    n_s = min(chunk, S - s0)
+                    parts.append([SplitSweep.norm_grad_nchw(grads[t.name], n_s, B)
+                                  if isinstance(grads[t.name], (SplitTensor, NhwcNormGrad)) else grads[t.name] for t in taps])
             if on_tap is not None:
                 return None
             return [torch.cat([p[i] for p in parts]) for i in range(len(taps))]
@@ -584,8 +596,7 @@ class _HipCurvatureMixin:
         """Writes this module's columns of ``Js[B, S, P]``; ``g`` is ``[S, B, ...]``."""
         K = get_kernels()
         if tap.kind == "norm":
-            xhat, Ch, layout = self._norm_xhat(tap)
-            K.jac_norm_affine(g.contiguous(), xhat, Ch, layout, Js, tap.w_off, tap.b_off)
+            self._norm_columns(tap, g, Js, tap.w_off, tap.b_off)
             return
         if tap.kind == "gconv":
             m = tap.module
@@ -679,13 +690,48 @@ class _HipCurvatureMixin:
             Ch *= int(d)
         return F.layer_norm(a, m.normalized_shape, None, None, m.eps).contiguous(), Ch, 1
 
+    @staticmethod
+    def _norm_channels(m) -> int:
+        if isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d)):
+            return int(m.num_features)
+        if isinstance(m, nn.GroupNorm):
+            return int(m.num_channels)
+        Ch = 1
+        for d in m.normalized_shape:
+            Ch *= int(d)
+        return Ch
+
+    def _norm_columns(self, tap, g, Js, wcol0, bcol0):
+        """a norm tap's columns of ``Js [B, S, P]``, by the form its gradient arrives in: the NHWC sweep's own split cotangent of a
+        BatchNorm output (csrc/lk_normtap.hip: xhat formed in registers from the tapped input and the running statistics), the
+        fp32 NHWC cotangent and xhat of a GroupNorm (layout 1 of csrc/lk_norm.hip), or ``[S, B, ...]`` fp32 from the NCHW sweep
+        and the tape"""
+        K = get_kernels()
+        if isinstance(g, SplitTensor):
+            m = tap.module
+            x = tap.a.to(torch.float32).permute(0, 2, 3, 1).contiguous()  # (a view: the NHWC forward left it channels-last)
+            mu = m.running_mean.detach().to(torch.float32).contiguous()
+            rstd = torch.rsqrt(m.running_var.detach().to(torch.float32) + m.eps)
+            K.jac_norm_affine_nhwc(g, x, mu, rstd, Js.shape[1], Js, wcol0, bcol0)
+        elif isinstance(g, NhwcNormGrad):
+            B = g.xhat.shape[0]
+            K.jac_norm_affine(g.g.reshape(g.g.shape[0] // B, *g.xhat.shape), g.xhat, self._norm_channels(tap.module), 1, Js,
+                              wcol0, bcol0)
+        else:
+            xhat, Ch, layout = self._norm_xhat(tap)
+            K.jac_norm_affine(g.contiguous(), xhat, Ch, layout, Js, wcol0, bcol0)
+
     def _norm_block(self, tap, g):
         """``(Jl [B, S, n_w + n_b], n_w, n_b)``: the layer's own Jacobian block (tiny: two values per channel)"""
-        xhat, Ch, layout = self._norm_xhat(tap)
-        S, B = g.shape[0], g.shape[1]
+        Ch = self._norm_channels(tap.module)
+        if isinstance(g, (SplitTensor, NhwcNormGrad)):
+            B = tap.a.shape[0]
+            S, dev = (g.shape[0] if isinstance(g, SplitTensor) else g.g.shape[0]) // B, tap.a.device
+        else:
+            S, B, dev = g.shape[0], g.shape[1], g.device
         n_w, n_b = (Ch if tap.w_off >= 0 else 0), (Ch if tap.b_off >= 0 else 0)
-        Jl = torch.zeros(B, S, n_w + n_b, dtype=torch.float32, device=g.device)
-        get_kernels().jac_norm_affine(g.contiguous(), xhat, Ch, layout, Jl, 0 if n_w else -1, n_w if n_b else -1)
+        Jl = torch.zeros(B, S, n_w + n_b, dtype=torch.float32, device=dev)
+        self._norm_columns(tap, g, Jl, 0 if n_w else -1, n_w if n_b else -1)
         return Jl, n_w, n_b
 
     # ---- shared implementations ------------------------------------------------------------------

@@ -16,7 +16,9 @@ laplace/curvature/curvlinops.py:87-100):
 Max and average pooling run on the fp32 NHWC maps (csrc/lk_pool.hip: one byte of window-local argmax per output element for
 all seeds, a gather-form VJP), and - with ``nhwc_depthwise = True`` - depthwise convolutions on their own streaming kernels
 (csrc/lk_dwconv.hip: an fp32 forward, a gather-form backward-data that reads the split cotangent and writes fp32 for all seeds in
-one launch).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
+one launch).  With ``nhwc_norm_taps = True`` a tapped eval-mode BatchNorm2d hands its Jacobian kernel the unscaled split cotangent of its
+output (csrc/lk_normtap.hip) and a tapped GroupNorm on a feature map the fp32 NHWC cotangent and ``xhat`` of its VJP (layout 1 of
+csrc/lk_norm.hip).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
 cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
@@ -49,6 +51,17 @@ class _F32:
 
     def __init__(self, t, amax):
         self.t, self.amax = t, amax
+
+
+class NhwcNormGrad:
+    """What a GroupNorm tapped on the NHWC sweep hands over (``nhwc_norm_taps``): the fp32 NHWC cotangent of its output
+    ``g`` ``[S*B, H, W, C]`` and the NHWC ``xhat`` ``[B, H, W, C]`` its forward kept - the operands of layout 1 of
+    lk_jac_norm_affine_f32 as they lie"""
+
+    __slots__ = ("g", "xhat")
+
+    def __init__(self, g, xhat):
+        self.g, self.xhat = g, xhat
 
 
 class _PendingConv:
@@ -130,8 +143,10 @@ def _materialize(parts):
 class SplitSweep(SeedBatchedSweep):
     """Seed-batched reverse sweep whose feature-map cotangents are NHWC split tensors (needs the HIP kernels)."""
 
-    def __init__(self, model, tap_modules, kernels=None):
+    def __init__(self, model, tap_modules, kernels=None, nhwc_norm_taps=None):
         super().__init__(model, tap_modules, kernels)
+        if nhwc_norm_taps is not None:
+            self.nhwc_norm_taps = bool(nhwc_norm_taps)
         self._prep: dict[str, cv.PreparedConv] = {}
         self._amax_cache: dict = {}
         self.split_reason = self._split_eligible()
@@ -149,10 +164,17 @@ class SplitSweep(SeedBatchedSweep):
     # ---- static eligibility ---------------------------------------------------------------------------------------
     def _split_eligible(self):
         for name in sorted(self.tap_names):
-            if isinstance(self.modules.get(name), (nn.BatchNorm2d, nn.BatchNorm1d)):
+            m = self.modules.get(name)
+            if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
+                if self._bn_tap_served(m):
+                    if self.kernels is None or not hasattr(self.kernels(), "jac_norm_affine_nhwc"):
+                        return f"{name}: tapped BatchNorm (kernels without the NHWC norm-tap entry point)"
+                    continue  # (its Jacobian reads the split cotangent where it lies: lk_normtap.hip)
                 # its weight / bias Jacobian reads the fp32 NCHW cotangent of the BatchNorm's output (lk_norm.hip, layout 0)
                 return f"{name}: tapped BatchNorm (its cotangent is delivered by the NCHW sweep)"
-            if isinstance(self.modules.get(name), (nn.GroupNorm, nn.LayerNorm)):
+            if isinstance(m, nn.GroupNorm) and self.nhwc_norm_taps:
+                continue  # (on a feature map, which the NORM rule below checks: layout 1 of lk_norm.hip on the NHWC cotangent)
+            if isinstance(m, (nn.GroupNorm, nn.LayerNorm)):
                 return f"{name}: tapped {type(self.modules[name]).__name__} (its cotangent is delivered by the NCHW sweep)"
         if self.kernels is None or not hasattr(self.kernels(), "conv_nhwc_f16x2"):
             return "kernels without the split-fp16 convolution"
@@ -190,6 +212,21 @@ class SplitSweep(SeedBatchedSweep):
 
     #: ``False``: a model with max / average pooling runs through the NCHW sweep, as it did before lk_pool.hip
     nhwc_pool = True
+    #: ``True``: a model whose eval-mode BatchNorm2d or feature-map GroupNorm parameters are tracked stays on the NHWC walk; the
+    #: BatchNorm's Jacobian reads the split cotangent of its output where it lies (csrc/lk_normtap.hip), the GroupNorm's the fp32
+    #: NHWC cotangent its VJP forms anyway (layout 1 of csrc/lk_norm.hip).  ``False`` (the default): such a model runs through the
+    #: NCHW sweep, as it did before lk_normtap.hip (tools/norm_tap_bench.py)
+    nhwc_norm_taps = False
+
+    def _bn_tap_served(self, m) -> bool:
+        """is this tapped BatchNorm one the NHWC walk delivers the cotangent of (``nhwc_norm_taps``)?"""
+        return bool(self.nhwc_norm_taps and isinstance(m, nn.BatchNorm2d) and m.running_var is not None and not m.training)
+
+    @staticmethod
+    def norm_grad_nchw(g, S, B):
+        """a norm tap's NHWC gradient (SplitTensor / NhwcNormGrad) as the ``[S, B, C, H, W]`` fp32 tensor of the NCHW sweep"""
+        t = g.g if isinstance(g, NhwcNormGrad) else g.float()
+        return t.reshape(S, B, *t.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
     #: ``True``: depthwise convolutions run on csrc/lk_dwconv.hip and their model stays on the NHWC walk.  ``False`` (the default):
     #: such a model runs through the NCHW sweep, as it did before lk_dwconv.hip.  Off by default because the route has to lose on
     #: neither line of tools/dwconv_bench.py and lost on one: on MobileNetV1 at minibatch 128 it halves `kron` with the depthwise
@@ -567,13 +604,19 @@ class SplitSweep(SeedBatchedSweep):
     @torch.no_grad()
     def backward(self, seeds, on_tap=None, defer_bn_scale: bool = False, keep_split: bool = False):
         """``keep_split``: hand conv-tap gradients back as NHWC SplitTensors (consumers with their own kernels for
-        them) instead of converting to ``[S, B, C, H, W]`` fp32."""
+        them) instead of converting to ``[S, B, C, H, W]`` fp32.  Norm-tap gradients (``nhwc_norm_taps``) always leave in NHWC
+        form: the unscaled SplitTensor of a BatchNorm's output cotangent, a :class:`NhwcNormGrad` for a GroupNorm."""
         if not self.split_ok:
             return super().backward(seeds, on_tap=on_tap, defer_bn_scale=defer_bn_scale)
         K = self.kernels()
         self.grad_scale = {}
         self._mult_cache = {}
         pending_scale: dict[fx.Node, torch.Tensor] = {}
+        # conv taps whose own gradient is owed a BatchNorm scale that the CALLER did not ask to receive (a tapped BatchNorm left
+        # it to the backward-data launch): applied in the conversion at the end, never handed out through ``grad_scale``
+        own_scale: set = set()
+        owed: dict[str, torch.Tensor] = {}
+        norm_names: set = set()
         deferred: dict[fx.Node, list] = {}
         S, B = seeds.shape[0], seeds.shape[1]
         SB = S * B
@@ -638,7 +681,9 @@ class SplitSweep(SeedBatchedSweep):
                 g = self._to_split(parts, S)
                 if node.target in self.tap_names:
                     grads[node.target] = g
-                    if node in pending_scale:
+                    if node in own_scale:
+                        owed[node.target] = pending_scale[node]
+                    elif node in pending_scale:
                         self.grad_scale[node.target] = pending_scale[node]
                     if on_tap is not None:
                         on_tap(node.target, g)
@@ -707,7 +752,31 @@ class SplitSweep(SeedBatchedSweep):
                 push(src, g @ m.weight)
             elif kind == BN:
                 scale = self._bn_scale(node.target, m)
-                if (defer_bn_scale and self._defers_scale_to(src, cot) and len(parts) == 1
+                if node.target in self.tap_names:
+                    # the cotangent of the BatchNorm's OWN output, unscaled, as one split tensor: what lk_normtap.hip reads
+                    u = parts[0] if len(parts) == 1 and isinstance(parts[0], SplitTensor) else self._to_split(parts, S)
+                    grads[node.target] = u
+                    norm_names.add(node.target)
+                    if on_tap is not None:
+                        on_tap(node.target, u)
+                    remaining.discard(node.target)
+                    if not remaining:
+                        break
+                    # the scale: left to the source convolution's backward-data launch (no pass over the cotangent) where that
+                    # convolution reads nothing else; a tapped one's own gradient is then owed the scale, which only the fp32
+                    # conversion at the end can pay unasked
+                    rs = self.rule.get(src)
+                    lone = (rs is not None and rs.kind == CONV and len(src.users) == 1 and src not in cot
+                            and not self._is_depthwise(rs.mod))
+                    src_tapped = lone and src.target in self.tap_names
+                    if lone and (not src_tapped or defer_bn_scale or (on_tap is None and not keep_split)):
+                        pending_scale[src] = scale
+                        if src_tapped and not defer_bn_scale:
+                            own_scale.add(src)
+                        push(src, u)
+                    else:
+                        push(src, self._to_split([u], S, scale=scale, scale_amax=self._amax_of(node.target, scale)))
+                elif (defer_bn_scale and self._defers_scale_to(src, cot) and len(parts) == 1
                         and isinstance(parts[0], SplitTensor)):
                     pending_scale[src] = scale
                     push(src, parts[0])
@@ -724,8 +793,18 @@ class SplitSweep(SeedBatchedSweep):
                     g = ts[0] if len(ts) == 1 else sum(ts[1:], ts[0])
                     xhat, rstd, G, _ = self.saved[node]
                     w = None if m.weight is None else m.weight.detach().to(torch.float32).contiguous()
+                    g = g.contiguous()
+                    if node.target in self.tap_names:
+                        # the Jacobian's operands as they lie (layout 1 of lk_jac_norm_affine_f32): no recomputed xhat, no NCHW copy
+                        grads[node.target] = NhwcNormGrad(g, xhat)
+                        norm_names.add(node.target)
+                        if on_tap is not None:
+                            on_tap(node.target, grads[node.target])
+                        remaining.discard(node.target)
+                        if not remaining:
+                            break
                     word = new_word()
-                    push(src, _F32(K.norm_vjp(g.contiguous(), xhat, rstd, w, S, G, 1, amax=word), word))
+                    push(src, _F32(K.norm_vjp(g, xhat, rstd, w, S, G, 1, amax=word), word))
             elif kind in _POOL:
                 # the parts as ONE fp32 NHWC tensor, as the NORM rule (a pool that reads split planes is out of scope)
                 ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
@@ -775,6 +854,9 @@ class SplitSweep(SeedBatchedSweep):
         if on_tap is None and not keep_split:
             # consumers that read the gradients as tensors (Jacobians, diagonal, predictive): [S, B, C, H, W] fp32
             for name, g in list(grads.items()):
-                if isinstance(g, SplitTensor):
-                    grads[name] = g.float().reshape(S, B, *g.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
+                if isinstance(g, SplitTensor) and name not in norm_names:
+                    t = g.float()
+                    if name in owed:
+                        t = t * owed[name]  # (channels are the last dim here)
+                    grads[name] = t.reshape(S, B, *g.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
         return grads
