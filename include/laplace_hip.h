@@ -486,6 +486,42 @@ int lk_norm_vjp_f32(const float* g, const float* xhat, const float* rstd, const 
                     int64_t Ch, int64_t G, int layout, float* dx, unsigned* amax, void* stream);
 int lk_norm_sweep_variant(int64_t S, int64_t B, int64_t L, int64_t Ch, int64_t G, int layout, int aligned);
 
+/* Scaled dot-product self-attention (F.scaled_dot_product_attention without mask tensor or dropout, Tq == Tk) for the
+ * seed-batched reverse sweep; they replace the reverse passes through an attention core of
+ * laplace/curvature/curvlinops.py:87-100 (the KFAC backward) and of the jacrev materialisation of
+ * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129 (one stock autograd pass per seed).  fp32 throughout,
+ * products on the exact fp32 matrix instructions.  Layout 0 is [B][H][T][D], layout 1 is [B][T][H][D]; go, dq, dk, dv carry a
+ * leading [S] in the same layout; lse is always [B][H][T].  Causal: key j <= query i.
+ *
+ * lk_attn_fwd_f32: P = softmax(scale * q k^T (+ causal mask)) by the running-maximum form (the row maximum is always
+ *   subtracted before exp), o = P v, lse = row maximum + log(row sum) of the scaled, masked scores.
+ * lk_attn_vjp_f32: ALL S seeds from ONE q, k, v, o, lse per sample; P is rebuilt on chip, P = exp(scale * q k^T - lse):
+ *   dv = P^T go,  dP = go v^T,  delta = rowsum(go o o),  dS = P o (dP - delta),  dq = scale dS k,  dk = scale dS^T q.
+ *   Two owner passes: 64 query rows own dq and delta [S][B][H][T] (in ws), 64 key rows own dk and dv.  One owner per
+ *   element, fixed reduction order, plain stores, no atomics: two equal calls are bit-equal.  T == 1 gives dq = dk = 0 and
+ *   dv = go exactly.  ws: lk_attn_vjp_workspace_bytes(S, B, H, T, D) bytes (0 for a refused shape), 16-byte aligned.
+ *   Minimal traffic: 4 S B H T D * (2 reads of go + 3 writes) + 8 S B H T (delta, written and read) + the per-sample
+ *   operands (q, k, v twice, o, lse: 24 B H T D + 8 B H T) bytes.
+ * Contract: pointers non-null and 16-byte aligned; layout 0 or 1; D % 4 == 0, 4 <= D <= 128; 1 <= T < 2^15; 1 <= S, 0 <= B,
+ * S * B < 2^31; 1 <= H < 2^16; S * B * H * T * D < 2^40; B * H * ceil(T / 64) < 2^31; scale finite; no output (ws included)
+ * overlaps an input; ws_bytes at least the workspace size.  B == 0 returns LK_OK.
+ * lk_attn_variant (host only): the path lk_attn_vjp_f32 takes for a shape.  Returns
+ *   resident | seed-split << 1 | log2(DP / 16) << 2 | causal << 4 | layout << 5 | seeds per grid.y slice (capped at 255) << 8 |
+ *   owner blocks per (b, h) (capped at 4095) << 16
+ *   resident: T <= LK_ATTN_RESIDENT_MAX_T, an owner's [64][T] block of P is built once into LDS and the seeds loop over it
+ *   (else it is rebuilt per seed); seed-split: the seeds are split over grid.y (each slice builds P once); DP: D padded to
+ *   16, 32, 64 or 128 (the kernel instantiation); owner blocks: ceil(T / 64), the rows of a workgroup (streamed side: stages
+ *   of 32 rows)
+ * or a negative value for a shape the entry points refuse. */
+#define LK_ATTN_RESIDENT_MAX_T 256
+int lk_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t B, int64_t H, int64_t T, int64_t D, int layout,
+                    float scale, int causal, float* o, float* lse, void* stream);
+size_t lk_attn_vjp_workspace_bytes(int64_t S, int64_t B, int64_t H, int64_t T, int64_t D);
+int lk_attn_vjp_f32(const float* go, const float* q, const float* k, const float* v, const float* o, const float* lse, int64_t S,
+                    int64_t B, int64_t H, int64_t T, int64_t D, int layout, float scale, int causal, float* dq, float* dk,
+                    float* dv, void* ws, size_t ws_bytes, void* stream);
+int lk_attn_variant(int64_t S, int64_t B, int64_t H, int64_t T, int64_t D, int layout, int causal);
+
 /* Max and average pooling (nn.MaxPool2d / nn.AvgPool2d, ceil_mode false, no dilation) on fp32 NHWC feature maps for the NHWC
  * reverse sweep; they replace, there, max_pool2d(return_indices=True) / avg_pool2d and the seed-expanded scatter_add_ of the
  * NCHW sweep (the reverse passes of laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through a pooling layer).

@@ -117,6 +117,11 @@ SIGNATURES = {
     "lk_norm_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp]),
     "lk_norm_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_norm_sweep_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
+    "lk_attn_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp]),
+    "lk_attn_vjp_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "lk_attn_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp, _vp,
+                               _sz, _vp]),
+    "lk_attn_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
     "lk_pool_fwd_nhwc_f32": (_int, [_int, _vp, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64] + [_int] * 7),
@@ -1325,6 +1330,68 @@ class HipKernels:
             return None
         return {"kernel": r & 1, "vec": bool(r & 2), "two_pass": bool(r & 4), "seed_split": bool(r & 8), "lanes": (r >> 4) & 0xFFF,
                 "groups": r >> 16, "layout": int(layout)}
+
+    #: largest ``T`` whose probability block stays in LDS over the seeds (LK_ATTN_RESIDENT_MAX_T of include/laplace_hip.h)
+    ATTN_RESIDENT_MAX_T = 256
+
+    @staticmethod
+    def _attn_operands(what, *named):
+        """``(layout, tensors)`` of attention operands ``[N, H, T, D]`` for csrc/lk_attn.hip: as they are when all lie in the
+        same one of the two layouts (0: contiguous, 1: ``transpose(1, 2)`` contiguous), else contiguous copies"""
+        from .sweep import attn_operands
+
+        for t, name in named:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+                raise LaplaceHipError(f"{what}: {name} must be a 4-d fp32 tensor on a ROCm device (no CPU path)")
+        return attn_operands(*(t for t, _ in named))
+
+    def attn_forward(self, q, k, v, scale, causal):
+        """``(o, lse)`` of scaled dot-product self-attention (csrc/lk_attn.hip) on ``q``, ``k``, ``v`` ``[B, H, T, D]``:
+        ``o = softmax(scale q k^T (+ causal mask)) v`` as a ``[B, H, T, D]`` view in the operands' layout, ``lse`` ``[B, H, T]``.
+        The layout is read off the strides; operands in neither layout, or in different ones, are made contiguous."""
+        layout, (q, k, v) = self._attn_operands("attn_forward", (q, "q"), (k, "k"), (v, "v"))
+        if not (q.shape == k.shape == v.shape):
+            raise LaplaceHipError("attn_forward: q, k and v must have equal shapes (self-attention)")
+        from .sweep import attn_like
+
+        B, H, T, D = q.shape
+        o = attn_like(q.shape, layout, q)
+        lse = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+        self._rc(self.lib.lk_attn_fwd_f32(_ptr(q), _ptr(k), _ptr(v), B, H, T, D, layout, float(scale), int(bool(causal)),
+                                          _ptr(o), _ptr(lse), self._stream(q.device)), "lk_attn_fwd_f32")
+        return o, lse
+
+    def attn_vjp(self, go, q, k, v, o, lse, S, scale, causal):
+        """``(dq, dk, dv)``, each a ``[S*B, H, T, D]`` view in the operands' layout, for the ``S`` seeds stacked in ``go``
+        ``[S*B, H, T, D]`` from ONE ``q``, ``k``, ``v``, ``o`` ``[B, H, T, D]`` and ``lse`` ``[B, H, T]`` per sample
+        (lk_attn_vjp_f32; the wrapper allocates the workspace)."""
+        layout, (q, k, v, o) = self._attn_operands("attn_vjp", (q, "q"), (k, "k"), (v, "v"), (o, "o"))
+        from .sweep import attn_layout, attn_like
+
+        B, H, T, D = q.shape
+        S = int(S)
+        _check(lse, "lse")
+        if tuple(go.shape) != (S * B, H, T, D) or not (q.shape == k.shape == v.shape == o.shape) or lse.numel() != B * H * T:
+            raise LaplaceHipError("attn_vjp: go [S*B, H, T, D], q / k / v / o [B, H, T, D] and lse [B, H, T] do not match")
+        self._attn_operands("attn_vjp", (go, "go"))
+        if attn_layout(go) != layout:  # (the cotangent in the operands' layout: one copy, only when it arrives otherwise)
+            go = go.contiguous() if layout == 0 else go.transpose(1, 2).contiguous().transpose(1, 2)
+        dq, dk, dv = (attn_like(go.shape, layout, go) for _ in range(3))
+        nbytes = int(self.lib.lk_attn_vjp_workspace_bytes(S, B, H, T, D))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=go.device)
+        self._rc(self.lib.lk_attn_vjp_f32(_ptr(go), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), S, B, H, T, D, layout,
+                                          float(scale), int(bool(causal)), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), ws.numel(),
+                                          self._stream(go.device)), "lk_attn_vjp_f32")
+        return dq, dk, dv
+
+    def attn_variant(self, S, B, H, T, D, layout=0, causal=False):
+        """lk_attn_variant: the path ``lk_attn_vjp_f32`` takes for a shape (host only, no device call), or ``None`` for a
+        shape the entry points refuse."""
+        r = int(self.lib.lk_attn_variant(int(S), int(B), int(H), int(T), int(D), int(layout), int(bool(causal))))
+        if r < 0:
+            return None
+        return {"resident": bool(r & 1), "seed_split": bool(r & 2), "dp": 16 << ((r >> 2) & 3), "causal": bool(r & 16),
+                "layout": (r >> 5) & 1, "seeds_per_slice": (r >> 8) & 0xFF, "owner_blocks": r >> 16}
 
     #: ``kind`` of the pooling entry points (LK_POOL_* of include/laplace_hip.h)
     POOL_MAX, POOL_AVG = 0, 1

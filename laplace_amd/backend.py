@@ -209,7 +209,8 @@ class _HipCurvatureMixin:
                     a.copy_(b)  # (casts)
             cur[0] = sig
         twin = cur[1]
-        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "nhwc_norm_taps", "use_gconv_kernels", "gconv_block_bytes",
+        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "use_attn_kernels", "nhwc_norm_taps", "use_gconv_kernels",
+                  "gconv_block_bytes",
                   "generator"):
             if k in self.__dict__:
                 setattr(twin, k, self.__dict__[k])
@@ -287,6 +288,9 @@ class _HipCurvatureMixin:
     #: ``False``: parameters of normalisation layers are not served by csrc/lk_norm.hip; a model that tracks one takes the
     #: reference's generic route, as it does when the active kernel object has no ``jac_norm_affine``
     use_norm_kernels = True
+    #: ``False``: an ``F.scaled_dot_product_attention`` node of the reverse sweep stays on the torch math of its rule
+    #: (`sweep.attn_forward_math`, `sweep.attn_vjp_math`) instead of csrc/lk_attn.hip.  Read at every forward
+    use_attn_kernels = True
     #: ``True``: a model with tracked eval-mode BatchNorm2d / feature-map GroupNorm parameters stays on the NHWC split-fp16 sweep
     #: (`SplitSweep.nhwc_norm_taps`, csrc/lk_normtap.hip); ``False`` (the default): it runs through the NCHW sweep.  Read when the
     #: sweep is built
@@ -364,6 +368,8 @@ class _HipCurvatureMixin:
         if sweep is False:
             return None
         try:
+            sweep.use_attn_kernels = bool(self.use_attn_kernels)
+            sweep.attn_mem_bytes = max(int(self.sweep_mem_bytes) // 4, 1)
             if isinstance(sweep, SplitSweep):
                 sweep.act_sink = getattr(self, "_act_sink", None)
             f = sweep.forward(x, keep_tap_splits=True) if keep_tap_splits and isinstance(sweep, SplitSweep) else sweep.forward(x)

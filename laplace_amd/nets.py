@@ -7,6 +7,8 @@ nn.Conv2d only (docs/index.md:364-366; baselaplace.py:115-125 treats frozen para
 """
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import nn
 
@@ -200,3 +202,73 @@ class MobileNetV1(nn.Module):
 
     def forward(self, x):
         return self.fc(torch.flatten(self.pool(self.layers(self.stem(x))), 1))
+
+
+class AttentionBlock(nn.Module):
+    """Pre-LN transformer block on ``[B, T, dim]``: ``x + proj(attention(LN(x)))`` then ``x + MLP(LN(x))``.  ``q`` / ``k`` /
+    ``v`` / ``proj`` are separate ``nn.Linear`` layers (KFAC hangs its factors on them) and the attention core is
+    ``F.scaled_dot_product_attention`` on ``Linear -> view -> transpose`` operands, which the seed-batched sweep serves
+    (csrc/lk_attn.hip).  The head split reads ``x.size(..)``: ``.shape[..]`` does not trace to a served node."""
+
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, act=nn.GELU, causal: bool = False):
+        super().__init__()
+        if dim % heads:
+            raise ValueError(f"heads ({heads}) must divide dim ({dim})")
+        self.heads, self.causal = heads, causal
+        self.norm1 = nn.LayerNorm(dim)
+        self.q, self.k, self.v, self.proj = (nn.Linear(dim, dim) for _ in range(4))
+        self.norm2 = nn.LayerNorm(dim)
+        hidden = int(dim * mlp_ratio)
+        self.fc1, self.act, self.fc2 = nn.Linear(dim, hidden), act(), nn.Linear(hidden, dim)
+
+    def forward(self, x):
+        B, T = x.size(0), x.size(1)
+        h = self.norm1(x)
+        q = self.q(h).view(B, T, self.heads, -1).transpose(1, 2)
+        k = self.k(h).view(B, T, self.heads, -1).transpose(1, 2)
+        v = self.v(h).view(B, T, self.heads, -1).transpose(1, 2)
+        a = nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
+        x = x + self.proj(a.transpose(1, 2).reshape(B, T, -1))
+        return x + self.fc2(self.act(self.fc1(self.norm2(x))))
+
+
+def sincos_positions(T: int, dim: int) -> torch.Tensor:
+    """fixed sine-cosine positional table ``[1, T, dim]``"""
+    pos = torch.arange(T, dtype=torch.float32).unsqueeze(1)
+    freq = torch.exp(torch.arange(0, dim, 2, dtype=torch.float32) * (-math.log(10000.0) / dim))
+    table = torch.zeros(T, dim)
+    table[:, 0::2] = torch.sin(pos * freq)
+    table[:, 1::2] = torch.cos(pos * freq)[:, :dim // 2]
+    return table.unsqueeze(0)
+
+
+class ViTSmall(nn.Module):
+    """Small vision transformer without a class token: ``Conv2d(3, dim, patch, patch)`` patch embedding, a fixed sin-cos
+    positional buffer, ``depth`` pre-LN :class:`AttentionBlock` s, a final LayerNorm, the mean over the positions and a
+    ``Linear`` head.  The defaults give ``T = 64`` positions and head dim 64.
+
+    ``freeze_norm=True`` freezes the LayerNorm affines, which KFAC needs (it refuses tracked norm parameters, as with
+    ``freeze_bn`` of :class:`ResNet18`); with ``freeze_norm=False``, ``diag`` / ``full`` / ``jacobians`` serve them through
+    csrc/lk_norm.hip."""
+
+    def __init__(self, num_classes: int = 10, image: int = 32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
+                 act=nn.GELU, freeze_norm: bool = True, causal: bool = False):
+        super().__init__()
+        if image % patch:
+            raise ValueError(f"patch ({patch}) must divide image ({image})")
+        self.embed = nn.Conv2d(3, dim, patch, patch)
+        self.register_buffer("pos", sincos_positions((image // patch) ** 2, dim))
+        self.blocks = nn.ModuleList(AttentionBlock(dim, heads, act=act, causal=causal) for _ in range(depth))
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.LayerNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, x):
+        x = self.embed(x).flatten(2).transpose(1, 2) + self.pos
+        for blk in self.blocks:
+            x = blk(x)
+        return self.head(self.norm(x).mean(1))

@@ -35,22 +35,24 @@ class SweepUnsupported(RuntimeError):
 
 
 # canonical node kinds ("placeholder" / "output" nodes carry their fx op as kind)
-CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM, NORM = (
+CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM, NORM, ATTN, PERMUTE, CONST = (
     "conv", "linear", "batch-norm", "activation", "identity", "reshape", "adaptive-avg-pool", "avg-pool", "max-pool",
-    "mean", "add", "size", "getitem", "per-sample-norm")
+    "mean", "add", "size", "getitem", "per-sample-norm", "attention", "permute", "constant")
 
 
 class Rule(NamedTuple):
     """What the sweeps know about one traced node, decided once at construction (:func:`classify`)."""
 
     kind: str
-    src: tuple = ()  # input node(s), where the cotangent goes: one, two for ADD (either may be a constant)
+    src: tuple = ()  # input node(s), where the cotangent goes: one, two for ADD (either may be a constant), three for ATTN
     fn: Any = None  # evaluates the node: ``fn(*args, **kwargs)`` on the forward values of ``call``
     call: tuple = ((), {})  # ``(args, kwargs)`` of ``fn`` as fx arguments (nodes and constants)
     what: str = ""  # the operation as messages name it
     flavour: str | None = None  # ACT: "relu" | "tanh" | "sigmoid" | "generic"
     mod: nn.Module | None = None  # CONV / LINEAR / BN / NORM: the module
-    args: tuple = ()  # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written
+    # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written, ATTN's (is_causal, scale),
+    # PERMUTE's (spelling, dims), CONST's attribute path
+    args: tuple = ()
 
 
 # any other element-wise activation: its per-sample derivative is taken ONCE from autograd on the [B, ...]
@@ -73,11 +75,14 @@ _FUNCTION_KINDS = {
     torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
     operator.add: (ADD, None), torch.add: (ADD, None), operator.iadd: (ADD, None), torch.flatten: (RESHAPE, None),
     F.adaptive_avg_pool2d: (GPOOL, None), F.avg_pool2d: (AVGPOOL, None), F.max_pool2d: (MAXPOOL, None),
-    torch.mean: (MEAN, None), operator.getitem: (GETITEM, None)}
+    torch.mean: (MEAN, None), operator.getitem: (GETITEM, None), F.scaled_dot_product_attention: (ATTN, None),
+    torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None)}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
-    "size": (SIZE, None)}
+    "size": (SIZE, None), "transpose": (PERMUTE, None), "permute": (PERMUTE, None)}
+_ATTN_PARAMS = (("key", "value", "attn_mask", "dropout_p", "is_causal", "scale", "enable_gqa"),
+                (None, None, None, 0.0, False, None, False))
 _POOL_PARAMS = {  # names and defaults of the functional form; the modules carry attributes of the same names
     MAXPOOL: (("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices"), (None, None, 0, 1, False, False)),
     AVGPOOL: (("kernel_size", "stride", "padding", "ceil_mode", "count_include_pad", "divisor_override"),
@@ -97,12 +102,82 @@ def _bind(node, names, defaults):
     return vals
 
 
+def _fetch_attr(root, target):
+    """the attribute a ``get_attr`` node names (``a.b.c`` below the traced module)"""
+    obj = root
+    for part in target.split("."):
+        obj = getattr(obj, part)
+    return obj
+
+
+def _classify_attn(node):
+    """``(src, (is_causal, scale))`` of an ``F.scaled_dot_product_attention`` call, or the refusal that names the argument"""
+    names, defaults = _ATTN_PARAMS
+    vals = dict(zip(names, defaults))
+    for n, a in zip(names, node.args[1:]):
+        vals[n] = a
+    for k, v in node.kwargs.items():
+        if k == "query":
+            continue
+        if k not in vals:
+            raise SweepUnsupported(f"scaled_dot_product_attention: unknown argument {k}")
+        vals[k] = v
+    q = node.args[0] if node.args else node.kwargs.get("query")
+    if vals["attn_mask"] is not None:
+        raise SweepUnsupported("scaled_dot_product_attention with an attn_mask (only is_causal is served)")
+    if isinstance(vals["dropout_p"], fx.Node) or vals["dropout_p"] != 0:
+        raise SweepUnsupported("scaled_dot_product_attention with dropout_p != 0")
+    if isinstance(vals["enable_gqa"], fx.Node) or vals["enable_gqa"]:
+        raise SweepUnsupported("scaled_dot_product_attention with enable_gqa (grouped-query attention)")
+    for n in ("is_causal", "scale"):
+        if isinstance(vals[n], fx.Node):
+            raise SweepUnsupported(f"scaled_dot_product_attention with a data-dependent {n}")
+    src = (q, vals["key"], vals["value"])
+    if not all(isinstance(t, fx.Node) for t in src):
+        raise SweepUnsupported("scaled_dot_product_attention: query, key and value must be traced tensors")
+    return src, (bool(vals["is_causal"]), None if vals["scale"] is None else float(vals["scale"]))
+
+
+def _classify_permute(node, what):
+    """``(spelling, dims)`` of a transpose / permute with static integer dims (the batch dim must stay: checked on the value)"""
+    dims = node.args[1:] if node.args[1:] else tuple(node.kwargs.values())
+    if len(dims) == 1 and isinstance(dims[0], (tuple, list)):
+        dims = tuple(dims[0])
+    if not dims or not all(isinstance(d, int) and not isinstance(d, bool) for d in dims):
+        raise SweepUnsupported(f"{what} with data-dependent dims")
+    spelling = "transpose" if str(getattr(node.target, "__name__", node.target)) == "transpose" else "permute"
+    if spelling == "transpose" and (len(dims) != 2 or 0 in dims):
+        raise SweepUnsupported(f"{what}{tuple(dims)} moves the batch dim (dim 0 must stay in place)")
+    if spelling == "permute" and dims[0] != 0:
+        raise SweepUnsupported(f"{what}{tuple(dims)} moves the batch dim (dim 0 must stay in place)")
+    return spelling, tuple(int(d) for d in dims)
+
+
+def permutation(spelling, dims, ndim):
+    """the full permutation of a PERMUTE rule on a value of ``ndim`` dims"""
+    if spelling == "transpose":
+        perm = list(range(ndim))
+        d0, d1 = dims[0] % ndim, dims[1] % ndim
+        perm[d0], perm[d1] = perm[d1], perm[d0]
+    else:
+        perm = [d % ndim for d in dims]
+    if len(perm) != ndim or sorted(perm) != list(range(ndim)) or perm[0] != 0:
+        raise SweepUnsupported(f"{spelling}{tuple(dims)} moves the batch dim (dim 0 must stay in place)")
+    return perm
+
+
 def classify(node: fx.Node, modules: dict) -> Rule:
     """The :class:`Rule` of a traced node — the one place that tells ``call_module`` / ``call_function`` / ``call_method``
     apart; whatever has no VJP rule is refused here, so that neither sweep meets it half-way."""
     if node.op in ("placeholder", "output"):
         return Rule(node.op)
     if node.op == "get_attr":
+        try:
+            attr = _fetch_attr(modules[""], node.target)
+        except (AttributeError, KeyError, TypeError):
+            attr = None
+        if torch.is_tensor(attr) and not attr.requires_grad:  # a buffer or a frozen parameter: a constant of the sweep
+            return Rule(CONST, what=f"constant {node.target}", args=(node.target,))
         raise SweepUnsupported("graph reads attributes directly")
     m, args, kwargs = None, node.args, dict(node.kwargs)
     if node.op == "call_module":
@@ -146,6 +221,10 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == MEAN:
         static = (kwargs.get("dim", args[1] if len(args) > 1 else None),
                   kwargs.get("keepdim", args[2] if len(args) > 2 else False))
+    elif kind == ATTN:
+        src, static = _classify_attn(node)
+    elif kind == PERMUTE:
+        static = _classify_permute(node, what)
     return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
 
 
@@ -203,6 +282,65 @@ def norm_vjp_math(g, xhat, rstd, w, S, G, layout):
     return dx.reshape(g.shape)
 
 
+def attn_layout(t):
+    """memory layout of an attention operand ``[B, H, T, D]`` in the convention of csrc/lk_attn.hip: 0 when it is contiguous
+    (``[B][H][T][D]``), 1 when its ``transpose(1, 2)`` is (``[B][T][H][D]``, what ``Linear -> view -> transpose`` leaves), else
+    ``None``"""
+    if t.is_contiguous():
+        return 0
+    return 1 if t.transpose(1, 2).is_contiguous() else None
+
+
+def attn_operands(*ts):
+    """``(layout, tensors)``: the operands as they are when all of them lie in the same one of the two layouts (nothing is
+    copied), else contiguous copies (layout 0)"""
+    layouts = {attn_layout(t) for t in ts}
+    if len(layouts) == 1 and None not in layouts:
+        return layouts.pop(), ts
+    return 0, tuple(t.contiguous() for t in ts)
+
+
+def attn_like(shape, layout, like):
+    """an uninitialised ``[N, H, T, D]`` tensor (a view, in ``layout``) of the dtype and device of ``like``"""
+    N, H, T, D = shape
+    if layout == 0:
+        return like.new_empty(N, H, T, D)
+    return like.new_empty(N, T, H, D).transpose(1, 2)
+
+
+def attn_forward_math(q, k, v, scale, causal):
+    """``(o, p)`` of scaled dot-product self-attention on ``[B, H, T, D]`` operands in plain torch (any dtype):
+    ``p = softmax(scale * q k^T (+ causal mask: key j <= query i))``, ``o = p v``"""
+    s = (q @ k.transpose(-1, -2)) * scale
+    if causal:
+        T = q.shape[-2]
+        s = s.masked_fill(~torch.ones(T, T, dtype=torch.bool, device=q.device).tril(), float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    return p @ v, p
+
+
+def attn_vjp_math(go, q, k, v, o, p, S, scale, max_bytes=None):
+    """``(dq, dk, dv)``, each ``[S*B, H, T, D]``, for the ``S`` seeds stacked in ``go`` ``[S*B, H, T, D]`` from ONE ``q``, ``k``,
+    ``v``, ``o``, ``p`` per sample - the formula of lk_attn_vjp_f32 in plain torch:
+    ``dv = p^T go``, ``dp = go v^T``, ``delta = rowsum(go * o)``, ``ds = p * (dp - delta)``, ``dq = scale ds k``,
+    ``dk = scale ds^T q``.  ``max_bytes``: the seeds go through in chunks whose three ``[s, B, H, T, T]`` temporaries stay below it."""
+    B, H, T, D = q.shape
+    g = go.reshape(S, B, H, T, D)
+    per_seed = 3 * max(B * H * T * T, 1) * go.element_size()
+    chunk = S if max_bytes is None else max(1, min(S, int(max_bytes) // per_seed))
+    dq, dk, dv = (go.new_empty(S, B, H, T, D) for _ in range(3))
+    pt, vt = p.transpose(-1, -2), v.transpose(-1, -2)
+    for s0 in range(0, S, chunk):
+        gc = g[s0:s0 + chunk]
+        torch.matmul(pt, gc, out=dv[s0:s0 + chunk])
+        ds = p * (gc @ vt - (gc * o).sum(-1, keepdim=True))
+        torch.matmul(ds, k, out=dq[s0:s0 + chunk])
+        torch.matmul(ds.transpose(-1, -2), q, out=dk[s0:s0 + chunk])
+    dq *= scale
+    dk *= scale
+    return dq.reshape(S * B, H, T, D), dk.reshape(S * B, H, T, D), dv.reshape(S * B, H, T, D)
+
+
 class SeedBatchedSweep:
     """Forward + seed-batched reverse sweep over an fx-traced module."""
 
@@ -251,6 +389,7 @@ class SeedBatchedSweep:
         self.taps: dict[str, dict] = {}
         fused_relu: dict[fx.Node, tuple] = {}  # ReLU node -> (output, mask) already produced by the BatchNorm kernel
         self.max_act_numel = 1  # largest per-sample activation: bounds the memory of a seed-batched cotangent
+        self._attn_math_numel = 0  # largest [B, H, T, T] an attention node on the torch math forms per seed
         for node, r in self.rule.items():
             if node in fused_relu:
                 env[node], keep = fused_relu.pop(node)
@@ -262,6 +401,9 @@ class SeedBatchedSweep:
                 env[node] = x
                 continue
             if kind == "output":
+                continue
+            if kind == CONST:
+                env[node] = _fetch_attr(self.gm, r.args[0]).detach()
                 continue
             args, kwargs = fx.node.map_arg(r.call, env.__getitem__)
             inp, keep = args[0], None  # (keep: what the node's VJP needs)
@@ -294,6 +436,14 @@ class SeedBatchedSweep:
             elif kind in (MAXPOOL, AVGPOOL):
                 out, keep = self._run_pool(node, r, args, kwargs)
                 keep = keep if need_vjp else None
+            elif kind == ATTN:
+                out, keep = self._run_attn(r, *(env[n] for n in r.src))
+                keep = keep if need_vjp else None
+            elif kind == PERMUTE:
+                perm = permutation(*r.args, inp.dim())
+                out, keep = inp.permute(perm), [perm.index(i) for i in range(len(perm))]  # (keep: the inverse permutation)
+            elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
+                out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
                 out, keep = self._with_derivative(lambda t: r.fn(t, *args[1:], **kwargs), inp)
             elif kind == GETITEM and torch.is_tensor(inp):
@@ -317,6 +467,7 @@ class SeedBatchedSweep:
         if not need_vjp:
             self.saved = {}
         nb = max(int(x.shape[0]), 1)
+        self.max_act_numel = max(self.max_act_numel, self._attn_math_numel // nb)
         for v in env.values():
             if torch.is_tensor(v):
                 self.max_act_numel = max(self.max_act_numel, v.numel() // nb)
@@ -388,6 +539,56 @@ class SeedBatchedSweep:
         if K is not None and xhat.dtype == torch.float32:
             return K.norm_vjp(gv, xhat, rstd, None if w is None else w.contiguous(), S, G, layout).reshape(g.shape)
         return norm_vjp_math(gv, xhat, rstd, w, S, G, layout).reshape(g.shape)
+
+    #: ``False``: attention nodes stay on the torch math (`attn_forward_math`, `attn_vjp_math`) whatever the kernel object offers
+    use_attn_kernels = True
+    #: what the ``[s, B, H, T, T]`` temporaries of the torch-math attention VJP may take (the seeds go through in chunks)
+    attn_mem_bytes = 4 << 30
+
+    def _attn_kernels(self, q, causal):
+        """the kernel object when csrc/lk_attn.hip serves this attention node (an object with the entry points - the stock
+        emulation has none -, fp32, a shape inside the kernels' contract), else ``None``: plain torch math"""
+        K = self.kernels() if self.kernels is not None and self.use_attn_kernels else None
+        if K is None or not hasattr(K, "attn_forward") or q.dtype != torch.float32:
+            return None
+        B, H, T, D = q.shape
+        return K if D % 4 == 0 and K.attn_variant(1, B, H, T, D, 0, causal) is not None else None
+
+    def _run_attn(self, r, q, k, v):
+        """scaled dot-product self-attention forward -> ``(out, keep)``; what the VJP needs belongs to the sample, not to the
+        seed: the operands and either ``(o, lse)`` (kernels: the probabilities are rebuilt on chip) or ``(o, p)`` (torch math)"""
+        causal, scale = r.args
+        if not (q.dim() == 4 and q.shape == k.shape == v.shape):
+            raise SweepUnsupported(f"scaled_dot_product_attention on query {tuple(q.shape)}, key {tuple(k.shape)}, value "
+                                   f"{tuple(v.shape)}: only self-attention with equal [B, H, T, D] operands (Tq == Tk) is served")
+        scale = float(q.shape[-1]) ** -0.5 if scale is None else scale
+        K = self._attn_kernels(q, causal)
+        if K is not None:
+            _, (q, k, v) = attn_operands(q, k, v)
+            o, lse = K.attn_forward(q, k, v, scale, causal)
+            return o, (K, q, k, v, o, lse, scale, causal)
+        o, p = attn_forward_math(q, k, v, scale, causal)
+        self._attn_math_numel = max(self._attn_math_numel, p.numel())
+        return o, (None, q, k, v, o, p, scale, causal)
+
+    def _attn_vjp(self, saved, g, S):
+        """``(dq, dk, dv)`` for all seeds: ONE call of lk_attn_vjp_f32 (views in the operands' layout), or the same formula in
+        torch; ``g`` is ``[S*B, H, T, D]``"""
+        K, q, k, v, o, aux, scale, causal = saved
+        if K is not None:
+            return K.attn_vjp(g, q, k, v, o, aux, S, scale, causal)
+        return attn_vjp_math(g, q, k, v, o, aux, S, scale, self.attn_mem_bytes)
+
+    def _add_const(self, r, args, kwargs):
+        """``x + constant``: the constant must broadcast to exactly the other operand's shape (the other way round the VJP is
+        a reduction, which has no rule)"""
+        a, b = args[0], args[1]
+        for n, c, other in ((r.src[0], a, b), (r.src[1], b, a)):
+            if isinstance(n, fx.Node) and self.rule[n].kind == CONST and torch.is_tensor(other):
+                if tuple(torch.broadcast_shapes(c.shape, other.shape)) != tuple(other.shape):
+                    raise SweepUnsupported(f"add: {tuple(other.shape)} broadcasts against the {self.rule[n].what} of shape "
+                                           f"{tuple(c.shape)} (the VJP needs a reduction)")
+        return r.fn(*args, **kwargs)
 
     @staticmethod
     def _pair2(v):
@@ -556,8 +757,8 @@ class SeedBatchedSweep:
         remaining = set(self.tap_names)
 
         def push(n, g):
-            if not isinstance(n, fx.Node) or n.op == "placeholder":
-                return
+            if not isinstance(n, fx.Node) or n.op == "placeholder" or self.rule[n].kind == CONST:
+                return  # (a constant has no cotangent)
             cot.setdefault(n, []).append(g)
 
         for node, r in reversed(self.rule.items()):
@@ -610,6 +811,11 @@ class SeedBatchedSweep:
                 push(src, self._maxpool_vjp(g, idx, shp, S, B))
             elif kind == MEAN:
                 push(src, self._mean_vjp(g, self.saved[node], S * B))
+            elif kind == ATTN:
+                for a, d in zip(r.src, self._attn_vjp(self.saved[node], g, S)):
+                    push(a, d)
+            elif kind == PERMUTE:
+                push(src, g.permute(self.saved[node]))
             elif kind == ADD:
                 for a in r.src:
                     push(a, g)

@@ -31,7 +31,7 @@ from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
-from laplace_amd.sweep import (ACT, ADD, AVGPOOL, BN, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, NORM, RESHAPE, SIZE,
+from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, NORM, PERMUTE, RESHAPE, SIZE,
                                SeedBatchedSweep, SweepUnsupported)
 
 # node kinds by what the NHWC walk does with them
@@ -41,7 +41,7 @@ GN_MAP = "group-norm on a feature map"  # what `_walk` reports for an nn.GroupNo
 _POOL = {MAXPOOL, AVGPOOL}  # spatial pooling: fp32 NHWC in, fp32 NHWC out (lk_pool.hip)
 _FEATURE = {CONV, BN, GPOOL, GN_MAP} | _POOL  # produce / consume NHWC feature maps
 _MAP_SOURCES = {CONV, BN, GN_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
-_NO_RULE = {MEAN, SIZE, GETITEM}  # a graph with one of these runs through the NCHW sweep
+_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST}  # a graph with one of these runs through the NCHW sweep
 
 
 class _F32:
@@ -163,6 +163,9 @@ class SplitSweep(SeedBatchedSweep):
 
     # ---- static eligibility ---------------------------------------------------------------------------------------
     def _split_eligible(self):
+        for node, r in self.rule.items():
+            if r.kind == ATTN:  # (named first: it is what decides the walk of a transformer block)
+                return f"{node.name}: {r.what} has no NHWC rule"
         for name in sorted(self.tap_names):
             m = self.modules.get(name)
             if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
