@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void unsplit_transpose_kernel(const _Float16* 
 // Workgroup = one (bi <= bj) pair of NB-channel blocks and one slice of the rows:
 //   NB = 64  (C = 64):  the four waves split the k16 steps of a stage between them (the tensor is huge, the output tiny);
 //   NB = 128 (C >= 128): 2 x 2 waves, each a 64 x 64 quadrant; lower-triangle quadrant / tiles of diagonal blocks idle.
-// Every wave writes its partial tiles to the workspace; gram16_reduce_kernel sums them in a fixed order.
+// Every wave writes its partial tiles to the workspace; gram16_reduce4_kernel sums them in a fixed order.
 template <int NB, int BKR, int KW>  // KW = waves that split k inside the workgroup (4 or 1)
 struct Gram16Cfg {
   static constexpr int PITCH = NB * 2;                   // bytes per row of a plane image
@@ -198,6 +198,13 @@ struct Gram16Cfg {
 template <int NB>
 __device__ __forceinline__ int gram16_swz(int row) {  // XOR on the 64-byte chunk index of a row
   return NB == 64 ? ((row >> 1) & 1) : (row & 3);
+}
+
+// old + alpha 2^(-2 sexp) v with inv = 2^-sexp, the shared epilogue of the three kernels below: the two powers of two go onto
+// the SUM one after the other (both exact), so nothing underflows before the result does — alpha * inv * inv as one factor is
+// subnormal from sexp = 64 and zero from 75 — and the last step is the one fused multiply-add that `old + factor * v` was.
+__device__ __forceinline__ float gram16_unscale_add(float old, float v, float alpha, float inv) {
+  return __builtin_fmaf(alpha, (v * inv) * inv, old);
 }
 
 typedef __attribute__((address_space(3))) void lds_void16;
@@ -392,11 +399,8 @@ __global__ __launch_bounds__(256) void gram16_kernel(const _Float16* __restrict_
         }
       }
     __syncthreads();
-    float tscale = 0.f;
-    if constexpr (TNP) {
-      const float inv = exp2i_sat(-tp.sexp[0]);
-      tscale = tp.alpha * inv * inv;
-    }
+    float inv = 0.f;
+    if constexpr (TNP) inv = exp2i_sat(-tp.sexp[0]);
 #pragma unroll
     for (int i = 0; i < TW * TW * 4; ++i) {
       const int e = tid + 256 * i;
@@ -404,17 +408,14 @@ __global__ __launch_bounds__(256) void gram16_kernel(const _Float16* __restrict_
       if (!TNP && a > b) continue;
       const float v = ((red[e] + red[TW * TW * 1024 + e]) + red[2 * TW * TW * 1024 + e]) + red[3 * TW * TW * 1024 + e];
       const int row = (e >> 5) & 31, col = e & 31;
-      if constexpr (TNP) tp.blocks[out_off + (int64_t)(a * 32 + row) * tp.ldc + b * 32 + col] = old[i] + tscale * v;
+      if constexpr (TNP) tp.blocks[out_off + (int64_t)(a * 32 + row) * tp.ldc + b * 32 + col] = gram16_unscale_add(old[i], v, tp.alpha, inv);
       else blk[(a * 32 + row) * NB + b * 32 + col] = v;
     }
     return;
   }
   if (!wave_active) return;
-  float tscale = 0.f;
-  if constexpr (TNP) {
-    const float inv = exp2i_sat(-tp.sexp[0]);
-    tscale = tp.alpha * inv * inv;
-  }
+  float inv = 0.f;
+  if constexpr (TNP) inv = exp2i_sat(-tp.sexp[0]);
 #pragma unroll
   for (int a = 0; a < TW; ++a)
 #pragma unroll
@@ -424,46 +425,18 @@ __global__ __launch_bounds__(256) void gram16_kernel(const _Float16* __restrict_
       for (int r = 0; r < 16; ++r) {
         const int row = wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int col = wc * 64 + b * 32 + lr;
-        if constexpr (TNP) tp.blocks[out_off + (int64_t)row * tp.ldc + col] = old[(a * TW + b) * 16 + r] + tscale * acc[a][b][r];
+        if constexpr (TNP)
+          tp.blocks[out_off + (int64_t)row * tp.ldc + col] = gram16_unscale_add(old[(a * TW + b) * 16 + r], acc[a][b][r], tp.alpha, inv);
         else blk[row * NB + col] = acc[a][b][r];
       }
     }
 }
 
-// G[upper tiles] += alpha * 2^(-2 sexp) * sum_partials, in a FIXED order: a workgroup owns 32 consecutive elements of one
-// tile row; its 8 lane groups each sum every 8th partial (coalesced 128-byte reads), then the 8 sums are added in order.
-template <int NB>
-__global__ __launch_bounds__(256) void gram16_reduce_kernel(const float* __restrict__ ws, int nparts, int npairs, int nbc,
-                                                            int C, const int* __restrict__ sexp, float alpha,
-                                                            float* __restrict__ Gm) {
-  __shared__ float red[8][32];
-  const int pair = blockIdx.y;
-  int bi = 0, bj = 0;
-  {
-    int p = pair;
-    while (p >= nbc - bi) p -= nbc - bi, ++bi;
-    bj = bi + p;
-  }
-  const int el = threadIdx.x & 31, pl = threadIdx.x >> 5;
-  const int e = blockIdx.x * 32 + el;  // element of the NB x NB block; the 32 of a workgroup share one tile row
-  const int row = e / NB, col = e % NB;
-  if (bi == bj && (row >> 5) > (col >> 5)) return;  // tile below the diagonal of a diagonal block: never computed
-  float s = 0.f;
-  for (int p = pl; p < nparts; p += 8) s += ws[((int64_t)p * npairs + pair) * (NB * NB) + e];
-  red[pl][el] = s;
-  __syncthreads();
-  if (pl == 0) {
-    float t = red[0][el];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) t += red[k][el];
-    const float inv = exp2i_sat(-sexp[0]);
-    Gm[(int64_t)(bi * NB + row) * C + bj * NB + col] += alpha * (t * inv) * inv;
-  }
-}
-
-// The same reduction for the split-K slabs of lk_gram_tn_f16x2 (a few dozen partials of 16 / 64 KB each): a workgroup owns
-// 256 consecutive floats of one block; wave g sums the partials p = g, g + 4, ... as float4s (1 KB contiguous per wave and
-// partial, where the kernel above reads 128 bytes), then the four sums are added in wave order.  Fixed order, no atomics.
+// G[upper tiles] += alpha * 2^(-2 sexp) * sum_partials for the split-K slabs of lk_gram_tn_f16x2 (a few dozen partials of
+// 16 / 64 KB each), in a FIXED order without atomics: a workgroup owns 256 consecutive floats of one block; wave g sums the
+// partials p = g, g + 4, ... as float4s (1 KB contiguous per wave and partial), then the four sums are added in wave order.
+// The sum is un-scaled in two steps, (t * 2^-sexp) * 2^-sexp: 2^(-2 sexp) by itself is subnormal from sexp = 64 and zero from
+// 75 (a tensor of max|x| ~ 4e-19), long before the Gram of such a tensor, ~ max|x|^2 R, leaves the normal range.
 template <int NB>
 __global__ __launch_bounds__(256) void gram16_reduce4_kernel(const float* __restrict__ ws, int nparts, int npairs, int nbc,
                                                              int C, const int* __restrict__ sexp, float alpha,
@@ -504,10 +477,10 @@ __global__ __launch_bounds__(256) void gram16_reduce4_kernel(const float* __rest
 #pragma unroll
     for (int k = 1; k < 4; ++k) t.x += red[k][q].x, t.y += red[k][q].y, t.z += red[k][q].z, t.w += red[k][q].w;
     const float inv = exp2i_sat(-sexp[0]);
-    const float f = alpha * inv * inv;
     float4* dst = reinterpret_cast<float4*>(Gm + (int64_t)(bi * NB + row) * C + bj * NB + col);
     float4 o = *dst;
-    o.x += f * t.x, o.y += f * t.y, o.z += f * t.z, o.w += f * t.w;
+    o.x = gram16_unscale_add(o.x, t.x, alpha, inv), o.y = gram16_unscale_add(o.y, t.y, alpha, inv);
+    o.z = gram16_unscale_add(o.z, t.z, alpha, inv), o.w = gram16_unscale_add(o.w, t.w, alpha, inv);
     *dst = o;
   }
 }
@@ -776,7 +749,6 @@ __global__ __launch_bounds__(512) void pixpair13_kernel(const Pix13Args p) {
 
   // blocks[slot][row][col] += alpha 2^(-2 sexp) acc: the block is this wave's alone (one workgroup per pixel, one wave per tile)
   const float inv = exp2i_sat(-p.sexp[0]);
-  const float tscale = p.alpha * inv * inv;
   const int lr = lane & 31, lh = lane >> 5;
   // (the old values of FOUR blocks — then three — are requested together: one round trip of memory latency per batch, not per block)
 #pragma unroll
@@ -794,7 +766,8 @@ __global__ __launch_bounds__(512) void pixpair13_kernel(const Pix13Args p) {
       if (myslot[i] < 0 || ((LK_PIX13_ABLATE & 1) && p.alpha != 12345.f)) continue;
       float* blk = p.blocks + (int64_t)myslot[i] * (C * C);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) blk[(t_a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * C + t_b * 32 + lr] = old[i - i0][r] + tscale * acc[i][r];
+      for (int r = 0; r < 16; ++r) blk[(t_a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * C + t_b * 32 + lr] =
+            gram16_unscale_add(old[i - i0][r], acc[i][r], p.alpha, inv);
     }
   }
 }

@@ -699,7 +699,7 @@ def test_conv3x3_banded_pixel_pair_form(K, B, Cin, H, W):
 
 
 @pytest.mark.parametrize("B,Cin,H,W", [(3, 64, 4, 4), (2, 64, 5, 7), (5, 128, 3, 3), (2, 256, 2, 5), (3, 64, 1, 1), (40, 128, 8, 8),
-                                        (130, 64, 3, 2), (72, 64, 6, 6)])
+                                        (130, 64, 3, 2), (72, 64, 6, 6), (3, 192, 3, 3)])
 def test_conv3x3_banded_pixel_pair_form_on_split_tensors(K, B, Cin, H, W):
     """lk_conv3x3_pixpair_accumulate_f16x2: the same blocks from the split images (fp16 MFMAs), two stacked launches of
     different scales, == patch Gram of both (fp64)."""
