@@ -590,6 +590,38 @@ int lk_dwconv_bwd_nhwc_f16x2(const void* g_h, const void* g_l, const int* sexp, 
 int lk_dwconv_variant(int64_t S, int64_t B, int64_t H, int64_t W, int64_t C, int kh, int kw, int sh, int sw, int ph, int pw,
                       int aligned);
 
+/* Channel concatenation (torch.cat along dim 1 of [B, C, H, W] maps) on NHWC feature maps for the NHWC reverse sweep; they
+ * replace, there, torch.cat and - in the reverse pass - a .float() per split part, a sum over the whole map, a strided
+ * narrow().contiguous() per source and a pass for max|.| (the reverse passes of laplace/curvature/curvlinops.py:87-100 and
+ * curvature.py:88-129 through a concatenation).  Rows are the R = N H W pixels of a map; a slice is channels [c0, c0 + Cs) of
+ * a map with Ct channels.
+ *
+ * lk_cat_fwd_nhwc_f32: dst[r Ct + c0 + c] = src[r Cs + c]; src [R][Cs] contiguous, dst [R][Ct]; one launch per source.
+ *   (replaces torch.cat in the forward of curvlinops.py:87-100.)  Minimal traffic 8 R Cs bytes.
+ * lk_cat_vjp_nhwc_f32: dst[r Cs + c] = sum_p value_p[r Ct + c0 + c] over nparts parts (1 <= nparts <= LK_CAT_MAX_PARTS); f32,
+ *   hi, lo and sexp are HOST arrays of nparts device pointers (read before the call returns, passed to the kernel by value).
+ *   Part p is the fp32 map f32[p] [R][Ct] when that pointer is non-null; otherwise a ONE-scale split tensor: fp16 planes hi[p]
+ *   and lo[p] [R][Ct] and the device word sexp[p][0], value = (float(hi) + float(lo)) * 2^-sexp.  The sum runs in fp32, left to
+ *   right in the listed order; dst is a contiguous [R][Cs] map; one owner per dst element, plain stores, no atomics on data:
+ *   deterministic.  amax, when given, receives max|dst| as the bit pattern of a non-negative float through atomicMax (as
+ *   lk_pool_vjp_nhwc_f32); the caller zeroes it.  dst must not overlap a part.  (replaces the reverse pass of curvature.py:88-129
+ *   through a concatenation.)  Minimal traffic: R Cs (4 + 4 n_f32 + 4 n_split) bytes - only the slice of every part is read.
+ * Contract of both: pointers non-null where used; 1 <= Cs, 0 <= c0, c0 + Cs <= Ct < 2^30; 0 <= R, R * Ct < 2^40; dst does not
+ * overlap src / a part.  R == 0 returns LK_OK.
+ * lk_cat_variant (host only): the path lk_cat_vjp_nhwc_f32 takes for a shape; split_mask: bit p set when part p is a split
+ * tensor; `aligned`: the fp32 maps and dst are 16-byte, the planes 8-byte aligned.  Returns
+ *   vec | nparts << 1 | split_mask << 4 | 64-bit lane index << 8 | workgroups of the grid << 12
+ *   vec: 16-byte fp32 loads and stores, 8-byte loads of four halves (Ct, c0 and Cs multiples of 4, and aligned), else one
+ *   element per lane; nparts and split_mask select the kernel instance and the loads of each part; 64-bit lane index: R * Cs
+ *   (/ 4 with vec) >= 2^31; the grid strides over the lanes with at most 2048 workgroups of 256 threads
+ * or a negative value for a shape the entry point refuses. */
+#define LK_CAT_MAX_PARTS 4
+int lk_cat_fwd_nhwc_f32(const float* src, int64_t R, int64_t Cs, float* dst, int64_t Ct, int64_t c0, void* stream);
+int lk_cat_vjp_nhwc_f32(int nparts, const float* const* f32, const void* const* hi, const void* const* lo,
+                        const int* const* sexp, int64_t R, int64_t Ct, int64_t c0, int64_t Cs, float* dst, unsigned* amax,
+                        void* stream);
+int lk_cat_variant(int nparts, int split_mask, int64_t R, int64_t Ct, int64_t c0, int64_t Cs, int aligned);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

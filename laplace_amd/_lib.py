@@ -125,6 +125,9 @@ SIGNATURES = {
     "lk_pool_fwd_nhwc_f32": (_int, [_int, _vp, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64] + [_int] * 7),
+    "lk_cat_fwd_nhwc_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "lk_cat_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "lk_cat_variant": (_int, [_int, _int, _i64, _i64, _i64, _i64, _int]),
     "lk_dwconv_fwd_nhwc_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp]),
     "lk_dwconv_bwd_nhwc_f16x2": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp, _vp]),
     "lk_dwconv_variant": (_int, [_i64, _i64, _i64, _i64, _i64] + [_int] * 7),
@@ -1465,6 +1468,76 @@ class HipKernels:
             return None
         return {"vec": bool(r & 1), "summing": bool(r & 2), "seed_split": bool(r & 4), "seeds_per_pass": (r >> 4) & 0xFF,
                 "seeds_per_slice": r >> 12}
+
+    #: most cotangent parts one launch of lk_cat_vjp_nhwc_f32 sums (LK_CAT_MAX_PARTS of include/laplace_hip.h)
+    CAT_MAX_PARTS = 4
+
+    def cat_forward(self, sources_nhwc):
+        """``y`` ``[B, H, W, sum C_j]``: the fp32 NHWC maps ``[B, H, W, C_j]`` concatenated along the channels into ONE
+        allocation, one launch of lk_cat_fwd_nhwc_f32 per source (csrc/lk_cat.hip)"""
+        sources = list(sources_nhwc)
+        if not sources:
+            raise LaplaceHipError("cat_forward: no source")
+        for j, x in enumerate(sources):
+            _check(x, f"sources_nhwc[{j}]")
+            if x.dim() != 4 or x.shape[3] < 1:
+                raise LaplaceHipError("cat_forward: expected NHWC maps [B, H, W, C] with C >= 1")
+            if tuple(x.shape[:3]) != tuple(sources[0].shape[:3]) or x.device != sources[0].device:
+                raise LaplaceHipError(f"cat_forward: source {j} {tuple(x.shape)} does not lie on the pixels of source 0 "
+                                      f"{tuple(sources[0].shape)}")
+        B, H, W = (int(d) for d in sources[0].shape[:3])
+        Ct = sum(int(x.shape[3]) for x in sources)
+        y = torch.empty(B, H, W, Ct, dtype=torch.float32, device=sources[0].device)
+        st, c0 = self._stream(y.device), 0
+        for x in sources:
+            Cs = int(x.shape[3])
+            self._rc(self.lib.lk_cat_fwd_nhwc_f32(_ptr(x), B * H * W, Cs, _ptr(y), Ct, c0, st), "lk_cat_fwd_nhwc_f32")
+            c0 += Cs
+        return y
+
+    def cat_vjp(self, parts, c0, Cs, amax=None):
+        """``dx`` ``[N, H, W, Cs]``: channels ``[c0, c0 + Cs)`` of the fp32 sum, in the listed order, of 1 to ``CAT_MAX_PARTS``
+        cotangent parts ``[N, H, W, Ct]`` - fp32 NHWC tensors or one-scale :class:`SplitTensor` s - in ONE launch of
+        lk_cat_vjp_nhwc_f32.  ``amax``: zeroed device word that receives the bit pattern of max|dx|."""
+        parts = list(parts)
+        if not 1 <= len(parts) <= self.CAT_MAX_PARTS:
+            raise LaplaceHipError(f"cat_vjp: 1 to {self.CAT_MAX_PARTS} parts, got {len(parts)}")
+        shape, dev = tuple(parts[0].shape), None
+        arrays = [(ctypes.c_void_p * len(parts))() for _ in range(4)]  # f32, hi, lo, sexp
+        for j, p in enumerate(parts):
+            if isinstance(p, SplitTensor):
+                _one_scale(p, "cat_vjp")
+                if p.chunked:
+                    raise LaplaceHipError("cat_vjp: a chunk-major split tensor is no NHWC map")
+                _check(p.planes, f"parts[{j}].planes", torch.float16)
+                _check(p.sexp, f"parts[{j}].sexp", torch.int32)
+                arrays[1][j], arrays[2][j], arrays[3][j] = p.planes[0].data_ptr(), p.planes[1].data_ptr(), p.sexp.data_ptr()
+                pdev = p.planes.device
+            else:
+                _check(p, f"parts[{j}]")
+                arrays[0][j], pdev = p.data_ptr(), p.device
+            if len(shape) != 4 or tuple(p.shape) != shape or (dev is not None and pdev != dev):
+                raise LaplaceHipError(f"cat_vjp: part {j} {tuple(p.shape)} is not an NHWC map [N, H, W, Ct] like part 0 {shape}")
+            dev = pdev
+        c0, Cs = int(c0), int(Cs)
+        N, H, W, Ct = (int(d) for d in shape)
+        if Cs < 1 or c0 < 0 or c0 + Cs > Ct:
+            raise LaplaceHipError(f"cat_vjp: channels [{c0}, {c0 + Cs}) are no slice of {Ct} channels")
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("cat_vjp: amax is one 32-bit device word")
+        dx = torch.empty(N, H, W, Cs, dtype=torch.float32, device=dev)
+        self._rc(self.lib.lk_cat_vjp_nhwc_f32(len(parts), *(ctypes.addressof(a) for a in arrays), N * H * W, Ct, c0, Cs, _ptr(dx),
+                                              _ptr(amax), self._stream(dev)), "lk_cat_vjp_nhwc_f32")
+        return dx
+
+    def cat_variant(self, nparts, split_mask, R, Ct, c0, Cs, aligned=True):
+        """lk_cat_variant: the path ``lk_cat_vjp_nhwc_f32`` takes for a shape (host only, no device call), or ``None`` for a
+        shape it refuses.  ``split_mask``: bit ``p`` set when part ``p`` is a split tensor."""
+        r = int(self.lib.lk_cat_variant(int(nparts), int(split_mask), int(R), int(Ct), int(c0), int(Cs), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "nparts": (r >> 1) & 7, "split_mask": (r >> 4) & 15, "wide_index": bool(r & 256),
+                "blocks": r >> 12}
 
     @staticmethod
     def _dwconv_geometry(x_hw, kernel, stride, padding, what):

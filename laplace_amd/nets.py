@@ -204,6 +204,58 @@ class MobileNetV1(nn.Module):
         return self.fc(torch.flatten(self.pool(self.layers(self.stem(x))), 1))
 
 
+class DenseLayer(nn.Module):
+    """DenseNet-BC layer: BN - act - 1x1 convolution (to ``4 * growth``) - BN - act - 3x3 convolution (to ``growth``), and the
+    result concatenated behind the input along the channels"""
+
+    def __init__(self, cin: int, growth: int, act=nn.ReLU):
+        super().__init__()
+        self.bn1, self.act1, self.conv1 = nn.BatchNorm2d(cin), act(), nn.Conv2d(cin, 4 * growth, 1, bias=False)
+        self.bn2, self.act2 = nn.BatchNorm2d(4 * growth), act()
+        self.conv2 = nn.Conv2d(4 * growth, growth, 3, 1, 1, bias=False)
+
+    def forward(self, x):
+        new = self.conv2(self.act2(self.bn2(self.conv1(self.act1(self.bn1(x))))))
+        return torch.cat([x, new], 1)
+
+
+class DenseNetSmall(nn.Module):
+    """A CIFAR DenseNet-BC for 3 x 32 x 32 inputs: 3x3 stem convolution, dense blocks of :class:`DenseLayer` s joined by
+    transitions (BN - act - 1x1 convolution - ``AvgPool2d(2)``; the width is half the input's, rounded down to a multiple of 32,
+    at least 32), then BN - act - global average - flatten - ``Linear``.  Every channel count is a multiple of 32 when ``growth``
+    and ``stem`` are, so every convolution matches the split-fp16 MFMA kernels; the concatenations run through csrc/lk_cat.hip
+    and the transitions' pools through csrc/lk_pool.hip: the workload of the concatenation rule of both reverse sweeps.  No
+    convolution has a bias.  ``act`` is the activation module's class, as with :class:`MobileNetV1`; ``freeze_bn`` as with
+    :class:`ResNet18` (KFAC needs it)."""
+
+    def __init__(self, num_classes: int = 10, growth: int = 32, blocks=(4, 4, 4), stem: int = 64, freeze_bn: bool = True,
+                 act=nn.ReLU):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, stem, 3, 1, 1, bias=False)
+        layers, cin = [], stem
+        for i, n in enumerate(blocks):
+            for _ in range(n):
+                layers.append(DenseLayer(cin, growth, act))
+                cin += growth
+            if i + 1 < len(blocks):
+                cout = max(32, cin // 2 // 32 * 32)
+                layers.append(nn.Sequential(nn.BatchNorm2d(cin), act(), nn.Conv2d(cin, cout, 1, bias=False), nn.AvgPool2d(2)))
+                cin = cout
+        self.layers = nn.Sequential(*layers)
+        self.bn, self.act = nn.BatchNorm2d(cin), act()
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+        if freeze_bn:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.weight.requires_grad_(False)
+                    m.bias.requires_grad_(False)
+
+    def forward(self, x):
+        x = self.layers(self.conv1(x))
+        return self.fc(torch.flatten(self.pool(self.act(self.bn(x))), 1))
+
+
 class AttentionBlock(nn.Module):
     """Pre-LN transformer block on ``[B, T, dim]``: ``x + proj(attention(LN(x)))`` then ``x + MLP(LN(x))``.  ``q`` / ``k`` /
     ``v`` / ``proj`` are separate ``nn.Linear`` layers (KFAC hangs its factors on them) and the attention core is

@@ -35,23 +35,25 @@ class SweepUnsupported(RuntimeError):
 
 
 # canonical node kinds ("placeholder" / "output" nodes carry their fx op as kind)
-CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM, NORM, ATTN, PERMUTE, CONST = (
+CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM, NORM, ATTN, PERMUTE, CONST, CAT = (
     "conv", "linear", "batch-norm", "activation", "identity", "reshape", "adaptive-avg-pool", "avg-pool", "max-pool",
-    "mean", "add", "size", "getitem", "per-sample-norm", "attention", "permute", "constant")
+    "mean", "add", "size", "getitem", "per-sample-norm", "attention", "permute", "constant", "concatenation")
 
 
 class Rule(NamedTuple):
     """What the sweeps know about one traced node, decided once at construction (:func:`classify`)."""
 
     kind: str
-    src: tuple = ()  # input node(s), where the cotangent goes: one, two for ADD (either may be a constant), three for ATTN
+    # input node(s), where the cotangent goes: one, two for ADD (either may be a constant), three for ATTN, the listed tensors in
+    # order for CAT (a node may be listed twice; a constant receives nothing)
+    src: tuple = ()
     fn: Any = None  # evaluates the node: ``fn(*args, **kwargs)`` on the forward values of ``call``
     call: tuple = ((), {})  # ``(args, kwargs)`` of ``fn`` as fx arguments (nodes and constants)
     what: str = ""  # the operation as messages name it
     flavour: str | None = None  # ACT: "relu" | "tanh" | "sigmoid" | "generic"
     mod: nn.Module | None = None  # CONV / LINEAR / BN / NORM: the module
     # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written, ATTN's (is_causal, scale),
-    # PERMUTE's (spelling, dims), CONST's attribute path
+    # PERMUTE's (spelling, dims), CONST's attribute path, CAT's (dim as written,)
     args: tuple = ()
 
 
@@ -76,7 +78,8 @@ _FUNCTION_KINDS = {
     operator.add: (ADD, None), torch.add: (ADD, None), operator.iadd: (ADD, None), torch.flatten: (RESHAPE, None),
     F.adaptive_avg_pool2d: (GPOOL, None), F.avg_pool2d: (AVGPOOL, None), F.max_pool2d: (MAXPOOL, None),
     torch.mean: (MEAN, None), operator.getitem: (GETITEM, None), F.scaled_dot_product_attention: (ATTN, None),
-    torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None)}
+    torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None),
+    torch.cat: (CAT, None), torch.concat: (CAT, None), torch.concatenate: (CAT, None)}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
@@ -153,6 +156,38 @@ def _classify_permute(node, what):
     return spelling, tuple(int(d) for d in dims)
 
 
+def _classify_cat(node, what):
+    """``(src, (dim,))`` of a ``torch.cat`` / ``concat`` / ``concatenate`` call: the listed tensors are traced nodes, the dim is
+    a static integer as written (it may be negative: resolved on the value, `cat_dim`), or the refusal that names the reason"""
+    kwargs = dict(node.kwargs)
+    if kwargs.pop("out", None) is not None:
+        raise SweepUnsupported(f"{what} with an out= argument (the sweep keeps its own values)")
+    tensors = node.args[0] if node.args else kwargs.pop("tensors", None)
+    dim = node.args[1] if len(node.args) > 1 else kwargs.pop("dim", kwargs.pop("axis", 0))
+    if kwargs or len(node.args) > 2:
+        raise SweepUnsupported(f"{what}: unknown argument {sorted(kwargs) or node.args[2:]}")
+    if isinstance(dim, fx.Node) or isinstance(dim, bool) or not isinstance(dim, int):
+        raise SweepUnsupported(f"{what} with a data-dependent dim")
+    if not isinstance(tensors, (tuple, list)) or not tensors:
+        raise SweepUnsupported(f"{what}: the tensors must be a non-empty list or tuple of traced tensors")
+    for t in tensors:
+        if not isinstance(t, fx.Node):
+            raise SweepUnsupported(f"{what}: an entry of the list is not a traced tensor ({type(t).__name__}: a Python constant or "
+                                   "a tensor literal has no node to push a cotangent to)")
+    if dim == 0:
+        raise SweepUnsupported(f"{what} along dim 0 (the batch dim: the seeds are stacked there)")
+    return tuple(tensors), (dim,)
+
+
+def cat_dim(dim, ndim, what="cat"):
+    """the dim of a CAT rule resolved on a value of ``ndim`` dims (never the batch dim)"""
+    if not -ndim <= dim < ndim:
+        raise SweepUnsupported(f"{what} along dim {dim} of a value with {ndim} dims")
+    if dim % ndim == 0:
+        raise SweepUnsupported(f"{what} along dim {dim} of a value with {ndim} dims (the batch dim: the seeds are stacked there)")
+    return dim % ndim
+
+
 def permutation(spelling, dims, ndim):
     """the full permutation of a PERMUTE rule on a value of ``ndim`` dims"""
     if spelling == "transpose":
@@ -225,6 +260,9 @@ def classify(node: fx.Node, modules: dict) -> Rule:
         src, static = _classify_attn(node)
     elif kind == PERMUTE:
         static = _classify_permute(node, what)
+    elif kind == CAT:
+        src, static = _classify_cat(node, what)
+        fn, args, kwargs = torch.cat, (list(src),), {}  # (one spelling; the dim is resolved on the value)
     return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
 
 
@@ -442,6 +480,11 @@ class SeedBatchedSweep:
             elif kind == PERMUTE:
                 perm = permutation(*r.args, inp.dim())
                 out, keep = inp.permute(perm), [perm.index(i) for i in range(len(perm))]  # (keep: the inverse permutation)
+            elif kind == CAT:
+                if not all(torch.is_tensor(t) for t in inp):
+                    raise SweepUnsupported(f"{r.what}: an entry of the list is not a tensor")
+                dim = cat_dim(r.args[0], inp[0].dim(), r.what)
+                out, keep = self._run_cat(node, r, inp, dim), (dim, tuple(int(t.shape[dim]) for t in inp))
             elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
                 out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
@@ -493,6 +536,10 @@ class SeedBatchedSweep:
             out, idx = r.fn(*args)
             return out, (idx, args[0].shape)
         return r.fn(*args, **kwargs), args[0].shape
+
+    def _run_cat(self, node, r, tensors, dim):
+        """concatenation forward along the resolved ``dim`` (the VJP needs the sources' sizes along it only)"""
+        return torch.cat(list(tensors), dim)
 
     @staticmethod
     def pool_params(r) -> dict:
@@ -819,6 +866,12 @@ class SeedBatchedSweep:
             elif kind == ADD:
                 for a in r.src:
                     push(a, g)
+            elif kind == CAT:
+                dim, sizes = self.saved[node]
+                off = 0
+                for a, n in zip(r.src, sizes):  # (a node listed twice receives two parts)
+                    push(a, g.narrow(dim, off, n).contiguous())
+                    off += n
         if remaining:
             raise SweepUnsupported(f"no cotangent reached {sorted(remaining)}")
         return grads

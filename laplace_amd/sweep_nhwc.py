@@ -18,7 +18,9 @@ all seeds, a gather-form VJP), and - with ``nhwc_depthwise = True`` - depthwise 
 (csrc/lk_dwconv.hip: an fp32 forward, a gather-form backward-data that reads the split cotangent and writes fp32 for all seeds in
 one launch).  With ``nhwc_norm_taps = True`` a tapped eval-mode BatchNorm2d hands its Jacobian kernel the unscaled split cotangent of its
 output (csrc/lk_normtap.hip) and a tapped GroupNorm on a feature map the fp32 NHWC cotangent and ``xhat`` of its VJP (layout 1 of
-csrc/lk_norm.hip).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
+csrc/lk_norm.hip).  A concatenation of feature maps along the channels (DenseNet blocks) runs on csrc/lk_cat.hip: one copy launch per
+source in the forward, and per source one launch that reads its channel slice of all cotangent parts - fp32 maps and split tensors as
+they lie - and writes their fp32 sum (``nhwc_cat``).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
 cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
@@ -31,16 +33,17 @@ from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
-from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, NORM, PERMUTE, RESHAPE, SIZE,
+from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, NORM, PERMUTE, RESHAPE, SIZE,
                                SeedBatchedSweep, SweepUnsupported)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
 _PASS_THROUGH = {ACT, IDENTITY, ADD}  # shape-preserving: the cotangent keeps the representation it arrives in
 GN_MAP = "group-norm on a feature map"  # what `_walk` reports for an nn.GroupNorm node (NORM covers nn.LayerNorm in the head too)
+CAT_MAP = "concatenation of feature maps"  # what `_walk` reports for a CAT whose sources sit on feature maps (CAT: one in the head)
 _POOL = {MAXPOOL, AVGPOOL}  # spatial pooling: fp32 NHWC in, fp32 NHWC out (lk_pool.hip)
-_FEATURE = {CONV, BN, GPOOL, GN_MAP} | _POOL  # produce / consume NHWC feature maps
-_MAP_SOURCES = {CONV, BN, GN_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
+_FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP} | _POOL  # produce / consume NHWC feature maps
+_MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
 _NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST}  # a graph with one of these runs through the NCHW sweep
 
 
@@ -149,6 +152,7 @@ class SplitSweep(SeedBatchedSweep):
             self.nhwc_norm_taps = bool(nhwc_norm_taps)
         self._prep: dict[str, cv.PreparedConv] = {}
         self._amax_cache: dict = {}
+        self._on_map_cache: dict = {}
         self.split_reason = self._split_eligible()
         self.split_ok = self.split_reason is None
 
@@ -209,6 +213,10 @@ class SplitSweep(SeedBatchedSweep):
                     return f"{node.target}: kernels without the per-sample normalisation entry points"
             elif r.kind == GPOOL and tuple(self._pair2(r.args[0])) != (1, 1):
                 return f"{node.target if node.op == 'call_module' else node.name}: adaptive pooling to more than one cell"
+            elif r.kind == CAT:
+                why = self._cat_refusal(node, r)
+                if why is not None:
+                    return f"{node.name}: {why}"
         if not n_conv:
             return "no convolution in the graph"
         return self._region_check()
@@ -220,6 +228,40 @@ class SplitSweep(SeedBatchedSweep):
     #: NHWC cotangent its VJP forms anyway (layout 1 of csrc/lk_norm.hip).  ``False`` (the default): such a model runs through the
     #: NCHW sweep, as it did before lk_normtap.hip (tools/norm_tap_bench.py)
     nhwc_norm_taps = False
+
+    #: ``False``: a model with a ``torch.cat`` runs through the NCHW sweep (whose CAT rule serves it), as it would without
+    #: csrc/lk_cat.hip (tools/cat_bench.py)
+    nhwc_cat = True
+
+    def _on_map(self, n) -> bool:
+        """does the value of node ``n`` sit on a feature map (decided on the graph alone)?"""
+        hit = self._on_map_cache.get(n)
+        if hit is None:
+            kind = self.rule[n].kind
+            if kind == CAT:
+                hit = any(self._on_map(a) for a in self.rule[n].src)
+            elif kind in _PASS_THROUGH:
+                hit = any(k in _MAP_SOURCES for k in self._walk(n, False))
+            else:
+                hit = (GN_MAP if kind == NORM and isinstance(self.rule[n].mod, nn.GroupNorm) else kind) in _MAP_SOURCES
+            self._on_map_cache[n] = hit
+        return hit
+
+    def _cat_refusal(self, node, r):
+        """why this CAT node keeps the model off the NHWC walk (None: lk_cat.hip serves it, or it is a concatenation of plain
+        tensors in the head region, which takes the parent-class math)"""
+        if not self.nhwc_cat:
+            return f"{r.what} has no NHWC rule"
+        on_map = [self._on_map(a) for a in r.src]
+        if not any(on_map):
+            return None
+        if not all(on_map):
+            return f"{r.what} of feature maps with tensors outside the feature maps"
+        if r.args[0] not in (1, -3):
+            return f"{r.what} of feature maps along dim {r.args[0]} (the NHWC kernels concatenate channels: dim 1 of a 4-D map)"
+        if not all(hasattr(self.kernels(), f) for f in ("cat_forward", "cat_vjp")):
+            return "kernels without the concatenation entry points"
+        return None
 
     def _bn_tap_served(self, m) -> bool:
         """is this tapped BatchNorm one the NHWC walk delivers the cotangent of (``nhwc_norm_taps``)?"""
@@ -287,6 +329,8 @@ class SplitSweep(SeedBatchedSweep):
                     continue
                 seen.add(m)
                 kind = self.rule[m].kind
+                if kind == CAT and self._on_map(m):
+                    kind = CAT_MAP  # (a producer and consumer of feature maps, not pass-through)
                 out.append(GN_MAP if kind == NORM and isinstance(self.rule[m].mod, nn.GroupNorm) else kind)
                 if kind in _PASS_THROUGH:
                     todo.append(m)
@@ -453,6 +497,26 @@ class SplitSweep(SeedBatchedSweep):
         if aux is not None and aux.get("bound") is not None and (is_max or p["divisor_override"] is None):
             self._aux_put(out, {"split": None, "bound": aux["bound"]})
         return out, ((arg, inp.shape) if is_max else inp.shape)
+
+    def _run_cat(self, node, r, tensors, dim):
+        """concatenation of feature maps along the channels: ONE NHWC allocation ``[B, H, W, Ct]`` and one lk_cat_fwd_nhwc_f32 per
+        source on the NHWC memory of each input; returns the NCHW-logical view over NHWC memory, as `_run_pool` does.  The output
+        inherits a per-image ``"bound"``: the element-wise maximum of the sources' bound words when every source has one; no
+        ``"split"`` is registered.  A concatenation of plain tensors in the head region runs the parent's math."""
+        if not (self.split_ok and self._on_map(node)):
+            return super()._run_cat(node, r, tensors, dim)
+        # (also with ``nhwc_forward = False``: the reverse sweep is NHWC either way)
+        if dim != 1 or not all(t.dim() == 4 and t.dtype == torch.float32 for t in tensors):
+            raise SweepUnsupported(f"{node.name}: concatenation of the NHWC sweep expects fp32 feature maps and dim 1")
+        y = self.kernels().cat_forward([t.permute(0, 2, 3, 1).contiguous() for t in tensors])  # (views of NHWC memory)
+        out = y.permute(0, 3, 1, 2)
+        bounds = [aux.get("bound") if aux is not None else None for aux in (self._aux_get(t) for t in tensors)]
+        if all(b is not None and b.shape == bounds[0].shape and b.dtype == bounds[0].dtype for b in bounds):
+            bound = bounds[0]
+            for b in bounds[1:]:
+                bound = torch.maximum(bound, b)
+            self._aux_put(out, {"split": None, "bound": bound})
+        return out
 
     #: ``False``: a convolution and the BatchNorm / add / ReLU behind it stay two launches
     fuse_conv_bn = True
@@ -836,6 +900,24 @@ class SplitSweep(SeedBatchedSweep):
                 for a in r.src:
                     for p in parts:
                         push(a, p)
+            elif kind == CAT:
+                dim, sizes = self.saved[node]
+                if all(torch.is_tensor(p) for p in parts):
+                    # concatenation in the head region (plain tensors after the flatten): parent-class math
+                    g, off = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0]), 0
+                    for a, n in zip(r.src, sizes):
+                        push(a, g.narrow(dim, off, n).contiguous())
+                        off += n
+                else:
+                    if len(parts) > K.CAT_MAX_PARTS:  # the surplus as ONE fp32 tensor (rare: a map read by more than four nodes)
+                        ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts[K.CAT_MAX_PARTS - 1:]]
+                        parts = parts[:K.CAT_MAX_PARTS - 1] + [_F32(sum(ts[1:], ts[0]).contiguous(), None)]
+                    ops, off = [p if isinstance(p, SplitTensor) else p.t for p in parts], 0
+                    for a, n in zip(r.src, sizes):  # one launch per source: its slice of the sum, and max|.| of it
+                        if isinstance(a, fx.Node) and a.op != "placeholder":
+                            word = new_word()
+                            push(a, _F32(K.cat_vjp(ops, off, n, amax=word), word))
+                        off += n
             elif kind == RESHAPE:
                 g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
                 if not torch.is_tensor(g):
