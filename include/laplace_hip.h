@@ -622,6 +622,38 @@ int lk_cat_vjp_nhwc_f32(int nparts, const float* const* f32, const void* const* 
                         void* stream);
 int lk_cat_variant(int nparts, int split_mask, int64_t R, int64_t Ct, int64_t c0, int64_t Cs, int aligned);
 
+/* Static slicing (Tensor.chunk / split / narrow, x[:, a:b], x[:, 0]) for the seed-batched reverse sweeps: the transpose of the
+ * concatenation above.  A slice along dim d of a contiguous [N, ...] tensor is a column range of the row matrix
+ * [R = N prod(dims before d)][Ct = prod(dims from d)]; a piece is columns [c0, c0 + cs) of it.  They replace, in the reverse
+ * pass of laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through a slice, a zero fill of the whole tensor and a
+ * strided read-modify-write per slice, a sum of the full-width tensors and a pass for max|.|.
+ *
+ * lk_slice_fwd_f32: dst[r Cs + c] = src[r Ct + c0 + c]; src [R][Ct], dst a contiguous [R][Cs].  Minimal traffic 8 R Cs bytes.
+ * lk_slice_vjp_f32: dst[r Ct + c] = the value of the first listed piece p with c0[p] <= c < c0[p] + cs[p], plus the later
+ *   covering pieces in the listed order, in fp32; +0.0f where no piece covers c.  f32, hi, lo, sexp, c0 and cs are HOST arrays of
+ *   npieces entries (read before the call returns; the metadata reaches the kernel by value).  Piece p is a contiguous
+ *   [R][cs[p]]: the fp32 map f32[p] when that pointer is non-null, otherwise a ONE-scale split tensor as in lk_cat_vjp_nhwc_f32:
+ *   fp16 planes hi[p], lo[p] and the device word sexp[p][0], value = (float(hi) + float(lo)) * 2^-sexp.  A full-width cotangent
+ *   is the piece (0, Ct); pieces may overlap or repeat.  One owner per dst element, plain stores, no atomics on data:
+ *   deterministic.  amax, when given, receives max|dst| as the bit pattern of a non-negative float through atomicMax (as
+ *   lk_cat_vjp_nhwc_f32); the caller zeroes it.  Minimal traffic: 4 R Ct bytes written plus every piece read once.
+ * Contract of both: pointers non-null where used; 1 <= npieces <= LK_SLICE_MAX_PIECES; 1 <= cs, 0 <= c0, c0 + cs <= Ct < 2^30;
+ * 0 <= R, R * Ct < 2^40; dst does not overlap src / a piece.  R == 0 returns LK_OK.
+ * lk_slice_variant (host only): the path lk_slice_vjp_f32 takes for a shape; split_mask: bit p set when piece p is a split
+ * tensor; `aligned`: the fp32 maps and dst are 16-byte, the planes 8-byte aligned.  Returns
+ *   vec | npieces << 1 | split_mask << 5 | 64-bit lane index << 13 | workgroups of the grid << 14
+ *   bit 0 vec: 16-byte fp32 loads and stores, 8-byte loads of four halves (Ct and every c0 and cs multiples of 4, and aligned),
+ *   else one element per lane; bits 1-4 npieces and bits 5-12 split_mask select the kernel instance and the loads of each
+ *   piece; bit 13: R * Ct (/ 4 with vec) >= 2^31 lanes; bits 14 and up: the grid, at most 2048 workgroups of 256 threads that
+ *   stride over the lanes
+ * or a negative value for a shape the entry point refuses. */
+#define LK_SLICE_MAX_PIECES 8
+int lk_slice_fwd_f32(const float* src, int64_t R, int64_t Ct, int64_t c0, int64_t Cs, float* dst, void* stream);
+int lk_slice_vjp_f32(int npieces, const float* const* f32, const void* const* hi, const void* const* lo,
+                     const int* const* sexp, const int64_t* c0, const int64_t* cs, int64_t R, int64_t Ct, float* dst,
+                     unsigned* amax, void* stream);
+int lk_slice_variant(int npieces, int split_mask, const int64_t* c0, const int64_t* cs, int64_t R, int64_t Ct, int aligned);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

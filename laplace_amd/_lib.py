@@ -128,6 +128,9 @@ SIGNATURES = {
     "lk_cat_fwd_nhwc_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "lk_cat_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "lk_cat_variant": (_int, [_int, _int, _i64, _i64, _i64, _i64, _int]),
+    "lk_slice_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "lk_slice_vjp_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "lk_slice_variant": (_int, [_int, _int, _vp, _vp, _i64, _i64, _int]),
     "lk_dwconv_fwd_nhwc_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp]),
     "lk_dwconv_bwd_nhwc_f16x2": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp, _vp]),
     "lk_dwconv_variant": (_int, [_i64, _i64, _i64, _i64, _i64] + [_int] * 7),
@@ -1538,6 +1541,70 @@ class HipKernels:
             return None
         return {"vec": bool(r & 1), "nparts": (r >> 1) & 7, "split_mask": (r >> 4) & 15, "wide_index": bool(r & 256),
                 "blocks": r >> 12}
+
+    #: most pieces one launch of lk_slice_vjp_f32 sums (LK_SLICE_MAX_PIECES of include/laplace_hip.h)
+    SLICE_MAX_PIECES = 8
+
+    def slice_forward(self, x, R, Ct, c0, Cs):
+        """``y`` ``[R, Cs]``: columns ``[c0, c0 + Cs)`` of the contiguous fp32 tensor ``x`` read as the row matrix ``[R, Ct]``, in
+        one launch of lk_slice_fwd_f32 (csrc/lk_slice.hip)"""
+        _check(x, "x")
+        R, Ct, c0, Cs = int(R), int(Ct), int(c0), int(Cs)
+        if R < 0 or Ct < 1 or x.numel() != R * Ct:
+            raise LaplaceHipError(f"slice_forward: x {tuple(x.shape)} is no row matrix [{R}, {Ct}]")
+        if Cs < 1 or c0 < 0 or c0 + Cs > Ct:
+            raise LaplaceHipError(f"slice_forward: columns [{c0}, {c0 + Cs}) are no slice of {Ct} columns")
+        y = torch.empty(R, Cs, dtype=torch.float32, device=x.device)
+        self._rc(self.lib.lk_slice_fwd_f32(_ptr(x), R, Ct, c0, Cs, _ptr(y), self._stream(x.device)), "lk_slice_fwd_f32")
+        return y
+
+    def slice_vjp(self, pieces, R, Ct, amax=None):
+        """``dx`` ``[R, Ct]``: per column the fp32 sum, in the listed order, of the pieces ``(value, c0, cs)`` that cover it - ``value``
+        a contiguous fp32 tensor or a one-scale :class:`SplitTensor` of ``R * cs`` elements, the columns ``[c0, c0 + cs)`` - and
+        ``+0.0`` where none does, in ONE launch of lk_slice_vjp_f32.  ``amax``: zeroed device word that receives the bit pattern
+        of max|dx|."""
+        pieces = list(pieces)
+        if not 1 <= len(pieces) <= self.SLICE_MAX_PIECES:
+            raise LaplaceHipError(f"slice_vjp: 1 to {self.SLICE_MAX_PIECES} pieces, got {len(pieces)}")
+        R, Ct, n, dev = int(R), int(Ct), len(pieces), None
+        arrays = [(ctypes.c_void_p * n)() for _ in range(4)]  # f32, hi, lo, sexp
+        c0s, css = (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)()
+        for j, (p, c0, cs) in enumerate(pieces):
+            c0, cs = int(c0), int(cs)
+            if cs < 1 or c0 < 0 or c0 + cs > Ct:
+                raise LaplaceHipError(f"slice_vjp: piece {j}: columns [{c0}, {c0 + cs}) are no slice of {Ct} columns")
+            if isinstance(p, SplitTensor):
+                _one_scale(p, "slice_vjp")
+                if p.chunked:
+                    raise LaplaceHipError("slice_vjp: a chunk-major split tensor is no row matrix")
+                _check(p.planes, f"pieces[{j}].planes", torch.float16)
+                _check(p.sexp, f"pieces[{j}].sexp", torch.int32)
+                arrays[1][j], arrays[2][j], arrays[3][j] = p.planes[0].data_ptr(), p.planes[1].data_ptr(), p.sexp.data_ptr()
+                pdev, numel = p.planes.device, p.planes[0].numel()
+            else:
+                _check(p, f"pieces[{j}]")
+                arrays[0][j], pdev, numel = p.data_ptr(), p.device, p.numel()
+            if numel != R * cs or (dev is not None and pdev != dev):
+                raise LaplaceHipError(f"slice_vjp: piece {j} {tuple(p.shape)} is no row matrix [{R}, {cs}]")
+            c0s[j], css[j], dev = c0, cs, pdev
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("slice_vjp: amax is one 32-bit device word")
+        dx = torch.empty(R, Ct, dtype=torch.float32, device=dev)
+        self._rc(self.lib.lk_slice_vjp_f32(n, *(ctypes.addressof(a) for a in arrays), ctypes.addressof(c0s), ctypes.addressof(css),
+                                           R, Ct, _ptr(dx), _ptr(amax), self._stream(dev)), "lk_slice_vjp_f32")
+        return dx
+
+    def slice_variant(self, split_mask, c0, cs, R, Ct, aligned=True):
+        """lk_slice_variant: the path ``lk_slice_vjp_f32`` takes for the pieces ``(c0[p], cs[p])`` (host only, no device call),
+        or ``None`` for a shape it refuses.  ``split_mask``: bit ``p`` set when piece ``p`` is a split tensor."""
+        n = len(c0)
+        c0s, css = (ctypes.c_int64 * max(n, 1))(*[int(v) for v in c0]), (ctypes.c_int64 * max(n, 1))(*[int(v) for v in cs])
+        r = int(self.lib.lk_slice_variant(n, int(split_mask), ctypes.addressof(c0s), ctypes.addressof(css), int(R), int(Ct),
+                                          int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "npieces": (r >> 1) & 15, "split_mask": (r >> 5) & 255, "wide_index": bool(r & (1 << 13)),
+                "blocks": r >> 14}
 
     @staticmethod
     def _dwconv_geometry(x_hw, kernel, stride, padding, what):

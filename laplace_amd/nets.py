@@ -324,3 +324,119 @@ class ViTSmall(nn.Module):
         for blk in self.blocks:
             x = blk(x)
         return self.head(self.norm(x).mean(1))
+
+
+class CSPBlock(nn.Module):
+    """Residual block of a CSP stage: ``act(x + BN(conv3x3(act(BN(conv3x3(x))))))`` at constant width; no convolution has a bias"""
+
+    def __init__(self, c: int, act=nn.ReLU):
+        super().__init__()
+        self.conv1, self.bn1, self.act1 = nn.Conv2d(c, c, 3, 1, 1, bias=False), nn.BatchNorm2d(c), act()
+        self.conv2, self.bn2, self.act2 = nn.Conv2d(c, c, 3, 1, 1, bias=False), nn.BatchNorm2d(c), act()
+
+    def forward(self, x):
+        return self.act2(self.bn2(self.conv2(self.act1(self.bn1(self.conv1(x))))) + x)
+
+
+class CSPStage(nn.Module):
+    """Cross-stage-partial stage: the channels are split in two halves (``a, b = x.chunk(2, 1)``), ``b`` runs through ``depth``
+    :class:`CSPBlock` s, the halves are concatenated again and mixed by a 1x1 convolution - BN - act transition"""
+
+    def __init__(self, c: int, depth: int, act=nn.ReLU):
+        super().__init__()
+        if c % 2:
+            raise ValueError(f"a CSP stage splits its width ({c}) in two halves")
+        self.blocks = nn.Sequential(*(CSPBlock(c // 2, act) for _ in range(depth)))
+        self.mix = nn.Sequential(nn.Conv2d(c, c, 1, bias=False), nn.BatchNorm2d(c), act())
+
+    def forward(self, x):
+        a, b = x.chunk(2, 1)
+        return self.mix(torch.cat([a, self.blocks(b)], 1))
+
+
+class CSPNetSmall(nn.Module):
+    """A CIFAR CSP-ResNet for 3 x 32 x 32 inputs: 3x3 stem convolution - BN - act, one :class:`CSPStage` per entry of ``widths``
+    joined by stride-2 3x3 convolution - BN - act down-sampling to the next width, then global average - flatten - ``Linear``.
+    With the default widths every half is a multiple of 32, so every convolution matches the split-fp16 MFMA kernels; the channel
+    splits run through csrc/lk_slice.hip and the concatenations through csrc/lk_cat.hip: the workload of the slicing rule of both
+    reverse sweeps.  No convolution has a bias.  ``act`` and ``freeze_bn`` as with :class:`DenseNetSmall`."""
+
+    def __init__(self, num_classes: int = 10, widths=(64, 128, 256), depth: int = 2, freeze_bn: bool = True, act=nn.ReLU):
+        super().__init__()
+        cin = widths[0]
+        self.stem = nn.Sequential(nn.Conv2d(3, cin, 3, 1, 1, bias=False), nn.BatchNorm2d(cin), act())
+        layers = []
+        for i, c in enumerate(widths):
+            if i:
+                layers.append(nn.Sequential(nn.Conv2d(cin, c, 3, 2, 1, bias=False), nn.BatchNorm2d(c), act()))
+            layers.append(CSPStage(c, depth, act))
+            cin = c
+        self.layers = nn.Sequential(*layers)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+        if freeze_bn:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.weight.requires_grad_(False)
+                    m.bias.requires_grad_(False)
+
+    def forward(self, x):
+        return self.fc(torch.flatten(self.pool(self.layers(self.stem(x))), 1))
+
+
+class PackedAttentionBlock(nn.Module):
+    """:class:`AttentionBlock` in the spelling of GPT-2 / nanoGPT: ONE packed projection ``qkv = nn.Linear(dim, 3 * dim)`` whose
+    output is split with ``.split(dim, dim=2)`` (KFAC hangs one weight-sharing factor on it).  The three slices are served by the
+    slicing rule of the seed-batched sweep; the attention operands it leaves are strided views, which the attention rule copies."""
+
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, act=nn.GELU, causal: bool = False):
+        super().__init__()
+        if dim % heads:
+            raise ValueError(f"heads ({heads}) must divide dim ({dim})")
+        self.dim, self.heads, self.causal = dim, heads, causal
+        self.norm1 = nn.LayerNorm(dim)
+        self.qkv, self.proj = nn.Linear(dim, 3 * dim), nn.Linear(dim, dim)
+        self.norm2 = nn.LayerNorm(dim)
+        hidden = int(dim * mlp_ratio)
+        self.fc1, self.act, self.fc2 = nn.Linear(dim, hidden), act(), nn.Linear(hidden, dim)
+
+    def forward(self, x):
+        B, T = x.size(0), x.size(1)
+        q, k, v = self.qkv(self.norm1(x)).split(self.dim, dim=2)
+        q = q.view(B, T, self.heads, -1).transpose(1, 2)
+        k = k.view(B, T, self.heads, -1).transpose(1, 2)
+        v = v.view(B, T, self.heads, -1).transpose(1, 2)
+        a = nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
+        x = x + self.proj(a.transpose(1, 2).reshape(B, T, -1))
+        return x + self.fc2(self.act(self.fc1(self.norm2(x))))
+
+
+class ViTClassToken(nn.Module):
+    """:class:`ViTSmall` as ViT / BERT classifiers are written: a FROZEN class token prepended to the patch sequence
+    (``torch.cat([self.cls.expand(B, -1, -1), x], 1)``; a frozen ``nn.Parameter``, so that the tracer sees the ``expand``),
+    ``depth`` :class:`PackedAttentionBlock` s, a final LayerNorm and the ``Linear`` head on the class token ``x[:, 0]``.  The
+    defaults give ``T = 65`` positions and head dim 64.  ``freeze_norm`` as with :class:`ViTSmall`."""
+
+    def __init__(self, num_classes: int = 10, image: int = 32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
+                 act=nn.GELU, freeze_norm: bool = True, causal: bool = False):
+        super().__init__()
+        if image % patch:
+            raise ValueError(f"patch ({patch}) must divide image ({image})")
+        self.embed = nn.Conv2d(3, dim, patch, patch)
+        self.cls = nn.Parameter(torch.zeros(1, 1, dim).normal_(0.0, 0.02), requires_grad=False)
+        self.register_buffer("pos", sincos_positions((image // patch) ** 2 + 1, dim))
+        self.blocks = nn.ModuleList(PackedAttentionBlock(dim, heads, act=act, causal=causal) for _ in range(depth))
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.LayerNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, x):
+        x = self.embed(x).flatten(2).transpose(1, 2)
+        x = torch.cat([self.cls.expand(x.size(0), -1, -1), x], 1) + self.pos
+        for blk in self.blocks:
+            x = blk(x)
+        return self.head(self.norm(x)[:, 0])

@@ -38,6 +38,9 @@ class SweepUnsupported(RuntimeError):
 CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SIZE, GETITEM, NORM, ATTN, PERMUTE, CONST, CAT = (
     "conv", "linear", "batch-norm", "activation", "identity", "reshape", "adaptive-avg-pool", "avg-pool", "max-pool",
     "mean", "add", "size", "getitem", "per-sample-norm", "attention", "permute", "constant", "concatenation")
+# SPLIT: a tuple-valued chunk / split node (no VJP of its own, like SIZE: its items are SLICE nodes that look through it);
+# SLICE: one static range along ONE non-batch dim of a traced tensor
+SPLIT, SLICE = "split", "slice"
 
 
 class Rule(NamedTuple):
@@ -45,7 +48,7 @@ class Rule(NamedTuple):
 
     kind: str
     # input node(s), where the cotangent goes: one, two for ADD (either may be a constant), three for ATTN, the listed tensors in
-    # order for CAT (a node may be listed twice; a constant receives nothing)
+    # order for CAT (a node may be listed twice; a constant receives nothing); for a SLICE that is a part of a SPLIT the split's source
     src: tuple = ()
     fn: Any = None  # evaluates the node: ``fn(*args, **kwargs)`` on the forward values of ``call``
     call: tuple = ((), {})  # ``(args, kwargs)`` of ``fn`` as fx arguments (nodes and constants)
@@ -53,7 +56,9 @@ class Rule(NamedTuple):
     flavour: str | None = None  # ACT: "relu" | "tanh" | "sigmoid" | "generic"
     mod: nn.Module | None = None  # CONV / LINEAR / BN / NORM: the module
     # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written, ATTN's (is_causal, scale),
-    # PERMUTE's (spelling, dims), CONST's attribute path, CAT's (dim as written,)
+    # PERMUTE's (spelling, dims), CONST's attribute path (none for an expanded constant, which has ``fn``), CAT's (dim as written,),
+    # SPLIT's (spelling, sizes, dim as written), SLICE's ("index", entries, position) / ("narrow", dim, start, length) /
+    # ("split", spelling, sizes, dim, item): resolved on the value by `slice_range`
     args: tuple = ()
 
 
@@ -79,11 +84,16 @@ _FUNCTION_KINDS = {
     F.adaptive_avg_pool2d: (GPOOL, None), F.avg_pool2d: (AVGPOOL, None), F.max_pool2d: (MAXPOOL, None),
     torch.mean: (MEAN, None), operator.getitem: (GETITEM, None), F.scaled_dot_product_attention: (ATTN, None),
     torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None),
-    torch.cat: (CAT, None), torch.concat: (CAT, None), torch.concatenate: (CAT, None)}
+    torch.cat: (CAT, None), torch.concat: (CAT, None), torch.concatenate: (CAT, None),
+    torch.chunk: (SPLIT, None), torch.split: (SPLIT, None), torch.narrow: (SLICE, None)}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
-    "size": (SIZE, None), "transpose": (PERMUTE, None), "permute": (PERMUTE, None)}
+    "size": (SIZE, None), "transpose": (PERMUTE, None), "permute": (PERMUTE, None),
+    "chunk": (SPLIT, None), "split": (SPLIT, None), "narrow": (SLICE, None), "expand": (CONST, None), "expand_as": (CONST, None)}
+# relatives of the slicing rules that have none: refused by name
+_NO_SLICE_RULE = {torch.unbind: "unbind", torch.tensor_split: "tensor_split", torch.stack: "stack", "unbind": "unbind",
+                  "tensor_split": "tensor_split"}
 _ATTN_PARAMS = (("key", "value", "attn_mask", "dropout_p", "is_causal", "scale", "enable_gqa"),
                 (None, None, None, 0.0, False, None, False))
 _POOL_PARAMS = {  # names and defaults of the functional form; the modules carry attributes of the same names
@@ -188,6 +198,165 @@ def cat_dim(dim, ndim, what="cat"):
     return dim % ndim
 
 
+_BATCH_SLICE = "dim 0 (the batch dim: the seeds are stacked there)"
+
+
+def _static_int(v, what, name):
+    """a static Python integer argument, or the refusal that names it"""
+    if isinstance(v, fx.Node) or torch.is_tensor(v):
+        raise SweepUnsupported(f"{what} with a data-dependent {name}")
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise SweepUnsupported(f"{what}: {name} must be a static integer, got {type(v).__name__}")
+    return int(v)
+
+
+def _classify_split(node, what):
+    """``(spelling, sizes, dim)`` of a ``chunk`` / ``split`` call (function or method) with static arguments: ``sizes`` is the
+    number of chunks, the size of a part or the tuple of sections; the dim as written (negative allowed: resolved on the value)"""
+    spelling = "chunk" if str(getattr(node.target, "__name__", node.target)) == "chunk" else "split"
+    kwargs = dict(node.kwargs)
+    names = ("chunks",) if spelling == "chunk" else ("split_size_or_sections", "split_size")
+    sizes = node.args[1] if len(node.args) > 1 else next((kwargs.pop(n) for n in names if n in kwargs), None)
+    dim = node.args[2] if len(node.args) > 2 else kwargs.pop("dim", 0)
+    kwargs.pop("input", None), kwargs.pop("tensor", None)
+    if kwargs or len(node.args) > 3 or sizes is None:
+        raise SweepUnsupported(f"{what}: unknown or missing argument {sorted(kwargs) or node.args[3:]}")
+    dim = _static_int(dim, what, "dim")
+    if isinstance(sizes, (tuple, list)):
+        if spelling == "chunk" or not sizes:
+            raise SweepUnsupported(f"{what}: the sections must be a non-empty list of static integers")
+        sizes = tuple(_static_int(s, what, "section") for s in sizes)
+        if min(sizes) < 0:
+            raise SweepUnsupported(f"{what}: negative section in {sizes}")
+    else:
+        sizes = _static_int(sizes, what, "number of chunks" if spelling == "chunk" else "split size")
+        if sizes < 1:
+            raise SweepUnsupported(f"{what}: {sizes} is no {'number of chunks' if spelling == 'chunk' else 'split size'}")
+    if dim == 0:
+        raise SweepUnsupported(f"{what} along {_BATCH_SLICE}")
+    return spelling, sizes, dim
+
+
+def _classify_index(idx, what):
+    """the static index of a ``tensor[idx]`` as a tuple of ``:`` / ``...`` / ints / unit-step slices with exactly one entry that
+    is not a full slice (``None`` when every entry is full: the node is an identity), or the refusal that names the reason"""
+    entries = tuple(idx) if isinstance(idx, tuple) else (idx,)
+    hit = []
+    for i, e in enumerate(entries):
+        if isinstance(e, fx.Node):
+            raise SweepUnsupported(f"{what} with a data-dependent index")
+        if e is None or isinstance(e, (bool, list)) or torch.is_tensor(e):
+            kind = "None" if e is None else "tensor" if torch.is_tensor(e) else "list" if isinstance(e, list) else "bool"
+            raise SweepUnsupported(f"{what} with a {kind} index (only ints, unit-step slices, ':' and '...' are served)")
+        if e is Ellipsis:
+            if sum(x is Ellipsis for x in entries) > 1:
+                raise SweepUnsupported(f"{what} with more than one '...'")
+        elif isinstance(e, slice):
+            if any(isinstance(v, fx.Node) or torch.is_tensor(v) for v in (e.start, e.stop, e.step)):
+                raise SweepUnsupported(f"{what} with data-dependent bounds")
+            for v in (e.start, e.stop, e.step):
+                if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+                    raise SweepUnsupported(f"{what}: slice bounds must be static integers, got {type(v).__name__}")
+            if e.step not in (None, 1):
+                raise SweepUnsupported(f"{what} with a step other than 1 (step {e.step})")
+            if not (e.start in (None, 0) and e.stop is None):
+                hit.append(i)
+        elif isinstance(e, int):
+            hit.append(i)
+        else:
+            raise SweepUnsupported(f"{what} with a {type(e).__name__} index (only ints, unit-step slices, ':' and '...' are served)")
+    if len(hit) > 1:
+        raise SweepUnsupported(f"{what} slices more than one dim (index one dim at a time)")
+    if hit and hit[0] == 0:
+        raise SweepUnsupported(f"{what} slices {_BATCH_SLICE}")
+    return (entries, hit[0]) if hit else None
+
+
+def slice_range(spec, shape, what="slice"):
+    """``(dim, start, length, dropped)`` of a SLICE rule resolved on a value of ``shape``: the sliced dim (never the batch dim),
+    the range along it and whether an int index drops the dim"""
+    ndim, dropped = len(shape), False
+    if spec[0] == "index":
+        entries, i = spec[1], spec[2]
+        n = sum(e is not Ellipsis for e in entries)
+        if n > ndim:
+            raise SweepUnsupported(f"{what}: {n} indices for a value with {ndim} dims")
+        dim = i if not any(e is Ellipsis for e in entries[:i]) else ndim - (len(entries) - i)
+        if dim <= 0:
+            raise SweepUnsupported(f"{what} slices {_BATCH_SLICE}")
+        e, D = entries[i], int(shape[dim])
+        if isinstance(e, slice):
+            start, stop, _ = e.indices(D)
+            length = stop - start
+        else:
+            if not -D <= e < D:
+                raise SweepUnsupported(f"{what}: index {e} is out of range for dim {dim} of size {D}")
+            start, length, dropped = e % D, 1, True
+    elif spec[0] == "narrow":
+        dim, start, length = cat_dim(spec[1], ndim, what), spec[2], spec[3]
+        D = int(shape[dim])
+        start = start + D if start < 0 else start
+        if not (0 <= start and 0 <= length and start + length <= D):
+            raise SweepUnsupported(f"{what}: range [{spec[2]}, {spec[2]} + {length}) leaves dim {dim} of size {D}")
+    else:  # item ``spec[4]`` of a chunk / split
+        _, spelling, sizes, dim, item = spec
+        dim = cat_dim(dim, ndim, what)
+        D = int(shape[dim])
+        if isinstance(sizes, tuple):
+            if sum(sizes) != D:
+                raise SweepUnsupported(f"{what}: sections {sizes} do not sum to dim {dim} of size {D}")
+            bounds = [0]
+            for s in sizes:
+                bounds.append(bounds[-1] + s)
+        else:
+            size = -(-D // sizes) if spelling == "chunk" else sizes  # (chunk: ceil(D / chunks) per part, fewer parts if need be)
+            bounds = list(range(0, D, max(size, 1))) + [D]
+        n = len(bounds) - 1
+        if not -n <= item < n:
+            raise SweepUnsupported(f"{what}: part {item} of {n}")
+        start, length = bounds[item % n], bounds[item % n + 1] - bounds[item % n]
+    if length < 1:
+        raise SweepUnsupported(f"{what}: an empty range along dim {dim}")
+    return dim, int(start), int(length), dropped
+
+
+def _classify_slice(node, modules, what):
+    """the Rule of a SLICE node - ``getitem`` of a chunk / split (looked through: the source is the split's source), ``getitem``
+    of a traced tensor with a static index, ``narrow`` - or ``None`` for a ``getitem`` of a non-tensor (a ``size()`` tuple)"""
+    src = node.args[0] if node.args else node.kwargs.get("input")
+    if node.target is operator.getitem:
+        up = classify(src, modules) if isinstance(src, fx.Node) else None
+        if up is None or up.kind in (SIZE, GETITEM):
+            return None
+        what = f"indexing of {src.name}"
+        if up.kind == SPLIT:
+            item = node.args[1]
+            if isinstance(item, fx.Node) or isinstance(item, bool) or not isinstance(item, int):
+                raise SweepUnsupported(f"{up.what}: its parts must be taken one by one with a static integer index")
+            return Rule(SLICE, up.src, None, (up.src, {}), f"part {item} of {up.what}", args=("split", *up.args, item))
+        hit = _classify_index(node.args[1], what)
+        if hit is None:  # (x[:], x[...]: a view of everything)
+            return Rule(IDENTITY, (src,), operator.getitem, (tuple(node.args), {}), what)
+        return Rule(SLICE, (src,), None, ((src,), {}), what, args=("index", *hit))
+    kwargs = dict(node.kwargs)
+    kwargs.pop("input", None)
+    vals = [*node.args[1:], *(kwargs.pop(n) for n in ("dim", "start", "length")[len(node.args) - 1:] if n in kwargs)]
+    if kwargs or len(vals) != 3 or not isinstance(src, fx.Node):
+        raise SweepUnsupported(f"{what}: expected (input, dim, start, length)")
+    dim, start, length = (_static_int(v, what, n) for v, n in zip(vals, ("dim", "start", "length")))
+    if dim == 0:
+        raise SweepUnsupported(f"{what} along {_BATCH_SLICE}")
+    return Rule(SLICE, (src,), None, ((src,), {}), what, args=("narrow", dim, start, length))
+
+
+def _no_slice_rule(target):
+    """what a refusal adds for a relative of the slicing rules (``unbind``, ``tensor_split``, ``stack``)"""
+    name = _NO_SLICE_RULE.get(target)
+    if name is None:
+        return ""
+    return f" ({name} is out of scope: chunk, split, narrow, static indexing of one dim and cat are what the sweep serves)"
+
+
 def permutation(spelling, dims, ndim):
     """the full permutation of a PERMUTE rule on a value of ``ndim`` dims"""
     if spelling == "transpose":
@@ -228,14 +397,27 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif node.op == "call_function":
         fn, hit, what = node.target, _FUNCTION_KINDS.get(node.target), getattr(node.target, "__name__", node.target)
         if hit is None:
-            raise SweepUnsupported(f"no VJP rule for function {what}")
+            raise SweepUnsupported(f"no VJP rule for function {what}" + _no_slice_rule(node.target))
     else:
         hit, what = _METHOD_KINDS.get(node.target), f"method {node.target}"
         if hit is None:
-            raise SweepUnsupported(f"no VJP rule for method {node.target}")
+            raise SweepUnsupported(f"no VJP rule for method {node.target}" + _no_slice_rule(node.target))
         fn = getattr(torch.Tensor, node.target)
     kind, flavour = hit
     src, static = tuple(args[:1]), ()
+    if kind in (GETITEM, SLICE):
+        r = _classify_slice(node, modules, what)
+        if r is not None:
+            return r
+    elif kind == SPLIT:
+        if not (args and isinstance(args[0], fx.Node)):
+            raise SweepUnsupported(f"{what}: the tensor must be the first positional argument and a traced tensor")
+        static = _classify_split(node, what)
+    elif kind == CONST:  # (`expand` / `expand_as`: a constant when what it expands is one; evaluated in the forward)
+        if not (args and isinstance(args[0], fx.Node) and classify(args[0], modules).kind == CONST):
+            raise SweepUnsupported(f"{what} of a traced tensor (its VJP is a reduction, which has no rule; expanding a buffer or a "
+                                   "frozen parameter is served)")
+        what = f"constant {what} of {args[0].name}"
     if kind == ADD:
         if kwargs.get("alpha", 1) != 1:
             raise SweepUnsupported("add with alpha")
@@ -408,6 +590,9 @@ class SeedBatchedSweep:
         self.rule: dict[fx.Node, Rule] = {node: classify(node, self.modules) for node in self.gm.graph.nodes}
         if sum(r.kind == "placeholder" for r in self.rule.values()) != 1:
             raise SweepUnsupported("models with one tensor input only")
+        for node, r in self.rule.items():  # (a tuple of parts has no cotangent: only its items do)
+            if r.kind == SPLIT and any(self.rule[u].kind != SLICE for u in node.users):
+                raise SweepUnsupported(f"{r.what}: its parts must be taken one by one with a static integer index")
         self.out_node = next(reversed(self.rule)).args[0]
         if not isinstance(self.out_node, fx.Node):
             raise SweepUnsupported("model must return a single tensor")
@@ -441,7 +626,11 @@ class SeedBatchedSweep:
             if kind == "output":
                 continue
             if kind == CONST:
-                env[node] = _fetch_attr(self.gm, r.args[0]).detach()
+                if r.fn is None:
+                    env[node] = _fetch_attr(self.gm, r.args[0]).detach()
+                else:  # (an expanded constant)
+                    args, kwargs = fx.node.map_arg(r.call, env.__getitem__)
+                    env[node] = r.fn(*args, **kwargs)
                 continue
             args, kwargs = fx.node.map_arg(r.call, env.__getitem__)
             inp, keep = args[0], None  # (keep: what the node's VJP needs)
@@ -485,6 +674,16 @@ class SeedBatchedSweep:
                     raise SweepUnsupported(f"{r.what}: an entry of the list is not a tensor")
                 dim = cat_dim(r.args[0], inp[0].dim(), r.what)
                 out, keep = self._run_cat(node, r, inp, dim), (dim, tuple(int(t.shape[dim]) for t in inp))
+            elif kind == SLICE:
+                if not torch.is_tensor(inp):
+                    raise SweepUnsupported(f"{r.what}: the source is not a tensor")
+                keep = (*slice_range(r.args, inp.shape, r.what), inp.shape)
+                out = self._run_slice(node, r, inp, *keep[:4])
+            elif kind == SPLIT:
+                try:
+                    out = r.fn(*args, **kwargs)
+                except (RuntimeError, TypeError, IndexError) as e:  # (sections that do not fit the value: torch's own words)
+                    raise SweepUnsupported(f"{r.what}: {e}") from e
             elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
                 out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
@@ -540,6 +739,65 @@ class SeedBatchedSweep:
     def _run_cat(self, node, r, tensors, dim):
         """concatenation forward along the resolved ``dim`` (the VJP needs the sources' sizes along it only)"""
         return torch.cat(list(tensors), dim)
+
+    def _run_slice(self, node, r, inp, dim, start, length, dropped):
+        """static slice forward: a view (the VJP needs the range and the input's shape only)"""
+        return inp.select(dim, start) if dropped else inp.narrow(dim, start, length)
+
+    #: ``False``: the cotangent of a sliced tensor is assembled by the torch sequence (zero fill, ``narrow(...).add_`` per
+    #: slice, a sum with the full-width parts) whatever the kernel object offers
+    use_slice_kernels = True
+
+    def _slice_kernels(self, ts):
+        """the kernel object when csrc/lk_slice.hip assembles the cotangent of a sliced tensor from ``ts`` (an object with the entry
+        points - the stock emulation has none -, fp32), else ``None``: the same formula in torch"""
+        K = self.kernels() if self.kernels is not None and self.use_slice_kernels else None
+        if K is None or not hasattr(K, "slice_vjp") or not all(t.dtype == torch.float32 for t in ts):
+            return None
+        return K
+
+    @staticmethod
+    def slice_columns(shape, dim, start, length):
+        """``(R, Ct, c0, cs)``: a slice along ``dim`` of a contiguous tensor of ``shape`` as the column range ``[c0, c0 + cs)`` of
+        the row matrix ``[R = prod(dims before dim)][Ct = prod(dims from dim)]``"""
+        R = inner = 1
+        for d in shape[:dim]:
+            R *= int(d)
+        for d in shape[dim + 1:]:
+            inner *= int(d)
+        return R, int(shape[dim]) * inner, start * inner, length * inner
+
+    @staticmethod
+    def slice_vjp_launches(K, pieces, R, Ct, amax=None):
+        """the ``[R, Ct]`` sum of the pieces ``(value, c0, cs)`` in ONE launch of lk_slice_vjp_f32; beyond ``K.SLICE_MAX_PIECES``
+        the result so far is the full-width first piece of a further launch (rare: a tensor read by more than eight nodes)"""
+        pieces, n = list(pieces), K.SLICE_MAX_PIECES
+        while len(pieces) > n:
+            pieces = [(K.slice_vjp(pieces[:n], R, Ct), 0, Ct)] + pieces[n:]
+        return K.slice_vjp(pieces, R, Ct, amax=amax)
+
+    def _assemble_slices(self, parts, pieces, shape):
+        """the cotangent ``[S*B, ...]`` (``shape``) of a tensor some of whose consumers are slices: the sum of the full-width
+        ``parts`` and, per range, of the ``pieces`` ``(g, dim, start, length)``; zero where no piece reaches.  One launch of
+        lk_slice_vjp_f32 per sliced dim (every network here slices one), or the same formula in torch."""
+        K = self._slice_kernels([*parts, *(p[0] for p in pieces)])
+        if K is not None and shape[0] > 0:
+            out, full = None, [(g.contiguous(), 0, None) for g in parts]
+            for dim in sorted({p[1] for p in pieces}):
+                R, Ct, _, _ = self.slice_columns(shape, dim, 0, 1)
+                if not (Ct < (1 << 30) and R * Ct < (1 << 40)):
+                    out = None
+                    break
+                cols = [(g, 0, Ct) for g, _, _ in full]
+                cols += [(g.contiguous(), *self.slice_columns(shape, dim, st, ln)[2:]) for g, d, st, ln in pieces if d == dim]
+                out = self.slice_vjp_launches(K, cols, R, Ct).reshape(shape)
+                full = [(out, 0, None)]
+            if out is not None:
+                return out
+        out = parts[0].clone() if len(parts) == 1 else sum(parts[1:], parts[0]) if parts else pieces[0][0].new_zeros(shape)
+        for g, dim, start, length in pieces:
+            out.narrow(dim, start, length).add_(g)
+        return out
 
     @staticmethod
     def pool_params(r) -> dict:
@@ -808,10 +1066,16 @@ class SeedBatchedSweep:
                 return  # (a constant has no cotangent)
             cot.setdefault(n, []).append(g)
 
+        # per node: the pieces ``(cotangent, dim, start, length)`` its SLICE consumers hand back, assembled with the full-width
+        # parts ONCE, when the node itself is reached
+        pieces: dict[fx.Node, list] = {}
         for node, r in reversed(self.rule.items()):
-            if node not in cot:
+            if node not in cot and node not in pieces:
                 continue
-            parts, g2 = cot.pop(node), None
+            parts, g2 = cot.pop(node, []), None
+            if node in pieces:
+                pcs = pieces.pop(node)
+                parts = [self._assemble_slices(parts, [p[:4] for p in pcs], (S * B,) + tuple(pcs[0][4][1:]))]
             g = parts[0]
             if len(parts) > 1:
                 if r.kind == ACT:
@@ -872,6 +1136,10 @@ class SeedBatchedSweep:
                 for a, n in zip(r.src, sizes):  # (a node listed twice receives two parts)
                     push(a, g.narrow(dim, off, n).contiguous())
                     off += n
+            elif kind == SLICE:
+                dim, start, length, dropped, in_shape = self.saved[node]
+                if isinstance(src, fx.Node) and src.op != "placeholder" and self.rule[src].kind != CONST:
+                    pieces.setdefault(src, []).append((g.unsqueeze(dim) if dropped else g, dim, start, length, in_shape))
         if remaining:
             raise SweepUnsupported(f"no cotangent reached {sorted(remaining)}")
         return grads

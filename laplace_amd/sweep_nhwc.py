@@ -20,7 +20,9 @@ one launch).  With ``nhwc_norm_taps = True`` a tapped eval-mode BatchNorm2d hand
 output (csrc/lk_normtap.hip) and a tapped GroupNorm on a feature map the fp32 NHWC cotangent and ``xhat`` of its VJP (layout 1 of
 csrc/lk_norm.hip).  A concatenation of feature maps along the channels (DenseNet blocks) runs on csrc/lk_cat.hip: one copy launch per
 source in the forward, and per source one launch that reads its channel slice of all cotangent parts - fp32 maps and split tensors as
-they lie - and writes their fp32 sum (``nhwc_cat``).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
+they lie - and writes their fp32 sum (``nhwc_cat``).  A channel slice of a feature map (``chunk`` / ``split`` / ``narrow`` / ``x[:, a:b]``:
+CSP stages) runs on csrc/lk_slice.hip: one copy launch in the forward, and per sliced map one launch that sums the pieces its slices hand
+back and the full-width parts into an fp32 map (``nhwc_slice``).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
 cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
@@ -34,16 +36,17 @@ from torch import nn
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
 from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, NORM, PERMUTE, RESHAPE, SIZE,
-                               SeedBatchedSweep, SweepUnsupported)
+                               SLICE, SPLIT, SeedBatchedSweep, SweepUnsupported)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
 _PASS_THROUGH = {ACT, IDENTITY, ADD}  # shape-preserving: the cotangent keeps the representation it arrives in
 GN_MAP = "group-norm on a feature map"  # what `_walk` reports for an nn.GroupNorm node (NORM covers nn.LayerNorm in the head too)
 CAT_MAP = "concatenation of feature maps"  # what `_walk` reports for a CAT whose sources sit on feature maps (CAT: one in the head)
+SLICE_MAP = "channel slice of a feature map"  # what `_walk` reports for a SLICE whose source sits on a feature map (SLICE: one in the head)
 _POOL = {MAXPOOL, AVGPOOL}  # spatial pooling: fp32 NHWC in, fp32 NHWC out (lk_pool.hip)
-_FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP} | _POOL  # produce / consume NHWC feature maps
-_MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
+_FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP, SLICE_MAP} | _POOL  # produce / consume NHWC feature maps
+_MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, SLICE_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
 _NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST}  # a graph with one of these runs through the NCHW sweep
 
 
@@ -217,6 +220,10 @@ class SplitSweep(SeedBatchedSweep):
                 why = self._cat_refusal(node, r)
                 if why is not None:
                     return f"{node.name}: {why}"
+            elif r.kind == SLICE:
+                why = self._slice_refusal(node, r)
+                if why is not None:
+                    return f"{node.name}: {why}"
         if not n_conv:
             return "no convolution in the graph"
         return self._region_check()
@@ -240,6 +247,8 @@ class SplitSweep(SeedBatchedSweep):
             kind = self.rule[n].kind
             if kind == CAT:
                 hit = any(self._on_map(a) for a in self.rule[n].src)
+            elif kind in (SLICE, SPLIT):
+                hit = self._on_map(self.rule[n].src[0])
             elif kind in _PASS_THROUGH:
                 hit = any(k in _MAP_SOURCES for k in self._walk(n, False))
             else:
@@ -261,6 +270,38 @@ class SplitSweep(SeedBatchedSweep):
             return f"{r.what} of feature maps along dim {r.args[0]} (the NHWC kernels concatenate channels: dim 1 of a 4-D map)"
         if not all(hasattr(self.kernels(), f) for f in ("cat_forward", "cat_vjp")):
             return "kernels without the concatenation entry points"
+        return None
+
+    #: ``False``: a model that slices a feature map (``chunk`` / ``split`` / ``narrow`` / static indexing) runs through the NCHW
+    #: sweep (whose SLICE rule serves it), as it would without csrc/lk_slice.hip (tools/slice_bench.py)
+    nhwc_slice = True
+
+    @staticmethod
+    def _slice_dim_as_written(spec):
+        """``(dim, drops)`` of a SLICE rule as far as the graph alone tells: the dim as written (counted from the end behind a
+        ``...``) and whether an int index drops it"""
+        if spec[0] == "index":
+            entries, i = spec[1], spec[2]
+            dim = i if not any(e is Ellipsis for e in entries[:i]) else i - len(entries)
+            return dim, not isinstance(entries[i], slice)
+        return (spec[1] if spec[0] == "narrow" else spec[3]), False
+
+    def _slice_refusal(self, node, r):
+        """why this SLICE node keeps the model off the NHWC walk (None: lk_slice.hip serves it, or it is a slice of a plain tensor
+        in the head region, which takes the parent-class math)"""
+        if not self.nhwc_slice:
+            return f"{r.what} has no NHWC rule"
+        if not self._on_map(r.src[0]):
+            return None
+        dim, drops = self._slice_dim_as_written(r.args)
+        if drops:
+            return f"{r.what}: an int index on a feature map (the NHWC kernels slice channel ranges and keep the dim)"
+        if dim not in (1, -3):
+            return f"{r.what}: slice of a feature map along dim {dim} (H or W; the NHWC kernels slice channels: dim 1 of a 4-D map)"
+        if any(k not in _FEATURE and k not in _PASS_THROUGH for k in self._walk(node, True)):
+            return f"{r.what}: slice of a feature map mixed with consumers outside the feature maps"
+        if not all(hasattr(self.kernels(), f) for f in ("slice_forward", "slice_vjp")):
+            return "kernels without the slicing entry points"
         return None
 
     def _bn_tap_served(self, m) -> bool:
@@ -329,8 +370,13 @@ class SplitSweep(SeedBatchedSweep):
                     continue
                 seen.add(m)
                 kind = self.rule[m].kind
+                if kind == SPLIT:  # (a tuple of parts: its items, which look through it, are what is walked)
+                    todo.append(m)
+                    continue
                 if kind == CAT and self._on_map(m):
                     kind = CAT_MAP  # (a producer and consumer of feature maps, not pass-through)
+                if kind == SLICE and self._on_map(m):
+                    kind = SLICE_MAP
                 out.append(GN_MAP if kind == NORM and isinstance(self.rule[m].mod, nn.GroupNorm) else kind)
                 if kind in _PASS_THROUGH:
                     todo.append(m)
@@ -518,6 +564,25 @@ class SplitSweep(SeedBatchedSweep):
             self._aux_put(out, {"split": None, "bound": bound})
         return out
 
+    def _run_slice(self, node, r, inp, dim, start, length, dropped):
+        """channel slice of a feature map: ONE lk_slice_fwd_f32 launch on the ``[B H W][C]`` view of the input's NHWC memory into a
+        contiguous NHWC map (what the convolutions read); returns the NCHW-logical view over NHWC memory, as `_run_cat` does.  A
+        slice cannot raise a map's maximum, so the output inherits the input's per-image ``"bound"`` words; no ``"split"`` is
+        registered.  A slice of a plain tensor in the head region is the parent's view."""
+        if not (self.split_ok and self._on_map(node)):
+            return super()._run_slice(node, r, inp, dim, start, length, dropped)
+        # (also with ``nhwc_forward = False``: the reverse sweep is NHWC either way)
+        if dim != 1 or dropped or not (inp.dim() == 4 and inp.dtype == torch.float32):
+            raise SweepUnsupported(f"{node.name}: slicing of the NHWC sweep expects an fp32 feature map and a channel range")
+        xh = inp.permute(0, 2, 3, 1).contiguous()  # (a view when inp is already NHWC in memory)
+        B, H, W, C = xh.shape
+        y = self.kernels().slice_forward(xh, B * H * W, C, start, length).reshape(B, H, W, length)
+        out = y.permute(0, 3, 1, 2)
+        aux = self._aux_get(inp)
+        if aux is not None and aux.get("bound") is not None:
+            self._aux_put(out, {"split": None, "bound": aux["bound"]})
+        return out
+
     #: ``False``: a convolution and the BatchNorm / add / ReLU behind it stay two launches
     fuse_conv_bn = True
 
@@ -703,6 +768,9 @@ class SplitSweep(SeedBatchedSweep):
             return w
 
         self._new_word = new_word
+        # per node: what its SLICE consumers hand back, ``(part, dim, start, length, input shape)``, assembled with the full-width
+        # parts ONCE, when the node itself is reached
+        pieces: dict[fx.Node, list] = {}
 
         def push(n, part):
             if not isinstance(n, fx.Node) or n.op == "placeholder":
@@ -727,12 +795,25 @@ class SplitSweep(SeedBatchedSweep):
                 for fn in fns[1:]:
                     fn(part)
                 cot[node] = [part]
-            if node not in cot:
+            if node not in cot and node not in pieces:
                 continue
-            parts = cot.pop(node)
+            parts = cot.pop(node, [])
             kind, m, src = r.kind, r.mod, r.src[0]
-            if node in deferred or kind not in _LAZY:
+            if node in deferred or node in pieces or kind not in _LAZY:
                 parts = _materialize(parts)
+            if node in pieces:
+                pcs = pieces.pop(node)
+                if torch.is_tensor(pcs[0][0]):
+                    # slices in the head region (plain tensors after the flatten): parent-class math
+                    parts = [self._assemble_slices(parts, [p[:4] for p in pcs], (SB,) + tuple(pcs[0][4][1:]))]
+                else:
+                    # ONE launch: the full-width parts and the channel pieces, as they lie, summed into an fp32 map with its max|.|
+                    Ct = int(pcs[0][4][1])
+                    ops = [(p if isinstance(p, SplitTensor) else p.t, 0, Ct) for p in parts]
+                    ops += [(p if isinstance(p, SplitTensor) else p.t, start, length) for p, _, start, length, _ in pcs]
+                    shape, word = (SB, int(pcs[0][4][2]), int(pcs[0][4][3]), Ct), new_word()
+                    t = self.slice_vjp_launches(K, ops, shape[0] * shape[1] * shape[2], Ct, amax=word)
+                    parts = [_F32(t.reshape(shape), word)]
             if node in deferred:
                 f32p = [p for p in parts if isinstance(p, _F32)]
                 fns = deferred.pop(node)
@@ -918,6 +999,16 @@ class SplitSweep(SeedBatchedSweep):
                             word = new_word()
                             push(a, _F32(K.cat_vjp(ops, off, n, amax=word), word))
                         off += n
+            elif kind == SLICE:
+                dim, start, length, dropped, in_shape = self.saved[node]
+                if not isinstance(src, fx.Node) or src.op == "placeholder" or self.rule[src].kind == CONST:
+                    continue
+                if all(torch.is_tensor(p) for p in parts):
+                    g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
+                    pieces.setdefault(src, []).append((g.unsqueeze(dim) if dropped else g, dim, start, length, in_shape))
+                else:  # the parts as they lie (split tensors and fp32 maps): channels [start, start + length) of the source
+                    for p in parts:
+                        pieces.setdefault(src, []).append((p, dim, start, length, in_shape))
             elif kind == RESHAPE:
                 g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
                 if not torch.is_tensor(g):
