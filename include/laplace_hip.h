@@ -654,6 +654,36 @@ int lk_slice_vjp_f32(int npieces, const float* const* f32, const void* const* hi
                      unsigned* amax, void* stream);
 int lk_slice_variant(int npieces, int split_mask, const int64_t* c0, const int64_t* cs, int64_t R, int64_t Ct, int aligned);
 
+/* Element-wise product of two traced tensors (squeeze-and-excitation gates, GLU / SwiGLU / GeGLU, self-gating) for the
+ * seed-batched reverse sweep.  It replaces, in the reverse pass of laplace/curvature/curvlinops.py:87-100 and
+ * curvature.py:88-129 through out = a * b as stock torch runs it once per seed, g * b, g * a and - for a gate - a sum over the
+ * trailing dims: five passes over [S*B, ...] tensors.
+ *
+ * lk_mul_vjp_f32: g [S][R][L] is the cotangent of a * b for all S seeds; a [R][L]; b [R][L] (b_row == 0, full form) or [R]
+ *   (b_row == 1, row gate: R = B * prod(dims before the gate's trailing ones), L the product of the remaining dims).
+ *     da[s][r][l] = g[s][r][l] * b[r][l] (b[r] for a row gate)                               da [S][R][L]
+ *     db[s][r][l] = g[s][r][l] * a[r][l]  /  db[s][r] = sum_l g[s][r][l] * a[r][l]           db [S][R][L] / [S][R]
+ *   da or db may be NULL (that output is not computed), not both.  One launch for all seeds: g is read once for both outputs,
+ *   a and b once per sample row.  Plain fp32, one rounding per product; the row sum adds in a fixed order (lane-strided partial
+ *   sums, then a xor-shuffle tree); one owner per output element, plain stores, no atomics, deterministic.
+ *   Minimal traffic: 4 S R L bytes of g, a and b once, and the outputs asked for.
+ * Contract: g, a, b and at least one output non-null; b_row 0 or 1; 1 <= S, 0 <= R, 1 <= L < 2^30, S * R * L < 2^40; no output
+ *   overlaps an input or the other output.  R == 0 returns LK_OK.
+ * lk_mul_variant (host only): the path lk_mul_vjp_f32 takes for a shape; want_da / want_db: which outputs are asked for;
+ * `aligned`: every pointer is 16-byte aligned.  Returns
+ *   form | vec << 1 | log2(lanes per row) << 2 | resident << 5 | seed-split << 6 | wide << 7 | da << 8 | db << 9 |
+ *   workgroups of grid.x << 10
+ *   bit 0 form: 1 row gate, 0 full form; bit 1 vec: 16-byte loads and stores (L % 4 == 0 and aligned), else 4-byte ones;
+ *   bits 2-4: a group of 1 .. 64 lanes owns a row (0 in the full form: a lane owns one vector of the flattened [R * L]);
+ *   bit 5 resident: a of a row stays in registers across the seed loop (at most 8 vectors per lane; always in the full form),
+ *   else it is re-read per seed; bit 6: the seeds are split over grid.y; bit 7 wide: S * R * L >= 2^31, an element offset
+ *   passes 31 bits (the kernel indexes with 64 bits throughout); bits 8 and 9: the outputs; bits 10 and up: at most 2048
+ *   workgroups of 256 threads that stride over the rows / vectors
+ * or a negative value for a shape the entry point refuses. */
+int lk_mul_vjp_f32(const float* g, const float* a, const float* b, int64_t S, int64_t R, int64_t L, int b_row, float* da,
+                   float* db, void* stream);
+int lk_mul_variant(int64_t S, int64_t R, int64_t L, int b_row, int want_da, int want_db, int aligned);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

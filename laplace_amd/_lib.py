@@ -131,6 +131,8 @@ SIGNATURES = {
     "lk_slice_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_slice_vjp_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "lk_slice_variant": (_int, [_int, _int, _vp, _vp, _i64, _i64, _int]),
+    "lk_mul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "lk_mul_variant": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
     "lk_dwconv_fwd_nhwc_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp]),
     "lk_dwconv_bwd_nhwc_f16x2": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp, _vp]),
     "lk_dwconv_variant": (_int, [_i64, _i64, _i64, _i64, _i64] + [_int] * 7),
@@ -1605,6 +1607,38 @@ class HipKernels:
             return None
         return {"vec": bool(r & 1), "npieces": (r >> 1) & 15, "split_mask": (r >> 5) & 255, "wide_index": bool(r & (1 << 13)),
                 "blocks": r >> 14}
+
+    def mul_vjp(self, g, a, b, S, b_row, want=(True, True)):
+        """``(da, db)`` of ``out = a * b`` for the ``S`` seeds stacked in the cotangent ``g`` (``S * a.numel()`` elements, seed-major)
+        from ONE ``a`` and ``b`` per sample, in ONE launch of lk_mul_vjp_f32 (csrc/lk_mul.hip).  ``b_row`` false: ``b`` has the
+        shape of ``a``, ``da = g * b`` and ``db = g * a``, both of the shape of ``g``.  ``b_row`` true: ``b`` is a row gate with one
+        value per row of ``a`` read as ``[R = b.numel(), L]``; ``da = g * b[r]`` and ``db[s, r] = sum_l g[s, r, l] * a[r, l]``, of
+        shape ``[S * b.shape[0], *b.shape[1:]]``.  ``want``: which of the two to compute (``None`` stands for the other)."""
+        _check(g, "g"), _check(a, "a"), _check(b, "b")
+        S, b_row, want_da, want_db = int(S), bool(b_row), bool(want[0]), bool(want[1])
+        R = b.numel() if b_row else (a.shape[0] if a.dim() else 1)  # (full form: any split of a.numel() into rows serves)
+        L = a.numel() // R if R else 1
+        if S < 1 or not (want_da or want_db) or g.numel() != S * a.numel() or R * L != a.numel() or (not b_row and b.numel() != a.numel()):
+            raise LaplaceHipError(f"mul_vjp: g {tuple(g.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)} do not belong together for "
+                                  f"S = {S}, b_row = {b_row}, want = {tuple(want)}")
+        if a.device != g.device or b.device != g.device:
+            raise LaplaceHipError("mul_vjp: g, a and b are on different devices")
+        da = torch.empty_like(g) if want_da else None
+        db = None
+        if want_db:
+            db = torch.empty((S * b.shape[0], *b.shape[1:]), dtype=torch.float32, device=g.device) if b_row else torch.empty_like(g)
+        self._rc(self.lib.lk_mul_vjp_f32(_ptr(g), _ptr(a), _ptr(b), S, R, L, int(b_row), _ptr(da), _ptr(db),
+                                         self._stream(g.device)), "lk_mul_vjp_f32")
+        return da, db
+
+    def mul_variant(self, S, R, L, b_row, want=(True, True), aligned=True):
+        """lk_mul_variant: the path ``lk_mul_vjp_f32`` takes for a shape (host only, no device call), or ``None`` for a shape it
+        refuses"""
+        r = int(self.lib.lk_mul_variant(int(S), int(R), int(L), int(b_row), int(bool(want[0])), int(bool(want[1])), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"row": bool(r & 1), "vec": bool(r & 2), "lanes_per_row": 1 << ((r >> 2) & 7), "resident": bool(r & 32),
+                "seed_split": bool(r & 64), "wide_index": bool(r & 128), "da": bool(r & 256), "db": bool(r & 512), "blocks": r >> 10}
 
     @staticmethod
     def _dwconv_geometry(x_hw, kernel, stride, padding, what):

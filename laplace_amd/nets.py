@@ -440,3 +440,123 @@ class ViTClassToken(nn.Module):
         for blk in self.blocks:
             x = blk(x)
         return self.head(self.norm(x)[:, 0])
+
+
+class SEBlock(nn.Module):
+    """Squeeze-and-excitation gate: ``x * sigmoid(fc2(act(fc1(avgpool(x)))))`` with 1x1 convolutions on the pooled ``[B, C, 1, 1]``
+    map (``C / reduction`` channels in between).  The product of the map with the ``[B, C, 1, 1]`` gate is the row-gate form of the
+    product rule of the seed-batched sweep (csrc/lk_mul.hip)."""
+
+    def __init__(self, c: int, reduction: int = 4, act=nn.ReLU):
+        super().__init__()
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc1, self.act, self.fc2 = nn.Conv2d(c, max(c // reduction, 1), 1), act(), nn.Conv2d(max(c // reduction, 1), c, 1)
+        self.gate = nn.Sigmoid()
+
+    def forward(self, x):
+        return x * self.gate(self.fc2(self.act(self.fc1(self.pool(x)))))
+
+
+class SEBasicBlock(nn.Module):
+    """:class:`BasicBlock` with an :class:`SEBlock` on the residual branch, before the add: ``act(se(bn2(conv2(..))) + shortcut)``"""
+
+    def __init__(self, cin: int, cout: int, stride: int, reduction: int = 4, act=nn.ReLU):
+        super().__init__()
+        self.conv1, self.bn1, self.act1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False), nn.BatchNorm2d(cout), act()
+        self.conv2, self.bn2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False), nn.BatchNorm2d(cout)
+        self.se, self.act2 = SEBlock(cout, reduction, act), act()
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        out = self.se(self.bn2(self.conv2(self.act1(self.bn1(self.conv1(x))))))
+        return self.act2(out + (x if self.downsample is None else self.downsample(x)))
+
+
+class SEResNetSmall(nn.Module):
+    """A CIFAR SE-ResNet for 3 x 32 x 32 inputs: 3x3 stem convolution - BN - act, ``depth`` :class:`SEBasicBlock` s per entry of
+    ``widths`` (stride 2 into every stage but the first), then global average - flatten - ``Linear``.  Eval-mode BatchNorm; the gate
+    branches are 1x1 convolutions on 1x1 maps with ``width / reduction`` channels, so the model runs the NCHW sweep (the split
+    sweep names the product): the workload of the row-gate form of the product rule.  ``act`` and ``freeze_bn`` as with
+    :class:`DenseNetSmall`."""
+
+    def __init__(self, num_classes: int = 10, widths=(32, 64, 128), depth: int = 2, reduction: int = 4, freeze_bn: bool = True,
+                 act=nn.ReLU):
+        super().__init__()
+        cin = widths[0]
+        self.stem = nn.Sequential(nn.Conv2d(3, cin, 3, 1, 1, bias=False), nn.BatchNorm2d(cin), act())
+        blocks = []
+        for i, c in enumerate(widths):
+            for j in range(depth):
+                blocks.append(SEBasicBlock(cin, c, 2 if i and j == 0 else 1, reduction, act))
+                cin = c
+        self.layers = nn.Sequential(*blocks)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+        if freeze_bn:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.weight.requires_grad_(False)
+                    m.bias.requires_grad_(False)
+
+    def forward(self, x):
+        return self.fc(torch.flatten(self.pool(self.layers(self.stem(x))), 1))
+
+
+class SwiGLUBlock(nn.Module):
+    """The pre-LN block of :class:`AttentionBlock` with the MLP replaced by the gated feed-forward of LLaMA / PaLM:
+    ``x + w2(silu(w1(LN(x))) * w3(LN(x)))``.  The product of the two ``[B, T, hidden]`` branches is the full form of the product
+    rule of the seed-batched sweep (csrc/lk_mul.hip).  ``hidden = round(dim * mlp_ratio)`` (8 / 3: the parameter count of a
+    plain MLP of ratio 4)."""
+
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 8.0 / 3.0, causal: bool = False):
+        super().__init__()
+        if dim % heads:
+            raise ValueError(f"heads ({heads}) must divide dim ({dim})")
+        self.heads, self.causal = heads, causal
+        self.norm1 = nn.LayerNorm(dim)
+        self.q, self.k, self.v, self.proj = (nn.Linear(dim, dim) for _ in range(4))
+        self.norm2 = nn.LayerNorm(dim)
+        hidden = int(round(dim * mlp_ratio))
+        self.w1, self.w3, self.w2 = nn.Linear(dim, hidden), nn.Linear(dim, hidden), nn.Linear(hidden, dim)
+
+    def forward(self, x):
+        B, T = x.size(0), x.size(1)
+        h = self.norm1(x)
+        q = self.q(h).view(B, T, self.heads, -1).transpose(1, 2)
+        k = self.k(h).view(B, T, self.heads, -1).transpose(1, 2)
+        v = self.v(h).view(B, T, self.heads, -1).transpose(1, 2)
+        a = nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
+        x = x + self.proj(a.transpose(1, 2).reshape(B, T, -1))
+        h = self.norm2(x)
+        return x + self.w2(nn.functional.silu(self.w1(h)) * self.w3(h))
+
+
+class ViTSwiGLU(nn.Module):
+    """:class:`ViTSmall` with :class:`SwiGLUBlock` s: patch embedding, the fixed sin-cos positional buffer, ``depth`` blocks, a final
+    LayerNorm, the mean over the positions and a ``Linear`` head.  The defaults give ``T = 64`` positions, head dim 64 and 512
+    hidden units.  ``image`` is the side of a square image or ``(height, width)``.  ``freeze_norm`` as with :class:`ViTSmall`."""
+
+    def __init__(self, num_classes: int = 10, image=32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
+                 mlp_ratio: float = 8.0 / 3.0, freeze_norm: bool = True, causal: bool = False):
+        super().__init__()
+        ih, iw = image if isinstance(image, (tuple, list)) else (image, image)
+        if ih % patch or iw % patch:
+            raise ValueError(f"patch ({patch}) must divide image ({image})")
+        self.embed = nn.Conv2d(3, dim, patch, patch)
+        self.register_buffer("pos", sincos_positions((ih // patch) * (iw // patch), dim))
+        self.blocks = nn.ModuleList(SwiGLUBlock(dim, heads, mlp_ratio, causal=causal) for _ in range(depth))
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.LayerNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, x):
+        x = self.embed(x).flatten(2).transpose(1, 2) + self.pos
+        for blk in self.blocks:
+            x = blk(x)
+        return self.head(self.norm(x).mean(1))

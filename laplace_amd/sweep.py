@@ -41,6 +41,8 @@ CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SI
 # SPLIT: a tuple-valued chunk / split node (no VJP of its own, like SIZE: its items are SLICE nodes that look through it);
 # SLICE: one static range along ONE non-batch dim of a traced tensor
 SPLIT, SLICE = "split", "slice"
+# MUL: the element-wise product of two tensors of the graph (gates, GLU); a product with a Python number is refused
+MUL = "product"
 
 
 class Rule(NamedTuple):
@@ -58,7 +60,8 @@ class Rule(NamedTuple):
     # static arguments: AVGPOOL's parameters, GPOOL's output size, MEAN's (dim, keepdim) as written, ATTN's (is_causal, scale),
     # PERMUTE's (spelling, dims), CONST's attribute path (none for an expanded constant, which has ``fn``), CAT's (dim as written,),
     # SPLIT's (spelling, sizes, dim as written), SLICE's ("index", entries, position) / ("narrow", dim, start, length) /
-    # ("split", spelling, sizes, dim, item): resolved on the value by `slice_range`
+    # ("split", spelling, sizes, dim, item): resolved on the value by `slice_range`; MUL has none (``src``: its two operands, a
+    # node may be both; a constant or the input receives nothing)
     args: tuple = ()
 
 
@@ -85,12 +88,14 @@ _FUNCTION_KINDS = {
     torch.mean: (MEAN, None), operator.getitem: (GETITEM, None), F.scaled_dot_product_attention: (ATTN, None),
     torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None),
     torch.cat: (CAT, None), torch.concat: (CAT, None), torch.concatenate: (CAT, None),
-    torch.chunk: (SPLIT, None), torch.split: (SPLIT, None), torch.narrow: (SLICE, None)}
+    torch.chunk: (SPLIT, None), torch.split: (SPLIT, None), torch.narrow: (SLICE, None),
+    operator.mul: (MUL, None), torch.mul: (MUL, None), torch.multiply: (MUL, None), operator.imul: (MUL, None)}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
     "size": (SIZE, None), "transpose": (PERMUTE, None), "permute": (PERMUTE, None),
-    "chunk": (SPLIT, None), "split": (SPLIT, None), "narrow": (SLICE, None), "expand": (CONST, None), "expand_as": (CONST, None)}
+    "chunk": (SPLIT, None), "split": (SPLIT, None), "narrow": (SLICE, None), "expand": (CONST, None), "expand_as": (CONST, None),
+    "mul": (MUL, None), "multiply": (MUL, None), "mul_": (MUL, None)}
 # relatives of the slicing rules that have none: refused by name
 _NO_SLICE_RULE = {torch.unbind: "unbind", torch.tensor_split: "tensor_split", torch.stack: "stack", "unbind": "unbind",
                   "tensor_split": "tensor_split"}
@@ -349,6 +354,46 @@ def _classify_slice(node, modules, what):
     return Rule(SLICE, (src,), None, ((src,), {}), what, args=("narrow", dim, start, length))
 
 
+def _classify_mul(node, modules):
+    """the two operands of a product (``*``, ``torch.mul`` / ``multiply``, the methods, ``*=`` / ``mul_``): each a traced tensor
+    or a constant of the sweep, at least one traced, or the refusal that names the reason (every message holds ``mul``)"""
+    if node.kwargs.get("out") is not None:
+        raise SweepUnsupported("mul with an out= argument (the sweep keeps its own values)")
+    if node.kwargs or len(node.args) != 2:
+        raise SweepUnsupported(f"mul: expected two positional operands, got {len(node.args)} and the keywords {sorted(node.kwargs)}")
+    for t in node.args:
+        if isinstance(t, (bool, int, float, complex)):
+            raise SweepUnsupported(f"mul by the Python number {t!r} is not served (fold the factor into the layer: scale its weights "
+                                   "and bias)")
+        if not isinstance(t, fx.Node):
+            raise SweepUnsupported(f"mul: an operand is not a tensor of the graph ({type(t).__name__})")
+    if all(classify(t, modules).kind == CONST for t in node.args):
+        raise SweepUnsupported("mul of two constants (at least one operand must be a traced tensor)")
+    return tuple(node.args)
+
+
+def mul_form(sa, sb):
+    """how the shapes of two traced operands of a product go together: ``("full", None, 0)`` for equal shapes, ``("row", gate, k)``
+    when operand ``gate`` (0 / 1) is ``other.shape[:k] + (1,) * (ndim - k)`` with ``1 <= k < ndim`` (``[B, C, 1, 1]`` against
+    ``[B, C, H, W]``); anything else is refused with both shapes"""
+    sa, sb = tuple(int(d) for d in sa), tuple(int(d) for d in sb)
+    if sa == sb:
+        return "full", None, 0
+    if len(sa) == len(sb):
+        for gate, (sg, so) in enumerate(((sa, sb), (sb, sa))):
+            k = next((i for i, d in enumerate(sg) if d == 1 and so[i] != 1), len(sg))
+            if 1 <= k < len(sg) and sg[:k] == so[:k] and all(d == 1 for d in sg[k:]):
+                return "row", gate, k
+        try:
+            torch.broadcast_shapes(sa, sb)
+        except RuntimeError:
+            pass
+        else:
+            raise SweepUnsupported(f"mul of {sa} and {sb}: a traced operand broadcast along a dim before the last kept one needs a "
+                                   "strided reduction (only a gate of trailing ones, [B, C, 1, 1] or [B, T, 1], is served)")
+    raise SweepUnsupported(f"mul of {sa} and {sb}: the traced operands must have equal shapes, or one must be a gate of trailing ones")
+
+
 def _no_slice_rule(target):
     """what a refusal adds for a relative of the slicing rules (``unbind``, ``tensor_split``, ``stack``)"""
     name = _NO_SLICE_RULE.get(target)
@@ -445,6 +490,10 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == CAT:
         src, static = _classify_cat(node, what)
         fn, args, kwargs = torch.cat, (list(src),), {}  # (one spelling; the dim is resolved on the value)
+    elif kind == MUL:
+        src = _classify_mul(node, modules)
+        if fn is operator.imul or node.target == "mul_":  # (`*=` / `mul_` must not write into a kept tensor)
+            fn = operator.mul
     return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
 
 
@@ -684,6 +733,9 @@ class SeedBatchedSweep:
                     out = r.fn(*args, **kwargs)
                 except (RuntimeError, TypeError, IndexError) as e:  # (sections that do not fit the value: torch's own words)
                     raise SweepUnsupported(f"{r.what}: {e}") from e
+            elif kind == MUL:
+                out, keep = self._run_mul(r, args)
+                keep = keep if need_vjp else None
             elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
                 out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
@@ -883,6 +935,65 @@ class SeedBatchedSweep:
         if K is not None:
             return K.attn_vjp(g, q, k, v, o, aux, S, scale, causal)
         return attn_vjp_math(g, q, k, v, o, aux, S, scale, self.attn_mem_bytes)
+
+    #: ``False``: the VJP of a product stays on the torch math of its rule (``g * b``, ``(g * a).sum(...)``) whatever the kernel
+    #: object offers
+    use_mul_kernels = True
+
+    def _mul_kernels(self, ts):
+        """the kernel object when csrc/lk_mul.hip serves the VJP of a product of ``ts`` (an object with the entry point - the stock
+        emulation has none -, fp32), else ``None``: the same formula in torch"""
+        K = self.kernels() if self.kernels is not None and self.use_mul_kernels else None
+        if K is None or not hasattr(K, "mul_vjp") or not all(t.dtype == torch.float32 for t in ts):
+            return None
+        return K
+
+    def _run_mul(self, r, args):
+        """product forward -> ``(out, (form, a, b, gate, k))``: both operands belong to the sample, not to the seed.  ``form``:
+        ``"const"`` (operand ``gate`` is a constant that broadcasts to exactly the other's shape and receives nothing), ``"full"``
+        or ``"row"`` (operand ``gate`` is the other's shape with trailing ones from dim ``k``: `mul_form`)"""
+        a, b = args
+        if not (torch.is_tensor(a) and torch.is_tensor(b)):
+            raise SweepUnsupported(f"mul: an operand is not a tensor ({type(a).__name__} * {type(b).__name__})")
+        const = [self.rule[n].kind == CONST for n in r.src]
+        if any(const):
+            gate = const.index(True)
+            c, other = (a, b) if gate == 0 else (b, a)
+            if tuple(torch.broadcast_shapes(c.shape, other.shape)) != tuple(other.shape):
+                raise SweepUnsupported(f"mul: {tuple(other.shape)} broadcasts against the {self.rule[r.src[gate]].what} of shape "
+                                       f"{tuple(c.shape)} (the VJP needs a reduction)")
+            form, k = "const", 0
+        else:
+            form, gate, k = mul_form(a.shape, b.shape)
+        return r.fn(a, b), (form, a, b, gate, k)
+
+    def _mul_vjp(self, saved, g, S, want):
+        """``(d first, d second)`` of a product for all seeds, ``g`` ``[S*B, ...]``: ``d first = g * second`` and ``d second =
+        g * first`` - summed over the trailing dims for a row gate - from ONE pair of operands per sample; an operand that is not
+        in ``want`` gets ``None``.  ONE launch of lk_mul_vjp_f32 (the gate as its ``b``), or the same formula in torch; a constant
+        operand is a plain torch product."""
+        form, a, b, gate, k = saved
+        if form == "const":
+            c, other = (a, b) if gate == 0 else (b, a)
+            d = (g.reshape(S, *other.shape) * c).reshape(g.shape) if want[1 - gate] else None
+            return (None, d) if gate == 0 else (d, None)
+        if form == "row" and gate == 0:  # (the kernel's and the formula's second operand is the gate)
+            db, da = self._mul_vjp((form, b, a, 1, k), g, S, (want[1], want[0]))
+            return da, db
+        row = form == "row"
+        K = self._mul_kernels((g, a, b))
+        L = 1
+        for d in a.shape[k:] if row else a.shape[1:]:
+            L *= int(d)
+        if K is not None and a.numel() > 0 and L < (1 << 30) and g.numel() < (1 << 40):
+            return K.mul_vjp(g.contiguous(), a.contiguous(), b.contiguous(), S, row, want)
+        gv = g.reshape(S, *a.shape)
+        da = (gv * b).reshape(g.shape) if want[0] else None
+        db = None
+        if want[1]:
+            db = gv * a
+            db = db.sum(tuple(range(k + 1, gv.dim())), keepdim=True).reshape(S * b.shape[0], *b.shape[1:]) if row else db.reshape(g.shape)
+        return da, db
 
     def _add_const(self, r, args, kwargs):
         """``x + constant``: the constant must broadcast to exactly the other operand's shape (the other way round the VJP is
@@ -1130,6 +1241,11 @@ class SeedBatchedSweep:
             elif kind == ADD:
                 for a in r.src:
                     push(a, g)
+            elif kind == MUL:
+                want = tuple(n.op != "placeholder" and self.rule[n].kind != CONST for n in r.src)
+                if any(want):
+                    for a, d in zip(r.src, self._mul_vjp(self.saved[node], g, S, want)):  # (`x * x`: x receives two parts)
+                        push(a, d)
             elif kind == CAT:
                 dim, sizes = self.saved[node]
                 off = 0
