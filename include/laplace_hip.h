@@ -684,6 +684,60 @@ int lk_mul_vjp_f32(const float* g, const float* a, const float* b, int64_t S, in
                    float* db, void* stream);
 int lk_mul_variant(int64_t S, int64_t R, int64_t L, int b_row, int want_da, int want_db, int aligned);
 
+/* Softmax / log-softmax along the last, contiguous dim (hand-written attention, attention pooling, soft mixture gates,
+ * log-softmax head features) for the seed-batched reverse sweep.  It replaces, in the reverse pass of
+ * laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through y = softmax(x) as stock torch runs it once per seed,
+ * S calls of the softmax backward that each read y again.
+ *
+ * lk_softmax_vjp_f32: g [S][R][L] is the cotangent of y for all S seeds; y [R][L] is the forward's OUTPUT (probabilities, or
+ *   log-probabilities with is_log == 1), one per sample row for all seeds.
+ *     is_log == 0:  dx[s][r][l] = y[r][l] * (g[s][r][l] - sum_j g[s][r][j] y[r][j])
+ *     is_log == 1:  dx[s][r][l] = g[s][r][l] - exp(y[r][l]) * sum_j g[s][r][j]
+ *   One launch for all seeds; y (exp(y), computed once) of a row stays in registers across the seeds while the row fits.  Plain
+ *   fp32; the row sum adds in a fixed order (lane-strided partial sums, then a xor-shuffle tree); one owner per output element,
+ *   plain stores, no atomics, deterministic.  y[r][l] == 0 gives dx == 0 exactly (for finite g).
+ *   Minimal traffic: 8 S R L bytes (g read, dx written) plus y once.
+ * Contract: g, y, dx non-null; is_log 0 or 1; 1 <= S, 0 <= R, 1 <= L < 2^30, S * R * L < 2^40; dx overlaps neither input.
+ *   R == 0 returns LK_OK.
+ * lk_softmax_vjp_variant (host only): the path lk_softmax_vjp_f32 takes for a shape; `aligned`: every pointer is 16-byte
+ * aligned.  Returns
+ *   vec | log2(lanes per row) << 1 | resident << 4 | seed-split << 5 | wide << 6 | is_log << 7 | workgroups of grid.x << 8
+ *   bit 0 vec: 16-byte loads and stores (L % 4 == 0 and aligned), else 4-byte ones; bits 1-3: a group of 1 .. 64 lanes owns a
+ *   row; bit 4 resident: y and the seed's g of a row stay in registers (at most 8 vectors per lane), else both are re-read per
+ *   seed; bit 5: the seeds are split over grid.y; bit 6 wide: S * R * L >= 2^31 (the kernel indexes with 64 bits throughout);
+ *   bits 8 and up: at most 2048 workgroups of 256 threads that stride over the rows
+ * or a negative value for a shape the entry point refuses. */
+int lk_softmax_vjp_f32(const float* g, const float* y, int64_t S, int64_t R, int64_t L, int is_log, float* dx, void* stream);
+int lk_softmax_vjp_variant(int64_t S, int64_t R, int64_t L, int is_log, int aligned);
+
+/* Batched matrix product of two traced tensors (hand-written attention q @ k^T and p @ v, bilinear heads) for the
+ * seed-batched reverse sweep.  It replaces, in the reverse pass of laplace/curvature/curvlinops.py:87-100 and
+ * curvature.py:88-129 through out = a @ b as stock torch runs it once per seed, two batched products per seed.
+ *
+ * lk_matmul_vjp_f32: g [S][NB][M][N] is the cotangent of a @ b for all S seeds (seed-major, as the sweep leaves it);
+ *   a [NB][M][K] and b [NB][K][N] are the per-sample operands, shared by all seeds.
+ *     da[s][n] = g[s][n] b[n]^T     da [S][NB][M][K]   (reduction over N)
+ *     db[s][n] = a[n]^T g[s][n]     db [S][NB][K][N]   (reduction over M)
+ *   da or db may be NULL (that output is not computed), not both.  One launch per requested output; a workgroup owns a
+ *   64 x 64 output tile of one sample matrix and loops over the seeds inside: the operand panel of the tile is staged into LDS
+ *   once for all seeds of the slice while the reduction depth (N for da, M for db) is at most 128, and restaged per seed
+ *   beyond that.  Exact fp32 matrix instruction, the reduction index ascends in a fixed order, one owner per output element,
+ *   plain stores, no atomics: deterministic.  No copy of g, a or b is made; sizes need not be multiples of anything.
+ *   Minimal traffic: g once per requested output, a and b once, the outputs once.
+ * Contract: g, a, b and at least one output non-null; 1 <= S, 0 <= NB, 1 <= M, K, N < 2^24; S * NB * M * N, S * NB * M * K
+ *   and S * NB * K * N < 2^40; NB * ceil(M / 64) * ceil(K / 64) and NB * ceil(K / 64) * ceil(N / 64) < 2^31; no output
+ *   overlaps an input or the other output.  NB == 0 returns LK_OK.
+ * lk_matmul_vjp_variant (host only): the path lk_matmul_vjp_f32 takes for a shape.  Returns
+ *   da | db << 1 | resident(da) << 2 | resident(db) << 3 | seed-split << 4 | wide << 5 | workgroups << 6
+ *   bits 0 and 1: the outputs asked for; bits 2 and 3: that output's operand panel stays in LDS across the seeds (4-byte
+ *   accesses throughout: there is no vector-width bit); bit 4: the seeds are split over grid.y; bit 5 wide: an element offset
+ *   passes 31 bits (64-bit offsets throughout); bits 6 and up: the workgroups of grid.x summed over the requested outputs
+ *   (saturating at 2^24 - 1)
+ * or a negative value for a shape the entry point refuses. */
+int lk_matmul_vjp_f32(const float* g, const float* a, const float* b, int64_t S, int64_t NB, int64_t M, int64_t K, int64_t N,
+                      float* da, float* db, void* stream);
+int lk_matmul_vjp_variant(int64_t S, int64_t NB, int64_t M, int64_t K, int64_t N, int want_da, int want_db);
+
 /* Per-sample weight Jacobian of a GROUPED convolution (nn.Conv2d(groups > 1): depthwise, channel multipliers, narrow
  * groups), written into Js[B][C][P] (replaces the grouped-convolution columns of the jacrev materialisation of
  * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129):

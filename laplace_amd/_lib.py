@@ -133,6 +133,10 @@ SIGNATURES = {
     "lk_slice_variant": (_int, [_int, _int, _vp, _vp, _i64, _i64, _int]),
     "lk_mul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_mul_variant": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
+    "lk_softmax_vjp_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp]),
+    "lk_softmax_vjp_variant": (_int, [_i64, _i64, _i64, _int, _int]),
+    "lk_matmul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "lk_matmul_vjp_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
     "lk_dwconv_fwd_nhwc_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp]),
     "lk_dwconv_bwd_nhwc_f16x2": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 6 + [_vp, _vp, _vp]),
     "lk_dwconv_variant": (_int, [_i64, _i64, _i64, _i64, _i64] + [_int] * 7),
@@ -1639,6 +1643,65 @@ class HipKernels:
             return None
         return {"row": bool(r & 1), "vec": bool(r & 2), "lanes_per_row": 1 << ((r >> 2) & 7), "resident": bool(r & 32),
                 "seed_split": bool(r & 64), "wide_index": bool(r & 128), "da": bool(r & 256), "db": bool(r & 512), "blocks": r >> 10}
+
+    def softmax_vjp(self, g, y, S, is_log=False):
+        """``dx`` (the shape of ``g``) of ``y = softmax(x, -1)`` / ``log_softmax(x, -1)`` for the ``S`` seeds stacked in the
+        cotangent ``g`` (``S * y.numel()`` elements, seed-major) from ONE output ``y`` ``[..., L]`` per sample, in ONE launch of
+        lk_softmax_vjp_f32 (csrc/lk_softmax.hip): ``y * (g - sum(g y))`` or ``g - exp(y) sum(g)`` along the last dim."""
+        _check(g, "g"), _check(y, "y")
+        S = int(S)
+        L = int(y.shape[-1]) if y.dim() else 1
+        R = y.numel() // L if L else 0
+        if S < 1 or L < 1 or g.numel() != S * y.numel():
+            raise LaplaceHipError(f"softmax_vjp: g {tuple(g.shape)} and y {tuple(y.shape)} do not belong together for S = {S}")
+        if y.device != g.device:
+            raise LaplaceHipError("softmax_vjp: g and y are on different devices")
+        dx = torch.empty_like(g)
+        self._rc(self.lib.lk_softmax_vjp_f32(_ptr(g), _ptr(y), S, R, L, int(bool(is_log)), _ptr(dx), self._stream(g.device)),
+                 "lk_softmax_vjp_f32")
+        return dx
+
+    def softmax_vjp_variant(self, S, R, L, is_log=False, aligned=True):
+        """lk_softmax_vjp_variant: the path ``lk_softmax_vjp_f32`` takes for a shape (host only, no device call), or ``None`` for a
+        shape it refuses"""
+        r = int(self.lib.lk_softmax_vjp_variant(int(S), int(R), int(L), int(is_log), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "lanes_per_row": 1 << ((r >> 1) & 7), "resident": bool(r & 16), "seed_split": bool(r & 32),
+                "wide_index": bool(r & 64), "log": bool(r & 128), "blocks": r >> 8}
+
+    def matmul_vjp(self, g, a, b, S, want=(True, True)):
+        """``(da, db)`` of ``out = a @ b`` for the ``S`` seeds stacked in the cotangent ``g`` ``[S * B, ..., M, N]`` (seed-major) from
+        ONE ``a`` ``[B, ..., M, K]`` and ``b`` ``[B, ..., K, N]`` per sample (equal leading dims), one launch of lk_matmul_vjp_f32's
+        kernel per output (csrc/lk_matmul.hip): ``da = g b^T`` ``[S * B, ..., M, K]``, ``db = a^T g`` ``[S * B, ..., K, N]``.
+        ``want``: which of the two to compute (``None`` stands for the other)."""
+        _check(g, "g"), _check(a, "a"), _check(b, "b")
+        S, want_da, want_db = int(S), bool(want[0]), bool(want[1])
+        ok = a.dim() >= 2 and a.dim() == b.dim() == g.dim() and a.shape[:-2] == b.shape[:-2] and a.shape[-1] == b.shape[-2]
+        if ok:
+            M, K, N = int(a.shape[-2]), int(a.shape[-1]), int(b.shape[-1])
+            NB = a.numel() // (M * K) if M * K else 0
+            ok = S >= 1 and (want_da or want_db) and min(M, K, N) >= 1 and g.numel() == S * NB * M * N and tuple(g.shape[-2:]) == (M, N)
+        if not ok:
+            raise LaplaceHipError(f"matmul_vjp: g {tuple(g.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)} do not belong together for "
+                                  f"S = {S}, want = {tuple(want)}")
+        if a.device != g.device or b.device != g.device:
+            raise LaplaceHipError("matmul_vjp: g, a and b are on different devices")
+        lead = (S * a.shape[0], *a.shape[1:-2]) if a.dim() > 2 else ()
+        da = torch.empty((*lead, M, K) if a.dim() > 2 else (S * M, K), dtype=torch.float32, device=g.device) if want_da else None
+        db = torch.empty((*lead, K, N) if a.dim() > 2 else (S * K, N), dtype=torch.float32, device=g.device) if want_db else None
+        self._rc(self.lib.lk_matmul_vjp_f32(_ptr(g), _ptr(a), _ptr(b), S, NB, M, K, N, _ptr(da), _ptr(db), self._stream(g.device)),
+                 "lk_matmul_vjp_f32")
+        return da, db
+
+    def matmul_vjp_variant(self, S, NB, M, K, N, want=(True, True)):
+        """lk_matmul_vjp_variant: the path ``lk_matmul_vjp_f32`` takes for a shape (host only, no device call), or ``None`` for a
+        shape it refuses"""
+        r = int(self.lib.lk_matmul_vjp_variant(int(S), int(NB), int(M), int(K), int(N), int(bool(want[0])), int(bool(want[1]))))
+        if r < 0:
+            return None
+        return {"da": bool(r & 1), "db": bool(r & 2), "resident_da": bool(r & 4), "resident_db": bool(r & 8),
+                "seed_split": bool(r & 16), "wide_index": bool(r & 32), "blocks": r >> 6}
 
     @staticmethod
     def _dwconv_geometry(x_hw, kernel, stride, padding, what):

@@ -560,3 +560,77 @@ class ViTSwiGLU(nn.Module):
         for blk in self.blocks:
             x = blk(x)
         return self.head(self.norm(x).mean(1))
+
+
+class EagerAttentionBlock(nn.Module):
+    """:class:`AttentionBlock` with the attention core written out, as BERT, the annotated transformer and every model that inspects
+    its attention maps spell it: ``softmax(q @ k^T / sqrt(head_dim) [+ bias]) @ v``.  The seed-batched sweep serves it with its
+    matrix-product, scale and softmax rules (csrc/lk_matmul.hip, csrc/lk_softmax.hip); the ``[B, H, T, T]`` scores live in device
+    memory.  ``bias``: an additive ``[1, H, T, T]`` tensor of the owner (a frozen relative-position table, a static mask), which
+    ``F.scaled_dot_product_attention``'s rule refuses.  ``head_dim`` is a Python int, so the scale is a number of the traced graph;
+    it is spelled ``/ math.sqrt(d)`` (``* d ** -0.5`` is a product with a number, which the sweep refuses).
+    ``softmax_module=True`` spells the softmax ``nn.Softmax(-1)``, else ``.softmax(-1)``."""
+
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, act=nn.GELU, softmax_module: bool = True):
+        super().__init__()
+        if dim % heads:
+            raise ValueError(f"heads ({heads}) must divide dim ({dim})")
+        self.heads, self.head_dim = heads, dim // heads
+        self.norm1 = nn.LayerNorm(dim)
+        self.q, self.k, self.v, self.proj = (nn.Linear(dim, dim) for _ in range(4))
+        self.softmax = nn.Softmax(-1) if softmax_module else None
+        self.norm2 = nn.LayerNorm(dim)
+        hidden = int(dim * mlp_ratio)
+        self.fc1, self.act, self.fc2 = nn.Linear(dim, hidden), act(), nn.Linear(hidden, dim)
+
+    def forward(self, x, bias=None):
+        B, T = x.size(0), x.size(1)
+        h = self.norm1(x)
+        q = self.q(h).view(B, T, self.heads, -1).transpose(1, 2)
+        k = self.k(h).view(B, T, self.heads, -1).transpose(1, 2)
+        v = self.v(h).view(B, T, self.heads, -1).transpose(1, 2)
+        scores = q @ k.transpose(-2, -1) / math.sqrt(self.head_dim)
+        if bias is not None:
+            scores = scores + bias
+        p = self.softmax(scores) if self.softmax is not None else scores.softmax(-1)
+        x = x + self.proj((p @ v).transpose(1, 2).reshape(B, T, -1))
+        return x + self.fc2(self.act(self.fc1(self.norm2(x))))
+
+
+class ViTEager(nn.Module):
+    """:class:`ViTSmall` with :class:`EagerAttentionBlock` s (the defaults give ``T = 64`` positions, 3 heads of dim 64).
+    ``rel_bias=True`` adds a frozen relative-position buffer ``[1, heads, T, T]`` (a Swin-style table over the offsets of the
+    patch grid, fixed at construction) to the scores of every block - what the fused attention rule cannot serve.  ``image`` is the
+    side of a square image or ``(height, width)``.  ``freeze_norm`` as with :class:`ViTSmall`."""
+
+    def __init__(self, num_classes: int = 10, image=32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
+                 act=nn.GELU, freeze_norm: bool = True, rel_bias: bool = True, softmax_module: bool = True):
+        super().__init__()
+        ih, iw = image if isinstance(image, (tuple, list)) else (image, image)
+        if ih % patch or iw % patch:
+            raise ValueError(f"patch ({patch}) must divide image ({image})")
+        gh, gw = ih // patch, iw // patch
+        self.embed = nn.Conv2d(3, dim, patch, patch)
+        self.register_buffer("pos", sincos_positions(gh * gw, dim))
+        self.blocks = nn.ModuleList(EagerAttentionBlock(dim, heads, act=act, softmax_module=softmax_module) for _ in range(depth))
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+        if rel_bias:
+            ys, xs = torch.meshgrid(torch.arange(gh), torch.arange(gw), indexing="ij")
+            dy = ys.reshape(-1, 1) - ys.reshape(1, -1) + gh - 1
+            dx = xs.reshape(-1, 1) - xs.reshape(1, -1) + gw - 1
+            table = torch.randn(heads, (2 * gh - 1) * (2 * gw - 1)) * 0.2
+            self.register_buffer("rel_bias", table[:, dy * (2 * gw - 1) + dx].unsqueeze(0).contiguous())
+        else:
+            self.rel_bias = None
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.LayerNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, x):
+        x = self.embed(x).flatten(2).transpose(1, 2) + self.pos
+        for blk in self.blocks:
+            x = blk(x, self.rel_bias)
+        return self.head(self.norm(x).mean(1))

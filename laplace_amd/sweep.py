@@ -43,6 +43,9 @@ CONV, LINEAR, BN, ACT, IDENTITY, RESHAPE, GPOOL, AVGPOOL, MAXPOOL, MEAN, ADD, SI
 SPLIT, SLICE = "split", "slice"
 # MUL: the element-wise product of two tensors of the graph (gates, GLU); a product with a Python number is refused
 MUL = "product"
+# MATMUL: the batched matrix product of two tensors of the graph (``@``, ``torch.matmul``, ``bmm``); SOFTMAX: softmax / log-softmax
+# along one static non-batch dim; SCALE: division by a Python number (the ``/ math.sqrt(d)`` of hand-written attention)
+MATMUL, SOFTMAX, SCALE = "matrix-product", "softmax", "scale"
 
 
 class Rule(NamedTuple):
@@ -79,7 +82,8 @@ _MODULE_KINDS = (
     ((nn.GroupNorm, nn.LayerNorm), NORM, None),
     ((nn.ReLU,), ACT, "relu"), ((nn.Tanh,), ACT, "tanh"), ((nn.Sigmoid,), ACT, "sigmoid"),
     (_GENERIC_ACT_MODULES, ACT, "generic"), ((nn.Identity, nn.Dropout), IDENTITY, None), ((nn.Flatten,), RESHAPE, None),
-    ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None))
+    ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None),
+    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None))
 _FUNCTION_KINDS = {
     torch.relu: (ACT, "relu"), F.relu: (ACT, "relu"), torch.tanh: (ACT, "tanh"), F.tanh: (ACT, "tanh"),
     torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
@@ -89,13 +93,20 @@ _FUNCTION_KINDS = {
     torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None),
     torch.cat: (CAT, None), torch.concat: (CAT, None), torch.concatenate: (CAT, None),
     torch.chunk: (SPLIT, None), torch.split: (SPLIT, None), torch.narrow: (SLICE, None),
-    operator.mul: (MUL, None), torch.mul: (MUL, None), torch.multiply: (MUL, None), operator.imul: (MUL, None)}
+    operator.mul: (MUL, None), torch.mul: (MUL, None), torch.multiply: (MUL, None), operator.imul: (MUL, None),
+    torch.matmul: (MATMUL, None), operator.matmul: (MATMUL, None), torch.bmm: (MATMUL, None),
+    F.softmax: (SOFTMAX, None), torch.softmax: (SOFTMAX, None), F.log_softmax: (SOFTMAX, None), torch.log_softmax: (SOFTMAX, None),
+    operator.truediv: (SCALE, None), operator.itruediv: (SCALE, None), torch.div: (SCALE, None), torch.true_divide: (SCALE, None)}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
     "size": (SIZE, None), "transpose": (PERMUTE, None), "permute": (PERMUTE, None),
     "chunk": (SPLIT, None), "split": (SPLIT, None), "narrow": (SLICE, None), "expand": (CONST, None), "expand_as": (CONST, None),
-    "mul": (MUL, None), "multiply": (MUL, None), "mul_": (MUL, None)}
+    "mul": (MUL, None), "multiply": (MUL, None), "mul_": (MUL, None),
+    "matmul": (MATMUL, None), "bmm": (MATMUL, None), "softmax": (SOFTMAX, None), "log_softmax": (SOFTMAX, None),
+    "div": (SCALE, None), "true_divide": (SCALE, None), "div_": (SCALE, None), "true_divide_": (SCALE, None)}
+# relatives of the matrix product that have no rule: refused by name
+_NO_MATMUL_RULE = {torch.einsum: "einsum", torch.baddbmm: "baddbmm", "baddbmm": "baddbmm"}
 # relatives of the slicing rules that have none: refused by name
 _NO_SLICE_RULE = {torch.unbind: "unbind", torch.tensor_split: "tensor_split", torch.stack: "stack", "unbind": "unbind",
                   "tensor_split": "tensor_split"}
@@ -394,8 +405,83 @@ def mul_form(sa, sb):
     raise SweepUnsupported(f"mul of {sa} and {sb}: the traced operands must have equal shapes, or one must be a gate of trailing ones")
 
 
+def _classify_matmul(node, modules):
+    """the two operands of a matrix product (``@``, ``torch.matmul`` / ``bmm``, the methods): each a traced tensor or a constant of
+    the sweep, at least one traced, or the refusal that names the reason (every message holds ``matmul``); the shapes are resolved
+    on the forward values (`SeedBatchedSweep._run_matmul`)"""
+    if node.kwargs.get("out") is not None:
+        raise SweepUnsupported("matmul with an out= argument (the sweep keeps its own values)")
+    if node.kwargs or len(node.args) != 2:
+        raise SweepUnsupported(f"matmul: expected two positional operands, got {len(node.args)} and the keywords {sorted(node.kwargs)}")
+    for t in node.args:
+        if not isinstance(t, fx.Node):
+            raise SweepUnsupported(f"matmul: an operand is not a tensor of the graph ({type(t).__name__})")
+    if all(classify(t, modules).kind == CONST for t in node.args):
+        raise SweepUnsupported("matmul of two constants (at least one operand must be a traced tensor)")
+    return tuple(node.args)
+
+
+def _classify_softmax(node, m, what):
+    """``(src, (dim as written, is_log))`` of a softmax / log-softmax (functions, methods, ``nn.Softmax`` / ``nn.LogSoftmax``) with
+    one static dim, or the refusal that names the reason (every message holds ``softmax``)"""
+    name = type(m).__name__ if m is not None else str(getattr(node.target, "__name__", node.target))
+    is_log = "log" in name.lower()
+    name = "log_softmax" if is_log else "softmax"
+    if m is not None:
+        dim, dtype = m.dim, None
+    else:
+        kwargs = dict(node.kwargs)
+        kwargs.pop("input", None), kwargs.pop("_stacklevel", None)
+        rest = list(node.args[1:])
+        dim = rest.pop(0) if rest else kwargs.pop("dim", None)
+        if node.target in (F.softmax, F.log_softmax) and rest:  # (the functional form: input, dim, _stacklevel, dtype)
+            rest.pop(0)
+        dtype = rest.pop(0) if rest else kwargs.pop("dtype", None)
+        if rest or kwargs:
+            raise SweepUnsupported(f"{name}: unknown argument {sorted(kwargs) or rest}")
+    if dtype is not None:
+        raise SweepUnsupported(f"{name} with dtype= (the sweep keeps the dtype of the traced value)")
+    if isinstance(dim, fx.Node) or torch.is_tensor(dim):
+        raise SweepUnsupported(f"{name} with a data-dependent dim")
+    if dim is None:
+        raise SweepUnsupported(f"{name} without a dim (the implicit-dim legacy picks one from the number of dims: name it)")
+    if isinstance(dim, bool) or not isinstance(dim, int):
+        raise SweepUnsupported(f"{name}: dim must be a static integer, got {type(dim).__name__}")
+    if dim == 0:
+        raise SweepUnsupported(f"{name} along {_BATCH_SLICE}")
+    if not (node.args and isinstance(node.args[0], fx.Node)):
+        raise SweepUnsupported(f"{name}: the tensor must be the first positional argument and a traced tensor")
+    return (node.args[0],), (int(dim), is_log), name
+
+
+def _classify_scale(node, modules):
+    """``(src, (divisor,))`` of a division by a Python number (``/``, ``torch.div`` / ``true_divide``, the methods, ``/=`` /
+    ``div_``), or the refusal that names the reason (every message holds ``div``)"""
+    kwargs = dict(node.kwargs)
+    if kwargs.pop("rounding_mode", None) is not None:
+        raise SweepUnsupported("div with a rounding_mode (floor and trunc have no derivative to sweep)")
+    if kwargs.pop("out", None) is not None:
+        raise SweepUnsupported("div with an out= argument (the sweep keeps its own values)")
+    if kwargs or len(node.args) != 2:
+        raise SweepUnsupported(f"div: expected two positional operands, got {len(node.args)} and the keywords {sorted(kwargs)}")
+    x, c = node.args
+    if not isinstance(x, fx.Node):
+        raise SweepUnsupported(f"div of the number {x!r} by a tensor (number / tensor needs the quotient rule: out of scope)")
+    if isinstance(c, fx.Node):
+        if classify(c, modules).kind in (SIZE, GETITEM):
+            raise SweepUnsupported(f"div by the traced value {c.name} (the divisor must be a Python number when the graph is traced)")
+        raise SweepUnsupported(f"div of the tensor {x.name} by the tensor {c.name} (tensor / tensor needs the quotient rule: out of scope)")
+    if isinstance(c, (bool, complex)) or not isinstance(c, (int, float)):
+        raise SweepUnsupported(f"div by a {type(c).__name__} (the divisor must be a Python int or float)")
+    return (x,), (c,)
+
+
 def _no_slice_rule(target):
-    """what a refusal adds for a relative of the slicing rules (``unbind``, ``tensor_split``, ``stack``)"""
+    """what a refusal adds for a relative of the slicing rules (``unbind``, ``tensor_split``, ``stack``) or of the matrix product
+    (``einsum``, ``baddbmm``)"""
+    name = _NO_MATMUL_RULE.get(target)
+    if name is not None:
+        return f" ({name} is out of scope: matmul, @ and bmm are what the sweep serves)"
     name = _NO_SLICE_RULE.get(target)
     if name is None:
         return ""
@@ -494,6 +580,15 @@ def classify(node: fx.Node, modules: dict) -> Rule:
         src = _classify_mul(node, modules)
         if fn is operator.imul or node.target == "mul_":  # (`*=` / `mul_` must not write into a kept tensor)
             fn = operator.mul
+    elif kind == MATMUL:
+        src = _classify_matmul(node, modules)
+        fn, what = torch.matmul, "matmul"  # (one spelling)
+    elif kind == SOFTMAX:
+        src, static, what = _classify_softmax(node, m, what)
+        fn, args, kwargs = (torch.log_softmax if static[1] else torch.softmax), src, {}
+    elif kind == SCALE:
+        src, static = _classify_scale(node, modules)
+        fn, args, kwargs, what = operator.truediv, (src[0], static[0]), {}, "div"  # (`/=` / `div_` must not write into a kept tensor)
     return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
 
 
@@ -608,6 +703,43 @@ def attn_vjp_math(go, q, k, v, o, p, S, scale, max_bytes=None):
     dq *= scale
     dk *= scale
     return dq.reshape(S * B, H, T, D), dk.reshape(S * B, H, T, D), dv.reshape(S * B, H, T, D)
+
+
+def matmul_vjp_math(g, a, b, S, want=(True, True), max_bytes=None):
+    """``(da, db)`` of ``out = a @ b`` for the ``S`` seeds stacked in ``g`` ``[S*B, *, M, N]`` from ONE ``a`` ``[B, *, M, K]`` and ``b``
+    ``[B, *, K, N]`` per sample - the formula of lk_matmul_vjp_f32 in plain torch (any dtype): ``da = g b^T``, ``db = a^T g``.
+    ``max_bytes``: the seeds go through in chunks whose broadcast operands (torch expands ``b`` / ``a`` once per seed) stay below it."""
+    gv = g.reshape(S, *a.shape[:-2], a.shape[-2], b.shape[-1])
+    per_seed = max(a.numel() + b.numel(), 1) * g.element_size()
+    chunk = S if max_bytes is None else max(1, min(S, int(max_bytes) // per_seed))
+    da = g.new_empty(S, *a.shape) if want[0] else None
+    db = g.new_empty(S, *b.shape) if want[1] else None
+    at, bt = a.transpose(-1, -2), b.transpose(-1, -2)
+    for s0 in range(0, S, chunk):
+        if want[0]:
+            torch.matmul(gv[s0:s0 + chunk], bt, out=da[s0:s0 + chunk])
+        if want[1]:
+            torch.matmul(at, gv[s0:s0 + chunk], out=db[s0:s0 + chunk])
+    return (None if da is None else da.reshape(S * a.shape[0], *a.shape[1:]),
+            None if db is None else db.reshape(S * b.shape[0], *b.shape[1:]))
+
+
+def softmax_vjp_math(g, y, S, dim, is_log=False, max_bytes=None):
+    """``dx`` for the ``S`` seeds stacked in ``g`` ``[S*B, ...]`` from ONE output ``y`` ``[B, ...]`` per sample - the formula of
+    lk_softmax_vjp_f32 in plain torch (any dtype, any non-batch ``dim`` of ``y``): ``y * (g - sum(g y))``, or
+    ``g - exp(y) sum(g)`` for a log-softmax.  ``max_bytes``: the seeds go through in chunks whose two temporaries stay below it."""
+    gv = g.reshape(S, *y.shape)
+    per_seed = 2 * max(y.numel(), 1) * g.element_size()
+    chunk = S if max_bytes is None else max(1, min(S, int(max_bytes) // per_seed))
+    dx = g.new_empty(S, *y.shape)
+    p = torch.exp(y) if is_log else y
+    for s0 in range(0, S, chunk):
+        gc = gv[s0:s0 + chunk]
+        if is_log:
+            dx[s0:s0 + chunk] = gc - p * gc.sum(dim + 1, keepdim=True)
+        else:
+            dx[s0:s0 + chunk] = p * (gc - (gc * p).sum(dim + 1, keepdim=True))
+    return dx.reshape(g.shape)
 
 
 class SeedBatchedSweep:
@@ -736,6 +868,16 @@ class SeedBatchedSweep:
             elif kind == MUL:
                 out, keep = self._run_mul(r, args)
                 keep = keep if need_vjp else None
+            elif kind == MATMUL:
+                out, keep = self._run_matmul(r, args)
+                keep = keep if need_vjp else None
+            elif kind == SOFTMAX:
+                out, keep = self._run_softmax(r, inp)
+                keep = keep if need_vjp else None
+            elif kind == SCALE:
+                if not torch.is_tensor(inp):
+                    raise SweepUnsupported(f"div: the dividend is not a tensor ({type(inp).__name__})")
+                out = inp / r.args[0]
             elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
                 out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
@@ -995,6 +1137,100 @@ class SeedBatchedSweep:
             db = db.sum(tuple(range(k + 1, gv.dim())), keepdim=True).reshape(S * b.shape[0], *b.shape[1:]) if row else db.reshape(g.shape)
         return da, db
 
+    #: ``False``: the VJP of a matrix product stays on the torch math of its rule (`matmul_vjp_math`) whatever the kernel object offers
+    use_matmul_kernels = True
+    #: ``False``: the VJP of a softmax stays on the torch math of its rule (`softmax_vjp_math`) whatever the kernel object offers
+    use_softmax_kernels = True
+
+    def _matmul_kernels(self, g, a, b):
+        """the kernel object when csrc/lk_matmul.hip serves the VJP of ``a @ b`` (an object with the entry point - the stock
+        emulation has none -, fp32, a shape inside the kernel's contract), else ``None``: the same formula in torch"""
+        K = self.kernels() if self.kernels is not None and self.use_matmul_kernels else None
+        if K is None or not hasattr(K, "matmul_vjp") or not all(t.dtype == torch.float32 for t in (g, a, b)):
+            return None
+        M, Kd, N = int(a.shape[-2]), int(a.shape[-1]), int(b.shape[-1])
+        if min(M, Kd, N) < 1 or a.numel() == 0:
+            return None
+        S = g.numel() // max(a.numel() // Kd * N, 1)
+        return K if K.matmul_vjp_variant(S, a.numel() // (M * Kd), M, Kd, N) is not None else None
+
+    def _run_matmul(self, r, args):
+        """matrix product forward -> ``(out, (form, a, b, gate))``: both operands belong to the sample, not to the seed.  ``form``:
+        ``"const"`` (operand ``gate`` is a constant - 2-D, or with the other's leading dims or ones there - and receives nothing)
+        or ``"full"`` (two traced ``[B, *, M, K] @ [B, *, K, N]`` with equal leading dims)"""
+        a, b = args
+        if not (torch.is_tensor(a) and torch.is_tensor(b)):
+            raise SweepUnsupported(f"matmul: an operand is not a tensor ({type(a).__name__} @ {type(b).__name__})")
+        const = [self.rule[n].kind == CONST for n in r.src]
+        form, gate = ("const", const.index(True)) if any(const) else ("full", None)
+        t = b if gate == 0 else a  # (a traced operand)
+        if t.dim() < 3 or (form == "full" and b.dim() < 3):
+            raise SweepUnsupported(f"matmul of {tuple(a.shape)} and {tuple(b.shape)}: a traced operand must be [B, *, rows, columns] "
+                                   "with at least three dims (a 1-D or 2-D one mixes the batch into the product: the VJP needs a reduction)")
+        if form == "const":
+            c = a if gate == 0 else b
+            lead = tuple(c.shape[:-2])
+            if c.dim() < 2 or (c.dim() > 2 and (c.dim() != t.dim() or any(d not in (1, e) for d, e in zip(lead, t.shape[:-2])))):
+                raise SweepUnsupported(f"matmul: the {self.rule[r.src[gate]].what} of shape {tuple(c.shape)} must be 2-D or have the leading "
+                                       f"dims of the other operand {tuple(t.shape)} (or ones there)")
+        elif a.dim() != b.dim() or a.shape[:-2] != b.shape[:-2]:
+            raise SweepUnsupported(f"matmul of {tuple(a.shape)} and {tuple(b.shape)}: the leading dims of two traced operands must be "
+                                   "equal (where they broadcast the VJP needs a reduction)")
+        try:
+            out = torch.matmul(a, b)
+        except RuntimeError as e:  # (inner dims that do not fit: torch's own words)
+            raise SweepUnsupported(f"matmul of {tuple(a.shape)} and {tuple(b.shape)}: {e}") from e
+        return out, (form, a, b, gate)
+
+    def _matmul_vjp(self, saved, g, S, want):
+        """``(d first, d second)`` of a matrix product for all seeds, ``g`` ``[S*B, *, M, N]``: ``d first = g second^T`` and
+        ``d second = first^T g`` from ONE pair of operands per sample; an operand that is not in ``want`` gets ``None``.  One launch
+        of lk_matmul_vjp_f32's kernel per output on ``g`` as it lies (the per-sample operands are made contiguous, 1/S of the
+        work), or the same formula in torch (`matmul_vjp_math`); a constant operand is a plain torch product."""
+        form, a, b, gate = saved
+        if form == "const":
+            t = b if gate == 0 else a
+            gv = g.reshape(S, t.shape[0], *g.shape[1:])
+            if gate == 0:  # (constant @ traced)
+                d = (a.transpose(-1, -2) @ gv).reshape(S * t.shape[0], *t.shape[1:]) if want[1] else None
+                return None, d
+            d = (gv @ b.transpose(-1, -2)).reshape(S * t.shape[0], *t.shape[1:]) if want[0] else None
+            return d, None
+        K = self._matmul_kernels(g, a, b)
+        if K is not None:
+            return K.matmul_vjp(g.contiguous(), a.contiguous(), b.contiguous(), S, want)
+        return matmul_vjp_math(g, a, b, S, want, self.attn_mem_bytes)
+
+    def _softmax_kernels(self, g, y, dim):
+        """the kernel object when csrc/lk_softmax.hip serves the VJP of a softmax along ``dim`` of ``y`` (an object with the entry
+        point, fp32, the last dim, a shape inside the contract), else ``None``: the same formula in torch"""
+        K = self.kernels() if self.kernels is not None and self.use_softmax_kernels else None
+        if K is None or not hasattr(K, "softmax_vjp") or g.dtype != torch.float32 or y.dtype != torch.float32:
+            return None
+        if dim != y.dim() - 1 or y.numel() == 0:
+            return None
+        L = int(y.shape[-1])
+        return K if K.softmax_vjp_variant(g.numel() // y.numel(), y.numel() // L, L) is not None else None
+
+    def _run_softmax(self, r, inp):
+        """softmax / log-softmax forward (torch's own, on the ``B`` samples) -> ``(y, (y, dim, is_log))``: the output is what the
+        VJP needs, one per sample for all seeds"""
+        dim, is_log = r.args
+        if not torch.is_tensor(inp):
+            raise SweepUnsupported(f"{r.what}: the input is not a tensor")
+        dim = cat_dim(dim, inp.dim(), r.what)
+        y = r.fn(inp, dim)
+        return y, (y, dim, is_log)
+
+    def _softmax_vjp(self, saved, g, S):
+        """input cotangent of a softmax / log-softmax for all seeds, ``g`` ``[S*B, ...]``: ONE launch of lk_softmax_vjp_f32 when the
+        dim is the last one, or the same formula in torch (`softmax_vjp_math`, any dim)"""
+        y, dim, is_log = saved
+        K = self._softmax_kernels(g, y, dim)
+        if K is not None:
+            return K.softmax_vjp(g.contiguous(), y.contiguous(), S, is_log)
+        return softmax_vjp_math(g, y, S, dim, is_log, self.attn_mem_bytes)
+
     def _add_const(self, r, args, kwargs):
         """``x + constant``: the constant must broadcast to exactly the other operand's shape (the other way round the VJP is
         a reduction, which has no rule)"""
@@ -1246,6 +1482,15 @@ class SeedBatchedSweep:
                 if any(want):
                     for a, d in zip(r.src, self._mul_vjp(self.saved[node], g, S, want)):  # (`x * x`: x receives two parts)
                         push(a, d)
+            elif kind == MATMUL:
+                want = tuple(n.op != "placeholder" and self.rule[n].kind != CONST for n in r.src)
+                if any(want):
+                    for a, d in zip(r.src, self._matmul_vjp(self.saved[node], g, S, want)):  # (`x @ x^T`: x receives two parts)
+                        push(a, d)
+            elif kind == SOFTMAX:
+                push(src, self._softmax_vjp(self.saved[node], g, S))
+            elif kind == SCALE:
+                push(src, g / r.args[0])
             elif kind == CAT:
                 dim, sizes = self.saved[node]
                 off = 0

@@ -35,8 +35,8 @@ from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
-from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MAXPOOL, MEAN, MUL, NORM, PERMUTE, RESHAPE,
-                               SIZE, SLICE, SPLIT, SeedBatchedSweep, SweepUnsupported)
+from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MATMUL, MAXPOOL, MEAN, MUL, NORM, PERMUTE,
+                               RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SeedBatchedSweep, SweepUnsupported)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
@@ -47,7 +47,7 @@ SLICE_MAP = "channel slice of a feature map"  # what `_walk` reports for a SLICE
 _POOL = {MAXPOOL, AVGPOOL}  # spatial pooling: fp32 NHWC in, fp32 NHWC out (lk_pool.hip)
 _FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP, SLICE_MAP} | _POOL  # produce / consume NHWC feature maps
 _MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, SLICE_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
-_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL}  # a graph with one of these runs through the NCHW sweep
+_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE}  # a graph with one of these runs through the NCHW sweep
 
 
 class _F32:
@@ -175,6 +175,9 @@ class SplitSweep(SeedBatchedSweep):
                 return f"{node.name}: {r.what} has no NHWC rule"
         for node, r in self.rule.items():
             if r.kind == MUL:  # (named before the narrow 1x1 convolutions of a gate branch, which only exist because of it)
+                return f"{r.what} has no NHWC rule"
+        for node, r in self.rule.items():
+            if r.kind in (MATMUL, SOFTMAX, SCALE):  # (hand-written attention: named before the transposes around it)
                 return f"{r.what} has no NHWC rule"
         for name in sorted(self.tap_names):
             m = self.modules.get(name)
