@@ -486,6 +486,34 @@ int lk_norm_vjp_f32(const float* g, const float* xhat, const float* rstd, const 
                     int64_t Ch, int64_t G, int layout, float* dx, unsigned* amax, void* stream);
 int lk_norm_sweep_variant(int64_t S, int64_t B, int64_t L, int64_t Ch, int64_t G, int layout, int aligned);
 
+/* Forward and input VJP of nn.RMSNorm (the pre-norm of LLaMA / Mistral / Gemma / T5 blocks) for the seed-batched reverse
+ * sweep; they replace the reverse passes through this layer of laplace/curvature/curvlinops.py:87-100 (the KFAC backward)
+ * and of the jacrev materialisation of CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129 (one stock
+ * autograd pass per seed).  x is [rows][D]: rows = product of the leading dims, D = prod(normalized_shape).
+ *
+ * lk_rmsnorm_fwd_f32: r = 1 / sqrt(mean_row(x^2) + eps) with the mean of squares in fp32 and no subtraction anywhere;
+ *   y = w[d] * (x * r); w may be null.  Writes y and rstd [rows] only: xhat = x * rstd is one multiply away from the input, so
+ *   no activation-sized xhat is stored.
+ * lk_rmsnorm_vjp_f32: g is [S][rows][D] (ONE x and rstd per row for all seeds):
+ *   t = w * g;  xh = x * rstd;  m2 = mean_row(t * xh);  dx = rstd * (t - xh * m2)          (there is no mean_row(t) term)
+ *   w may be null.  amax, when given, receives max|dx| as the bit pattern of a non-negative float through atomicMax (as
+ *   lk_norm_vjp_f32); the caller zeroes it.  dx must not overlap g.  Deterministic: one owner per element, a fixed xor-shuffle
+ *   tree per row, plain vector stores, no atomics on data.  Minimal traffic: 4 (2 S + 1) rows D bytes.
+ * Contract of both: x, y / g, dx and rstd non-null; 1 <= S < 2^31, 0 <= rows < 2^31, 1 <= D < 2^30, S * rows * D < 2^40 (the
+ *   forward has S = 1); rows == 0 returns LK_OK.
+ * lk_rmsnorm_variant (host only): the path lk_rmsnorm_vjp_f32 takes for a shape; `aligned`: g, x, dx and w are 16-byte
+ * aligned.  Returns
+ *   vec | two-pass << 1 | seed-split << 2 | log2(lanes) << 3 | min(seeds per slice, 2^24 - 1) << 6
+ *   vec: 16-byte loads and stores (D % 4 == 0 and aligned), else 4-byte ones; two-pass: the row does not stay in registers
+ *   (more than 8 vectors per lane), g is read twice; seed-split: the seeds are split over grid.y; lanes: a group of 1 .. 64
+ *   lanes owns a row; seeds per slice: how many seeds one workgroup loops over
+ * or a negative value for a shape the entry points refuse. */
+int lk_rmsnorm_fwd_f32(const float* x, const float* w, int64_t rows, int64_t D, float eps, float* y, float* rstd,
+                       void* stream);
+int lk_rmsnorm_vjp_f32(const float* g, const float* x, const float* rstd, const float* w, int64_t S, int64_t rows, int64_t D,
+                       float* dx, unsigned* amax, void* stream);
+int lk_rmsnorm_variant(int64_t S, int64_t rows, int64_t D, int aligned);
+
 /* Scaled dot-product self-attention (F.scaled_dot_product_attention without mask tensor or dropout, Tq == Tk) for the
  * seed-batched reverse sweep; they replace the reverse passes through an attention core of
  * laplace/curvature/curvlinops.py:87-100 (the KFAC backward) and of the jacrev materialisation of

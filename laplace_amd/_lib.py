@@ -117,6 +117,9 @@ SIGNATURES = {
     "lk_norm_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp]),
     "lk_norm_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_norm_sweep_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
+    "lk_rmsnorm_fwd_f32": (_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp]),
+    "lk_rmsnorm_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "lk_rmsnorm_variant": (_int, [_i64, _i64, _i64, _int]),
     "lk_attn_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp]),
     "lk_attn_vjp_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "lk_attn_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp, _vp,
@@ -1342,6 +1345,57 @@ class HipKernels:
             return None
         return {"kernel": r & 1, "vec": bool(r & 2), "two_pass": bool(r & 4), "seed_split": bool(r & 8), "lanes": (r >> 4) & 0xFFF,
                 "groups": r >> 16, "layout": int(layout)}
+
+    def rmsnorm_forward(self, x2d, w, eps):
+        """``(y, rstd)`` of nn.RMSNorm on ``x2d`` ``[rows, D]`` (csrc/lk_rmsnorm.hip): ``rstd = 1 / sqrt(mean_row(x^2) + eps)``
+        ``[rows]``, ``y = w * x * rstd`` (``w`` ``[D]`` or None).  No ``xhat`` is stored: the VJP forms it from ``x`` and ``rstd``."""
+        _check(x2d, "x")
+        if x2d.dim() != 2 or x2d.shape[1] < 1:
+            raise LaplaceHipError("rmsnorm_forward: x must be [rows, D] with D >= 1")
+        rows, D = int(x2d.shape[0]), int(x2d.shape[1])
+        if w is not None:
+            _check(w, "w")
+            if w.numel() != D:
+                raise LaplaceHipError(f"rmsnorm_forward: w must have {D} elements")
+        y = torch.empty_like(x2d)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x2d.device)
+        if rows == 0:  # (an empty tensor has no address to hand over)
+            return y, rstd
+        self._rc(self.lib.lk_rmsnorm_fwd_f32(_ptr(x2d), _ptr(w), rows, D, float(eps), _ptr(y), _ptr(rstd),
+                                             self._stream(x2d.device)), "lk_rmsnorm_fwd_f32")
+        return y, rstd
+
+    def rmsnorm_vjp(self, g, x2d, rstd, w, S, amax=None):
+        """``dx`` of nn.RMSNorm for the ``S`` seeds stacked in ``g`` (``[S*rows, D]``, ``x2d`` ``[rows, D]``): ``t = w * g``,
+        ``xh = x * rstd``, ``dx = rstd * (t - xh * mean_row(t * xh))``.  ``amax``: zeroed device word that receives the bit
+        pattern of max|dx|."""
+        _check(g, "g"), _check(x2d, "x"), _check(rstd, "rstd")
+        if x2d.dim() != 2 or x2d.shape[1] < 1:
+            raise LaplaceHipError("rmsnorm_vjp: x must be [rows, D] with D >= 1")
+        rows, D = int(x2d.shape[0]), int(x2d.shape[1])
+        if g.numel() != int(S) * x2d.numel() or rstd.numel() != rows:
+            raise LaplaceHipError("rmsnorm_vjp: g [S*rows, D], x [rows, D] and rstd [rows] do not match")
+        if w is not None:
+            _check(w, "w")
+            if w.numel() != D:
+                raise LaplaceHipError(f"rmsnorm_vjp: w must have {D} elements")
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("rmsnorm_vjp: amax is one 32-bit device word")
+        dx = torch.empty_like(g)
+        if rows == 0:
+            return dx
+        self._rc(self.lib.lk_rmsnorm_vjp_f32(_ptr(g), _ptr(x2d), _ptr(rstd), _ptr(w), int(S), rows, D, _ptr(dx), _ptr(amax),
+                                             self._stream(g.device)), "lk_rmsnorm_vjp_f32")
+        return dx
+
+    def rmsnorm_variant(self, S, rows, D, aligned=True):
+        """lk_rmsnorm_variant: the path ``lk_rmsnorm_vjp_f32`` takes for a shape (host only, no device call), or ``None`` for a
+        shape it refuses."""
+        r = int(self.lib.lk_rmsnorm_variant(int(S), int(rows), int(D), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "two_pass": bool(r & 2), "seed_split": bool(r & 4), "lanes": 1 << ((r >> 3) & 7),
+                "seeds_per_slice": r >> 6}
 
     #: largest ``T`` whose probability block stays in LDS over the seeds (LK_ATTN_RESIDENT_MAX_T of include/laplace_hip.h)
     ATTN_RESIDENT_MAX_T = 256

@@ -694,6 +694,10 @@ class _HipCurvatureMixin:
         Ch = 1
         for d in m.normalized_shape:
             Ch *= int(d)
+        if isinstance(m, nn.RMSNorm):  # (no centring: xhat = a * rsqrt(mean(a^2) + eps) over the normalised dims; torch's eps rule)
+            eps = m.eps if m.eps is not None else torch.finfo(tap.a.dtype).eps
+            dims = tuple(range(a.dim() - len(m.normalized_shape), a.dim()))
+            return (a * torch.rsqrt((a * a).mean(dims, keepdim=True) + eps)).contiguous(), Ch, 1
         return F.layer_norm(a, m.normalized_shape, None, None, m.eps).contiguous(), Ch, 1
 
     @staticmethod

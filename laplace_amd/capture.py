@@ -19,7 +19,7 @@ from torch import nn
 
 SUPPORTED = (nn.Linear, nn.Conv2d)
 #: affine normalisation layers: their weight / bias Jacobian is a per-channel reduction of ``g * xhat`` (csrc/lk_norm.hip)
-NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm)
+NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm, nn.RMSNorm)
 
 
 @dataclass
@@ -115,7 +115,8 @@ class Tape:
         owned = set()
         for t in self.norm_taps:
             if norm_servable(t.module):
-                owned.update(id(p) for p in (t.module.weight, t.module.bias) if p is not None)
+                # (nn.RMSNorm has no bias attribute)
+                owned.update(id(p) for p in (t.module.weight, getattr(t.module, "bias", None)) if p is not None)
         return [p for p in self.uncovered if id(p) not in owned]
 
     def refuse_kfac(self):

@@ -18,6 +18,7 @@
 // vector stores, no atomics on data; `amax` receives max|dx| as the bit pattern of a non-negative float through atomicMax, which
 // is order-independent (lk_conv.hip does the same for amax_out).  Few rows: the seeds are split over grid.y.
 #include "lk_common.h"
+#include "lk_rowvec.h"  // nv_ld, nv_st, nv_wave_amax
 
 namespace lk {
 
@@ -26,35 +27,6 @@ constexpr int NVJP_NV = 8;     // vectors of a row (ROW) / positions (TILE) a la
 constexpr int NVJP_WIDE = 16;  // layout 1, L > 1: channels per group from which a lane group owns a whole row
 constexpr int NVJP_TILE_LANES = 16;  // TILE: channel vectors a workgroup aims to read per position
 constexpr int NVJP_MAX_GT = 64;      // TILE: most groups per workgroup (one channel per group, 16-byte loads)
-
-template <int VEC>
-__device__ __forceinline__ void nv_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void nv_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-
-// one atomic per wave: the lanes' maxima of |dx| (non-negative floats order like their bit patterns)
-__device__ __forceinline__ void nv_wave_amax(float m, unsigned* __restrict__ amax) {
-  unsigned b = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
-  if (amax != nullptr && (threadIdx.x & 63) == 0 && b) atomicMax(amax, b);
-}
 
 // Where the elements of a statistics row are: vector i of the row (VEC floats) is run i / cvt, vector i % cvt of that run
 struct RowGeom {

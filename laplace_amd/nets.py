@@ -634,3 +634,85 @@ class ViTEager(nn.Module):
         for blk in self.blocks:
             x = blk(x, self.rel_bias)
         return self.head(self.norm(x).mean(1))
+
+
+def rope_tables(T: int, d: int, base: float = 10000.0):
+    """``(cos, sin)``, each ``[T, d]``, of a rotary position embedding in the rotate-half convention (LLaMA, GPT-NeoX): the angle
+    of position ``t`` and channel pair ``(i, i + d / 2)`` is ``t * base ** (-2 i / d)``"""
+    if d % 2:
+        raise ValueError(f"rotary embeddings need an even head dim, got {d}")
+    inv = base ** (-torch.arange(0, d, 2, dtype=torch.float32) / d)
+    ang = torch.arange(T, dtype=torch.float32).unsqueeze(1) * inv.unsqueeze(0)
+    ang = torch.cat((ang, ang), -1)
+    return ang.cos(), ang.sin()
+
+
+class LlamaBlock(nn.Module):
+    """The block of LLaMA / Mistral / Gemma: RMSNorm pre-norms, rotary position embeddings on ``q`` and ``k``, causal
+    ``scaled_dot_product_attention`` and the SwiGLU feed-forward of :class:`SwiGLUBlock`, no biases.  The rotary embedding is
+    written the usual way, ``x * cos + cat((-x[..., half:], x[..., :half]), -1) * sin`` with non-persistent ``cos`` / ``sin``
+    buffers ``[T, head_dim]``: the seed-batched sweep serves it with its slice, negation, concatenation, product and add rules, the
+    norms with csrc/lk_rmsnorm.hip."""
+
+    def __init__(self, dim: int, heads: int, T: int, mlp_ratio: float = 8.0 / 3.0, causal: bool = True, eps: float | None = 1e-6):
+        super().__init__()
+        if dim % heads:
+            raise ValueError(f"heads ({heads}) must divide dim ({dim})")
+        self.heads, self.causal, self.half = heads, causal, dim // heads // 2
+        self.norm1 = nn.RMSNorm(dim, eps=eps)
+        self.q, self.k, self.v, self.proj = (nn.Linear(dim, dim, bias=False) for _ in range(4))
+        self.norm2 = nn.RMSNorm(dim, eps=eps)
+        hidden = int(round(dim * mlp_ratio))
+        self.w1, self.w3 = nn.Linear(dim, hidden, bias=False), nn.Linear(dim, hidden, bias=False)
+        self.w2 = nn.Linear(hidden, dim, bias=False)
+        cos, sin = rope_tables(T, dim // heads)
+        self.register_buffer("cos", cos, persistent=False)
+        self.register_buffer("sin", sin, persistent=False)
+
+    def rope(self, x):
+        rot = torch.cat((-x[..., self.half:], x[..., :self.half]), -1)
+        return x * self.cos + rot * self.sin
+
+    def forward(self, x):
+        B, T = x.size(0), x.size(1)
+        h = self.norm1(x)
+        q = self.rope(self.q(h).view(B, T, self.heads, -1).transpose(1, 2))
+        k = self.rope(self.k(h).view(B, T, self.heads, -1).transpose(1, 2))
+        v = self.v(h).view(B, T, self.heads, -1).transpose(1, 2)
+        a = nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
+        x = x + self.proj(a.transpose(1, 2).reshape(B, T, -1))
+        h = self.norm2(x)
+        return x + self.w2(nn.functional.silu(self.w1(h)) * self.w3(h))
+
+
+class ViTLlama(nn.Module):
+    """:class:`ViTSwiGLU` with :class:`LlamaBlock` s: the patches of the image through a ``Linear`` embedding, no positional buffer
+    (the rotary embedding of every block carries the positions), ``depth`` blocks, a final RMSNorm, the mean over the tokens and a
+    ``Linear`` head.  The defaults give ``T = 64`` tokens, head dim 64 and 512 hidden units.  ``image`` is the side of a square
+    image or ``(height, width)``.  ``freeze_norm``: the RMSNorm weights are not tracked, so that KFAC runs."""
+
+    def __init__(self, num_classes: int = 10, image=32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
+                 mlp_ratio: float = 8.0 / 3.0, freeze_norm: bool = True, causal: bool = True, eps: float | None = 1e-6):
+        super().__init__()
+        ih, iw = image if isinstance(image, (tuple, list)) else (image, image)
+        if ih % patch or iw % patch:
+            raise ValueError(f"patch ({patch}) must divide image ({image})")
+        self.patch, self.grid = patch, (ih // patch, iw // patch)
+        T = self.grid[0] * self.grid[1]
+        self.embed = nn.Linear(3 * patch * patch, dim)
+        self.blocks = nn.ModuleList(LlamaBlock(dim, heads, T, mlp_ratio, causal=causal, eps=eps) for _ in range(depth))
+        self.norm = nn.RMSNorm(dim, eps=eps)
+        self.head = nn.Linear(dim, num_classes)
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.RMSNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, x):
+        (gh, gw), p = self.grid, self.patch
+        x = x.view(x.size(0), 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(x.size(0), gh * gw, 3 * p * p)
+        x = self.embed(x)
+        for blk in self.blocks:
+            x = blk(x)
+        return self.head(self.norm(x).mean(1))

@@ -11,7 +11,8 @@ element-wise kernels per step.  This module is the "fused host-side extraction" 
 * the reverse sweep pushes a cotangent of batch ``S*B`` (seed-major) through closed-form VJP rules:
   one MIOpen backward-data call per conv for *all* seeds, one element-wise kernel per activation, one row-reduction kernel
   per GroupNorm / LayerNorm (csrc/lk_normvjp.hip: these normalise with per-sample statistics, so their VJP is a reduction per
-  statistics row that reuses one ``xhat`` / ``rstd`` per sample for all seeds).
+  statistics row that reuses one ``xhat`` / ``rstd`` per sample for all seeds; csrc/lk_rmsnorm.hip does the same for RMSNorm from
+  the layer's input and ``rstd`` alone).
 
 It produces exactly what :class:`laplace_amd.capture.Tape` produces (layer inputs ``a`` and output
 gradients ``g`` per tapped module), so everything downstream is unchanged.  Unsupported graphs
@@ -46,6 +47,9 @@ MUL = "product"
 # MATMUL: the batched matrix product of two tensors of the graph (``@``, ``torch.matmul``, ``bmm``); SOFTMAX: softmax / log-softmax
 # along one static non-batch dim; SCALE: division by a Python number (the ``/ math.sqrt(d)`` of hand-written attention)
 MATMUL, SOFTMAX, SCALE = "matrix-product", "softmax", "scale"
+# NEG: ``-x`` (the rotate-half of a rotary embedding); SUB: the difference of two tensors of the graph, or of one and a constant
+# or a Python number.  A sign has no reduction and nothing to fuse: both are torch math
+NEG, SUB = "negation", "difference"
 
 
 class Rule(NamedTuple):
@@ -79,7 +83,7 @@ _GENERIC_ACT_FN = (F.gelu, F.silu, F.leaky_relu, F.elu, F.softplus, F.hardtanh, 
 _MODULE_KINDS = (
     ((nn.Conv2d,), CONV, None), ((nn.Linear,), LINEAR, None), ((nn.BatchNorm2d, nn.BatchNorm1d), BN, None),
     # (normalisation with per-sample statistics; the functional spellings read their weights through `get_attr` and stay refused)
-    ((nn.GroupNorm, nn.LayerNorm), NORM, None),
+    ((nn.GroupNorm, nn.LayerNorm, nn.RMSNorm), NORM, None),
     ((nn.ReLU,), ACT, "relu"), ((nn.Tanh,), ACT, "tanh"), ((nn.Sigmoid,), ACT, "sigmoid"),
     (_GENERIC_ACT_MODULES, ACT, "generic"), ((nn.Identity, nn.Dropout), IDENTITY, None), ((nn.Flatten,), RESHAPE, None),
     ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None),
@@ -96,7 +100,9 @@ _FUNCTION_KINDS = {
     operator.mul: (MUL, None), torch.mul: (MUL, None), torch.multiply: (MUL, None), operator.imul: (MUL, None),
     torch.matmul: (MATMUL, None), operator.matmul: (MATMUL, None), torch.bmm: (MATMUL, None),
     F.softmax: (SOFTMAX, None), torch.softmax: (SOFTMAX, None), F.log_softmax: (SOFTMAX, None), torch.log_softmax: (SOFTMAX, None),
-    operator.truediv: (SCALE, None), operator.itruediv: (SCALE, None), torch.div: (SCALE, None), torch.true_divide: (SCALE, None)}
+    operator.truediv: (SCALE, None), operator.itruediv: (SCALE, None), torch.div: (SCALE, None), torch.true_divide: (SCALE, None),
+    operator.neg: (NEG, None), torch.neg: (NEG, None), torch.negative: (NEG, None),
+    operator.sub: (SUB, None), operator.isub: (SUB, None), torch.sub: (SUB, None), torch.subtract: (SUB, None)}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
@@ -104,7 +110,9 @@ _METHOD_KINDS = {
     "chunk": (SPLIT, None), "split": (SPLIT, None), "narrow": (SLICE, None), "expand": (CONST, None), "expand_as": (CONST, None),
     "mul": (MUL, None), "multiply": (MUL, None), "mul_": (MUL, None),
     "matmul": (MATMUL, None), "bmm": (MATMUL, None), "softmax": (SOFTMAX, None), "log_softmax": (SOFTMAX, None),
-    "div": (SCALE, None), "true_divide": (SCALE, None), "div_": (SCALE, None), "true_divide_": (SCALE, None)}
+    "div": (SCALE, None), "true_divide": (SCALE, None), "div_": (SCALE, None), "true_divide_": (SCALE, None),
+    "neg": (NEG, None), "negative": (NEG, None), "neg_": (NEG, None),
+    "sub": (SUB, None), "subtract": (SUB, None), "sub_": (SUB, None)}
 # relatives of the matrix product that have no rule: refused by name
 _NO_MATMUL_RULE = {torch.einsum: "einsum", torch.baddbmm: "baddbmm", "baddbmm": "baddbmm"}
 # relatives of the slicing rules that have none: refused by name
@@ -476,6 +484,41 @@ def _classify_scale(node, modules):
     return (x,), (c,)
 
 
+def _classify_neg(node):
+    """the operand of a negation (``-x``, ``torch.neg`` / ``negative``, the methods, ``neg_``), or the refusal that names the
+    reason (every message holds ``neg``)"""
+    if node.kwargs.get("out") is not None:
+        raise SweepUnsupported("neg with an out= argument (the sweep keeps its own values)")
+    x = node.args[0] if node.args else node.kwargs.get("input")
+    if len(node.args) > 1 or set(node.kwargs) - {"input", "out"} or not isinstance(x, fx.Node):
+        raise SweepUnsupported("neg: expected one operand, a tensor of the graph")
+    return (x,)
+
+
+def _classify_sub(node, modules):
+    """the two operands of a difference (``-``, ``torch.sub`` / ``subtract``, the methods, ``-=`` / ``sub_``): each a traced tensor,
+    a constant of the sweep or a Python number, at least one a tensor that is not a constant, or the refusal that names the reason
+    (every message holds ``sub``); the shapes are resolved on the forward values (`SeedBatchedSweep._run_sub`)"""
+    kwargs = dict(node.kwargs)
+    alpha = kwargs.pop("alpha", 1)
+    if isinstance(alpha, fx.Node) or alpha != 1:
+        raise SweepUnsupported("sub with alpha != 1 (fold the factor into the layer that produces the subtrahend)")
+    if kwargs.pop("out", None) is not None:
+        raise SweepUnsupported("sub with an out= argument (the sweep keeps its own values)")
+    if kwargs or len(node.args) != 2:
+        raise SweepUnsupported(f"sub: expected two positional operands, got {len(node.args)} and the keywords {sorted(kwargs)}")
+    nodes = [t for t in node.args if isinstance(t, fx.Node)]
+    for t in node.args:
+        if not isinstance(t, fx.Node) and (isinstance(t, (bool, complex)) or not isinstance(t, (int, float))):
+            raise SweepUnsupported(f"sub: an operand is neither a tensor of the graph nor a Python int or float ({type(t).__name__})")
+    if not nodes:
+        raise SweepUnsupported("sub of two Python numbers")
+    if all(classify(t, modules).kind == CONST for t in nodes):
+        raise SweepUnsupported("sub of two constants (at least one operand must be a traced tensor)" if len(nodes) == 2 else
+                               "sub of a constant and a Python number (at least one operand must be a traced tensor)")
+    return tuple(node.args)
+
+
 def _no_slice_rule(target):
     """what a refusal adds for a relative of the slicing rules (``unbind``, ``tensor_split``, ``stack``) or of the matrix product
     (``einsum``, ``baddbmm``)"""
@@ -589,6 +632,14 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == SCALE:
         src, static = _classify_scale(node, modules)
         fn, args, kwargs, what = operator.truediv, (src[0], static[0]), {}, "div"  # (`/=` / `div_` must not write into a kept tensor)
+    elif kind == NEG:
+        src = _classify_neg(node)
+        fn, args, kwargs, what = torch.neg, src, {}, "neg"  # (`neg_` must not write into a kept tensor)
+        if classify(src[0], modules).kind == CONST:  # (`-sin` of a frozen buffer: a constant of the sweep, evaluated in the forward)
+            return Rule(CONST, (), fn, (src, {}), f"constant neg of {src[0].name}")
+    elif kind == SUB:
+        src = _classify_sub(node, modules)
+        fn, args, kwargs, what = operator.sub, src, {}, "sub"  # (`-=` / `sub_` must not write into a kept tensor)
     return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
 
 
@@ -644,6 +695,38 @@ def norm_vjp_math(g, xhat, rstd, w, S, G, layout):
     rs = rstd.reshape(rstd.shape[0], G, 1, 1) if layout == 0 else rstd.reshape(rstd.shape[0], 1, G, 1)
     dx = rs * (t - t.mean(dims, keepdim=True) - xr * (t * xr).mean(dims, keepdim=True))
     return dx.reshape(g.shape)
+
+
+def rmsnorm_geometry(m, inp):
+    """``(rows, D, eps)`` of an nn.RMSNorm on ``inp`` in the convention of csrc/lk_rmsnorm.hip: ``D = prod(normalized_shape)``,
+    ``rows`` the product of the leading dims; ``eps`` is the module's, or torch's default for the input's dtype"""
+    D = 1
+    for d in m.normalized_shape:
+        D *= int(d)
+    if tuple(inp.shape[inp.dim() - len(m.normalized_shape):]) != tuple(m.normalized_shape) or inp.dim() < len(m.normalized_shape):
+        raise SweepUnsupported(f"RMSNorm({tuple(m.normalized_shape)}) on an input of shape {tuple(inp.shape)}")
+    return inp.numel() // max(D, 1), D, float(m.eps) if m.eps is not None else torch.finfo(inp.dtype).eps
+
+
+def rmsnorm_forward_math(x, w, eps):
+    """``(y, rstd)`` of csrc/lk_rmsnorm.hip's forward in plain torch (any dtype): ``x`` is ``[rows, D]``,
+    ``rstd = 1 / sqrt(mean_row(x^2) + eps)`` ``[rows]``, ``y = w * (x * rstd)`` (a tensor of its own: ``x`` is kept for the VJP)"""
+    rstd = 1.0 / torch.sqrt((x * x).mean(-1) + eps)
+    y = x * rstd.unsqueeze(-1)
+    if w is not None:
+        y = y * w.detach().reshape(-1)
+    return y, rstd
+
+
+def rmsnorm_vjp_math(g, x, rstd, w, S):
+    """``dx = rstd * (t - xh * mean_row(t * xh))``, ``t = w * g``, ``xh = x * rstd``, for the ``S`` seeds stacked in ``g``
+    (``[S*rows, D]``, ``x`` ``[rows, D]``) - the formula of lk_rmsnorm_vjp_f32 in plain torch"""
+    t = g.reshape(S, *x.shape)
+    if w is not None:
+        t = t * w.detach().reshape(-1)
+    rs = rstd.unsqueeze(-1)
+    xh = x * rs
+    return (rs * (t - xh * (t * xh).mean(-1, keepdim=True))).reshape(g.shape)
 
 
 def attn_layout(t):
@@ -878,6 +961,12 @@ class SeedBatchedSweep:
                 if not torch.is_tensor(inp):
                     raise SweepUnsupported(f"div: the dividend is not a tensor ({type(inp).__name__})")
                 out = inp / r.args[0]
+            elif kind == NEG:
+                if not torch.is_tensor(inp):
+                    raise SweepUnsupported(f"neg: the operand is not a tensor ({type(inp).__name__})")
+                out = torch.neg(inp)
+            elif kind == SUB:
+                out = self._run_sub(r, args)
             elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
                 out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
@@ -1013,9 +1102,68 @@ class SeedBatchedSweep:
         K = self.kernels() if self.kernels is not None else None
         return K if K is not None and hasattr(K, "norm_forward") and t.dtype == torch.float32 else None
 
+    #: ``False``: nn.RMSNorm stays on the torch math of its rule (`rmsnorm_forward_math`, `rmsnorm_vjp_math`) whatever the kernel
+    #: object offers
+    use_rmsnorm_kernels = True
+
+    def _rmsnorm_kernels(self, t, S, rows, D):
+        """the kernel object when csrc/lk_rmsnorm.hip serves an nn.RMSNorm on ``t`` (an object with the entry points - the stock
+        emulation has none -, fp32, a shape inside the contract), else ``None``: the same formulas in torch"""
+        K = self.kernels() if self.kernels is not None and self.use_rmsnorm_kernels else None
+        if K is None or not hasattr(K, "rmsnorm_forward") or t.dtype != torch.float32 or rows == 0:
+            return None
+        return K if K.rmsnorm_variant(S, rows, D) is not None else None
+
+    def _run_rmsnorm(self, m, inp):
+        """nn.RMSNorm forward -> ``(out, ("rms", x [rows, D], rstd))``: ``xhat = x * rstd`` is one multiply away from the input,
+        so the VJP keeps the input's view and one ``rstd`` per row, shared by all seeds (csrc/lk_rmsnorm.hip)"""
+        rows, D, eps = rmsnorm_geometry(m, inp)
+        x = inp.contiguous().reshape(rows, D)
+        w = None if m.weight is None else m.weight.detach().reshape(-1)
+        K = self._rmsnorm_kernels(x, 1, rows, D)
+        if K is not None:
+            y, rstd = K.rmsnorm_forward(x, None if w is None else w.contiguous(), eps)
+        else:
+            y, rstd = rmsnorm_forward_math(x, w, eps)
+        return y.reshape(inp.shape), ("rms", x, rstd)
+
+    def _rmsnorm_vjp(self, m, saved, g, S):
+        """input cotangent of an nn.RMSNorm for all seeds: ONE launch of lk_rmsnorm_vjp_f32 (or the same formula in torch);
+        ``g`` is ``[S*B, ...]``"""
+        _, x, rstd = saved
+        w = None if m.weight is None else m.weight.detach().reshape(-1)
+        gv = g.contiguous().reshape(S * x.shape[0], x.shape[1])
+        K = self._rmsnorm_kernels(gv, S, x.shape[0], x.shape[1]) if x.dtype == torch.float32 else None
+        if K is not None:
+            return K.rmsnorm_vjp(gv, x, rstd, None if w is None else w.contiguous(), S).reshape(g.shape)
+        return rmsnorm_vjp_math(gv, x, rstd, w, S).reshape(g.shape)
+
+    def _run_sub(self, r, args):
+        """difference forward: two traced tensors of equal shape, a traced tensor and a constant that broadcasts to exactly its
+        shape (`_add_const`'s condition), or a traced tensor and a Python number on either side; the VJP is a sign and keeps
+        nothing"""
+        a, b = args
+        nodes = [isinstance(n, fx.Node) for n in r.src]
+        for t, is_node in zip((a, b), nodes):
+            if is_node and not torch.is_tensor(t):
+                raise SweepUnsupported(f"sub: an operand is not a tensor ({type(t).__name__})")
+        if all(nodes):
+            const = [self.rule[n].kind == CONST for n in r.src]
+            if any(const):
+                c, other = (a, b) if const[0] else (b, a)
+                if tuple(torch.broadcast_shapes(c.shape, other.shape)) != tuple(other.shape):
+                    raise SweepUnsupported(f"sub: {tuple(other.shape)} broadcasts against the {self.rule[r.src[const.index(True)]].what} "
+                                           f"of shape {tuple(c.shape)} (the VJP needs a reduction)")
+            elif a.shape != b.shape:
+                raise SweepUnsupported(f"sub of {tuple(a.shape)} and {tuple(b.shape)}: traced operands of different shapes (the VJP "
+                                       "needs a reduction)")
+        return a - b
+
     def _run_norm(self, node, m, inp):
         """GroupNorm / LayerNorm forward -> ``(out, (xhat, rstd, G, layout))``: what the VJP needs is one normalised input
-        and one ``rstd`` per statistics row, shared by all seeds (csrc/lk_normvjp.hip)"""
+        and one ``rstd`` per statistics row, shared by all seeds (csrc/lk_normvjp.hip); nn.RMSNorm: `_run_rmsnorm`"""
+        if isinstance(m, nn.RMSNorm):
+            return self._run_rmsnorm(m, inp)
         view, G, layout = norm_geometry(m, inp)
         x = inp.contiguous().reshape(view)
         K = self._norm_kernels(x)
@@ -1031,6 +1179,8 @@ class SeedBatchedSweep:
     def _norm_vjp(self, m, saved, g, S):
         """input cotangent of a GroupNorm / LayerNorm for all seeds: ONE launch of lk_norm_vjp_f32 (or the same formula in
         torch); ``g`` is ``[S*B, ...]``"""
+        if saved[0] == "rms":
+            return self._rmsnorm_vjp(m, saved, g, S)
         xhat, rstd, G, layout = saved
         K = self._norm_kernels(g)
         w = None if m.weight is None else m.weight.detach().reshape(-1)
@@ -1491,6 +1641,13 @@ class SeedBatchedSweep:
                 push(src, self._softmax_vjp(self.saved[node], g, S))
             elif kind == SCALE:
                 push(src, g / r.args[0])
+            elif kind == NEG:
+                push(src, -g)
+            elif kind == SUB:  # (the minuend receives g, the subtrahend -g; a constant, a number or the input nothing)
+                push(r.src[0], g)
+                sub = r.src[1]
+                if isinstance(sub, fx.Node) and sub.op != "placeholder" and self.rule[sub].kind != CONST:
+                    push(sub, -g)
             elif kind == CAT:
                 dim, sizes = self.saved[node]
                 off = 0

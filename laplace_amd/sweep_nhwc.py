@@ -35,8 +35,8 @@ from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
-from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MATMUL, MAXPOOL, MEAN, MUL, NORM, PERMUTE,
-                               RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SeedBatchedSweep, SweepUnsupported)
+from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MATMUL, MAXPOOL, MEAN, MUL, NEG, NORM,
+                               PERMUTE, RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SUB, SeedBatchedSweep, SweepUnsupported)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
@@ -179,6 +179,12 @@ class SplitSweep(SeedBatchedSweep):
         for node, r in self.rule.items():
             if r.kind in (MATMUL, SOFTMAX, SCALE):  # (hand-written attention: named before the transposes around it)
                 return f"{r.what} has no NHWC rule"
+        for node, r in self.rule.items():
+            if r.kind in (NEG, SUB):  # (a sign: the rotate-half of a rotary embedding, a hand-written residual)
+                return f"{r.what} has no NHWC rule"
+        for node, r in self.rule.items():
+            if r.kind == NORM and isinstance(r.mod, nn.RMSNorm):  # (normalises rows of the last dims: never a channel group of a map)
+                return f"{node.target}: RMSNorm has no NHWC rule"
         for name in sorted(self.tap_names):
             m = self.modules.get(name)
             if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
