@@ -21,21 +21,34 @@ __global__ __launch_bounds__(256) void softmax_hess_sqrt_kernel(const float* __r
     for (int j = lane; j < C; j += 64) m = fmaxf(m, fr[j]);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    float z = 0.f;
-    for (int j = lane; j < C; j += 64) z += expf(fr[j] - m);
+    // the first class that holds the maximum: the only one whose p can approach 1 (every other p is <= 1/2)
+    int am = C;
+    for (int j = lane; j < C; j += 64) am = (fr[j] == m && j < am) ? j : am;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) am = min(am, __shfl_xor(am, off, 64));
+    float z = 0.f, rest = 0.f;  // rest = sum_{j != am} exp(f_j - m)
+    for (int j = lane; j < C; j += 64) {
+      const float e = expf(fr[j] - m);
+      z += e;
+      rest += (j == am) ? 0.f : e;
+    }
     z = wave_sum(z);
-    const float logz = logf(z) + m;
+    rest = wave_sum(rest);
+    // the shift is taken first, p_j = exp((f_j - m) - log z): adding m back into log z would round it to an ulp of |m|
+    const float lz = logf(z);
     if (y != nullptr && lane == 0) {
       const int64_t lab = y[n];  // labels outside [0, C) (e.g. an ignore_index of -100) contribute nothing
-      if (lab >= 0 && lab < C) nll = logz - fr[lab];
+      if (lab >= 0 && lab < C) nll = lz - (fr[lab] - m);
     }
     for (int c = 0; c < C; ++c) {
-      const float pc = expf(fr[c] - logz);
+      const float pc = expf((fr[c] - m) - lz);
       const float spc = sqrtf(pc);
+      // sqrt(p_c) (1 - p_c): for c == am as sqrt(p_c) * rest / z, free of the difference of two numbers near 1
+      const float dg = (c == am) ? spc * (rest / z) : spc - pc * spc;
       float* out = S + ((int64_t)c * B + n) * C;
       for (int j = lane; j < C; j += 64) {
-        const float pj = expf(fr[j] - logz);
-        out[j] = (j == c ? spc : 0.f) - pj * spc;
+        const float pj = expf((fr[j] - m) - lz);
+        out[j] = (j == c) ? dg : -(pj * spc);
       }
     }
   }
@@ -68,12 +81,13 @@ __global__ __launch_bounds__(256) void softmax_hess_chol_kernel(const float* __r
     float z = 0.f;
     for (int j = lane; j < C; j += 64) z += expf(fr[j] - m);
     z = wave_sum(z);
-    const float logz = logf(z) + m;
+    // the shift is taken first, p_j = exp((f_j - m) - log z): adding m back into log z would round it to an ulp of |m|
+    const float lz = logf(z);
     if (y != nullptr && lane == 0) {
       const int64_t lab = y[n];  // labels outside [0, C) (e.g. an ignore_index of -100) contribute nothing
-      if (lab >= 0 && lab < C) nll = logz - fr[lab];
+      if (lab >= 0 && lab < C) nll = lz - (fr[lab] - m);
     }
-    for (int j = lane; j < C; j += 64) p[j] = expf(fr[j] - logz);
+    for (int j = lane; j < C; j += 64) p[j] = expf((fr[j] - m) - lz);
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {  // suffix sums of positive numbers (C is small)
       float acc = 0.f;

@@ -31,13 +31,22 @@ class EmulatedKernels:
                 S[c, :, c] = r0 * torch.sqrt(sn)
                 S[c, :, c + 1:] = -(p[:, c + 1:] * rs[:, None]) * r0[:, None]
             if y is not None and loss_accum is not None:
-                loss_accum += -torch.log_softmax(f, -1).gather(1, y.view(-1, 1)).sum()
+                loss_accum += self._ce_sum(f, y)
             return S
         sp = p.sqrt()
         S = torch.diag_embed(sp) - p.unsqueeze(2) * sp.unsqueeze(1)  # [B, j, c]
         if y is not None and loss_accum is not None:
-            loss_accum += -torch.log_softmax(f, -1).gather(1, y.view(-1, 1)).sum()
+            loss_accum += self._ce_sum(f, y)
         return S.permute(2, 0, 1).contiguous()  # [c, B, j]
+
+    @staticmethod
+    def _ce_sum(f, y):
+        """labels outside [0, C) (e.g. an ignore_index of -100) contribute nothing; a batch without a valid label adds
+        nothing at all"""
+        ok = (y >= 0) & (y < f.shape[1])
+        if not bool(ok.any()):
+            return 0
+        return -torch.log_softmax(f[ok], -1).gather(1, y[ok].view(-1, 1)).sum()
 
     def sq_err_sum(self, f, y, scale, loss_accum):
         loss_accum += scale * ((f - y) ** 2).sum()
@@ -613,6 +622,32 @@ class EmulatedKernels:
             return out, None, None, None
         inv = 1.0 / M
         return out, (inv * l2.view(1, -1)).sum(1), (inv * l1.view(-1, 1)).sum(0), inv.sum().reshape(1)
+
+    # eigenvalue algebra of KronDecomposed._bmm (csrc/lk_gemm.hip)
+    def kron_pow(self, l1, l2, delta, exponent, damping=False):
+        """lk_kron_pow_f32: (l1 (x) l2 + delta)^e as [n1, n2]; damping: ((l1 + sqrt(delta)) (x) (l2 + sqrt(delta)))^e;
+        l2 None: (l1 + delta)^e as [n1]"""
+        d = delta.detach().reshape(-1)[0].to(l1.dtype)
+        if l2 is None:
+            return (l1 + d) ** exponent
+        if damping:
+            sd = d.sqrt()
+            return torch.outer(l1 + sd, l2 + sd) ** exponent
+        return (torch.outer(l1, l2) + d) ** exponent
+
+    def kron_sandwich(self, W, col0, P, R, Q1, Q2, lam, out):
+        """out[r, col0:col0+p] = vec(Q1 ((Q1^T W_r Q2) (.) lam) Q2^T), W_r = W[r, col0:col0+p] as [p_in, p_out];
+        Q2 None: ((W_r Q1) (.) lam) Q1^T.  The other columns of ``out`` are not touched."""
+        Wv, Ov = W.reshape(R, P), out.view(R, P)
+        if Q2 is None:
+            p = Q1.shape[0]
+            Ov[:, col0:col0 + p] = ((Wv[:, col0:col0 + p] @ Q1) * lam.reshape(1, p)) @ Q1.T
+            return out
+        pi, po = Q1.shape[0], Q2.shape[0]
+        Wr = Wv[:, col0:col0 + pi * po].reshape(R, pi, po)
+        M = (Q1.T @ Wr @ Q2) * lam.reshape(1, pi, po)
+        Ov[:, col0:col0 + pi * po] = (Q1 @ M @ Q2.T).reshape(R, pi * po)
+        return out
 
     quadform_shared_max_outputs = 10
 
