@@ -712,6 +712,40 @@ int lk_mul_vjp_f32(const float* g, const float* a, const float* b, int64_t S, in
                    float* db, void* stream);
 int lk_mul_variant(int64_t S, int64_t R, int64_t L, int b_row, int want_da, int want_db, int aligned);
 
+/* Squeeze-and-excitation gate out = x * gate[B, C, 1, 1] on NHWC feature maps for the NHWC reverse sweep.  They replace, there,
+ * the reverse pass of laplace/curvature/curvlinops.py:87-100 through such a block as the NCHW route runs it: the product rule on
+ * an NCHW copy of the cotangent, the pooling cotangent expanded to the whole map, and the add of the two.
+ * N = S B maps, seed-major; P = H W positions; C channels innermost.  The cotangent g [N][P][C] is EITHER the fp32 map g (g_h,
+ * g_l and sexp null) OR - g null - a ONE-scale split tensor read as it lies: fp16 planes g_h and g_l [N][P][C] and the device
+ * word sexp[0], value = (float(g_h) + float(g_l)) * 2^-sexp, exactly as lk_cat_vjp_nhwc_f32 forms it.
+ *
+ * lk_gate_reduce_nhwc_f32: ds[s][b][c] = sum_p g[s B + b][p][c] * x[b][p][c]; x [B][P][C] fp32, one copy per sample shared by
+ *   all seeds; ds [S B][C] fp32.  One launch for all seeds; fp32 accumulation; lanes across the channels, the sum over the
+ *   positions in a fixed order (per thread every (256 / lanes)-th position in ascending order, then a fixed tree over the
+ *   position groups); one owner per ds element, no atomics: bit-reproducible.  x stays in registers across the seed loop while
+ *   a thread owns at most 16 positions, else it is re-read per seed; few (sample, channel tile) units: the seeds go over grid.y.
+ *   Minimal traffic: g once, x once, 4 S B C bytes of ds.
+ * lk_gate_vjp_nhwc_f32: dx[s B + b][p][c] = g[s B + b][p][c] * gate[b][c] + r[s B + b][c]; gate [B][C] fp32; r [S B][C] fp32 or
+ *   NULL (the cotangent of the pooled tensor, already divided by P); dx [N][P][C] fp32.  One launch for all seeds, g read
+ *   once; gate of the sample and r of the map stay in registers along the positions; one owner per element, plain stores, no
+ *   atomics on data.  With r NULL dx is the fp32 product (one rounding).  amax, when given, receives max|dx| as the bit pattern
+ *   of a non-negative float through atomicMax (as lk_cat_vjp_nhwc_f32); the caller zeroes it.
+ * Contract of both: pointers non-null where used; exactly one form of g; 1 <= S, 0 <= B, 1 <= P < 2^30, 1 <= C < 2^30,
+ *   S * B * P * C < 2^40; no output overlaps an input.  B == 0 returns LK_OK before any device call.
+ * lk_gate_variant (host only): the path a shape takes; vjp: 0 the reduce, 1 the VJP; `aligned`: the fp32 bases are 16-byte, the
+ * planes 8-byte aligned.  Returns
+ *   vec | resident << 1 | seed-split << 2 | wide << 3 | log2(lanes across the channel vectors) << 4 | workgroups of grid.x << 8
+ *   bit 0 vec: 16-byte fp32 accesses, 8-byte loads of four halves (C % 4 == 0 and aligned), else one element per lane; bit 1
+ *   resident (reduce): x stays in registers across the seed loop; bit 2 (reduce): the seeds are split over grid.y; bit 3 wide:
+ *   S * B * P * C >= 2^31, an element offset passes 31 bits (the kernels index with 64 bits throughout); bits 4-6: 1 .. 64 lanes
+ *   across the channel vectors of a position (256 / lanes position groups); bits 8 and up: at most 2048 workgroups of 256 threads
+ * or a negative value for a shape the entry points refuse. */
+int lk_gate_reduce_nhwc_f32(const float* g, const void* g_h, const void* g_l, const int* sexp, const float* x, int64_t S,
+                            int64_t B, int64_t P, int64_t C, float* ds, void* stream);
+int lk_gate_vjp_nhwc_f32(const float* g, const void* g_h, const void* g_l, const int* sexp, const float* gate, const float* r,
+                         int64_t S, int64_t B, int64_t P, int64_t C, float* dx, unsigned* amax, void* stream);
+int lk_gate_variant(int vjp, int64_t S, int64_t B, int64_t P, int64_t C, int aligned);
+
 /* Softmax / log-softmax along the last, contiguous dim (hand-written attention, attention pooling, soft mixture gates,
  * log-softmax head features) for the seed-batched reverse sweep.  It replaces, in the reverse pass of
  * laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through y = softmax(x) as stock torch runs it once per seed,

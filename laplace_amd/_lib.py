@@ -136,6 +136,9 @@ SIGNATURES = {
     "lk_slice_variant": (_int, [_int, _int, _vp, _vp, _i64, _i64, _int]),
     "lk_mul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_mul_variant": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
+    "lk_gate_reduce_nhwc_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "lk_gate_vjp_nhwc_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "lk_gate_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int]),
     "lk_softmax_vjp_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp]),
     "lk_softmax_vjp_variant": (_int, [_i64, _i64, _i64, _int, _int]),
     "lk_matmul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
@@ -1697,6 +1700,68 @@ class HipKernels:
             return None
         return {"row": bool(r & 1), "vec": bool(r & 2), "lanes_per_row": 1 << ((r >> 2) & 7), "resident": bool(r & 32),
                 "seed_split": bool(r & 64), "wide_index": bool(r & 128), "da": bool(r & 256), "db": bool(r & 512), "blocks": r >> 10}
+
+    @staticmethod
+    def _gate_g(g, what):
+        """the four pointer arguments ``(g, g_h, g_l, sexp)`` of the gate kernels for a cotangent ``[N, H, W, C]`` - an fp32 NHWC
+        tensor or a one-scale :class:`SplitTensor` read as it lies - with its shape and device"""
+        if isinstance(g, SplitTensor):
+            _one_scale(g, what)
+            if g.chunked:
+                raise LaplaceHipError(f"{what}: a chunk-major split tensor is no NHWC map")
+            _check(g.planes, "g.planes", torch.float16)
+            _check(g.sexp, "g.sexp", torch.int32)
+            ptrs, dev = (None, g.planes[0].data_ptr(), g.planes[1].data_ptr(), g.sexp.data_ptr()), g.planes.device
+        else:
+            _check(g, "g")
+            ptrs, dev = (g.data_ptr(), None, None, None), g.device
+        if len(g.shape) != 4:
+            raise LaplaceHipError(f"{what}: g {tuple(g.shape)} is no NHWC map [N, H, W, C]")
+        return ptrs, tuple(int(d) for d in g.shape), dev
+
+    def gate_reduce(self, g, x, S):
+        """``ds`` ``[S * B, C]``: ``ds[s B + b, c] = sum_hw g[s B + b, h, w, c] * x[b, h, w, c]`` for the ``S`` seeds stacked in the
+        NHWC cotangent ``g`` ``[S * B, H, W, C]`` - an fp32 tensor or a one-scale :class:`SplitTensor` read as it lies - from ONE
+        fp32 NHWC map ``x`` ``[B, H, W, C]`` per sample, in ONE launch of lk_gate_reduce_nhwc_f32 (csrc/lk_gate.hip)"""
+        ptrs, (N, H, W, C), dev = self._gate_g(g, "gate_reduce")
+        _check(x, "x")
+        S = int(S)
+        if S < 1 or x.dim() != 4 or N != S * x.shape[0] or tuple(x.shape[1:]) != (H, W, C) or x.device != dev:
+            raise LaplaceHipError(f"gate_reduce: g {(N, H, W, C)} and x {tuple(x.shape)} do not belong together for S = {S}")
+        ds = torch.empty(N, C, dtype=torch.float32, device=dev)
+        self._rc(self.lib.lk_gate_reduce_nhwc_f32(*ptrs, _ptr(x), S, N // S, H * W, C, _ptr(ds), self._stream(dev)),
+                 "lk_gate_reduce_nhwc_f32")
+        return ds
+
+    def gate_vjp(self, g, gate, r, S, amax=None):
+        """``dx`` ``[S * B, H, W, C]`` fp32: ``g[s B + b, h, w, c] * gate[b, c] + r[s B + b, c]`` for the ``S`` seeds stacked in the
+        NHWC cotangent ``g`` (an fp32 tensor or a one-scale :class:`SplitTensor` read as it lies), ``gate`` ``[B, C]`` fp32 and
+        ``r`` ``[S * B, C]`` fp32 or ``None``, in ONE launch of lk_gate_vjp_nhwc_f32.  ``amax``: zeroed device word that receives
+        the bit pattern of max|dx|."""
+        ptrs, (N, H, W, C), dev = self._gate_g(g, "gate_vjp")
+        _check(gate, "gate")
+        S = int(S)
+        if S < 1 or gate.dim() != 2 or N != S * gate.shape[0] or gate.shape[1] != C or gate.device != dev:
+            raise LaplaceHipError(f"gate_vjp: g {(N, H, W, C)} and gate {tuple(gate.shape)} do not belong together for S = {S}")
+        if r is not None:
+            _check(r, "r")
+            if tuple(r.shape) != (N, C) or r.device != dev:
+                raise LaplaceHipError(f"gate_vjp: r {tuple(r.shape)} is not [{N}, {C}]")
+        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+            raise LaplaceHipError("gate_vjp: amax is one 32-bit device word")
+        dx = torch.empty(N, H, W, C, dtype=torch.float32, device=dev)
+        self._rc(self.lib.lk_gate_vjp_nhwc_f32(*ptrs, _ptr(gate), _ptr(r), S, N // S, H * W, C, _ptr(dx), _ptr(amax),
+                                               self._stream(dev)), "lk_gate_vjp_nhwc_f32")
+        return dx
+
+    def gate_variant(self, vjp, S, B, P, C, aligned=True):
+        """lk_gate_variant: the path ``lk_gate_reduce_nhwc_f32`` (``vjp`` false) or ``lk_gate_vjp_nhwc_f32`` (true) takes for a
+        shape (host only, no device call), or ``None`` for a shape they refuse"""
+        r = int(self.lib.lk_gate_variant(int(bool(vjp)), int(S), int(B), int(P), int(C), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "resident": bool(r & 2), "seed_split": bool(r & 4), "wide_index": bool(r & 8),
+                "lanes": 1 << ((r >> 4) & 7), "blocks": r >> 8}
 
     def softmax_vjp(self, g, y, S, is_log=False):
         """``dx`` (the shape of ``g``) of ``y = softmax(x, -1)`` / ``log_softmax(x, -1)`` for the ``S`` seeds stacked in the

@@ -477,9 +477,10 @@ class SEBasicBlock(nn.Module):
 class SEResNetSmall(nn.Module):
     """A CIFAR SE-ResNet for 3 x 32 x 32 inputs: 3x3 stem convolution - BN - act, ``depth`` :class:`SEBasicBlock` s per entry of
     ``widths`` (stride 2 into every stage but the first), then global average - flatten - ``Linear``.  Eval-mode BatchNorm; the gate
-    branches are 1x1 convolutions on 1x1 maps with ``width / reduction`` channels, so the model runs the NCHW sweep (the split
-    sweep names the product): the workload of the row-gate form of the product rule.  ``act`` and ``freeze_bn`` as with
-    :class:`DenseNetSmall`."""
+    branches are 1x1 convolutions on 1x1 maps with ``width / reduction`` channels.  By default the model runs the NCHW sweep (the
+    split sweep names the product): the workload of the row-gate form of the product rule.  With ``SplitSweep.nhwc_mul = True`` it
+    stays on the NHWC split-fp16 walk: the gates run on csrc/lk_gate.hip and the gate branches on plain ``[B, C, 1, 1]`` tensors.
+    ``act`` and ``freeze_bn`` as with :class:`DenseNetSmall`."""
 
     def __init__(self, num_classes: int = 10, widths=(32, 64, 128), depth: int = 2, reduction: int = 4, freeze_bn: bool = True,
                  act=nn.ReLU):

@@ -22,7 +22,11 @@ csrc/lk_norm.hip).  A concatenation of feature maps along the channels (DenseNet
 source in the forward, and per source one launch that reads its channel slice of all cotangent parts - fp32 maps and split tensors as
 they lie - and writes their fp32 sum (``nhwc_cat``).  A channel slice of a feature map (``chunk`` / ``split`` / ``narrow`` / ``x[:, a:b]``:
 CSP stages) runs on csrc/lk_slice.hip: one copy launch in the forward, and per sliced map one launch that sums the pieces its slices hand
-back and the full-width parts into an fp32 map (``nhwc_slice``).  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
+back and the full-width parts into an fp32 map (``nhwc_slice``).  With ``nhwc_mul = True`` a squeeze-and-excitation gate - a feature map
+times the ``[B, C, 1, 1]`` end of a chain of pointwise convolutions / Linear layers / activations that starts at the global average
+pooling of that same map - runs on csrc/lk_gate.hip: per block and sweep one launch that reduces the cotangent against the map for
+all seeds and one that writes the map's cotangent, gate product and pooling cotangent together; the chain in between runs on plain
+``[S*B, C]`` tensors and its taps leave as fp32, as the NCHW sweep hands them out.  Graphs with nodes this path has no rule for (pooling with ``ceil_mode`` or dilation, adaptive pooling to several
 cells, convolutions whose channel counts are not multiples of 32, ...) run through the parent class unchanged.
 """
 from __future__ import annotations
@@ -44,10 +48,14 @@ _PASS_THROUGH = {ACT, IDENTITY, ADD}  # shape-preserving: the cotangent keeps th
 GN_MAP = "group-norm on a feature map"  # what `_walk` reports for an nn.GroupNorm node (NORM covers nn.LayerNorm in the head too)
 CAT_MAP = "concatenation of feature maps"  # what `_walk` reports for a CAT whose sources sit on feature maps (CAT: one in the head)
 SLICE_MAP = "channel slice of a feature map"  # what `_walk` reports for a SLICE whose source sits on a feature map (SLICE: one in the head)
+GATE_MAP = "gated feature map"  # what `_walk` reports for a MUL that `nhwc_mul` serves: a feature map times its [B, C, 1, 1] gate
 _POOL = {MAXPOOL, AVGPOOL}  # spatial pooling: fp32 NHWC in, fp32 NHWC out (lk_pool.hip)
-_FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP, SLICE_MAP} | _POOL  # produce / consume NHWC feature maps
-_MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, SLICE_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
-_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE}  # a graph with one of these runs through the NCHW sweep
+_FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP, SLICE_MAP, GATE_MAP} | _POOL  # produce / consume NHWC feature maps
+_MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, SLICE_MAP, GATE_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
+# a graph with one of these runs through the NCHW sweep (MUL: unless ``nhwc_mul`` serves it as a squeeze-and-excitation gate on
+# csrc/lk_gate.hip, or both its operands lie in the head region)
+_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE}
+_GATE_CHAIN = {CONV, LINEAR, ACT, IDENTITY, RESHAPE}  # what the branch from the pooled tensor to a served gate may hold
 
 
 class _F32:
@@ -156,6 +164,11 @@ class SplitSweep(SeedBatchedSweep):
         self._prep: dict[str, cv.PreparedConv] = {}
         self._amax_cache: dict = {}
         self._on_map_cache: dict = {}
+        # MUL node -> (index of the gate operand, node of the gated map, chain [GPOOL, ..., gate]) of a product `nhwc_mul` serves;
+        # chain node -> its MUL node; id(rule) of a MUL -> its node (`_run_mul` receives the rule)
+        self._gates: dict = {}
+        self._gate_nodes: dict = {}
+        self._mul_node = {id(r): n for n, r in self.rule.items() if r.kind == MUL}
         self.split_reason = self._split_eligible()
         self.split_ok = self.split_reason is None
 
@@ -175,7 +188,11 @@ class SplitSweep(SeedBatchedSweep):
                 return f"{node.name}: {r.what} has no NHWC rule"
         for node, r in self.rule.items():
             if r.kind == MUL:  # (named before the narrow 1x1 convolutions of a gate branch, which only exist because of it)
-                return f"{r.what} has no NHWC rule"
+                if not self.nhwc_mul:
+                    return f"{r.what} has no NHWC rule"
+                why = self._mul_refusal(node, r)
+                if why is not None:
+                    return why
         for node, r in self.rule.items():
             if r.kind in (MATMUL, SOFTMAX, SCALE):  # (hand-written attention: named before the transposes around it)
                 return f"{r.what} has no NHWC rule"
@@ -204,6 +221,8 @@ class SplitSweep(SeedBatchedSweep):
         for node, r in self.rule.items():
             if r.kind == CONV:
                 m, first = r.mod, r.src[0].op == "placeholder"
+                if node in self._gate_nodes:
+                    continue  # (a 1x1 convolution on the pooled [B, C, 1, 1] tensor of a gate branch: parent-class math)
                 if m.groups != 1:
                     why = self._depthwise_refusal(node, m)
                     if why is not None:
@@ -212,6 +231,8 @@ class SplitSweep(SeedBatchedSweep):
                 if not cv.supported(m) and not (first and node.target in self.tap_names and m.out_channels % 8 == 0):
                     return f"{node.target}: convolution outside the implicit-GEMM kernel's coverage"
                 n_conv += 1
+            elif r.kind == MUL:
+                continue  # (`_mul_refusal` above: a served gate, or a product in the head region)
             elif r.kind in _NO_RULE or isinstance(r.mod, nn.BatchNorm1d) or (r.kind in _POOL and not self.nhwc_pool):
                 return (f"{node.target}: " if node.op == "call_module" else "") + f"{r.what} has no NHWC rule"
             elif r.kind in _POOL:
@@ -259,6 +280,8 @@ class SplitSweep(SeedBatchedSweep):
             kind = self.rule[n].kind
             if kind == CAT:
                 hit = any(self._on_map(a) for a in self.rule[n].src)
+            elif kind == MUL:
+                hit = n in self._gates
             elif kind in (SLICE, SPLIT):
                 hit = self._on_map(self.rule[n].src[0])
             elif kind in _PASS_THROUGH:
@@ -315,6 +338,77 @@ class SplitSweep(SeedBatchedSweep):
         if not all(hasattr(self.kernels(), f) for f in ("slice_forward", "slice_vjp")):
             return "kernels without the slicing entry points"
         return None
+
+    #: ``True``: a squeeze-and-excitation gate - a feature map times the ``[B, C, 1, 1]`` end of a chain that starts at the
+    #: ``AdaptiveAvgPool2d(1)`` of that same map - runs on csrc/lk_gate.hip and its model stays on the NHWC walk.  ``False`` (the
+    #: default): a model with a product runs through the NCHW sweep (whose MUL rule serves it), as it did before lk_gate.hip
+    #: (tools/se_nhwc_bench.py)
+    nhwc_mul = False
+
+    def _back_to_pool(self, n):
+        """the GPOOL node that the first inputs upstream of ``n`` lead to, or ``None``"""
+        for _ in range(len(self.rule)):
+            if not isinstance(n, fx.Node) or n.op == "placeholder":
+                return None
+            r = self.rule[n]
+            if r.kind == GPOOL:
+                return n
+            if r.kind == CONST or len(r.src) != 1:
+                return None
+            n = r.src[0]
+        return None
+
+    def _gate_chain(self, gate, pool):
+        """the chain ``[pool, ..., gate]`` of a gate branch, or the reason (a string that names the offending node) why the branch
+        is none: every node has one traced input and one consumer and is a pointwise convolution, a Linear, an activation, an
+        identity or a reshape with static arguments"""
+        chain, n = [], gate
+        while True:
+            r = self.rule[n]
+            if len(n.users) != 1:
+                return f"mul: gate branch node {n.name} has {len(n.users)} consumers (a gate branch is a chain without a fork)"
+            if n is pool:
+                if tuple(self._pair2(r.args[0])) != (1, 1):
+                    return f"mul: gate branch node {n.name}: adaptive pooling to more than one cell"
+                chain.append(n)
+                return chain[::-1]
+            if len(n.all_input_nodes) != 1:
+                return (f"mul: gate branch node {n.name} reads {len(n.all_input_nodes)} traced values (a gate branch is a chain: no "
+                        "join, no view built from x.size())")
+            if r.kind not in _GATE_CHAIN:
+                return f"mul: gate branch node {n.name} ({r.what}) is no pointwise convolution, Linear, activation, identity or reshape"
+            if r.kind == CONV:
+                m = r.mod
+                if not (tuple(m.kernel_size) == (1, 1) and tuple(m.stride) == (1, 1) and m.padding in ((0, 0), 0, "valid")
+                        and m.groups == 1):
+                    return f"mul: gate branch node {n.name}: {n.target} is no pointwise convolution (1x1, stride 1, no padding, one group)"
+            chain.append(n)
+            n = r.src[0]
+
+    def _mul_refusal(self, node, r):
+        """why this MUL node keeps the model off the NHWC walk (None: lk_gate.hip serves it and it is entered in ``_gates``, or it is
+        a product of plain tensors in the head region, which takes the parent-class math)"""
+        for gi in (1, 0):
+            gate, x = r.src[gi], r.src[1 - gi]
+            pool = self._back_to_pool(gate)
+            if pool is None or gate is x or self.rule[pool].src[0] is not x or not self._on_map(x):
+                continue
+            chain = self._gate_chain(gate, pool)
+            if isinstance(chain, str):
+                return chain
+            if self.kernels is None or not all(hasattr(self.kernels(), f) for f in ("gate_reduce", "gate_vjp")):
+                return "mul: kernels without the gate entry points"
+            self._gates[node] = (gi, x, chain)
+            for n in chain:
+                self._gate_nodes[n] = node
+            return None
+        on_map = [isinstance(a, fx.Node) and self._on_map(a) for a in r.src]
+        if not any(on_map):
+            return None
+        if all(on_map):
+            return "mul: product of two feature maps (the NHWC kernels serve a [B, C, 1, 1] gate)"
+        return (f"mul: {node.name} multiplies a feature map by a tensor that is no [B, C, 1, 1] gate of that map (a chain from its "
+                "global average pooling)")
 
     def _bn_tap_served(self, m) -> bool:
         """is this tapped BatchNorm one the NHWC walk delivers the cotangent of (``nhwc_norm_taps``)?"""
@@ -389,6 +483,8 @@ class SplitSweep(SeedBatchedSweep):
                     kind = CAT_MAP  # (a producer and consumer of feature maps, not pass-through)
                 if kind == SLICE and self._on_map(m):
                     kind = SLICE_MAP
+                if kind == MUL and m in self._gates:
+                    kind = GATE_MAP
                 out.append(GN_MAP if kind == NORM and isinstance(self.rule[m].mod, nn.GroupNorm) else kind)
                 if kind in _PASS_THROUGH:
                     todo.append(m)
@@ -396,6 +492,8 @@ class SplitSweep(SeedBatchedSweep):
 
     def _region_check(self):
         for node, r in self.rule.items():
+            if node in self._gate_nodes:
+                continue  # (a gate branch: plain [B, C, 1, 1] / [B, C] tensors between the pooling and the product)
             if r.kind == RESHAPE and any(k in _FEATURE for k in self._walk(node, True)):
                 return f"{node.name}: view / reshape / flatten whose result is used as a feature map"
             if r.kind == GPOOL:
@@ -485,6 +583,8 @@ class SplitSweep(SeedBatchedSweep):
         return out
 
     def _run_conv(self, node, m, inp):
+        if node in self._gate_nodes:
+            return m(inp)  # (a gate branch's convolution on [B, C, 1, 1]: no own-convolution launch, no split copy)
         if self._is_depthwise(m):
             return self._run_depthwise(node, m, inp)
         if not (self._use_nhwc_forward(inp) and cv.forward_supported(m)):
@@ -594,6 +694,39 @@ class SplitSweep(SeedBatchedSweep):
         if aux is not None and aux.get("bound") is not None:
             self._aux_put(out, {"split": None, "bound": aux["bound"]})
         return out
+
+    def _gate_is_bounded_by_one(self, n) -> bool:
+        """is the value of node ``n`` in [0, 1] whatever its input (a Sigmoid / Hardsigmoid)?"""
+        r = self.rule[n]
+        if r.kind != ACT:
+            return False
+        if r.flavour == "sigmoid":
+            return True
+        if n.op == "call_module":
+            return isinstance(self.modules.get(n.target), nn.Hardsigmoid)
+        return n.op == "call_function" and n.target is torch.nn.functional.hardsigmoid
+
+    def _run_mul(self, r, args):
+        """a feature map times its ``[B, C, 1, 1]`` gate (``nhwc_mul``): torch's product on the NHWC memory of the map (1 / S of the
+        sweep's work); returns the NCHW-logical view over NHWC memory, as `_run_pool` does, and keeps the map's ``[B, H, W, C]``
+        view and the gate ``[B, C]`` for lk_gate.hip.  A gate in [0, 1] cannot raise the map's maximum, so the output then inherits
+        the map's per-image ``"bound"`` words; otherwise nothing is registered.  Any other product runs the parent's math."""
+        node = self._mul_node.get(id(r))
+        if not (self.split_ok and node in self._gates):
+            return super()._run_mul(r, args)
+        gi, _, chain = self._gates[node]
+        gate, x = args[gi], args[1 - gi]
+        if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and torch.is_tensor(gate)
+                and gate.dtype == torch.float32 and tuple(gate.shape) == (x.shape[0], x.shape[1], 1, 1)):
+            raise SweepUnsupported(f"{node.name}: the gate of the NHWC sweep expects an fp32 feature map [B, C, H, W] and a gate "
+                                   f"[B, C, 1, 1], got {tuple(getattr(x, 'shape', ()))} and {tuple(getattr(gate, 'shape', ()))}")
+        xh = x.permute(0, 2, 3, 1).contiguous()  # (a view when x is already NHWC in memory)
+        g2 = gate.reshape(gate.shape[0], gate.shape[1]).contiguous()
+        out = (xh * g2[:, None, None, :]).permute(0, 3, 1, 2)
+        aux = self._aux_get(x)
+        if aux is not None and aux.get("bound") is not None and self._gate_is_bounded_by_one(chain[-1]):
+            self._aux_put(out, {"split": None, "bound": aux["bound"]})
+        return out, ("gate", xh, g2)
 
     #: ``False``: a convolution and the BatchNorm / add / ReLU behind it stay two launches
     fuse_conv_bn = True
@@ -1021,6 +1154,54 @@ class SplitSweep(SeedBatchedSweep):
                 else:  # the parts as they lie (split tensors and fp32 maps): channels [start, start + length) of the source
                     for p in parts:
                         pieces.setdefault(src, []).append((p, dim, start, length, in_shape))
+            elif kind == MUL and node not in self._gates:
+                # a product in the head region (plain tensors after the flatten): parent-class math
+                if not all(torch.is_tensor(p) for p in parts):
+                    raise SweepUnsupported("product of a feature map outside the gate rule of the NHWC region")
+                g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
+                want = tuple(n.op != "placeholder" and self.rule[n].kind != CONST for n in r.src)
+                if any(want):
+                    for a, d in zip(r.src, self._mul_vjp(self.saved[node], g, S, want)):
+                        if d is not None:
+                            push(a, d)
+            elif kind == MUL:
+                # a feature map times its gate (lk_gate.hip).  The cotangent as ONE operand, as it lies (several parts: folded
+                # through fp32, as the NORM rule does)
+                _, x_node, chain = self._gates[node]
+                _, xh, gate = self.saved[node]
+                if len(parts) == 1:
+                    op = parts[0] if isinstance(parts[0], SplitTensor) else parts[0].t
+                else:
+                    ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
+                    op = sum(ts[1:], ts[0]).contiguous()
+                C = int(xh.shape[3])
+                # ds [S*B, C], the cotangent of the [B, C, 1, 1] gate: one launch for all seeds
+                t = K.gate_reduce(op, xh, S).reshape(SB, C, 1, 1)
+                # the chain back to the pooled tensor on plain [S*B, ...] tensors; its taps leave as the NCHW sweep hands them out
+                for n in reversed(chain[1:]):
+                    rn = self.rule[n]
+                    if rn.kind == ACT:
+                        t = self._scale_mask(t, S, self._act_mult(rn.flavour, self.saved[n]), None)
+                    elif rn.kind in (CONV, LINEAR):
+                        if n.target in self.tap_names:
+                            grads[n.target] = t.reshape(S, B, *t.shape[1:])
+                            if on_tap is not None:
+                                on_tap(n.target, grads[n.target])
+                            remaining.discard(n.target)
+                        w = rn.mod.weight
+                        if rn.kind == CONV:
+                            t = (t.reshape(SB, -1) @ w.reshape(w.shape[0], w.shape[1])).reshape(SB, w.shape[1], 1, 1)
+                        else:
+                            t = t @ w
+                    elif rn.kind == RESHAPE:
+                        t = t.reshape((SB,) + tuple(self.saved[n])[1:])
+                if not remaining:
+                    break
+                if isinstance(x_node, fx.Node) and x_node.op != "placeholder":
+                    # the pooled tensor's cotangent, divided by H W, rides on the gate's VJP: ONE launch writes the map's cotangent
+                    rp = (t.reshape(SB, C) / float(xh.shape[1] * xh.shape[2])).contiguous()
+                    word = new_word()
+                    push(x_node, _F32(K.gate_vjp(op, gate, rp, S, amax=word), word))
             elif kind == RESHAPE:
                 g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
                 if not torch.is_tensor(g):
