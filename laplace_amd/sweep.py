@@ -825,6 +825,45 @@ def softmax_vjp_math(g, y, S, dim, is_log=False, max_bytes=None):
     return dx.reshape(g.shape)
 
 
+def _sum(parts):
+    """the sum of a non-empty list of cotangent parts, left to right"""
+    return parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
+
+
+class _Walk:
+    """The state of ONE reverse walk (`SeedBatchedSweep.backward` creates it; nothing of it outlives the call)."""
+
+    def __init__(self, sweep, seeds, on_tap, defer_bn_scale):
+        self.rule, self.on_tap, self.defer_bn_scale = sweep.rule, on_tap, defer_bn_scale
+        self.S, self.B = seeds.shape[0], seeds.shape[1]
+        # per node: the pending addends of its output cotangent (summed lazily, so that an activation can fold
+        # the residual-branch addition into its own kernel)
+        self.cot: dict[fx.Node, list] = {sweep.out_node: [seeds.reshape(self.S * self.B, *seeds.shape[2:])]}
+        # per node: the pieces ``(cotangent, dim, start, length, input shape)`` its SLICE consumers hand back, assembled with the
+        # full-width parts ONCE, when the node itself is reached
+        self.pieces: dict[fx.Node, list] = {}
+        self.grads: dict = {}
+        self.remaining = set(sweep.tap_names)
+        self.pending_scale: dict[fx.Node, torch.Tensor] = {}  # conv node -> the BatchNorm scale its backward-data applies
+        self.grad_scale: dict[str, torch.Tensor] = {}  # (the sweep's public ``grad_scale`` of this walk)
+
+    def live(self, n) -> bool:
+        """does ``n`` receive a cotangent?  (a constant, a Python number and the input have none)"""
+        return isinstance(n, fx.Node) and n.op != "placeholder" and self.rule[n].kind != CONST
+
+    def push(self, n, g):
+        if self.live(n):
+            self.cot.setdefault(n, []).append(g)
+
+    def tap(self, name, g) -> bool:
+        """record the gradient of the tapped module ``name``; ``True``: it was the last one the walk owed"""
+        self.grads[name] = g
+        if self.on_tap is not None:
+            self.on_tap(name, g)
+        self.remaining.discard(name)
+        return not self.remaining
+
+
 class SeedBatchedSweep:
     """Forward + seed-batched reverse sweep over an fx-traced module."""
 
@@ -1549,118 +1588,144 @@ class SeedBatchedSweep:
         backward-data uses the pre-scaled weights ``s[co] * W`` and the tap receives the UNSCALED gradient ``g`` with
         ``self.grad_scale[name] = s`` — the caller owes ``G <- diag(s) G diag(s)``, which a KFAC accumulator applies
         once per fit because ``s`` is constant."""
-        self.grad_scale: dict[str, torch.Tensor] = {}
-        pending_scale: dict[fx.Node, torch.Tensor] = {}
-        S, B = seeds.shape[0], seeds.shape[1]
-        # per node: the pending addends of its output cotangent (summed lazily, so that an activation can fold
-        # the residual-branch addition into its own kernel)
-        cot: dict[fx.Node, list] = {self.out_node: [seeds.reshape(S * B, *seeds.shape[2:])]}
-        grads: dict[str, torch.Tensor] = {}
-        remaining = set(self.tap_names)
-
-        def push(n, g):
-            if not isinstance(n, fx.Node) or n.op == "placeholder" or self.rule[n].kind == CONST:
-                return  # (a constant has no cotangent)
-            cot.setdefault(n, []).append(g)
-
-        # per node: the pieces ``(cotangent, dim, start, length)`` its SLICE consumers hand back, assembled with the full-width
-        # parts ONCE, when the node itself is reached
-        pieces: dict[fx.Node, list] = {}
+        walk = _Walk(self, seeds, on_tap, defer_bn_scale)
+        self.grad_scale = walk.grad_scale
+        S, B = walk.S, walk.B
         for node, r in reversed(self.rule.items()):
-            if node not in cot and node not in pieces:
+            if node not in walk.cot and node not in walk.pieces:
                 continue
-            parts, g2 = cot.pop(node, []), None
-            if node in pieces:
-                pcs = pieces.pop(node)
+            parts, g2 = walk.cot.pop(node, []), None
+            if node in walk.pieces:
+                pcs = walk.pieces.pop(node)
                 parts = [self._assemble_slices(parts, [p[:4] for p in pcs], (S * B,) + tuple(pcs[0][4][1:]))]
             g = parts[0]
             if len(parts) > 1:
-                if r.kind == ACT:
-                    g2 = parts[1] if len(parts) == 2 else sum(parts[2:], parts[1])
+                if r.kind == ACT:  # (the activation's kernel folds the residual-branch addition in)
+                    g2 = _sum(parts[1:])
                 else:
-                    g = sum(parts[1:], parts[0])
-            kind, m, src = r.kind, r.mod, r.src[0]
-            if m is not None and node.target in self.tap_names:
-                grads[node.target] = g.reshape(S, B, *g.shape[1:])
-                if node in pending_scale:
-                    self.grad_scale[node.target] = pending_scale[node]
-                if on_tap is not None:
-                    on_tap(node.target, grads[node.target])
-                remaining.discard(node.target)
-                if not remaining:
+                    g = _sum(parts)
+            if r.mod is not None and node.target in self.tap_names:
+                if node in walk.pending_scale:
+                    self.grad_scale[node.target] = walk.pending_scale[node]
+                if walk.tap(node.target, g.reshape(S, B, *g.shape[1:])):
                     break  # nothing upstream of the first tapped module is needed
-            if kind == CONV:
-                in_shape = (S * B,) + tuple(self.saved[node][1:])
-                push(src, self._conv_input_grad(in_shape, m, g, self._scaled_weight(node.target, m, pending_scale.get(node))))
-            elif kind == LINEAR:
-                push(src, g @ m.weight)
-            elif kind == BN:
-                scale = self._bn_scale(node.target, m)
-                if defer_bn_scale and self._defers_scale_to(src, cot):
-                    pending_scale[src] = scale  # the conv sees the unscaled cotangent (see the docstring)
-                    push(src, g)
-                else:
-                    push(src, self._scale_mask(g, S, None, scale))
-            elif kind == NORM:
-                push(src, self._norm_vjp(m, self.saved[node], g, S))
-            elif kind == ACT:
-                scale, dst = self._fold_bn(src)
-                push(dst, self._scale_mask(g, S, self._act_mult(r.flavour, self.saved[node]), scale, g2))
-            elif kind == IDENTITY:
-                push(src, g)
-            elif kind == RESHAPE:
-                push(src, g.reshape((S * B,) + tuple(self.saved[node][1:])))
-            elif kind == GPOOL:
-                push(src, self._adaptive_avgpool_vjp(g, self.saved[node], S * B))
-            elif kind == AVGPOOL:
-                push(src, self._avgpool_vjp(g, self.saved[node], S * B, *r.args))
-            elif kind == MAXPOOL:
-                idx, shp = self.saved[node]
-                push(src, self._maxpool_vjp(g, idx, shp, S, B))
-            elif kind == MEAN:
-                push(src, self._mean_vjp(g, self.saved[node], S * B))
-            elif kind == ATTN:
-                for a, d in zip(r.src, self._attn_vjp(self.saved[node], g, S)):
-                    push(a, d)
-            elif kind == PERMUTE:
-                push(src, g.permute(self.saved[node]))
-            elif kind == ADD:
-                for a in r.src:
-                    push(a, g)
-            elif kind == MUL:
-                want = tuple(n.op != "placeholder" and self.rule[n].kind != CONST for n in r.src)
-                if any(want):
-                    for a, d in zip(r.src, self._mul_vjp(self.saved[node], g, S, want)):  # (`x * x`: x receives two parts)
-                        push(a, d)
-            elif kind == MATMUL:
-                want = tuple(n.op != "placeholder" and self.rule[n].kind != CONST for n in r.src)
-                if any(want):
-                    for a, d in zip(r.src, self._matmul_vjp(self.saved[node], g, S, want)):  # (`x @ x^T`: x receives two parts)
-                        push(a, d)
-            elif kind == SOFTMAX:
-                push(src, self._softmax_vjp(self.saved[node], g, S))
-            elif kind == SCALE:
-                push(src, g / r.args[0])
-            elif kind == NEG:
-                push(src, -g)
-            elif kind == SUB:  # (the minuend receives g, the subtrahend -g; a constant, a number or the input nothing)
-                push(r.src[0], g)
-                sub = r.src[1]
-                if isinstance(sub, fx.Node) and sub.op != "placeholder" and self.rule[sub].kind != CONST:
-                    push(sub, -g)
-            elif kind == CAT:
-                dim, sizes = self.saved[node]
-                off = 0
-                for a, n in zip(r.src, sizes):  # (a node listed twice receives two parts)
-                    push(a, g.narrow(dim, off, n).contiguous())
-                    off += n
-            elif kind == SLICE:
-                dim, start, length, dropped, in_shape = self.saved[node]
-                if isinstance(src, fx.Node) and src.op != "placeholder" and self.rule[src].kind != CONST:
-                    pieces.setdefault(src, []).append((g.unsqueeze(dim) if dropped else g, dim, start, length, in_shape))
-        if remaining:
-            raise SweepUnsupported(f"no cotangent reached {sorted(remaining)}")
-        return grads
+            rule = self._vjp_rule(r)
+            if rule is not None:
+                rule(walk, node, r, g, g2)
+        if walk.remaining:
+            raise SweepUnsupported(f"no cotangent reached {sorted(walk.remaining)}")
+        return walk.grads
+
+    #: kind -> the method that pushes a node's cotangent ``g`` on to its sources, ``(walk, node, r, g, g2)`` (``g2``: the second
+    #: addend of an ACT, which its kernel folds in); ``None``: a kind that has no cotangent by design.  A kind that `classify`
+    #: learns and this table does not know is refused by name (`_vjp_rule`)
+    _VJP = {CONV: "_vjp_conv", LINEAR: "_vjp_linear", BN: "_vjp_bn", NORM: "_vjp_norm", ACT: "_vjp_act", IDENTITY: "_vjp_identity",
+            RESHAPE: "_vjp_reshape", GPOOL: "_vjp_gpool", AVGPOOL: "_vjp_avgpool", MAXPOOL: "_vjp_maxpool", MEAN: "_vjp_mean",
+            ATTN: "_vjp_attn", PERMUTE: "_vjp_permute", ADD: "_vjp_add", MUL: "_vjp_mul", MATMUL: "_vjp_matmul",
+            SOFTMAX: "_vjp_softmax", SCALE: "_vjp_scale", NEG: "_vjp_neg", SUB: "_vjp_sub", CAT: "_vjp_cat", SLICE: "_vjp_slice",
+            SIZE: None, GETITEM: None, SPLIT: None, CONST: None, "placeholder": None, "output": None}
+
+    def _vjp_rule(self, r):
+        """the bound method of `_VJP` for the rule ``r`` (``None``: nothing to push), or the refusal that names the operation"""
+        try:
+            name = self._VJP[r.kind]
+        except KeyError:
+            raise SweepUnsupported(f"no reverse rule for {r.what} (kind {r.kind!r})") from None
+        return None if name is None else getattr(self, name)
+
+    def _vjp_conv(self, walk, node, r, g, g2):
+        in_shape = (walk.S * walk.B,) + tuple(self.saved[node][1:])
+        walk.push(r.src[0], self._conv_input_grad(in_shape, r.mod, g,
+                                                  self._scaled_weight(node.target, r.mod, walk.pending_scale.get(node))))
+
+    def _vjp_linear(self, walk, node, r, g, g2):
+        walk.push(r.src[0], g @ r.mod.weight)
+
+    def _vjp_bn(self, walk, node, r, g, g2):
+        src, scale = r.src[0], self._bn_scale(node.target, r.mod)
+        if walk.defer_bn_scale and self._defers_scale_to(src, walk.cot):
+            walk.pending_scale[src] = scale  # the conv sees the unscaled cotangent (see the docstring of `backward`)
+            walk.push(src, g)
+        else:
+            walk.push(src, self._scale_mask(g, walk.S, None, scale))
+
+    def _vjp_norm(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._norm_vjp(r.mod, self.saved[node], g, walk.S))
+
+    def _vjp_act(self, walk, node, r, g, g2):
+        scale, dst = self._fold_bn(r.src[0])
+        walk.push(dst, self._scale_mask(g, walk.S, self._act_mult(r.flavour, self.saved[node]), scale, g2))
+
+    def _vjp_identity(self, walk, node, r, g, g2):
+        walk.push(r.src[0], g)
+
+    def _vjp_reshape(self, walk, node, r, g, g2, as_map=None):
+        """``as_map``: what the NHWC walk makes of a 4-D result (a feature map again)"""
+        g = g.reshape((walk.S * walk.B,) + tuple(self.saved[node][1:]))
+        walk.push(r.src[0], as_map(g) if as_map is not None and g.dim() == 4 else g)
+
+    def _vjp_gpool(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._adaptive_avgpool_vjp(g, self.saved[node], walk.S * walk.B))
+
+    def _vjp_avgpool(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._avgpool_vjp(g, self.saved[node], walk.S * walk.B, *r.args))
+
+    def _vjp_maxpool(self, walk, node, r, g, g2):
+        idx, shp = self.saved[node]
+        walk.push(r.src[0], self._maxpool_vjp(g, idx, shp, walk.S, walk.B))
+
+    def _vjp_mean(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._mean_vjp(g, self.saved[node], walk.S * walk.B))
+
+    def _vjp_attn(self, walk, node, r, g, g2):
+        for a, d in zip(r.src, self._attn_vjp(self.saved[node], g, walk.S)):
+            walk.push(a, d)
+
+    def _vjp_permute(self, walk, node, r, g, g2):
+        walk.push(r.src[0], g.permute(self.saved[node]))
+
+    def _vjp_add(self, walk, node, r, g, g2):
+        for a in r.src:
+            walk.push(a, g)
+
+    def _vjp_mul(self, walk, node, r, g, g2):
+        want = tuple(walk.live(n) for n in r.src)
+        if any(want):
+            for a, d in zip(r.src, self._mul_vjp(self.saved[node], g, walk.S, want)):  # (`x * x`: x receives two parts)
+                walk.push(a, d)
+
+    def _vjp_matmul(self, walk, node, r, g, g2):
+        want = tuple(walk.live(n) for n in r.src)
+        if any(want):
+            for a, d in zip(r.src, self._matmul_vjp(self.saved[node], g, walk.S, want)):  # (`x @ x^T`: x receives two parts)
+                walk.push(a, d)
+
+    def _vjp_softmax(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._softmax_vjp(self.saved[node], g, walk.S))
+
+    def _vjp_scale(self, walk, node, r, g, g2):
+        walk.push(r.src[0], g / r.args[0])
+
+    def _vjp_neg(self, walk, node, r, g, g2):
+        walk.push(r.src[0], -g)
+
+    def _vjp_sub(self, walk, node, r, g, g2):
+        """the minuend receives g, the subtrahend -g; a constant, a number or the input nothing"""
+        walk.push(r.src[0], g)
+        if walk.live(r.src[1]):
+            walk.push(r.src[1], -g)
+
+    def _vjp_cat(self, walk, node, r, g, g2):
+        dim, sizes = self.saved[node]
+        off = 0
+        for a, n in zip(r.src, sizes):  # (a node listed twice receives two parts)
+            walk.push(a, g.narrow(dim, off, n).contiguous())
+            off += n
+
+    def _vjp_slice(self, walk, node, r, g, g2):
+        dim, start, length, dropped, in_shape = self.saved[node]
+        if walk.live(r.src[0]):
+            walk.pieces.setdefault(r.src[0], []).append((g.unsqueeze(dim) if dropped else g, dim, start, length, in_shape))
 
     def release(self):
         self.saved = {}

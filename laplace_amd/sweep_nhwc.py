@@ -40,7 +40,7 @@ from torch import nn
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
 from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, GETITEM, GPOOL, IDENTITY, LINEAR, MATMUL, MAXPOOL, MEAN, MUL, NEG, NORM,
-                               PERMUTE, RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SUB, SeedBatchedSweep, SweepUnsupported)
+                               PERMUTE, RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SUB, SeedBatchedSweep, SweepUnsupported, _sum, _Walk)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
@@ -54,8 +54,13 @@ _FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP, SLICE_MAP, GATE_MAP} | _POOL  # pr
 _MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, SLICE_MAP, GATE_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
 # a graph with one of these runs through the NCHW sweep (MUL: unless ``nhwc_mul`` serves it as a squeeze-and-excitation gate on
 # csrc/lk_gate.hip, or both its operands lie in the head region)
-_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE}
+_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE, NEG, SUB}
 _GATE_CHAIN = {CONV, LINEAR, ACT, IDENTITY, RESHAPE}  # what the branch from the pooled tensor to a served gate may hold
+# kinds the head region holds too (plain tensors after the flatten): a node of these whose parts are all plain tensors, and that is
+# no served gate, runs the parent's rule for its kind (`SplitSweep._head_vjp`).  The value: the refusal where another part reaches
+# it; ``None``: the NHWC table has a rule for feature maps
+_HEAD = {LINEAR: "Linear layer inside the NHWC region", NORM: None, ACT: None, CAT: None, SLICE: None,
+         MUL: "product of a feature map outside the gate rule of the NHWC region", RESHAPE: "reshape inside the NHWC region"}
 
 
 class _F32:
@@ -152,6 +157,57 @@ def _materialize(parts):
             first = first if first is not None else p
         out.append(p)
     return out
+
+
+def _as_f32(parts):
+    """the parts as plain fp32 NHWC tensors: a split tensor converted, an fp32 map as it lies"""
+    return [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
+
+
+def _run_deferred(fns):
+    """deferred strided branches that nothing else joins: the first makes the fp32 tensor, the others add into it"""
+    part = fns[0](None)
+    for fn in fns[1:]:
+        fn(part)
+    return part
+
+
+class _NhwcWalk(_Walk):
+    """The state of one reverse walk of :class:`SplitSweep`: the parent's, and what the NHWC rules share."""
+
+    def __init__(self, sweep, seeds, on_tap, defer_bn_scale, keep_split):
+        super().__init__(sweep, seeds, on_tap, defer_bn_scale)
+        self.keep_split, self.K = keep_split, sweep.kernels()
+        # conv taps whose own gradient is owed a BatchNorm scale that the CALLER did not ask to receive (a tapped BatchNorm left
+        # it to the backward-data launch): applied in the conversion at the end, never handed out through ``grad_scale``
+        self.own_scale: set = set()
+        self.owed: dict[str, torch.Tensor] = {}
+        self.norm_names: set = set()  # taps that leave in NHWC form whatever the caller asked for
+        self.deferred: dict[fx.Node, list] = {}  # node -> strided 1x1 branches waiting for the main branch's tensor
+        self.mult_cache: dict = {}  # activation node -> its NHWC multiplier (`SplitSweep._nhwc_mult`)
+        # zeroed max|.| words of this sweep's conv outputs (one fill per 64 of them)
+        self._words, self._word_i = torch.zeros(64, dtype=torch.float32, device=seeds.device), 0
+
+    def new_word(self):
+        if self._word_i == self._words.numel():
+            self._words, self._word_i = torch.zeros_like(self._words), 0
+        self._word_i += 1
+        return self._words[self._word_i - 1:self._word_i]
+
+    def push(self, n, part):
+        if not isinstance(n, fx.Node) or n.op == "placeholder":  # (no CONST test: such a graph never takes this walk, `_NO_RULE`)
+            return
+        if isinstance(part, _LazyConv) and n in self.deferred:
+            part = part.f32()
+        if isinstance(part, _F32) and n in self.deferred:
+            for fn in self.deferred.pop(n):  # strided 1x1 branches waiting for the main branch's tensor: add into it
+                fn(part)
+        self.cot.setdefault(n, []).append(part)
+
+    def feature_f32(self, t4_nchw_like):
+        """fp32 [S*B, C, H, W]-shaped tensor -> NHWC _F32"""
+        t = t4_nchw_like.permute(0, 2, 3, 1).contiguous()
+        return _F32(t, self.K.absmax(t))
 
 
 class SplitSweep(SeedBatchedSweep):
@@ -815,9 +871,9 @@ class SplitSweep(SeedBatchedSweep):
             self._amax_cache[key] = hit
         return hit[1]
 
-    def _nhwc_mult(self, node, flavour):
+    def _nhwc_mult(self, walk, node, flavour):
         """per-sample multiplier of an activation as an NHWC tensor (+ its max| | word for generic derivatives)"""
-        hit = self._mult_cache.get(node)
+        hit = walk.mult_cache.get(node)
         if hit is None:
             saved = self.saved[node]
             mult = self._act_mult(flavour, saved)
@@ -831,12 +887,12 @@ class SplitSweep(SeedBatchedSweep):
                 if flavour == "generic":  # tanh' and sigmoid' are bounded by 1; anything else is measured
                     amax = self.kernels().absmax(mult)
             hit = (mult, amax)
-            self._mult_cache[node] = hit
+            walk.mult_cache[node] = hit
         return hit
 
-    def _to_split(self, parts, S, mult=None, mult_amax=None, scale=None, scale_amax=None):
+    def _to_split(self, walk, parts, mult=None, mult_amax=None, scale=None, scale_amax=None):
         """sum of cotangent parts (x multiplier x channel scale) -> one SplitTensor"""
-        K = self.kernels()
+        K, S = self.kernels(), walk.S
         lazy = [p for p in parts if isinstance(p, _LazyConv)]
         if lazy:
             rest = [p for p in parts if not isinstance(p, _LazyConv)]
@@ -846,11 +902,10 @@ class SplitSweep(SeedBatchedSweep):
                     and cv.strided_taps([p.desc for p in strided], strided[0].hw) is not None):
                 return cv.conv_backward_data_vjp_strided(
                     [p.desc for p in strided], strided[0].hw, add=rest[0] if rest else None, mult=mult, mult_amax=mult_amax,
-                    scale=scale, scale_amax=scale_amax, amax_word=self._new_word() if self._new_word is not None else None)
+                    scale=scale, scale_amax=scale_amax, amax_word=walk.new_word())
             if len(lazy) == 1 and not strided and lazy[0]._done is None and len(rest) <= 1 and all(isinstance(p, SplitTensor) for p in rest):
                 return lazy[0].fused(add=rest[0] if rest else None, mult=mult, mult_amax=mult_amax, scale=scale,
-                                     scale_amax=scale_amax,
-                                     amax_word=self._new_word() if self._new_word is not None else None)
+                                     scale_amax=scale_amax, amax_word=walk.new_word())
             parts = _materialize(parts)
         f32 = [p for p in parts if isinstance(p, _F32)]
         spl = [p for p in parts if isinstance(p, SplitTensor)]
@@ -876,8 +931,6 @@ class SplitSweep(SeedBatchedSweep):
                                 scale_amax, S, tuple(shape))
 
     # ---- reverse sweep ------------------------------------------------------------------------------------------------
-    _new_word = None  # zeroed device words of the running sweep (one fill per 64 of them)
-
     @torch.no_grad()
     def backward(self, seeds, on_tap=None, defer_bn_scale: bool = False, keep_split: bool = False):
         """``keep_split``: hand conv-tap gradients back as NHWC SplitTensors (consumers with their own kernels for
@@ -885,347 +938,283 @@ class SplitSweep(SeedBatchedSweep):
         form: the unscaled SplitTensor of a BatchNorm's output cotangent, a :class:`NhwcNormGrad` for a GroupNorm."""
         if not self.split_ok:
             return super().backward(seeds, on_tap=on_tap, defer_bn_scale=defer_bn_scale)
-        K = self.kernels()
-        self.grad_scale = {}
-        self._mult_cache = {}
-        pending_scale: dict[fx.Node, torch.Tensor] = {}
-        # conv taps whose own gradient is owed a BatchNorm scale that the CALLER did not ask to receive (a tapped BatchNorm left
-        # it to the backward-data launch): applied in the conversion at the end, never handed out through ``grad_scale``
-        own_scale: set = set()
-        owed: dict[str, torch.Tensor] = {}
-        norm_names: set = set()
-        deferred: dict[fx.Node, list] = {}
-        S, B = seeds.shape[0], seeds.shape[1]
-        SB = S * B
-        cot: dict[fx.Node, list] = {self.out_node: [seeds.reshape(SB, *seeds.shape[2:])]}
-        grads: dict = {}
-        remaining = set(self.tap_names)
-        words = torch.zeros(64, dtype=torch.float32, device=seeds.device)  # max|.| words of this sweep's conv outputs
-        word_i = [0]
-
-        def new_word():
-            nonlocal words
-            if word_i[0] == words.numel():
-                words = torch.zeros(64, dtype=torch.float32, device=seeds.device)
-                word_i[0] = 0
-            w = words[word_i[0]:word_i[0] + 1]
-            word_i[0] += 1
-            return w
-
-        self._new_word = new_word
-        # per node: what its SLICE consumers hand back, ``(part, dim, start, length, input shape)``, assembled with the full-width
-        # parts ONCE, when the node itself is reached
-        pieces: dict[fx.Node, list] = {}
-
-        def push(n, part):
-            if not isinstance(n, fx.Node) or n.op == "placeholder":
-                return
-            if isinstance(part, _LazyConv) and n in deferred:
-                part = part.f32()
-            if isinstance(part, _F32) and n in deferred:
-                for fn in deferred.pop(n):  # strided 1x1 branches waiting for the main branch's tensor: add into it
-                    fn(part)
-            cot.setdefault(n, []).append(part)
-
-        def feature_f32(t4_nchw_like):
-            """fp32 [S*B, C, H, W]-shaped tensor -> NHWC _F32"""
-            t = t4_nchw_like.permute(0, 2, 3, 1).contiguous()
-            return _F32(t, K.absmax(t))
-
+        walk = _NhwcWalk(self, seeds, on_tap, defer_bn_scale, keep_split)
+        self.grad_scale = walk.grad_scale
         for node, r in reversed(self.rule.items()):
-            if node in deferred and node not in cot:
-                # nothing else reached this node: the deferred branches produce the cotangent on their own
-                fns = deferred.pop(node)
-                part = fns[0](None)
-                for fn in fns[1:]:
-                    fn(part)
-                cot[node] = [part]
-            if node not in cot and node not in pieces:
-                continue
-            parts = cot.pop(node, [])
-            kind, m, src = r.kind, r.mod, r.src[0]
-            if node in deferred or node in pieces or kind not in _LAZY:
-                parts = _materialize(parts)
-            if node in pieces:
-                pcs = pieces.pop(node)
-                if torch.is_tensor(pcs[0][0]):
-                    # slices in the head region (plain tensors after the flatten): parent-class math
-                    parts = [self._assemble_slices(parts, [p[:4] for p in pcs], (SB,) + tuple(pcs[0][4][1:]))]
-                else:
-                    # ONE launch: the full-width parts and the channel pieces, as they lie, summed into an fp32 map with its max|.|
-                    Ct = int(pcs[0][4][1])
-                    ops = [(p if isinstance(p, SplitTensor) else p.t, 0, Ct) for p in parts]
-                    ops += [(p if isinstance(p, SplitTensor) else p.t, start, length) for p, _, start, length, _ in pcs]
-                    shape, word = (SB, int(pcs[0][4][2]), int(pcs[0][4][3]), Ct), new_word()
-                    t = self.slice_vjp_launches(K, ops, shape[0] * shape[1] * shape[2], Ct, amax=word)
-                    parts = [_F32(t.reshape(shape), word)]
-            if node in deferred:
-                f32p = [p for p in parts if isinstance(p, _F32)]
-                fns = deferred.pop(node)
-                if f32p:
-                    for fn in fns:
-                        fn(f32p[0])
-                else:
-                    part = fns[0](None)
-                    for fn in fns[1:]:
-                        fn(part)
-                    parts.append(part)
-            if kind == CONV:
-                g = self._to_split(parts, S)
-                if node.target in self.tap_names:
-                    grads[node.target] = g
-                    if node in own_scale:
-                        owed[node.target] = pending_scale[node]
-                    elif node in pending_scale:
-                        self.grad_scale[node.target] = pending_scale[node]
-                    if on_tap is not None:
-                        on_tap(node.target, g)
-                    remaining.discard(node.target)
-                    if not remaining:
-                        break
-                if src.op == "placeholder":
-                    continue
-                if self._is_depthwise(m):
-                    # one launch for all seeds into fp32 (lk_dwconv_bwd_nhwc_f16x2): no lazy part, no fused epilogue
-                    prep = self._prep.get(node.target)
-                    if prep is None:
-                        prep = self._prep[node.target] = cv.PreparedDepthwise(m)
-                    in_shape, word = self.saved[node], new_word()  # [B, C, Hin, Win]
-                    push(src, _F32(K.dwconv_backward(g, prep.w_tap, S, (int(in_shape[2]), int(in_shape[3])), m.kernel_size,
-                                                     m.stride, m.padding, amax=word), word))
-                    continue
-                prep = self._prep.get(node.target)
-                if prep is None:
-                    prep = self._prep[node.target] = cv.PreparedConv(m)
-                in_shape = self.saved[node]  # [B, Cin, Hin, Win]
-                hw = (int(in_shape[2]), int(in_shape[3]))
-                cscale = pending_scale.get(node)
-                sparse = any(not p[4] for p in cv.backward_plan(m, *hw))
-
-                def run(into, g=g, prep=prep, hw=hw, cscale=cscale):
-                    if into is None:
-                        w = new_word()
-                        out = cv.conv_backward_data(prep, g, hw, cscale=cscale, amax_out=w)
-                        return _F32(out, w)
-                    cv.conv_backward_data(prep, g, hw, cscale=cscale, out=into.t, accumulate=True, amax_out=into.amax)
-                    return into
-
-                if (self.fuse_vjp and self.fuse_strided and cv.strided_fused_ok(m, hw) and src not in deferred
-                        and hasattr(K, "conv_nhwc_f16x2_vjp_strided")
-                        and all(isinstance(p, (_LazyStrided, SplitTensor)) for p in cot.get(src, []))):
-                    # (the consumer of the cotangent decides: alone or with the block's other strided branch in one
-                    # fused launch, or — something else joined — class by class into an fp32 tensor)
-                    push(src, _LazyStrided(run, (prep, g, cscale), hw))
-                    continue
-                if src in cot:
-                    cot[src] = _materialize(cot[src])
-                existing = [p for p in cot.get(src, []) if isinstance(p, _F32)]
-                if existing:
-                    run(existing[0])
-                elif sparse and len(src.users) > 1:
-                    deferred.setdefault(src, []).append(run)  # wait for the dense branch, then add into it
-                elif self.fuse_vjp and cv.fused_backward_ok(m) and hasattr(K, "conv_nhwc_f16x2_vjp"):
-                    def run_fused(g=g, prep=prep, hw=hw, cscale=cscale, **kw):
-                        return cv.conv_backward_data_vjp(prep, g, hw, cscale=cscale, **kw)
-
-                    push(src, _LazyConv(lambda run=run: run(None), run_fused))
-                else:
-                    push(src, run(None))
-            elif kind == LINEAR:
-                g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                if not torch.is_tensor(g):
-                    raise SweepUnsupported("Linear layer inside the NHWC region")
-                if node.target in self.tap_names:
-                    grads[node.target] = g.reshape(S, B, *g.shape[1:])
-                    if on_tap is not None:
-                        on_tap(node.target, grads[node.target])
-                    remaining.discard(node.target)
-                    if not remaining:
-                        break
-                push(src, g @ m.weight)
-            elif kind == BN:
-                scale = self._bn_scale(node.target, m)
-                if node.target in self.tap_names:
-                    # the cotangent of the BatchNorm's OWN output, unscaled, as one split tensor: what lk_normtap.hip reads
-                    u = parts[0] if len(parts) == 1 and isinstance(parts[0], SplitTensor) else self._to_split(parts, S)
-                    grads[node.target] = u
-                    norm_names.add(node.target)
-                    if on_tap is not None:
-                        on_tap(node.target, u)
-                    remaining.discard(node.target)
-                    if not remaining:
-                        break
-                    # the scale: left to the source convolution's backward-data launch (no pass over the cotangent) where that
-                    # convolution reads nothing else; a tapped one's own gradient is then owed the scale, which only the fp32
-                    # conversion at the end can pay unasked
-                    rs = self.rule.get(src)
-                    lone = (rs is not None and rs.kind == CONV and len(src.users) == 1 and src not in cot
-                            and not self._is_depthwise(rs.mod))
-                    src_tapped = lone and src.target in self.tap_names
-                    if lone and (not src_tapped or defer_bn_scale or (on_tap is None and not keep_split)):
-                        pending_scale[src] = scale
-                        if src_tapped and not defer_bn_scale:
-                            own_scale.add(src)
-                        push(src, u)
-                    else:
-                        push(src, self._to_split([u], S, scale=scale, scale_amax=self._amax_of(node.target, scale)))
-                elif (defer_bn_scale and self._defers_scale_to(src, cot) and len(parts) == 1
-                        and isinstance(parts[0], SplitTensor)):
-                    pending_scale[src] = scale
-                    push(src, parts[0])
-                else:
-                    push(src, self._to_split(parts, S, scale=scale, scale_amax=self._amax_of(node.target, scale)))
-            elif kind == NORM:
-                if all(torch.is_tensor(p) for p in parts):
-                    # LayerNorm in the head region (plain tensors after the flatten): parent-class math
-                    g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                    push(src, self._norm_vjp(m, self.saved[node], g, S))
-                else:
-                    # the parts as ONE fp32 NHWC tensor (the VJP reads fp32; a kernel that reads split planes is out of scope)
-                    ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
-                    g = ts[0] if len(ts) == 1 else sum(ts[1:], ts[0])
-                    xhat, rstd, G, _ = self.saved[node]
-                    w = None if m.weight is None else m.weight.detach().to(torch.float32).contiguous()
-                    g = g.contiguous()
-                    if node.target in self.tap_names:
-                        # the Jacobian's operands as they lie (layout 1 of lk_jac_norm_affine_f32): no recomputed xhat, no NCHW copy
-                        grads[node.target] = NhwcNormGrad(g, xhat)
-                        norm_names.add(node.target)
-                        if on_tap is not None:
-                            on_tap(node.target, grads[node.target])
-                        remaining.discard(node.target)
-                        if not remaining:
-                            break
-                    word = new_word()
-                    push(src, _F32(K.norm_vjp(g, xhat, rstd, w, S, G, 1, amax=word), word))
-            elif kind in _POOL:
-                # the parts as ONE fp32 NHWC tensor, as the NORM rule (a pool that reads split planes is out of scope)
-                ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
-                g = ts[0] if len(ts) == 1 else sum(ts[1:], ts[0])
-                pp, keep = self.pool_params(r), self.saved[node]
-                arg, shp = keep if kind == MAXPOOL else (None, keep)  # [B, C, H, W]
-                word = new_word()
-                dx = K.pool_vjp(g.contiguous(), arg, S, (int(shp[2]), int(shp[3])), K.POOL_MAX if kind == MAXPOOL else K.POOL_AVG,
-                                pp["kernel"], pp["stride"], pp["padding"], pp["count_include_pad"], pp["divisor_override"],
-                                amax=word)
-                push(src, _F32(dx, word))
-            elif kind == ACT:
-                scale, dst = self._fold_bn(src)
-                if all(torch.is_tensor(p) for p in parts):
-                    # activation in the head region (MLP head after the flatten): parent-class math on plain tensors
-                    g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                    push(dst, self._scale_mask(g, S, self._act_mult(r.flavour, self.saved[node]), scale))
-                else:
-                    mult, mult_amax = self._nhwc_mult(node, r.flavour)
-                    scale_amax = None if scale is None else self._amax_of(src.target, scale)
-                    push(dst, self._to_split(parts, S, mult=mult, mult_amax=mult_amax, scale=scale, scale_amax=scale_amax))
-            elif kind == IDENTITY:
-                for p in parts:
-                    push(src, p)
-            elif kind == ADD:
-                for a in r.src:
-                    for p in parts:
-                        push(a, p)
-            elif kind == CAT:
-                dim, sizes = self.saved[node]
-                if all(torch.is_tensor(p) for p in parts):
-                    # concatenation in the head region (plain tensors after the flatten): parent-class math
-                    g, off = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0]), 0
-                    for a, n in zip(r.src, sizes):
-                        push(a, g.narrow(dim, off, n).contiguous())
-                        off += n
-                else:
-                    if len(parts) > K.CAT_MAX_PARTS:  # the surplus as ONE fp32 tensor (rare: a map read by more than four nodes)
-                        ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts[K.CAT_MAX_PARTS - 1:]]
-                        parts = parts[:K.CAT_MAX_PARTS - 1] + [_F32(sum(ts[1:], ts[0]).contiguous(), None)]
-                    ops, off = [p if isinstance(p, SplitTensor) else p.t for p in parts], 0
-                    for a, n in zip(r.src, sizes):  # one launch per source: its slice of the sum, and max|.| of it
-                        if isinstance(a, fx.Node) and a.op != "placeholder":
-                            word = new_word()
-                            push(a, _F32(K.cat_vjp(ops, off, n, amax=word), word))
-                        off += n
-            elif kind == SLICE:
-                dim, start, length, dropped, in_shape = self.saved[node]
-                if not isinstance(src, fx.Node) or src.op == "placeholder" or self.rule[src].kind == CONST:
-                    continue
-                if all(torch.is_tensor(p) for p in parts):
-                    g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                    pieces.setdefault(src, []).append((g.unsqueeze(dim) if dropped else g, dim, start, length, in_shape))
-                else:  # the parts as they lie (split tensors and fp32 maps): channels [start, start + length) of the source
-                    for p in parts:
-                        pieces.setdefault(src, []).append((p, dim, start, length, in_shape))
-            elif kind == MUL and node not in self._gates:
-                # a product in the head region (plain tensors after the flatten): parent-class math
-                if not all(torch.is_tensor(p) for p in parts):
-                    raise SweepUnsupported("product of a feature map outside the gate rule of the NHWC region")
-                g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                want = tuple(n.op != "placeholder" and self.rule[n].kind != CONST for n in r.src)
-                if any(want):
-                    for a, d in zip(r.src, self._mul_vjp(self.saved[node], g, S, want)):
-                        if d is not None:
-                            push(a, d)
-            elif kind == MUL:
-                # a feature map times its gate (lk_gate.hip).  The cotangent as ONE operand, as it lies (several parts: folded
-                # through fp32, as the NORM rule does)
-                _, x_node, chain = self._gates[node]
-                _, xh, gate = self.saved[node]
-                if len(parts) == 1:
-                    op = parts[0] if isinstance(parts[0], SplitTensor) else parts[0].t
-                else:
-                    ts = [p.float() if isinstance(p, SplitTensor) else p.t for p in parts]
-                    op = sum(ts[1:], ts[0]).contiguous()
-                C = int(xh.shape[3])
-                # ds [S*B, C], the cotangent of the [B, C, 1, 1] gate: one launch for all seeds
-                t = K.gate_reduce(op, xh, S).reshape(SB, C, 1, 1)
-                # the chain back to the pooled tensor on plain [S*B, ...] tensors; its taps leave as the NCHW sweep hands them out
-                for n in reversed(chain[1:]):
-                    rn = self.rule[n]
-                    if rn.kind == ACT:
-                        t = self._scale_mask(t, S, self._act_mult(rn.flavour, self.saved[n]), None)
-                    elif rn.kind in (CONV, LINEAR):
-                        if n.target in self.tap_names:
-                            grads[n.target] = t.reshape(S, B, *t.shape[1:])
-                            if on_tap is not None:
-                                on_tap(n.target, grads[n.target])
-                            remaining.discard(n.target)
-                        w = rn.mod.weight
-                        if rn.kind == CONV:
-                            t = (t.reshape(SB, -1) @ w.reshape(w.shape[0], w.shape[1])).reshape(SB, w.shape[1], 1, 1)
-                        else:
-                            t = t @ w
-                    elif rn.kind == RESHAPE:
-                        t = t.reshape((SB,) + tuple(self.saved[n])[1:])
-                if not remaining:
-                    break
-                if isinstance(x_node, fx.Node) and x_node.op != "placeholder":
-                    # the pooled tensor's cotangent, divided by H W, rides on the gate's VJP: ONE launch writes the map's cotangent
-                    rp = (t.reshape(SB, C) / float(xh.shape[1] * xh.shape[2])).contiguous()
-                    word = new_word()
-                    push(x_node, _F32(K.gate_vjp(op, gate, rp, S, amax=word), word))
-            elif kind == RESHAPE:
-                g = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0])
-                if not torch.is_tensor(g):
-                    raise SweepUnsupported("reshape inside the NHWC region")
-                g = g.reshape((SB,) + tuple(self.saved[node])[1:])
-                push(src, feature_f32(g) if g.dim() == 4 else g)
-            elif kind == GPOOL:
-                shp, p = self.saved[node], parts[0]  # [B, C, H, W]
-                if len(parts) != 1 or not isinstance(p, _F32):
-                    raise SweepUnsupported("global average pooling expects one fp32 cotangent")
-                H, W = int(shp[-2]), int(shp[-1])
-                t = (p.t / (H * W)).expand(SB, H, W, p.t.shape[-1]).contiguous()
-                push(src, _F32(t, K.absmax(t)))
-            else:
-                raise SweepUnsupported(f"no NHWC rule for {r.what}")
-        self._new_word = None
-        if remaining:
-            raise SweepUnsupported(f"no cotangent reached {sorted(remaining)}")
+            parts = self._nhwc_parts(walk, node, r)
+            if parts is not None and self._nhwc_vjp_rule(node, r, parts)(walk, node, r, parts):
+                break  # (a rule returns ``True`` when its tap was the last one owed)
+        if walk.remaining:
+            raise SweepUnsupported(f"no cotangent reached {sorted(walk.remaining)}")
+        grads = walk.grads
         if on_tap is None and not keep_split:
             # consumers that read the gradients as tensors (Jacobians, diagonal, predictive): [S, B, C, H, W] fp32
             for name, g in list(grads.items()):
-                if isinstance(g, SplitTensor) and name not in norm_names:
+                if isinstance(g, SplitTensor) and name not in walk.norm_names:
                     t = g.float()
-                    if name in owed:
-                        t = t * owed[name]  # (channels are the last dim here)
-                    grads[name] = t.reshape(S, B, *g.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
+                    if name in walk.owed:
+                        t = t * walk.owed[name]  # (channels are the last dim here)
+                    grads[name] = t.reshape(walk.S, walk.B, *g.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
         return grads
+
+    def _nhwc_parts(self, walk, node, r):
+        """the cotangent parts of ``node`` as its rule takes them, or ``None`` where no cotangent reached it: deferred strided
+        branches run or added in, lazy convolutions materialised for every kind but `_LAZY`, the pieces of its SLICE consumers
+        assembled with the full-width parts"""
+        cot, deferred, pieces = walk.cot, walk.deferred, walk.pieces
+        if node in deferred and node not in cot:
+            # nothing else reached this node: the deferred branches produce the cotangent on their own
+            cot[node] = [_run_deferred(deferred.pop(node))]
+        if node not in cot and node not in pieces:
+            return None
+        parts = cot.pop(node, [])
+        if node in deferred or node in pieces or r.kind not in _LAZY:
+            parts = _materialize(parts)
+        if node in pieces:
+            pcs = pieces.pop(node)
+            SB = walk.S * walk.B
+            if torch.is_tensor(pcs[0][0]):
+                # slices in the head region (plain tensors after the flatten): parent-class math
+                parts = [self._assemble_slices(parts, [p[:4] for p in pcs], (SB,) + tuple(pcs[0][4][1:]))]
+            else:
+                # ONE launch: the full-width parts and the channel pieces, as they lie, summed into an fp32 map with its max|.|
+                Ct = int(pcs[0][4][1])
+                ops = [(p if isinstance(p, SplitTensor) else p.t, 0, Ct) for p in parts]
+                ops += [(p if isinstance(p, SplitTensor) else p.t, start, length) for p, _, start, length, _ in pcs]
+                shape, word = (SB, int(pcs[0][4][2]), int(pcs[0][4][3]), Ct), walk.new_word()
+                t = self.slice_vjp_launches(walk.K, ops, shape[0] * shape[1] * shape[2], Ct, amax=word)
+                parts = [_F32(t.reshape(shape), word)]
+        if node in deferred:
+            f32p = [p for p in parts if isinstance(p, _F32)]
+            fns = deferred.pop(node)
+            if f32p:
+                for fn in fns:
+                    fn(f32p[0])
+            else:
+                parts.append(_run_deferred(fns))
+        return parts
+
+    #: kind -> the method that pushes a node's cotangent parts on to its sources, ``(walk, node, r, parts) -> True`` when its tap
+    #: was the last one the walk owed.  The kinds of `_HEAD` that are missing here live in the head region only
+    _NHWC_VJP = {CONV: "_nhwc_vjp_conv", BN: "_nhwc_vjp_bn", NORM: "_nhwc_vjp_norm", MAXPOOL: "_nhwc_vjp_pool",
+                 AVGPOOL: "_nhwc_vjp_pool", ACT: "_nhwc_vjp_act", IDENTITY: "_nhwc_vjp_identity", ADD: "_nhwc_vjp_add",
+                 CAT: "_nhwc_vjp_cat", SLICE: "_nhwc_vjp_slice", MUL: "_nhwc_vjp_gate", GPOOL: "_nhwc_vjp_gpool"}
+
+    def _nhwc_vjp_rule(self, node, r, parts):
+        """the bound method that serves ``node``: the head-region fallback, its rule of `_NHWC_VJP`, or the refusal by name"""
+        if r.kind in _HEAD and node not in self._gates:
+            if all(torch.is_tensor(p) for p in parts):
+                return self._head_vjp
+            if _HEAD[r.kind] is not None:
+                raise SweepUnsupported(_HEAD[r.kind])
+        name = self._NHWC_VJP.get(r.kind)
+        if name is None:
+            raise SweepUnsupported(f"no NHWC rule for {r.what}")
+        return getattr(self, name)
+
+    def _head_vjp(self, walk, node, r, parts):
+        """a node of the head region (plain tensors after the flatten): the parent's rule for its kind on the sum of the parts
+        (an activation without a second addend; a 4-D result of a reshape is a feature map again)"""
+        g = _sum(parts)
+        if r.mod is not None and node.target in self.tap_names and walk.tap(node.target, g.reshape(walk.S, walk.B, *g.shape[1:])):
+            return True
+        if r.kind == RESHAPE:
+            self._vjp_reshape(walk, node, r, g, None, as_map=walk.feature_f32)
+        else:
+            self._vjp_rule(r)(walk, node, r, g, None)
+
+    def _nhwc_vjp_conv(self, walk, node, r, parts):
+        m, src, K = r.mod, r.src[0], walk.K
+        g = self._to_split(walk, parts)
+        if node.target in self.tap_names:
+            if node in walk.own_scale:
+                walk.owed[node.target] = walk.pending_scale[node]
+            elif node in walk.pending_scale:
+                walk.grad_scale[node.target] = walk.pending_scale[node]
+            if walk.tap(node.target, g):
+                return True
+        if src.op == "placeholder":
+            return
+        if self._is_depthwise(m):
+            # one launch for all seeds into fp32 (lk_dwconv_bwd_nhwc_f16x2): no lazy part, no fused epilogue
+            prep = self._prep.get(node.target)
+            if prep is None:
+                prep = self._prep[node.target] = cv.PreparedDepthwise(m)
+            in_shape, word = self.saved[node], walk.new_word()  # [B, C, Hin, Win]
+            walk.push(src, _F32(K.dwconv_backward(g, prep.w_tap, walk.S, (int(in_shape[2]), int(in_shape[3])), m.kernel_size,
+                                                  m.stride, m.padding, amax=word), word))
+            return
+        prep = self._prep.get(node.target)
+        if prep is None:
+            prep = self._prep[node.target] = cv.PreparedConv(m)
+        in_shape = self.saved[node]  # [B, Cin, Hin, Win]
+        hw = (int(in_shape[2]), int(in_shape[3]))
+        cscale = walk.pending_scale.get(node)
+        sparse = any(not p[4] for p in cv.backward_plan(m, *hw))
+
+        def run(into):
+            if into is None:
+                w = walk.new_word()
+                out = cv.conv_backward_data(prep, g, hw, cscale=cscale, amax_out=w)
+                return _F32(out, w)
+            cv.conv_backward_data(prep, g, hw, cscale=cscale, out=into.t, accumulate=True, amax_out=into.amax)
+            return into
+
+        cot, deferred = walk.cot, walk.deferred
+        if (self.fuse_vjp and self.fuse_strided and cv.strided_fused_ok(m, hw) and src not in deferred
+                and hasattr(K, "conv_nhwc_f16x2_vjp_strided")
+                and all(isinstance(p, (_LazyStrided, SplitTensor)) for p in cot.get(src, []))):
+            # (the consumer of the cotangent decides: alone or with the block's other strided branch in one
+            # fused launch, or — something else joined — class by class into an fp32 tensor)
+            walk.push(src, _LazyStrided(run, (prep, g, cscale), hw))
+            return
+        if src in cot:
+            cot[src] = _materialize(cot[src])
+        existing = [p for p in cot.get(src, []) if isinstance(p, _F32)]
+        if existing:
+            run(existing[0])
+        elif sparse and len(src.users) > 1:
+            deferred.setdefault(src, []).append(run)  # wait for the dense branch, then add into it
+        elif self.fuse_vjp and cv.fused_backward_ok(m) and hasattr(K, "conv_nhwc_f16x2_vjp"):
+            def run_fused(**kw):
+                return cv.conv_backward_data_vjp(prep, g, hw, cscale=cscale, **kw)
+
+            walk.push(src, _LazyConv(lambda: run(None), run_fused))
+        else:
+            walk.push(src, run(None))
+
+    def _nhwc_vjp_bn(self, walk, node, r, parts):
+        src, scale = r.src[0], self._bn_scale(node.target, r.mod)
+        if node.target in self.tap_names:
+            # the cotangent of the BatchNorm's OWN output, unscaled, as one split tensor: what lk_normtap.hip reads
+            u = parts[0] if len(parts) == 1 and isinstance(parts[0], SplitTensor) else self._to_split(walk, parts)
+            walk.norm_names.add(node.target)
+            if walk.tap(node.target, u):
+                return True
+            # the scale: left to the source convolution's backward-data launch (no pass over the cotangent) where that
+            # convolution reads nothing else; a tapped one's own gradient is then owed the scale, which only the fp32
+            # conversion at the end can pay unasked
+            rs = self.rule.get(src)
+            lone = (rs is not None and rs.kind == CONV and len(src.users) == 1 and src not in walk.cot
+                    and not self._is_depthwise(rs.mod))
+            src_tapped = lone and src.target in self.tap_names
+            if lone and (not src_tapped or walk.defer_bn_scale or (walk.on_tap is None and not walk.keep_split)):
+                walk.pending_scale[src] = scale
+                if src_tapped and not walk.defer_bn_scale:
+                    walk.own_scale.add(src)
+                walk.push(src, u)
+            else:
+                walk.push(src, self._to_split(walk, [u], scale=scale, scale_amax=self._amax_of(node.target, scale)))
+        elif (walk.defer_bn_scale and self._defers_scale_to(src, walk.cot) and len(parts) == 1
+                and isinstance(parts[0], SplitTensor)):
+            walk.pending_scale[src] = scale
+            walk.push(src, parts[0])
+        else:
+            walk.push(src, self._to_split(walk, parts, scale=scale, scale_amax=self._amax_of(node.target, scale)))
+
+    def _nhwc_vjp_norm(self, walk, node, r, parts):
+        """GroupNorm on a feature map: the parts as ONE fp32 NHWC tensor (the VJP reads fp32; a kernel that reads split planes is
+        out of scope)"""
+        m = r.mod
+        g = _sum(_as_f32(parts)).contiguous()
+        xhat, rstd, G, _ = self.saved[node]
+        w = None if m.weight is None else m.weight.detach().to(torch.float32).contiguous()
+        if node.target in self.tap_names:
+            # the Jacobian's operands as they lie (layout 1 of lk_jac_norm_affine_f32): no recomputed xhat, no NCHW copy
+            walk.norm_names.add(node.target)
+            if walk.tap(node.target, NhwcNormGrad(g, xhat)):
+                return True
+        word = walk.new_word()
+        walk.push(r.src[0], _F32(walk.K.norm_vjp(g, xhat, rstd, w, walk.S, G, 1, amax=word), word))
+
+    def _nhwc_vjp_pool(self, walk, node, r, parts):
+        """max / average pooling: the parts as ONE fp32 NHWC tensor, as the NORM rule (a pool that reads split planes is out of
+        scope)"""
+        K, is_max = walk.K, r.kind == MAXPOOL
+        g = _sum(_as_f32(parts))
+        pp, keep = self.pool_params(r), self.saved[node]
+        arg, shp = keep if is_max else (None, keep)  # [B, C, H, W]
+        word = walk.new_word()
+        dx = K.pool_vjp(g.contiguous(), arg, walk.S, (int(shp[2]), int(shp[3])), K.POOL_MAX if is_max else K.POOL_AVG,
+                        pp["kernel"], pp["stride"], pp["padding"], pp["count_include_pad"], pp["divisor_override"], amax=word)
+        walk.push(r.src[0], _F32(dx, word))
+
+    def _nhwc_vjp_act(self, walk, node, r, parts):
+        scale, dst = self._fold_bn(r.src[0])
+        mult, mult_amax = self._nhwc_mult(walk, node, r.flavour)
+        scale_amax = None if scale is None else self._amax_of(r.src[0].target, scale)
+        walk.push(dst, self._to_split(walk, parts, mult=mult, mult_amax=mult_amax, scale=scale, scale_amax=scale_amax))
+
+    def _nhwc_vjp_identity(self, walk, node, r, parts):
+        for p in parts:
+            walk.push(r.src[0], p)
+
+    def _nhwc_vjp_add(self, walk, node, r, parts):
+        for a in r.src:
+            for p in parts:
+                walk.push(a, p)
+
+    def _nhwc_vjp_cat(self, walk, node, r, parts):
+        """concatenation of feature maps: one launch per source writes its channel slice of the sum of the parts, as they lie"""
+        K = walk.K
+        dim, sizes = self.saved[node]
+        if len(parts) > K.CAT_MAX_PARTS:  # the surplus as ONE fp32 tensor (rare: a map read by more than four nodes)
+            parts = parts[:K.CAT_MAX_PARTS - 1] + [_F32(_sum(_as_f32(parts[K.CAT_MAX_PARTS - 1:])).contiguous(), None)]
+        ops, off = [p if isinstance(p, SplitTensor) else p.t for p in parts], 0
+        for a, n in zip(r.src, sizes):  # one launch per source: its slice of the sum, and max|.| of it
+            if walk.live(a):
+                word = walk.new_word()
+                walk.push(a, _F32(K.cat_vjp(ops, off, n, amax=word), word))
+            off += n
+
+    def _nhwc_vjp_slice(self, walk, node, r, parts):
+        """channel slice of a feature map: the parts as they lie (split tensors and fp32 maps) are channels
+        [start, start + length) of the source"""
+        dim, start, length, dropped, in_shape = self.saved[node]
+        if walk.live(r.src[0]):
+            for p in parts:
+                walk.pieces.setdefault(r.src[0], []).append((p, dim, start, length, in_shape))
+
+    def _nhwc_vjp_gate(self, walk, node, r, parts):
+        """a feature map times its gate (lk_gate.hip).  The cotangent as ONE operand, as it lies (several parts: folded through
+        fp32, as the NORM rule does)"""
+        K, S, SB = walk.K, walk.S, walk.S * walk.B
+        _, x_node, chain = self._gates[node]
+        _, xh, gate = self.saved[node]
+        if len(parts) == 1:
+            op = parts[0] if isinstance(parts[0], SplitTensor) else parts[0].t
+        else:
+            op = _sum(_as_f32(parts)).contiguous()
+        C = int(xh.shape[3])
+        # ds [S*B, C], the cotangent of the [B, C, 1, 1] gate: one launch for all seeds
+        t = K.gate_reduce(op, xh, S).reshape(SB, C, 1, 1)
+        # the chain back to the pooled tensor on plain [S*B, ...] tensors; its taps leave as the NCHW sweep hands them out
+        for n in reversed(chain[1:]):
+            rn = self.rule[n]
+            if rn.kind == ACT:
+                t = self._scale_mask(t, S, self._act_mult(rn.flavour, self.saved[n]), None)
+            elif rn.kind in (CONV, LINEAR):
+                if n.target in self.tap_names:
+                    walk.tap(n.target, t.reshape(S, walk.B, *t.shape[1:]))
+                w = rn.mod.weight
+                if rn.kind == CONV:
+                    t = (t.reshape(SB, -1) @ w.reshape(w.shape[0], w.shape[1])).reshape(SB, w.shape[1], 1, 1)
+                else:
+                    t = t @ w
+            elif rn.kind == RESHAPE:
+                t = t.reshape((SB,) + tuple(self.saved[n])[1:])
+        if not walk.remaining:
+            return True  # (only after the whole chain: every tap of it has left)
+        if walk.live(x_node):
+            # the pooled tensor's cotangent, divided by H W, rides on the gate's VJP: ONE launch writes the map's cotangent
+            rp = (t.reshape(SB, C) / float(xh.shape[1] * xh.shape[2])).contiguous()
+            word = walk.new_word()
+            walk.push(x_node, _F32(K.gate_vjp(op, gate, rp, S, amax=word), word))
+
+    def _nhwc_vjp_gpool(self, walk, node, r, parts):
+        shp, p = self.saved[node], parts[0]  # [B, C, H, W]
+        if len(parts) != 1 or not isinstance(p, _F32):
+            raise SweepUnsupported("global average pooling expects one fp32 cotangent")
+        H, W = int(shp[-2]), int(shp[-1])
+        t = (p.t / (H * W)).expand(walk.S * walk.B, H, W, p.t.shape[-1]).contiguous()
+        walk.push(r.src[0], _F32(t, walk.K.absmax(t)))

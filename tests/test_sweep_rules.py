@@ -162,3 +162,83 @@ def test_adaptive_pooling_to_several_cells_keeps_the_nhwc_walk_off_in_either_spe
             assert not s.split_ok and "adaptive pooling to more than one cell" in s.split_reason
     finally:
         _lib.set_kernels_for_testing(prev)
+
+
+# ---- the rule tables of the two reverse walks (``SeedBatchedSweep._VJP``; ``SplitSweep._NHWC_VJP`` and the head-region fallback) ----
+# every kind constant of sweep.py (its public upper-case strings), and the two fx ops that are their own kind
+KINDS = sorted(v for k, v in vars(sw_mod).items() if k.isupper() and not k.startswith("_") and isinstance(v, str)) + ["placeholder", "output"]
+
+
+def test_every_kind_has_an_entry_in_the_parents_table():
+    assert len(KINDS) == 28 and len(set(KINDS)) == 28  # (26 constants: a new one is found by name, not listed here)
+    table = SeedBatchedSweep._VJP
+    assert set(KINDS) <= set(table), sorted(set(KINDS) - set(table))
+    for kind, name in table.items():  # a method that exists, or the explicit "no cotangent by design"
+        assert name is None or callable(getattr(SeedBatchedSweep, name)), (kind, name)
+    assert {k for k, name in table.items() if name is None} == {sw_mod.SIZE, sw_mod.GETITEM, sw_mod.SPLIT, sw_mod.CONST, "placeholder", "output"}
+
+
+def test_every_kind_the_nhwc_walk_can_meet_is_served_or_falls_back():
+    """a kind with a cotangent that `_split_eligible` does not send to the NCHW sweep has an NHWC rule or the parent's in the head"""
+    from laplace_amd import sweep_nhwc
+    from laplace_amd.sweep_nhwc import SplitSweep
+
+    for kind in KINDS:
+        if SeedBatchedSweep._VJP[kind] is None or kind in sweep_nhwc._NO_RULE:
+            continue
+        assert kind in SplitSweep._NHWC_VJP or kind in sweep_nhwc._HEAD, kind
+    for name in SplitSweep._NHWC_VJP.values():
+        assert callable(getattr(SplitSweep, name)), name
+    # the fallback calls the parent's rule of the kind: it has one; and what it refuses by name is what the NHWC table lacks
+    assert all(SeedBatchedSweep._VJP[k] is not None for k in sweep_nhwc._HEAD)
+    assert {k for k, why in sweep_nhwc._HEAD.items() if why is None} == set(sweep_nhwc._HEAD) & set(SplitSweep._NHWC_VJP) - {sw_mod.MUL}
+
+
+def test_an_unknown_kind_is_refused_by_name_instead_of_dropping_the_cotangent():
+    """before the table the walk's ``if / elif`` chain had no ``else``: the cotangent was dropped and this passed silently"""
+    torch.manual_seed(0)
+    model = nn.Sequential(nn.Linear(6, 5), nn.Tanh(), nn.Linear(5, 3)).eval()
+    sw = SeedBatchedSweep(model, {"0": model[0], "2": model[2]})
+    f = sw.forward(torch.randn(2, 6))
+    act = next(n for n, r in sw.rule.items() if r.kind == sw_mod.ACT)
+    sw.rule[act] = sw.rule[act]._replace(kind="invented", what="frobnicate")
+    with pytest.raises(SweepUnsupported, match="frobnicate"):
+        sw.backward(torch.randn(3, *f.shape))
+
+
+def test_a_walk_that_raises_leaves_no_state_on_the_sweep():
+    """a `SplitSweep.backward` that is refused mid-walk keeps nothing of that walk on the object (it used to keep the closure over
+    its device words and the multiplier cache), and the next walk on it returns the bits of a fresh sweep"""
+    from laplace_amd import _lib
+    from laplace_amd._lib import get_kernels
+    from laplace_amd.sweep_nhwc import SplitSweep
+    from tests.emulated_kernels import EmulatedKernels
+    from tests.test_sweep_nhwc import _model
+
+    prev = _lib.set_kernels_for_testing(EmulatedKernels())
+    try:
+        model = _model(torch.relu)
+        taps = {n: m for n, m in model.named_modules() if isinstance(m, (nn.Conv2d, nn.Linear))}
+        torch.manual_seed(1)
+        x, seeds = torch.randn(2, 3, 8, 8), torch.randn(3, 2, 5)
+        sw = SplitSweep(model, taps, kernels=get_kernels)
+        assert sw.split_ok, sw.split_reason
+        sw.forward(x)
+        before = set(vars(sw))
+        # the last residual join receives the split cotangent of the activation behind it: as a reshape it is refused mid-walk
+        join = [n for n, r in sw.rule.items() if r.kind == sw_mod.ADD][-1]
+        rule = sw.rule[join]
+        sw.rule[join] = rule._replace(kind=sw_mod.RESHAPE)
+        with pytest.raises(SweepUnsupported, match="reshape inside the NHWC region"):
+            sw.backward(seeds)
+        sw.rule[join] = rule
+        assert set(vars(sw)) - before <= {"grad_scale"}, sorted(set(vars(sw)) - before)
+        assert not any(isinstance(v, sw_mod._Walk) or getattr(v, "__closure__", None) for v in vars(sw).values())
+        fresh = SplitSweep(model, taps, kernels=get_kernels)
+        fresh.forward(x)
+        for defer in (False, True):
+            got, want = sw.backward(seeds, defer_bn_scale=defer), fresh.backward(seeds, defer_bn_scale=defer)
+            assert list(got) == list(want) and all(torch.equal(got[n], want[n]) for n in want)
+            assert list(sw.grad_scale) == list(fresh.grad_scale)
+    finally:
+        _lib.set_kernels_for_testing(prev)
