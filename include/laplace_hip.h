@@ -1070,6 +1070,52 @@ int lk_comm_init_rank(void** comm, int nranks, const void* id128, int rank);
 int lk_comm_destroy(void* comm);
 int lk_allreduce_sum_f32(void* comm, float* buf, int64_t count, void* stream);
 
+/* ---- dense Laplace in the eigenbasis of the curvature (csrc/lk_spectral.hip) ----------------------------------------------------
+ * H = Q diag(lam) Q^T once (lk_syevj_f32); for a SCALAR prior precision delta the posterior precision is Q diag(mu) Q^T with
+ * mu_j = hfac lam_j + delta, and with R = J Q (which does not depend on delta)
+ *   COV   fvar[n][c][k]  = sum_j R[n][c][j] R[n][k][j] / (hfac lam_j + delta)     (FullLaplace.functional_variance,
+ *                                                                                  laplace/baselaplace.py:1683-1684, without the
+ *                                                                                  Cholesky + inverse per prior of utils.py:118-129)
+ *   GRID  var[g][n][c]  += sum_j R[n][c][j]^2 / (hfac lam_j + deltas[g])          (the diagonal at G priors in one pass: the grid
+ *                                                                                  search of baselaplace.py:487-561; the caller zeroes var)
+ * lk_spectral_quadform_ll_f32 / lk_spectral_grid_ll_f32: last layer, J = I (x) [phi, 1]: R[n][c][j] = sum_d phi[n][d] Q[c D + d][j]
+ *   (+ Q[C D + c][j] with a bias) is formed per tile on the exact-fp32 matrix instruction and never stored; phi [B][D], Q [P][P]
+ *   row-major with the eigenvectors in its columns, rows in the reference's parameter order (weight [C][D], then bias),
+ *   P = C D (+ C); lam [P]; delta / deltas on the device; fvar [B][C][C], var [G][B][C].
+ * lk_spectral_quadform_f32 / lk_spectral_grid_f32: R [N][C][P] is given (Js Q by one lk_gemm_f32).
+ * Tiles of LK_SP_TILE_N samples x LK_SP_TILE_J eigen-columns; a workgroup owns a sample tile and a contiguous range of column
+ * tiles, the ranges' partial sums go to the workspace and are added in ascending order: one owner per output element, no float
+ * atomics, fixed order, repeated calls give the same bits; fvar is written in both triangles from one value.  COV holds up to 10
+ * outputs (1, 2, 5 or 10 accumulators); more run in pairs of blocks of 5.  GRID serves any C in blocks of 1, 2, 5 or 10 outputs
+ * and walks the grid in chunks of 64 / CT (5 for ten outputs) points, 128 points per launch.  Pointers need no alignment.
+ * Contract: pointers non-null; 0 <= B, N < 2^24; 1 <= C < 2^15; 1 <= G < 2^20; LL: 1 <= D <= 896 and P <= 32768; R: 1 <= P <=
+ *   32768; hfac positive and finite; the output overlaps neither an input nor the workspace; ws_bytes >=
+ *   lk_spectral_workspace_bytes (else LK_EWORKSPACE).  B, N == 0 returns LK_OK before any device call.
+ * `form`: LK_SP_* (| LK_SP_BIAS for the LL forms with a bias row); D_or_P: D for the LL forms, P for the others; G is ignored
+ * by the COV forms (pass 1).
+ * lk_spectral_variant (host only; `aligned` is ignored, every form reads single dwords) returns
+ *   CT | grid << 4 | pairs << 5 | LL << 6 | (split > 1) << 7 | split << 8 | GC << 20
+ *   CT: outputs held in accumulators; grid: the GRID epilogue; pairs: COV in pairs of blocks of 5 (C > 10); LL: the last-layer
+ *   loader; split: workgroups per sample tile (column ranges); GC: grid points per epilogue chunk
+ * or a negative value for a shape the entry points refuse. */
+#define LK_SP_TILE_N 32
+#define LK_SP_TILE_J 128
+#define LK_SP_QUAD_LL 0 /* lk_spectral_quadform_ll_f32 */
+#define LK_SP_GRID_LL 1 /* lk_spectral_grid_ll_f32 */
+#define LK_SP_QUAD_R 2  /* lk_spectral_quadform_f32 */
+#define LK_SP_GRID_R 3  /* lk_spectral_grid_f32 */
+#define LK_SP_BIAS 4
+size_t lk_spectral_workspace_bytes(int form, int64_t N, int64_t C, int64_t D_or_P, int64_t G);
+int lk_spectral_quadform_ll_f32(const float* phi, const float* Q, const float* lam, float hfac, const float* delta, int64_t B,
+                                int64_t C, int64_t D, int has_bias, float* fvar, void* ws, size_t ws_bytes, void* stream);
+int lk_spectral_grid_ll_f32(const float* phi, const float* Q, const float* lam, float hfac, const float* deltas, int64_t G,
+                            int64_t B, int64_t C, int64_t D, int has_bias, float* var, void* ws, size_t ws_bytes, void* stream);
+int lk_spectral_quadform_f32(const float* R, const float* lam, float hfac, const float* delta, int64_t N, int64_t C, int64_t P,
+                             float* fvar, void* ws, size_t ws_bytes, void* stream);
+int lk_spectral_grid_f32(const float* R, const float* lam, float hfac, const float* deltas, int64_t G, int64_t N, int64_t C,
+                         int64_t P, float* var, void* ws, size_t ws_bytes, void* stream);
+int lk_spectral_variant(int form, int64_t N, int64_t C, int64_t D_or_P, int64_t G, int aligned);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,12 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int)]),
     "lk_conv_strided_launch_variant": (_int, [_i64] * 9 + [ctypes.POINTER(ctypes.c_int), _int, ctypes.POINTER(ctypes.c_int)]),
     "lk_probit_nll_grid_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "lk_spectral_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),
+    "lk_spectral_quadform_ll_f32": (_int, [_vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    "lk_spectral_grid_ll_f32": (_int, [_vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    "lk_spectral_quadform_f32": (_int, [_vp, _vp, _f32, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "lk_spectral_grid_f32": (_int, [_vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "lk_spectral_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int]),
 }
 
 
@@ -2288,6 +2294,73 @@ class HipKernels:
             _ptr(phi), _ptr(Sigma), B, C, D, 1 if has_bias else 0, _ptr(fvar), _ptr(ws), ws.numel(), self._stream(phi.device)),
             nbytes=4.0 * (B * D + (C * Dt) ** 2 + B * C * C)), "lk_dense_quadform_ll_f32")
         return fvar
+
+    # ---- dense Laplace in the eigenbasis of the curvature (lk_spectral.hip) ---------------------------------
+    SP_QUAD_LL, SP_GRID_LL, SP_QUAD_R, SP_GRID_R, SP_BIAS = 0, 1, 2, 3, 4
+    SP_TILE_N, SP_TILE_J = 32, 128
+
+    def spectral_quadform_ll(self, phi, Q, lam, hfac, delta, C, has_bias):
+        """``fvar [B, C, C] = sum_j R_c R_k / (hfac lam_j + delta)`` with ``R = (I (x) [phi, 1]) Q`` formed per tile;
+        ``phi [B, D]``, ``Q [P, P]`` (eigenvectors in columns), ``lam [P]``, ``delta`` a device scalar"""
+        _check(phi, "phi"), _check(Q, "Q"), _check(lam, "lam"), _check(delta, "delta")
+        B, D = phi.shape
+        P = C * D + (C if has_bias else 0)
+        if Q.shape != (P, P) or lam.shape != (P,) or delta.numel() != 1:
+            raise LaplaceHipError("spectral_quadform_ll: phi [B, D], Q [P, P], lam [P], P = C D (+ C), delta a scalar tensor")
+        fvar = torch.empty(B, C, C, dtype=torch.float32, device=phi.device)
+        form = self.SP_QUAD_LL | (self.SP_BIAS if has_bias else 0)
+        ws = self._workspace(self.lib.lk_spectral_workspace_bytes(form, B, C, D, 1), phi.device)
+        self._rc(self._timed("spectral", 2.0 * B * P * P, phi.device, lambda: self.lib.lk_spectral_quadform_ll_f32(
+            _ptr(phi), _ptr(Q), _ptr(lam), float(hfac), _ptr(delta), B, C, D, 1 if has_bias else 0, _ptr(fvar), _ptr(ws),
+            ws.numel(), self._stream(phi.device)), nbytes=4.0 * (B * D + P * P + B * C * C)), "lk_spectral_quadform_ll_f32")
+        return fvar
+
+    def spectral_grid_ll(self, phi, Q, lam, hfac, deltas, C, has_bias, var):
+        """``var [G, B, C] +=`` the diagonal of :meth:`spectral_quadform_ll` at every prior precision of ``deltas [G]``"""
+        _check(phi, "phi"), _check(Q, "Q"), _check(lam, "lam"), _check(deltas, "deltas"), _check(var, "var")
+        B, D = phi.shape
+        P = C * D + (C if has_bias else 0)
+        G = deltas.numel()
+        if Q.shape != (P, P) or lam.shape != (P,) or var.shape != (G, B, C):
+            raise LaplaceHipError("spectral_grid_ll: phi [B, D], Q [P, P], lam [P], P = C D (+ C), var [G, B, C]")
+        form = self.SP_GRID_LL | (self.SP_BIAS if has_bias else 0)
+        ws = self._workspace(self.lib.lk_spectral_workspace_bytes(form, B, C, D, G), phi.device)
+        self._rc(self.lib.lk_spectral_grid_ll_f32(_ptr(phi), _ptr(Q), _ptr(lam), float(hfac), _ptr(deltas), G, B, C, D,
+                                                  1 if has_bias else 0, _ptr(var), _ptr(ws), ws.numel(),
+                                                  self._stream(phi.device)), "lk_spectral_grid_ll_f32")
+        return var
+
+    def spectral_quadform(self, R, lam, hfac, delta):
+        """``fvar [N, C, C] = sum_j R[n, c, j] R[n, k, j] / (hfac lam_j + delta)``; ``R [N, C, P]`` = ``Js Q``"""
+        _check(R, "R"), _check(lam, "lam"), _check(delta, "delta")
+        N, C, P = R.shape
+        if lam.shape != (P,) or delta.numel() != 1:
+            raise LaplaceHipError("spectral_quadform: R [N, C, P], lam [P], delta a scalar tensor")
+        fvar = torch.empty(N, C, C, dtype=torch.float32, device=R.device)
+        ws = self._workspace(self.lib.lk_spectral_workspace_bytes(self.SP_QUAD_R, N, C, P, 1), R.device)
+        self._rc(self.lib.lk_spectral_quadform_f32(_ptr(R), _ptr(lam), float(hfac), _ptr(delta), N, C, P, _ptr(fvar), _ptr(ws),
+                                                   ws.numel(), self._stream(R.device)), "lk_spectral_quadform_f32")
+        return fvar
+
+    def spectral_grid(self, R, lam, hfac, deltas, var):
+        """``var [G, N, C] += sum_j R[n, c, j]^2 / (hfac lam_j + deltas[g])``"""
+        _check(R, "R"), _check(lam, "lam"), _check(deltas, "deltas"), _check(var, "var")
+        N, C, P = R.shape
+        G = deltas.numel()
+        if lam.shape != (P,) or var.shape != (G, N, C):
+            raise LaplaceHipError("spectral_grid: R [N, C, P], lam [P], var [G, N, C]")
+        ws = self._workspace(self.lib.lk_spectral_workspace_bytes(self.SP_GRID_R, N, C, P, G), R.device)
+        self._rc(self.lib.lk_spectral_grid_f32(_ptr(R), _ptr(lam), float(hfac), _ptr(deltas), G, N, C, P, _ptr(var), _ptr(ws),
+                                               ws.numel(), self._stream(R.device)), "lk_spectral_grid_f32")
+        return var
+
+    def spectral_variant(self, form, N, C, D_or_P, G=1, aligned=True):
+        """what a shape launches (host only): ``dict(ct, grid, pairs, ll, split, gc)`` or None for a refused shape"""
+        r = self.lib.lk_spectral_variant(int(form), N, C, D_or_P, G, 1 if aligned else 0)
+        if r < 0:
+            return None
+        return {"ct": r & 15, "grid": bool(r & 16), "pairs": bool(r & 32), "ll": bool(r & 64), "split": (r >> 8) & 4095,
+                "gc": r >> 20}
 
 
 _KERNELS = None

@@ -877,10 +877,26 @@ class HipFullLaplace(_HipLaplace):
 
     """Dense Laplace (FullLaplace, baselaplace.py:1572-1701).  The one-off ``P^3`` factorisation of
     the posterior precision stays a library call (torch.linalg.cholesky -> rocSOLVER), exactly where
-    the reference calls it (utils/utils.py:118-129); accumulation and the predictive are HIP."""
+    the reference calls it (utils/utils.py:118-129); accumulation and the predictive are HIP.
+
+    ``spectral=True`` (opt-in; the default is unchanged): the curvature is decomposed ONCE, ``H = Q diag(lam) Q^T``
+    (``lk_syevj_f32``, lazily at the first need, dropped whenever ``H`` changes, never stored in ``state_dict``), and for
+    a prior precision that is a scalar - or whose entries are all equal - everything prior-dependent is ``O(P)``:
+    ``mu = H_factor lam + delta``, ``log det = sum log mu``, ``f_var = sum_j R_c R_k / mu_j`` with ``R = J Q``
+    (csrc/lk_spectral.hip), a sample is ``mean + Q (z / sqrt mu)``.  A change of the prior precision or of ``sigma_noise``
+    then costs no factorisation, ``optimize_prior_precision(method="marglik")`` differentiates through ``sum log mu``, and
+    ``validation_loss_grid`` / ``gridsearch_prior_precision(batched=True)`` evaluate a whole grid in one pass.  A layer-wise
+    or diagonal prior precision with differing entries, and a model that is not float32, silently take the Cholesky route
+    above."""
+
+    def __init__(self, *args, spectral: bool = False, **kwargs):
+        self.spectral = bool(spectral)
+        self._spectrum = None
+        super().__init__(*args, **kwargs)
 
     def _init_H(self):
         self.H = torch.zeros(self.n_params, self.n_params, device=self._device, dtype=self._dtype)
+        self._spectrum = None
 
     def _curv_closure(self, X, y, N):
         return self.backend.full(X, y, N=N)
@@ -888,39 +904,148 @@ class HipFullLaplace(_HipLaplace):
     def _curvature_tensors(self):
         return [self.H]
 
+    def fit(self, *args, **kwargs):
+        super().fit(*args, **kwargs)
+        self._spectrum = None  # (H changed, also with override=False)
+
+    def _set_H_from_state(self, H):
+        self.H = H
+        self._spectrum = None
+
+    # ---- the spectral route ------------------------------------------------------------------------------------
+    def _spectral_route(self) -> bool:
+        """spectral=True, a float32 model, and a prior precision with one value"""
+        if not self.spectral or self._dtype != torch.float32 or self.H is None:
+            return False
+        pp = self.prior_precision
+        if len(pp) == 1:
+            return True
+        # (one host read per prior-precision TENSOR, not per call: the answer is kept with the tensor it was asked of)
+        seen = getattr(self, "_pp_equal", None)
+        if seen is None or seen[0] is not pp:
+            seen = self._pp_equal = (pp, bool((pp.detach() == pp.detach()[0]).all()))
+        return seen[1]
+
+    @property
+    def spectrum(self):
+        """``(lam [P], Q [P, P])`` of ``H`` (eigenvectors in the columns of ``Q``, eigenvalues clamped at 0), cached.  A solve
+        that runs out of sweeps gets the treatment of ``HipKron.decompose``: ``H + I`` is solved instead and 1 subtracted;
+        if that fails too: RuntimeError."""
+        if self._spectrum is None:
+            K = _pred.get_kernels()
+            H = self.H.detach().to(torch.float32).contiguous()
+            lam, Q, info = K.syevj(H, clamp=True)
+            if int(info.reshape(-1)[0].item()) != 0:
+                Hj = (H + torch.eye(H.shape[0], device=H.device, dtype=H.dtype)).contiguous()
+                lam, Q, info = K.syevj(Hj, clamp=False)
+                if int(info.reshape(-1)[0].item()) != 0:
+                    raise RuntimeError(f"lk_syevj_f32: eigendecomposition of the {H.shape[0]} x {H.shape[0]} curvature did "
+                                       "not converge, also not with jitter")
+                lam, Q = torch.nan_to_num((lam - 1.0).clamp(min=0.0)), torch.nan_to_num(Q)
+            self._spectrum = (lam.contiguous(), Q.contiguous())
+        return self._spectrum
+
+    def _delta(self) -> torch.Tensor:
+        return self.prior_precision.reshape(-1)[:1]
+
+    def _mu(self) -> torch.Tensor:
+        """the posterior precision's eigenvalues ``H_factor lam + delta`` (differentiable in both hyper-parameters)"""
+        return self._H_factor * self.spectrum[0] + self._delta()
+
+    def _spectral_args(self):
+        lam, Q = self.spectrum
+        return lam, Q, float(self._H_factor), self._delta().detach().to(torch.float32).contiguous()
+
+    def _rotate(self, Js: torch.Tensor) -> torch.Tensor:
+        return _pred.rotate_jacobians(Js, self.spectrum[1])
+
     @property
     def posterior_precision(self):
         return self._H_factor * self.H + torch.diag(self.prior_precision_diag)
 
     @property
     def posterior_covariance(self):
+        """On the spectral route: ``Q diag(1 / mu) Q^T``, formed only when asked for: the columns of a copy of ``Q`` are scaled
+        (the weight sits BETWEEN the two factors, where the GEMM's element-wise ``E`` - a weight on the product - cannot put
+        it), then one ``lk_gemm_f32``."""
         if self._posterior_cache is None:
-            L = torch.linalg.cholesky(self.posterior_precision)
-            self._posterior_cache = torch.cholesky_inverse(L)
+            if self._spectral_route():
+                lam, Q = self.spectrum
+                P = self.n_params
+                Qs = (Q / self._mu().detach()[None, :]).contiguous()
+                Sigma = torch.empty(P, P, device=Q.device, dtype=torch.float32)
+                _pred.get_kernels().gemm(Qs, Q, Sigma, 1, P, P, P, P, P, P, tb=True)
+                self._posterior_cache = Sigma
+            else:
+                L = torch.linalg.cholesky(self.posterior_precision)
+                self._posterior_cache = torch.cholesky_inverse(L)
         return self._posterior_cache
 
     @property
     def log_det_posterior_precision(self):
+        if self._spectral_route():
+            return self._mu().log().sum()
         return self.posterior_precision.logdet()
 
     def functional_variance(self, Js):
+        if self._spectral_route() and Js.dtype == torch.float32:
+            lam, _, hfac, delta = self._spectral_args()
+            return _pred.get_kernels().spectral_quadform(self._rotate(Js), lam, hfac, delta)
         return torch.einsum("ncp,pq,nkq->nck", Js, self.posterior_covariance, Js)
 
     def functional_covariance(self, Js: torch.Tensor) -> torch.Tensor:
-        """baselaplace.py:1686-1689"""
+        """baselaplace.py:1686-1689.  Spectral route: the stacked rows are ONE sample with ``M = n_batch n_outs`` outputs; up to
+        10 of them fit the covariance kernel's accumulators, more go as ``(R / mu) R^T`` through one ``lk_gemm_f32`` (the
+        kernel's block pairs are meant for a modest number of classes, not for thousands of stacked rows)."""
         n_batch, n_outs, n_params = Js.shape
         Js = Js.reshape(n_batch * n_outs, n_params)
+        M = n_batch * n_outs
+        if self._spectral_route() and Js.dtype == torch.float32 and M > 0:
+            K = _pred.get_kernels()
+            R = self._rotate(Js[None])
+            if M <= 10:
+                lam, _, hfac, delta = self._spectral_args()
+                return K.spectral_quadform(R, lam, hfac, delta)[0]
+            R = R[0]
+            Rs = (R / self._mu().detach()[None, :]).contiguous()
+            out = torch.empty(M, M, device=R.device, dtype=torch.float32)
+            K.gemm(Rs, R, out, 1, M, M, n_params, n_params, n_params, M, tb=True)
+            return out
         return torch.einsum("np,pq,mq->nm", Js, self.posterior_covariance, Js)
+
+    def _sample_transform(self, z: torch.Tensor) -> torch.Tensor:
+        """``z T^T`` with ``T = Q diag(mu^-1/2)``, ``T T^T`` = the posterior covariance (one ``lk_gemm_f32``)"""
+        _, Q = self.spectrum
+        P = self.n_params
+        zs = (z.to(torch.float32) * self._mu().detach().rsqrt()[None, :]).contiguous()
+        out = torch.empty_like(zs)
+        _pred.get_kernels().gemm(zs, Q, out, 1, zs.shape[0], P, P, P, P, P, tb=True)
+        return out
 
     def sample(self, n_samples: int = 100, generator=None) -> torch.Tensor:
         """baselaplace.py:1691-1703: ``mean + z L^T``; ``L`` = lower Cholesky factor of the posterior covariance
-        (what ``invsqrt_precision`` / ``_precision_to_scale_tril`` return, utils/utils.py:118-129)."""
+        (what ``invsqrt_precision`` / ``_precision_to_scale_tril`` return, utils/utils.py:118-129).
+
+        On the spectral route the draws are ``mean + (z / sqrt mu) Q^T``: the same distribution, but NOT draw for draw
+        what the Cholesky route (and the reference) returns for the same generator state; the default route keeps that
+        parity."""
         z = self._randn(n_samples, self.n_params, generator=generator)
+        if self._spectral_route():
+            return self.mean.reshape(1, self.n_params) + self._sample_transform(z)
         scale = torch.linalg.cholesky(self.posterior_covariance)
         return self.mean.reshape(1, self.n_params) + z @ scale.T
 
+    def _glm_variance_grid(self, X, deltas):
+        if not (self.spectral and self._dtype == torch.float32):
+            return super()._glm_variance_grid(X, deltas)
+        lam, Q = self.spectrum
+        return _pred.glm_variance_full_spectral_grid(self.backend, X, lam, Q, float(self._H_factor), deltas,
+                                                     budget_bytes=self.grid_var_budget_bytes)
+
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
-        if self.subset_of_weights == "last_layer":
+        if self._spectral_route():
+            f_mu, f_var = _pred.glm_variance_full_spectral(self.backend, X, *self._spectral_args())
+        elif self.subset_of_weights == "last_layer":
             f_mu, f_var = _pred.glm_variance_full_last_layer(self.backend, X, self.posterior_covariance)
         else:
             Js, f_mu = self.backend.jacobians(X)

@@ -326,3 +326,73 @@ def glm_variance_full_last_layer(backend, x, Sigma: torch.Tensor):
     fvar = K.dense_quadform_ll(phi, Sigma.detach().to(torch.float32).contiguous(), f.shape[1], tap.has_bias)
     tape.release()
     return f, fvar
+
+
+# ---- dense posterior in the eigenbasis of the curvature (csrc/lk_spectral.hip) -------------------------------------------
+def rotate_jacobians(Js: torch.Tensor, Q: torch.Tensor) -> torch.Tensor:
+    """``R [N, C, P] = Js Q`` (one ``lk_gemm_f32``): the Jacobians in the eigenbasis, the same for every prior precision"""
+    K = get_kernels()
+    N, C, P = Js.shape
+    Js = Js.detach().to(torch.float32).contiguous()
+    R = torch.empty(N, C, P, dtype=torch.float32, device=Js.device)
+    if N * C:
+        K.gemm(Js, Q, R, 1, N * C, P, P, P, P, P)
+    return R
+
+
+def _spectral_operands(backend, x):
+    """``(f_mu, phi, has_bias, Js)``: the head's input features (``Js`` None) where the last-layer loader serves them, else
+    the Jacobians for the R loader.  ``x`` may be what ``backend.cache_features`` returned (the grid driver's one feature pass
+    per validation batch): ``backend._forward`` then runs the head only.  A head wider than the last-layer loader admits
+    (``lk_spectral_variant`` is asked, D <= 896 today) takes the R loader through its materialised ``[B, C, P]`` Jacobian,
+    whole on the predictive route and in chunks of the budget on the grid route."""
+    K = get_kernels()
+    if backend.last_layer:
+        f, tape, _ = backend._forward(x)
+        tap = tape.taps[0]
+        phi = tap.a.to(torch.float32).contiguous().clone()  # (its own copy: the tape's buffers go back with release())
+        has_bias = tap.has_bias
+        tape.release()
+        form = K.SP_QUAD_LL | (K.SP_BIAS if has_bias else 0)
+        if phi.ndim == 2 and K.spectral_variant(form, max(phi.shape[0], 1), f.shape[1], phi.shape[1]) is not None:
+            return f, phi, has_bias, None
+        return f, None, has_bias, K.jac_last_layer(phi, f.shape[1], has_bias)
+    Js, f = backend.jacobians(x)
+    return f, None, False, Js
+
+
+def glm_variance_full_spectral(backend, x, lam, Q, hfac, delta):
+    """``(f_mu, f_var [B, C, C])`` under the dense posterior ``Q diag(hfac lam + delta)^-1 Q^T``: ``lam [P]``, ``Q [P, P]`` the
+    spectrum of the curvature, ``delta`` the scalar prior precision as a one-element device tensor.  Last layer: the features
+    go straight into ``lk_spectral_quadform_ll_f32`` (no Jacobian, no rotated Jacobian in memory); all weights:
+    ``backend.jacobians`` -> ``lk_gemm_f32`` -> ``lk_spectral_quadform_f32``."""
+    _fp32_only(backend)
+    K = get_kernels()
+    f, phi, has_bias, Js = _spectral_operands(backend, x)
+    if Js is None:
+        return f, K.spectral_quadform_ll(phi, Q, lam, hfac, delta, f.shape[1], has_bias)
+    return f, K.spectral_quadform(rotate_jacobians(Js, Q), lam, hfac, delta)
+
+
+def glm_variance_full_spectral_grid(backend, x, lam, Q, hfac, deltas, budget_bytes: int = 256 << 20):
+    """``(f_mu, var [G, B, C])``: the diagonal of :func:`glm_variance_full_spectral`'s ``f_var`` at every prior precision of
+    ``deltas [G]`` in one pass; on the Jacobian route the batch is rotated in chunks of at most ``budget_bytes``."""
+    _fp32_only(backend)
+    K = get_kernels()
+    f, phi, has_bias, Js = _spectral_operands(backend, x)
+    B, C = f.shape
+    dg = _grid_deltas(deltas, f.device)
+    var = torch.zeros(dg.numel(), B, C, dtype=torch.float32, device=f.device)
+    if Js is None:
+        K.spectral_grid_ll(phi, Q, lam, hfac, dg, C, has_bias, var)
+        return f, var
+    P = Js.shape[2]
+    per = max(1, int(budget_bytes) // (4 * C * P))
+    if per >= B:
+        K.spectral_grid(rotate_jacobians(Js, Q), lam, hfac, dg, var)
+    else:
+        for n0 in range(0, B, per):
+            part = torch.zeros(dg.numel(), min(per, B - n0), C, dtype=torch.float32, device=f.device)
+            K.spectral_grid(rotate_jacobians(Js[n0:n0 + per], Q), lam, hfac, dg, part)
+            var[:, n0:n0 + per] = part
+    return f, var
