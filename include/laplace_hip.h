@@ -814,6 +814,35 @@ int lk_jac_gconv_f32(const float* x_nchw, const float* g, int64_t B, int64_t Cc,
                      int64_t Do, int64_t groups, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                      float* Js, int64_t P, int64_t col0, int64_t bcol0, void* stream);
 
+/* nn.Embedding weight W[V][D] with token ids ids[B][T]: the per-sample Jacobian is a segmented sum of the cotangent
+ * g[S][B][T][D] of the module's output (replaces the embedding columns of the jacrev materialisation of
+ * CurvatureInterface.jacobians, laplace/curvature/curvature.py:88-129, and of GGNInterface.diag / EFInterface.diag,
+ * curvature.py:413-433, 494-505):
+ *   lk_jac_embed_f32:            Js[b][s][col0 + v*D + d]  = sum over {t : ids[b][t] == v} of g[s][b][t][d]
+ *   lk_diag_embed_f32:           h[v*D + d]               += alpha * sum_(s, b) (that sum)^2        (never forms [B][S][V*D])
+ *   lk_diag_quadform_embed_f32:  fvar[b][c][k]            += sum_v sum_d r_c[d] * r_k[d] * var[v*D + d],  r_c the sum of class c
+ * The ids arrive SORTED (int64, torch's stable sort; the host never reads them): `order` / `sorted_ids` are the argsort and the
+ * sorted values of ids.reshape(-1) (b-major, so one id's positions are ordered by (b, t)); `order_row` / `sorted_ids_row`, both
+ * [B][T], those of ids.sort(dim=1, stable=True).  The thread group at the first sorted position of a run of equal keys owns
+ * the run's outputs and walks it in ascending order; every other group exits: one owner per output element, no atomics, the same
+ * bits on every launch.  A run whose id is padding_idx (-1: the module has none) or lies outside [0, V) writes nothing;
+ * lk_jac_embed_f32 leaves every element of Js that is no such sum untouched (the caller has zeroed it).
+ * 1 <= S (or C) < 2^31, 0 <= B, 1 <= T, 1 <= D, 1 <= V, B*T < 2^31, V*D < 2^31, 0 <= col0, col0 + V*D <= P; B == 0 is LK_OK.
+ * 16-byte accesses where D % 4 == 0 and the pointers (and P, col0) are 16-byte aligned, 4-byte otherwise.
+ *
+ * lk_embed_variant (host only): vec | slots << 1 | lanes << 12 | chunks << 20 for a shape, `aligned` as above.  vec: 16-byte
+ * accesses; lanes (<= 16): across the d vectors of lk_diag_embed_f32's workgroup; slots = 1024 / lanes: the row slots a long run
+ * of one id is cut into (the long-run path, reduced through LDS in ascending order); chunks: its grid.y (saturating at 2047).  Negative for
+ * a shape the entry points refuse. */
+int lk_jac_embed_f32(const float* g, const int64_t* order, const int64_t* sorted_ids, int64_t S, int64_t B, int64_t T, int64_t D,
+                     int64_t V, int64_t padding_idx, float* Js, int64_t P, int64_t col0, void* stream);
+int lk_diag_embed_f32(const float* g, const int64_t* order, const int64_t* sorted_ids, int64_t S, int64_t B, int64_t T, int64_t D,
+                      int64_t V, int64_t padding_idx, float alpha, float* h, void* stream);
+int lk_diag_quadform_embed_f32(const float* g, const int64_t* order_row, const int64_t* sorted_ids_row, int64_t C, int64_t B,
+                               int64_t T, int64_t D, int64_t V, int64_t padding_idx, const float* var, float* fvar,
+                               void* stream);
+int lk_embed_variant(int64_t S, int64_t B, int64_t T, int64_t D, int aligned);
+
 /* h[p] += alpha * sum_r Js[r][col0 + p]^2 for p < width (rows r = (sample, class)); the conv-layer
  * diagonal GGN / EF is the squared per-sample weight Jacobian summed over samples. */
 int lk_sq_colsum_f32(const float* Js, int64_t rows, int64_t P, int64_t col0, int64_t width, float alpha,

@@ -112,6 +112,10 @@ SIGNATURES = {
         [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _i64, _i64,
          _vp],
     ),
+    "lk_jac_embed_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "lk_diag_embed_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
+    "lk_diag_quadform_embed_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "lk_embed_variant": (_int, [_i64, _i64, _i64, _i64, _int]),
     "lk_sq_colsum_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
     "lk_jac_norm_affine_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _i64, _vp]),
     "lk_norm_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp]),
@@ -1240,6 +1244,62 @@ class HipKernels:
                                       _ptr(Js), Js.shape[-1], int(col0), int(bcol0), self._stream(x.device)),
             "lk_jac_gconv_f32",
         )
+
+    # ---- nn.Embedding weights (csrc/lk_embed.hip) ----
+    @staticmethod
+    def _embed_operands(g, ids, what):
+        """``(S, B, T, D)`` of a cotangent ``g [S, B, ..., D]`` and token ids ``ids [B, ...]`` (int64)"""
+        _check(g, "g"), _check(ids, "ids", torch.int64)
+        if g.dim() < 3 or ids.dim() < 1 or tuple(g.shape[1:-1]) != tuple(ids.shape):
+            raise LaplaceHipError(f"{what}: g [S, B, ..., D] and ids [B, ...] do not match")
+        T = 1
+        for n in ids.shape[1:]:
+            T *= int(n)
+        return g.shape[0], ids.shape[0], T, g.shape[-1]
+
+    def jac_embed(self, g, ids, V, padding_idx, Js, col0):
+        """``Js[b, s, col0 + v*D + d] = sum_{t: ids[b, t] == v} g[s, b, t, d]``; every other element of ``Js [B, S, P]`` is left
+        as it is.  The ids are sorted here (stable), the kernel finds the runs."""
+        S, B, T, D = self._embed_operands(g, ids, "jac_embed")
+        _check(Js, "Js")
+        if Js.shape[:2] != (B, S):
+            raise LaplaceHipError("jac_embed: Js must be [B, S, P]")
+        sid, order = torch.sort(ids.reshape(-1), stable=True)
+        pad = -1 if padding_idx is None else int(padding_idx)
+        self._rc(self.lib.lk_jac_embed_f32(_ptr(g), _ptr(order), _ptr(sid), S, B, T, D, int(V), pad, _ptr(Js), Js.shape[-1],
+                                           int(col0), self._stream(g.device)), "lk_jac_embed_f32")
+
+    def diag_embed(self, g, ids, V, padding_idx, alpha, h):
+        """``h[v*D + d] += alpha * sum_(s, b) (sum_{t: ids[b, t] == v} g[s, b, t, d])^2`` for ``h [V*D]``"""
+        S, B, T, D = self._embed_operands(g, ids, "diag_embed")
+        _check(h, "h")
+        if h.numel() != int(V) * D:
+            raise LaplaceHipError("diag_embed: h must hold V*D values")
+        sid, order = torch.sort(ids.reshape(-1), stable=True)
+        pad = -1 if padding_idx is None else int(padding_idx)
+        self._rc(self.lib.lk_diag_embed_f32(_ptr(g), _ptr(order), _ptr(sid), S, B, T, D, int(V), pad, float(alpha), _ptr(h),
+                                            self._stream(g.device)), "lk_diag_embed_f32")
+
+    def diag_quadform_embed(self, g, ids, V, padding_idx, var, fvar):
+        """``fvar[b, c, k] += sum_v sum_d r_c[d] r_k[d] var[v*D + d]`` with ``r_c`` the per-(sample, id) sum of ``g[c]``"""
+        C, B, T, D = self._embed_operands(g, ids, "diag_quadform_embed")
+        _check(var, "var"), _check(fvar, "fvar")
+        if var.numel() != int(V) * D or tuple(fvar.shape) != (B, C, C):
+            raise LaplaceHipError("diag_quadform_embed: var must hold V*D values and fvar be [B, C, C]")
+        sid, order = torch.sort(ids.reshape(B, T), dim=1, stable=True)
+        pad = -1 if padding_idx is None else int(padding_idx)
+        self._rc(self.lib.lk_diag_quadform_embed_f32(_ptr(g), _ptr(order.contiguous()), _ptr(sid.contiguous()), C, B, T, D, int(V),
+                                                     pad, _ptr(var), _ptr(fvar), self._stream(g.device)),
+                 "lk_diag_quadform_embed_f32")
+        return fvar
+
+    def embed_variant(self, S, B, T, D, aligned=True):
+        """lk_embed_variant: the vector class and the long-run split the embedding kernels take for a shape (host only), or
+        ``None`` for a shape they refuse."""
+        r = int(self.lib.lk_embed_variant(int(S), int(B), int(T), int(D), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": 4 if r & 1 else 1, "slots": (r >> 1) & 0x7FF, "lanes": (r >> 12) & 0xFF, "chunks": r >> 20}
 
     def jac_norm_affine(self, g, xhat, Ch, layout, Js, wcol0, bcol0=-1):
         """``Js[n, s, wcol0 + ch] = sum_l g * xhat``, ``Js[n, s, bcol0 + ch] = sum_l g`` for an affine normalisation

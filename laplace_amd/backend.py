@@ -36,7 +36,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from laplace_amd._lib import SplitTensor, get_kernels, is_channels_last, keep_layout
-from laplace_amd.capture import NormTapReused, Tape, norm_servable
+from laplace_amd.capture import EmbedTapForeign, NormTapReused, Tape, norm_servable
 from laplace_amd.sweep import SeedBatchedSweep, SweepUnsupported
 from laplace_amd.sweep_nhwc import NhwcNormGrad, SplitSweep
 from laplace_amd.kron import HipKron
@@ -210,7 +210,7 @@ class _HipCurvatureMixin:
             cur[0] = sig
         twin = cur[1]
         for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "use_attn_kernels", "nhwc_norm_taps", "use_gconv_kernels",
-                  "gconv_block_bytes",
+                  "gconv_block_bytes", "use_embed_kernels",
                   "generator"):
             if k in self.__dict__:
                 setattr(twin, k, self.__dict__[k])
@@ -252,8 +252,11 @@ class _HipCurvatureMixin:
         ``norm``: the normalisation layers are tapped too (``grad_fn`` then returns ``tape.taps + tape.norm_taps``
         gradients, in that order) when :meth:`_norm_route` allows it."""
         tape = self._tape()
-        gconv = bool(norm and not self.last_layer and self._gconv_route(tape))  # (the callers that tap the extra layers)
-        norm = bool(norm and not self.last_layer and self._norm_route(tape))
+        extra = bool(norm and not self.last_layer)  # (the callers that tap the extra layers)
+        gconv = bool(extra and self._gconv_route(tape))
+        embed = bool(extra and self._embed_route(tape))
+        param = bool(extra and self._param_route(tape))
+        norm = bool(extra and self._norm_route(tape))
         if self.last_layer:
             # f = last_layer(phi): the gradient w.r.t. the head's output IS the seed -> no reverse pass
             swept = (x.f, x.phi) if isinstance(x, CachedFeatures) else self._features_swept(x, tape)
@@ -269,14 +272,22 @@ class _HipCurvatureMixin:
             B = phi.shape[0]
             f = f.detach().reshape(B, -1).contiguous()
             return f, tape, lambda seeds, stack=True: [seeds.contiguous()]
-        swept = self._forward_swept(x, tape, keep_tap_splits, norm, gconv)
+        swept = self._forward_swept(x, tape, keep_tap_splits, norm, gconv, embed, param)
         if swept is not None:
             return swept
+        if param:
+            # the sweep that `_param_route` classified does not serve THIS call (training mode, a shape its rules refuse): a lone
+            # parameter has no other device route, so the tape's lone parameters stay unserved from here on, as without the switch
+            tape.param_off = True
+            return self._forward(x, keep_tap_splits, norm=True)
         try:
-            f = tape.forward(x, norm=norm, gconv=gconv)
+            f = tape.forward(x, norm=norm, gconv=gconv, embed=embed)
         except NormTapReused:
             tape.norm_off = True  # (a norm layer applied twice per forward: this model stays on the generic route)
             return self._forward(x, keep_tap_splits)
+        except EmbedTapForeign:
+            tape.embed_off = True  # (an embedding of something else than the input: its weight stays unserved)
+            return self._forward(x, keep_tap_splits, norm=True)
         self._check_dtype(f)
         if f.ndim == 1:
             f = f.unsqueeze(-1)
@@ -298,6 +309,11 @@ class _HipCurvatureMixin:
     #: ``False``: weights of grouped convolutions are not served by csrc/lk_gconv.hip; a model that tracks one takes the
     #: reference's generic route, as it does when the active kernel object has no ``jac_gconv``
     use_gconv_kernels = True
+    #: ``True``: nn.Embedding weights and lone parameters (class tokens, position tables) are served by csrc/lk_embed.hip and the
+    #: sweep's parameter rule.  OPT-IN: with ``False`` (the default), or a kernel object without ``jac_embed``, a model that tracks
+    #: one takes the reference's generic route as before.  The default follows the gate of tools/embed_bench.py: the kernels are
+    #: bit-reproducible and atomic-free, and slower than the atomic ``index_add_`` formulation on some lines of that file
+    use_embed_kernels = False
     #: ``False`` forces the autograd tape (one reverse pass per seed).  (Path selectors are plain attributes — of the class
     #: for a process-wide default, of an object for one backend; nothing here reads the environment.)
     use_sweep = True
@@ -343,17 +359,14 @@ class _HipCurvatureMixin:
         fs.release()
         return f, phi
 
-    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, norm: bool = False, gconv: bool = False):
-        """Seed-batched reverse sweep (laplace_amd/sweep.py) when the model is fx-traceable and built from
-        modules with a closed-form VJP; ``None`` -> caller uses the autograd tape.  ``norm``: the sweep that also taps the
-        normalisation layers, built and cached beside the Linear / Conv2d one (``tape.norm_sweep``); ``gconv``: the one that
-        taps the grouped convolutions (``tape.gconv_sweep``, ``tape.gconv_norm_sweep``)."""
-        if not self.use_sweep or not torch.is_tensor(x) or not tape.taps:
-            return None
-        slot = ("gconv_" if gconv else "") + ("norm_sweep" if norm else "sweep")
-        taps = tape.active_taps(norm, gconv)
+    def _sweep_for(self, tape, norm: bool = False, gconv: bool = False, embed: bool = False, param: bool = False):
+        """the reverse sweep that taps ``tape.active_taps(norm, gconv, embed, param)``, built once per combination and kept on
+        the tape (``tape.sweep``, ``tape.norm_sweep``, ``tape.gconv_sweep``, ...); ``False``: the model has none
+        (``tape.sweep_reason`` says why).  Needs no input: tracing and classifying the graph is all it does."""
+        slot = ("param_" if param else "") + ("embed_" if embed else "") + ("gconv_" if gconv else "") + ("norm_sweep" if norm else "sweep")
         sweep = getattr(tape, slot, None)
         if sweep is None:
+            taps = tape.active_taps(norm, gconv, embed, param)
             try:
                 # NHWC split-fp16 sweep (own convolution kernels) where the graph allows it, else the NCHW sweep
                 if self.use_split_sweep:
@@ -365,6 +378,18 @@ class _HipCurvatureMixin:
                 sweep = False
                 tape.sweep_reason = str(e)
             setattr(tape, slot, sweep)
+        return sweep
+
+    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, norm: bool = False, gconv: bool = False, embed: bool = False,
+                       param: bool = False):
+        """Seed-batched reverse sweep (laplace_amd/sweep.py) when the model is fx-traceable and built from
+        modules with a closed-form VJP; ``None`` -> caller uses the autograd tape.  ``norm``: the sweep that also taps the
+        normalisation layers, built and cached beside the Linear / Conv2d one (``tape.norm_sweep``); ``gconv``: the one that
+        taps the grouped convolutions (``tape.gconv_sweep``, ``tape.gconv_norm_sweep``)."""
+        if not self.use_sweep or not torch.is_tensor(x) or not tape.taps:
+            return None
+        taps = tape.active_taps(norm, gconv, embed, param)
+        sweep = self._sweep_for(tape, norm, gconv, embed, param)
         if sweep is False:
             return None
         try:
@@ -609,6 +634,14 @@ class _HipCurvatureMixin:
             K.jac_gconv(tap.a.to(torch.float32).contiguous(), g.contiguous(), m.kernel_size, m.stride, m.padding, m.dilation,
                         m.groups, Js, tap.w_off, tap.b_off)
             return
+        if tap.kind == "embed":  # (Js arrives zeroed: the kernel writes the columns of the ids that occur, csrc/lk_embed.hip)
+            m = tap.module
+            K.jac_embed(g.contiguous(), self._embed_ids(tap), m.num_embeddings, m.padding_idx, Js, tap.w_off)
+            return
+        if tap.kind == "param":  # (the per-sample cotangent IS the block: a strided copy, no reduction)
+            Jl = self._param_block(g)
+            Js[:, :, tap.w_off:tap.w_off + Jl.shape[-1]] = Jl
+            return
         a = tap.a.to(torch.float32)
         if tap.kind == "linear" and a.ndim == 2:
             K.jac_linear(a.contiguous(), g.contiguous(), Js, tap.w_off, tap.b_off)
@@ -649,15 +682,40 @@ class _HipCurvatureMixin:
         (the stock emulation of the CPU test tier has none: such a model then takes the generic route)."""
         return bool(tape.gconv_taps and self.use_gconv_kernels and getattr(get_kernels(), "jac_gconv", None) is not None)
 
+    def _embed_route(self, tape) -> bool:
+        """Are the tracked nn.Embedding weights served by csrc/lk_embed.hip?  Needs the switch and a kernel object with the
+        entry point (the emulations below tests/emulated_embed_kernels.py have none)."""
+        return bool(tape.embed_taps and self.use_embed_kernels and not getattr(tape, "embed_off", False)
+                    and getattr(get_kernels(), "jac_embed", None) is not None)
+
+    def _param_route(self, tape) -> bool:
+        """Are the tracked lone parameters (class token, position table) served?  Only the seed-batched sweep delivers their
+        per-sample cotangent (autograd alone yields the batch sum), so: the same switch, ``use_sweep``, and a sweep whose rules
+        accept every consumer of every such parameter - decided on the traced graph, before any forward."""
+        if not (tape.param_taps and self.use_embed_kernels and self.use_sweep and tape.taps and not self.last_layer
+                and not getattr(tape, "param_off", False) and getattr(get_kernels(), "jac_embed", None) is not None):
+            return False
+        return self._sweep_for(tape, self._norm_route(tape), self._gconv_route(tape), self._embed_route(tape), True) is not False
+
     def _unserved(self, tape):
-        """tracked parameters that no device rule serves in this call (``tape.uncovered`` when the norm and grouped-
-        convolution routes are off)"""
-        return tape.unserved_by(self._norm_route(tape), self._gconv_route(tape))
+        """tracked parameters that no device rule serves in this call (``tape.uncovered`` when the norm, grouped-convolution,
+        embedding and lone-parameter routes are off)"""
+        return tape.unserved_by(self._norm_route(tape), self._gconv_route(tape), self._embed_route(tape), self._param_route(tape))
 
     def _served_taps(self, tape):
         if self.last_layer:
             return tape.taps
-        return tape.active_taps(self._norm_route(tape), self._gconv_route(tape))
+        return tape.active_taps(self._norm_route(tape), self._gconv_route(tape), self._embed_route(tape), self._param_route(tape))
+
+    @staticmethod
+    def _embed_ids(tap):
+        """the token ids an embedding tap recorded, as the kernels read them (int64, contiguous; never cast to a float)"""
+        return tap.a.to(torch.int64).contiguous()
+
+    @staticmethod
+    def _param_block(g):
+        """``[B, S, n]``: the Jacobian block of a lone parameter from its cotangent ``g [S, B, ...]``"""
+        return g.reshape(g.shape[0], g.shape[1], -1).transpose(0, 1).contiguous()
 
     #: bytes a grouped convolution's own Jacobian block ``[b, S, width]`` may take; larger minibatches are cut along the batch
     gconv_block_bytes = 256 << 20
@@ -800,6 +858,15 @@ class _HipCurvatureMixin:
                     K.sq_colsum(Jl, 0, n_w, alpha, h[tap.w_off:tap.w_off + n_w])
                 if n_b:
                     K.sq_colsum(Jl, n_w, n_b, alpha, h[tap.b_off:tap.b_off + n_b])
+                continue
+            if tap.kind == "embed":  # straight into h: the [B, S, V*D] block is never formed
+                m = tap.module
+                K.diag_embed(g.contiguous(), self._embed_ids(tap), m.num_embeddings, m.padding_idx, alpha,
+                             h[tap.w_off:tap.w_off + m.weight.numel()])
+                continue
+            if tap.kind == "param":
+                Jl = self._param_block(g)
+                K.sq_colsum(Jl, 0, Jl.shape[-1], alpha, h[tap.w_off:tap.w_off + Jl.shape[-1]])
                 continue
             if tap.kind == "gconv":
                 # the layer's own block (a depthwise 3x3 layer has 9 columns per channel), its columns square-summed

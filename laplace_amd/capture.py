@@ -26,7 +26,7 @@ NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm, nn.RMSNorm)
 class Tap:
     name: str
     module: nn.Module
-    kind: str  # 'linear' | 'conv2d' | 'gconv' | 'norm'
+    kind: str  # 'linear' | 'conv2d' | 'gconv' | 'norm' | 'embed' | 'param'
     w_off: int  # column offset of the weight in the flattened parameter vector (a norm tap: -1 if absent / frozen)
     b_off: int  # column offset of the bias, -1 if the module has no (tracked) bias
     a: torch.Tensor | None = None  # module input (detached)
@@ -40,6 +40,11 @@ class Tap:
 
 class NormTapReused(NotImplementedError):
     """a tapped normalisation layer ran twice in one forward: the caller goes back to the route without norm taps"""
+
+
+class EmbedTapForeign(NotImplementedError):
+    """a tapped nn.Embedding does not read the model's input (a position table written ``nn.Embedding(arange)``): its cotangent is
+    not per sample; the caller goes back to the route without embedding taps"""
 
 
 def norm_servable(m: nn.Module) -> bool:
@@ -107,6 +112,48 @@ class Tape:
                 b_off = offsets[id(mod.bias)]
             if w_off >= 0 or b_off >= 0:
                 self.norm_taps.append(Tap(name, mod, "norm", w_off, b_off))
+        # nn.Embedding layers with a tracked weight that no other module owns, in a list of their own (csrc/lk_embed.hip).  What
+        # is refused by name in `embed_refused` (module name -> reason) stays unserved: a weight tied to a Linear head,
+        # `max_norm` (the forward renormalises the rows in place), `scale_grad_by_freq`, `sparse=True`, nn.EmbeddingBag.
+        self.embed_taps: list[Tap] = []
+        self.embed_refused: dict[str, str] = {}
+        for name, mod in model.named_modules():
+            if isinstance(mod, nn.EmbeddingBag) and id(mod.weight) in offsets:
+                self.embed_refused[name] = f"{name}: nn.EmbeddingBag has no device rule"
+            if not isinstance(mod, nn.Embedding) or id(mod.weight) not in offsets:
+                continue
+            why = None
+            if id(mod.weight) in covered:
+                why = "its weight is tied to a Linear / Conv2d layer"
+            elif mod.max_norm is not None:
+                why = "max_norm renormalises the weight in the forward pass"
+            elif mod.scale_grad_by_freq:
+                why = "scale_grad_by_freq has no device rule"
+            elif mod.sparse:
+                why = "sparse=True has no device rule"
+            elif any(t.module.weight is mod.weight for t in self.embed_taps):
+                why = "its weight is shared with another nn.Embedding"
+            if why is not None:
+                self.embed_refused[name] = f"{name}: nn.Embedding is not served ({why})"
+                continue
+            self.embed_taps.append(Tap(name, mod, "embed", offsets[id(mod.weight)], -1))
+        # tracked parameters that NO module of the model owns (a class token, a learned position table: bare nn.Parameter
+        # attributes), served only by the seed-batched sweep (autograd alone yields their batch-summed gradient); `name`: the
+        # attribute path, which is what the traced graph's `get_attr` node names
+        self.param_taps: list[Tap] = []
+        for name, p in model.named_parameters():
+            if id(p) in offsets and isinstance(p, nn.Parameter) and self._is_lone(model, name):
+                self.param_taps.append(Tap(name, None, "param", offsets[id(p)], -1))
+        self._lone = {t.name: p for t in self.param_taps for n, p in model.named_parameters() if n == t.name}
+
+    @staticmethod
+    def _is_lone(model, path) -> bool:
+        """is the parameter ``path`` a bare attribute of a module that does not use it as a layer parameter?  (Linear, Conv2d,
+        the norm layers and Embedding own theirs; every module type this package taps is a leaf of torch.nn)"""
+        owner = model
+        for part in path.split(".")[:-1]:
+            owner = getattr(owner, part)
+        return not type(owner).__module__.startswith("torch.nn.")
 
     @property
     def unserved(self):
@@ -127,23 +174,32 @@ class Tape:
             raise NotImplementedError(f"{t.name}: KFAC has no rule for a grouped convolution (groups={t.module.groups}); "
                                       "freeze the layer (requires_grad=False) or use hessian_structure 'diag' or 'full'")
 
-    def unserved_by(self, norm: bool, gconv: bool):
-        """``uncovered`` minus what the norm taps (``norm``) and the grouped-convolution taps (``gconv``) own"""
+    def unserved_by(self, norm: bool, gconv: bool, embed: bool = False, param: bool = False):
+        """``uncovered`` minus what the norm taps (``norm``), the grouped-convolution taps (``gconv``), the embedding taps
+        (``embed``) and the lone-parameter taps (``param``) own"""
         left = self.unserved if norm else self.uncovered
         if gconv:
             owned = {id(p) for t in self.gconv_taps for p in (t.module.weight, t.module.bias) if p is not None}
             left = [p for p in left if id(p) not in owned]
+        if embed:
+            owned = {id(t.module.weight) for t in self.embed_taps}
+            left = [p for p in left if id(p) not in owned]
+        if param:
+            owned = {id(p) for p in self._lone.values()}
+            left = [p for p in left if id(p) not in owned]
         return left
 
-    def active_taps(self, norm: bool = False, gconv: bool = False):
+    def active_taps(self, norm: bool = False, gconv: bool = False, embed: bool = False, param: bool = False):
         """the taps of one call, in the order in which ``grad_fn`` returns their gradients"""
-        return self.taps + (self.gconv_taps if gconv else []) + (self.norm_taps if norm else [])
+        return (self.taps + (self.gconv_taps if gconv else []) + (self.norm_taps if norm else [])
+                + (self.embed_taps if embed else []) + (self.param_taps if param else []))
 
-    def forward(self, x, norm: bool = False, gconv: bool = False):
+    def forward(self, x, norm: bool = False, gconv: bool = False, embed: bool = False):
         """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph).  ``norm``: tap the norm layers too;
-        ``gconv``: and the grouped convolutions."""
+        ``gconv``: and the grouped convolutions; ``embed``: and the embeddings (``tap.a``: the token ids).  Lone parameters
+        have no module to hook: the seed-batched sweep alone serves them."""
         handles, seen = [], set()
-        self._active = self.active_taps(norm, gconv)
+        self._active = self.active_taps(norm, gconv, embed)
         for tap in self._active:
             def hook(m, inp, out, tap=tap):
                 if id(m) in seen:
@@ -151,6 +207,8 @@ class Tape:
                         raise NormTapReused(f"{tap.name}: module is applied more than once per forward")
                     raise NotImplementedError(f"{tap.name}: module is applied more than once per forward")
                 seen.add(id(m))
+                if tap.kind == "embed" and inp[0] is not x:
+                    raise EmbedTapForeign(f"{tap.name}: the Embedding does not read the model's input")
                 tap.a = inp[0].detach()
                 # the gradient EDGE of the output as it is now: models that go on to modify the tensor in place
                 # (torchvision's `out += identity; relu_(out)`) would otherwise hand back the gradient w.r.t. the
@@ -204,11 +262,10 @@ class Tape:
         return result
 
     def release(self):
-        for t in self.taps + self.gconv_taps + self.norm_taps:
+        for t in self.taps + self.gconv_taps + self.norm_taps + self.embed_taps + self.param_taps:
             t.a = None
             t.a_split = None
             t.out = None
-        for attr in ("sweep", "norm_sweep", "gconv_sweep", "gconv_norm_sweep"):
-            sweep = getattr(self, attr, None)
-            if sweep:
+        for attr, sweep in list(vars(self).items()):
+            if (attr == "sweep" or attr.endswith("_sweep")) and sweep:
                 sweep.release()

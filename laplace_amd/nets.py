@@ -415,16 +415,23 @@ class ViTClassToken(nn.Module):
     """:class:`ViTSmall` as ViT / BERT classifiers are written: a FROZEN class token prepended to the patch sequence
     (``torch.cat([self.cls.expand(B, -1, -1), x], 1)``; a frozen ``nn.Parameter``, so that the tracer sees the ``expand``),
     ``depth`` :class:`PackedAttentionBlock` s, a final LayerNorm and the ``Linear`` head on the class token ``x[:, 0]``.  The
-    defaults give ``T = 65`` positions and head dim 64.  ``freeze_norm`` as with :class:`ViTSmall`."""
+    defaults give ``T = 65`` positions and head dim 64.  ``freeze_norm`` as with :class:`ViTSmall`.
+
+    ``train_tokens=True`` is the model as it is actually trained: the class token is trainable and the sin-cos buffer is replaced
+    by a trainable position parameter (initialised to the same table).  Both are lone parameters: ``diag`` / ``full`` /
+    ``jacobians`` serve them through the parameter rule of the seed-batched sweep; KFAC refuses them, as the reference does."""
 
     def __init__(self, num_classes: int = 10, image: int = 32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
-                 act=nn.GELU, freeze_norm: bool = True, causal: bool = False):
+                 act=nn.GELU, freeze_norm: bool = True, causal: bool = False, train_tokens: bool = False):
         super().__init__()
         if image % patch:
             raise ValueError(f"patch ({patch}) must divide image ({image})")
         self.embed = nn.Conv2d(3, dim, patch, patch)
-        self.cls = nn.Parameter(torch.zeros(1, 1, dim).normal_(0.0, 0.02), requires_grad=False)
-        self.register_buffer("pos", sincos_positions((image // patch) ** 2 + 1, dim))
+        self.cls = nn.Parameter(torch.zeros(1, 1, dim).normal_(0.0, 0.02), requires_grad=bool(train_tokens))
+        if train_tokens:
+            self.pos = nn.Parameter(sincos_positions((image // patch) ** 2 + 1, dim))
+        else:
+            self.register_buffer("pos", sincos_positions((image // patch) ** 2 + 1, dim))
         self.blocks = nn.ModuleList(PackedAttentionBlock(dim, heads, act=act, causal=causal) for _ in range(depth))
         self.norm = nn.LayerNorm(dim)
         self.head = nn.Linear(dim, num_classes)
@@ -440,6 +447,39 @@ class ViTClassToken(nn.Module):
         for blk in self.blocks:
             x = blk(x)
         return self.head(self.norm(x)[:, 0])
+
+
+class TextTransformer(nn.Module):
+    """Token classifier on ids ``[B, T]`` (int64): ``nn.Embedding(vocab, dim, padding_idx)`` plus a learned ``[1, T, dim]``
+    position parameter, ``depth`` pre-LN :class:`AttentionBlock` s, a final LayerNorm, the mean over the tokens and a ``Linear``
+    head - the workload of the embedding route (csrc/lk_embed.hip, tools/embed_bench.py).
+
+    ``freeze_embed=True`` freezes the embedding and the position table, which KFAC needs (it has no rule for either, as the
+    reference); ``freeze_norm`` as with :class:`ViTSmall`."""
+
+    def __init__(self, vocab: int = 1000, T: int = 64, dim: int = 192, depth: int = 6, heads: int = 3, num_classes: int = 10,
+                 padding_idx: int | None = 0, act=nn.GELU, freeze_embed: bool = False, freeze_norm: bool = True,
+                 causal: bool = False):
+        super().__init__()
+        self.embed = nn.Embedding(vocab, dim, padding_idx=padding_idx)
+        self.pos = nn.Parameter(torch.zeros(1, T, dim).normal_(0.0, 0.02))
+        self.blocks = nn.ModuleList(AttentionBlock(dim, heads, act=act, causal=causal) for _ in range(depth))
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+        if freeze_embed:
+            self.embed.weight.requires_grad_(False)
+            self.pos.requires_grad_(False)
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.LayerNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, ids):
+        x = self.embed(ids) + self.pos
+        for blk in self.blocks:
+            x = blk(x)
+        return self.head(self.norm(x).mean(1))
 
 
 class SEBlock(nn.Module):

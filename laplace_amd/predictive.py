@@ -212,6 +212,15 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
             var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])
             fvar += K.diag_quadform_js(Jl, var.contiguous())
             continue
+        if tap.kind == "embed":  # run sums against the rows of the posterior variance, no Jacobian block (csrc/lk_embed.hip)
+            m = tap.module
+            K.diag_quadform_embed(g.contiguous(), backend._embed_ids(tap), m.num_embeddings, m.padding_idx,
+                                  post_var[tap.w_off:tap.w_off + m.weight.numel()].contiguous(), fvar)
+            continue
+        if tap.kind == "param":  # the cotangent is the block
+            Jl = backend._param_block(g)
+            fvar += K.diag_quadform_js(Jl, post_var[tap.w_off:tap.w_off + Jl.shape[-1]].contiguous())
+            continue
         if tap.kind == "gconv":  # likewise, in batch chunks of a bounded block
             for n0, Jl, n_w, n_b in backend._gconv_blocks(tap, g):
                 var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])

@@ -50,6 +50,13 @@ MATMUL, SOFTMAX, SCALE = "matrix-product", "softmax", "scale"
 # NEG: ``-x`` (the rotate-half of a rotary embedding); SUB: the difference of two tensors of the graph, or of one and a constant
 # or a Python number.  A sign has no reduction and nothing to fuse: both are torch math
 NEG, SUB = "negation", "difference"
+# _EMBED: nn.Embedding applied to the (integer) input: a gather, no input cotangent - the walk ends there; _PARAM: a TRACKED parameter
+# that the graph reads through ``get_attr`` (a class token, a learned position table); _EXPAND: ``expand`` / ``expand_as`` of such a
+# parameter along the batch dim only.  A _PARAM is live: its cotangent is its Jacobian block (`backend._layer_jacobian`).  (The rules
+# EMBED / PARAM of token models; module-private names: these kinds live at the integer input and at leaves of the graph, which the
+# NHWC walk never meets - `SplitSweep._split_eligible` sends such a model to the NCHW walk - so they are no part of the public kind list
+# that the two walks' tables are held against)
+_EMBED, _PARAM, _EXPAND = "embedding", "parameter", "batch-expansion"
 
 
 class Rule(NamedTuple):
@@ -87,7 +94,7 @@ _MODULE_KINDS = (
     ((nn.ReLU,), ACT, "relu"), ((nn.Tanh,), ACT, "tanh"), ((nn.Sigmoid,), ACT, "sigmoid"),
     (_GENERIC_ACT_MODULES, ACT, "generic"), ((nn.Identity, nn.Dropout), IDENTITY, None), ((nn.Flatten,), RESHAPE, None),
     ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None),
-    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None))
+    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None), ((nn.Embedding,), _EMBED, None))
 _FUNCTION_KINDS = {
     torch.relu: (ACT, "relu"), F.relu: (ACT, "relu"), torch.tanh: (ACT, "tanh"), F.tanh: (ACT, "tanh"),
     torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
@@ -556,6 +563,8 @@ def classify(node: fx.Node, modules: dict) -> Rule:
             attr = None
         if torch.is_tensor(attr) and not attr.requires_grad:  # a buffer or a frozen parameter: a constant of the sweep
             return Rule(CONST, what=f"constant {node.target}", args=(node.target,))
+        if isinstance(attr, nn.Parameter):  # a tracked parameter no module owns: live, served where its consumers allow it
+            return Rule(_PARAM, what=f"parameter {node.target}", args=(node.target,))
         raise SweepUnsupported("graph reads attributes directly")
     m, args, kwargs = None, node.args, dict(node.kwargs)
     if node.op == "call_module":
@@ -587,11 +596,26 @@ def classify(node: fx.Node, modules: dict) -> Rule:
         if not (args and isinstance(args[0], fx.Node)):
             raise SweepUnsupported(f"{what}: the tensor must be the first positional argument and a traced tensor")
         static = _classify_split(node, what)
+    elif kind == CONST and args and isinstance(args[0], fx.Node) and classify(args[0], modules).kind == _PARAM:
+        # (`expand` / `expand_as` of a tracked parameter: the batch dim only, checked on the value in the forward)
+        return Rule(_EXPAND, (args[0],), fn, (tuple(args), kwargs), f"{what} of parameter {args[0].target}", args=(args[0].target,))
     elif kind == CONST:  # (`expand` / `expand_as`: a constant when what it expands is one; evaluated in the forward)
         if not (args and isinstance(args[0], fx.Node) and classify(args[0], modules).kind == CONST):
             raise SweepUnsupported(f"{what} of a traced tensor (its VJP is a reduction, which has no rule; expanding a buffer or a "
                                    "frozen parameter is served)")
         what = f"constant {what} of {args[0].name}"
+    if kind == _EMBED:
+        ids = args[0] if args else None
+        src_kind = classify(ids, modules).kind if isinstance(ids, fx.Node) else None
+        if src_kind == CONST:  # (`nn.Embedding(arange)`: a position table written as a module)
+            if m.weight.requires_grad:
+                raise SweepUnsupported(f"{node.target}: Embedding of a constant index buffer with a tracked weight has no rule "
+                                       "(write the position table as a parameter, or freeze it)")
+            return Rule(CONST, (), m, ((ids,), {}), f"constant Embedding {node.target}")
+        if src_kind != "placeholder":
+            raise SweepUnsupported(f"{node.target}: Embedding of a traced tensor (the token ids must be the model's input)")
+        if m.max_norm is not None:
+            raise SweepUnsupported(f"{node.target}: Embedding with max_norm renormalises its weight in the forward pass")
     if kind == ADD:
         if kwargs.get("alpha", 1) != 1:
             raise SweepUnsupported("add with alpha")
@@ -640,7 +664,7 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == SUB:
         src = _classify_sub(node, modules)
         fn, args, kwargs, what = operator.sub, src, {}, "sub"  # (`-=` / `sub_` must not write into a kept tensor)
-    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM) else None, static)
+    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM, _EMBED) else None, static)
 
 
 def norm_geometry(m, inp):
@@ -890,7 +914,21 @@ class SeedBatchedSweep:
         self.modules = dict(self.gm.named_modules())
         self.tap_names = set(tap_modules)
         #: node -> :class:`Rule`, in graph order (the graph does not change after tracing)
-        self.rule: dict[fx.Node, Rule] = {node: classify(node, self.modules) for node in self.gm.graph.nodes}
+        self.rule: dict[fx.Node, Rule] = {}
+        for node in self.gm.graph.nodes:
+            try:
+                self.rule[node] = classify(node, self.modules)
+            except SweepUnsupported as e:  # (a refusal of an operation that reads a tracked parameter names the parameter)
+                lone = [a.target for a in node.all_input_nodes if self.rule.get(a, Rule("")).kind == _PARAM]
+                if not lone:
+                    raise
+                raise SweepUnsupported(f"parameter {lone[0]}: {e}") from e
+        for node, r in self.rule.items():
+            if r.kind == _PARAM:
+                if node.target not in self.tap_names:  # (nobody asked for its cotangent: the refusal such a graph always got)
+                    raise SweepUnsupported("graph reads attributes directly")
+                for u in node.users:
+                    self._param_consumer(node.target, u, self.rule[u])
         if sum(r.kind == "placeholder" for r in self.rule.values()) != 1:
             raise SweepUnsupported("models with one tensor input only")
         for node, r in self.rule.items():  # (a tuple of parts has no cotangent: only its items do)
@@ -901,6 +939,29 @@ class SeedBatchedSweep:
             raise SweepUnsupported("model must return a single tensor")
         # the modules whose VJP rules assume eval mode
         self._mode_mods = [m for m in self.gm.modules() if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d, nn.Dropout))]
+
+    _PARAM_REFUSALS = {MUL: "a product with a tracked parameter (LayerScale) has no rule",
+                       MATMUL: "matmul with a tracked parameter has no rule"}
+
+    def _param_consumer(self, target, user, ru):
+        """a tracked lone parameter is served where its per-sample cotangent is the arriving one: under ``+`` and under an
+        ``expand`` of the batch dim; everything else is refused by a message that names the parameter"""
+        if ru.kind == _EXPAND:
+            return
+        if ru.kind == ADD:
+            if all(isinstance(a, fx.Node) and self.rule[a].kind in (_PARAM, _EXPAND, CONST) for a in ru.src):
+                raise SweepUnsupported(f"parameter {target}: the sum has no per-sample operand")
+            return
+        why = self._PARAM_REFUSALS.get(ru.kind, f"{ru.what} reads a tracked parameter, which has no rule")
+        raise SweepUnsupported(f"parameter {target}: {why}")
+
+    @staticmethod
+    def _param_shape_check(target, p_shape, full_shape, what):
+        """the parameter's shape is the per-sample operand's with a 1, or nothing, at the batch dim: no reduction is owed"""
+        p, full = tuple(p_shape), tuple(full_shape)
+        if not (p == full[1:] or (len(p) == len(full) and p[0] == 1 and p[1:] == full[1:])):
+            raise SweepUnsupported(f"parameter {target}: {what} broadcasts {p} along a non-batch dim of {full}: its cotangent "
+                                   "needs a reduction, which has no rule")
 
     # ---- forward ---------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -935,7 +996,25 @@ class SeedBatchedSweep:
                     args, kwargs = fx.node.map_arg(r.call, env.__getitem__)
                     env[node] = r.fn(*args, **kwargs)
                 continue
+            if kind == _PARAM:
+                env[node] = _fetch_attr(self.gm, r.args[0]).detach()
+                if node.target in self.tap_names:
+                    self.taps[node.target] = {"a": None, "node": node}
+                continue
             args, kwargs = fx.node.map_arg(r.call, env.__getitem__)
+            if kind == _EXPAND:
+                out = r.fn(*args, **kwargs)
+                self._param_shape_check(r.args[0], args[0].shape, (x.shape[0],) + tuple(out.shape[1:]), "expand")
+                if out.shape[0] != x.shape[0] or args[0].dim() != out.dim():
+                    raise SweepUnsupported(f"parameter {r.args[0]}: expand along a non-batch dim needs a reduction, which has no rule")
+                env[node] = out
+                continue
+            if kind == ADD:
+                for a, other in zip(r.src, reversed(r.src)):
+                    if isinstance(a, fx.Node) and self.rule[a].kind == _PARAM:
+                        if not torch.is_tensor(env.get(other)):
+                            raise SweepUnsupported(f"parameter {a.target}: add with a Python number")
+                        self._param_shape_check(a.target, env[a].shape, env[other].shape, "add")
             inp, keep = args[0], None  # (keep: what the node's VJP needs)
             if (kind == BN and self.kernels is not None and inp.dim() >= 2 and inp.dtype == torch.float32
                     and r.mod.running_var is not None):
@@ -1604,7 +1683,7 @@ class SeedBatchedSweep:
                     g2 = _sum(parts[1:])
                 else:
                     g = _sum(parts)
-            if r.mod is not None and node.target in self.tap_names:
+            if (r.mod is not None or r.kind == _PARAM) and node.target in self.tap_names:
                 if node in walk.pending_scale:
                     self.grad_scale[node.target] = walk.pending_scale[node]
                 if walk.tap(node.target, g.reshape(S, B, *g.shape[1:])):
@@ -1623,6 +1702,7 @@ class SeedBatchedSweep:
             RESHAPE: "_vjp_reshape", GPOOL: "_vjp_gpool", AVGPOOL: "_vjp_avgpool", MAXPOOL: "_vjp_maxpool", MEAN: "_vjp_mean",
             ATTN: "_vjp_attn", PERMUTE: "_vjp_permute", ADD: "_vjp_add", MUL: "_vjp_mul", MATMUL: "_vjp_matmul",
             SOFTMAX: "_vjp_softmax", SCALE: "_vjp_scale", NEG: "_vjp_neg", SUB: "_vjp_sub", CAT: "_vjp_cat", SLICE: "_vjp_slice",
+            _EXPAND: "_vjp_identity", _EMBED: "_vjp_leaf", _PARAM: "_vjp_leaf",
             SIZE: None, GETITEM: None, SPLIT: None, CONST: None, "placeholder": None, "output": None}
 
     def _vjp_rule(self, r):
@@ -1658,6 +1738,9 @@ class SeedBatchedSweep:
 
     def _vjp_identity(self, walk, node, r, g, g2):
         walk.push(r.src[0], g)
+
+    def _vjp_leaf(self, walk, node, r, g, g2):
+        """an embedding of the integer input, a tapped parameter: the cotangent is the tap's (handed over in `backward`), the walk ends here"""
 
     def _vjp_reshape(self, walk, node, r, g, g2, as_map=None):
         """``as_map``: what the NHWC walk makes of a 4-D result (a feature map again)"""
