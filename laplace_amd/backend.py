@@ -246,17 +246,13 @@ class _HipCurvatureMixin:
             return tuple(_HipCurvatureMixin._cast(o, dt) for o in out)
         return out
 
-    def _forward(self, x, keep_tap_splits: bool = False, norm: bool = False):
+    def _forward(self, x, keep_tap_splits: bool = False, extra: bool = False):
         """Returns (f [B,C] detached, tape, grad_fn) where grad_fn(seeds[S,B,C]) -> per-tap [S,B,...].
         ``keep_tap_splits``: the NHWC sweep also keeps the split copies of the tapped inputs (``tap.a_split``).
-        ``norm``: the normalisation layers are tapped too (``grad_fn`` then returns ``tape.taps + tape.norm_taps``
-        gradients, in that order) when :meth:`_norm_route` allows it."""
+        ``extra``: the kinds of :meth:`_route` are tapped too.  The route is decided HERE, once per call, and left in
+        ``tape.route``: ``grad_fn`` returns the gradients of ``tape.active_taps(tape.route)``, in that order."""
         tape = self._tape()
-        extra = bool(norm and not self.last_layer)  # (the callers that tap the extra layers)
-        gconv = bool(extra and self._gconv_route(tape))
-        embed = bool(extra and self._embed_route(tape))
-        param = bool(extra and self._param_route(tape))
-        norm = bool(extra and self._norm_route(tape))
+        route = tape.route = self._route(tape) if extra and not self.last_layer else frozenset()
         if self.last_layer:
             # f = last_layer(phi): the gradient w.r.t. the head's output IS the seed -> no reverse pass
             swept = (x.f, x.phi) if isinstance(x, CachedFeatures) else self._features_swept(x, tape)
@@ -272,22 +268,22 @@ class _HipCurvatureMixin:
             B = phi.shape[0]
             f = f.detach().reshape(B, -1).contiguous()
             return f, tape, lambda seeds, stack=True: [seeds.contiguous()]
-        swept = self._forward_swept(x, tape, keep_tap_splits, norm, gconv, embed, param)
+        swept = self._forward_swept(x, tape, keep_tap_splits, route)
         if swept is not None:
             return swept
-        if param:
-            # the sweep that `_param_route` classified does not serve THIS call (training mode, a shape its rules refuse): a lone
+        if "param" in route:
+            # the sweep that `_route` classified does not serve THIS call (training mode, a shape its rules refuse): a lone
             # parameter has no other device route, so the tape's lone parameters stay unserved from here on, as without the switch
-            tape.param_off = True
-            return self._forward(x, keep_tap_splits, norm=True)
+            tape.disabled.add("param")
+            return self._forward(x, keep_tap_splits, extra=True)
         try:
-            f = tape.forward(x, norm=norm, gconv=gconv, embed=embed)
+            f = tape.forward(x, route)
         except NormTapReused:
-            tape.norm_off = True  # (a norm layer applied twice per forward: this model stays on the generic route)
+            tape.disabled.add("norm")  # (a norm layer applied twice per forward: this model stays on the generic route)
             return self._forward(x, keep_tap_splits)
         except EmbedTapForeign:
-            tape.embed_off = True  # (an embedding of something else than the input: its weight stays unserved)
-            return self._forward(x, keep_tap_splits, norm=True)
+            tape.disabled.add("embed")  # (an embedding of something else than the input: its weight stays unserved)
+            return self._forward(x, keep_tap_splits, extra=True)
         self._check_dtype(f)
         if f.ndim == 1:
             f = f.unsqueeze(-1)
@@ -359,14 +355,12 @@ class _HipCurvatureMixin:
         fs.release()
         return f, phi
 
-    def _sweep_for(self, tape, norm: bool = False, gconv: bool = False, embed: bool = False, param: bool = False):
-        """the reverse sweep that taps ``tape.active_taps(norm, gconv, embed, param)``, built once per combination and kept on
-        the tape (``tape.sweep``, ``tape.norm_sweep``, ``tape.gconv_sweep``, ...); ``False``: the model has none
-        (``tape.sweep_reason`` says why).  Needs no input: tracing and classifying the graph is all it does."""
-        slot = ("param_" if param else "") + ("embed_" if embed else "") + ("gconv_" if gconv else "") + ("norm_sweep" if norm else "sweep")
-        sweep = getattr(tape, slot, None)
+    def _sweep_for(self, tape, route=frozenset()):
+        """the reverse sweep that taps ``tape.active_taps(route)``, built once per route and kept in ``tape.sweeps``; ``False``:
+        the model has none (``tape.sweep_reason`` says why).  Needs no input: tracing and classifying the graph is all it does."""
+        sweep = tape.sweeps.get(route)
         if sweep is None:
-            taps = tape.active_taps(norm, gconv, embed, param)
+            taps = tape.active_taps(route)
             try:
                 # NHWC split-fp16 sweep (own convolution kernels) where the graph allows it, else the NCHW sweep
                 if self.use_split_sweep:
@@ -377,19 +371,17 @@ class _HipCurvatureMixin:
             except SweepUnsupported as e:
                 sweep = False
                 tape.sweep_reason = str(e)
-            setattr(tape, slot, sweep)
+            tape.sweeps[route] = sweep
         return sweep
 
-    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, norm: bool = False, gconv: bool = False, embed: bool = False,
-                       param: bool = False):
+    def _forward_swept(self, x, tape, keep_tap_splits: bool = False, route=frozenset()):
         """Seed-batched reverse sweep (laplace_amd/sweep.py) when the model is fx-traceable and built from
-        modules with a closed-form VJP; ``None`` -> caller uses the autograd tape.  ``norm``: the sweep that also taps the
-        normalisation layers, built and cached beside the Linear / Conv2d one (``tape.norm_sweep``); ``gconv``: the one that
-        taps the grouped convolutions (``tape.gconv_sweep``, ``tape.gconv_norm_sweep``)."""
+        modules with a closed-form VJP; ``None`` -> caller uses the autograd tape.  ``route``: the sweep that also taps these
+        kinds, built and cached beside the Linear / Conv2d one (:meth:`_sweep_for`)."""
         if not self.use_sweep or not torch.is_tensor(x) or not tape.taps:
             return None
-        taps = tape.active_taps(norm, gconv, embed, param)
-        sweep = self._sweep_for(tape, norm, gconv, embed, param)
+        taps = tape.active_taps(route)
+        sweep = self._sweep_for(tape, route)
         if sweep is False:
             return None
         try:
@@ -623,36 +615,42 @@ class _HipCurvatureMixin:
         g5 = g.reshape(S, B, -1, g.shape[-1]).transpose(2, 3).unsqueeze(-1).contiguous()       # [S, B, Do, T, 1]
         return a4, g5, (1, 1), (1, 1), (0, 0), (1, 1)
 
-    def _layer_jacobian(self, tap, g, Js):
-        """Writes this module's columns of ``Js[B, S, P]``; ``g`` is ``[S, B, ...]``."""
-        K = get_kernels()
-        if tap.kind == "norm":
-            self._norm_columns(tap, g, Js, tap.w_off, tap.b_off)
-            return
-        if tap.kind == "gconv":
-            m = tap.module
-            K.jac_gconv(tap.a.to(torch.float32).contiguous(), g.contiguous(), m.kernel_size, m.stride, m.padding, m.dilation,
-                        m.groups, Js, tap.w_off, tap.b_off)
-            return
-        if tap.kind == "embed":  # (Js arrives zeroed: the kernel writes the columns of the ids that occur, csrc/lk_embed.hip)
-            m = tap.module
-            K.jac_embed(g.contiguous(), self._embed_ids(tap), m.num_embeddings, m.padding_idx, Js, tap.w_off)
-            return
-        if tap.kind == "param":  # (the per-sample cotangent IS the block: a strided copy, no reduction)
-            Jl = self._param_block(g)
-            Js[:, :, tap.w_off:tap.w_off + Jl.shape[-1]] = Jl
-            return
+    # one writer per tap kind: this module's columns of ``Js[B, S, P]`` from ``g [S, B, ...]``, straight into ``Js``
+    def _jac_dense(self, tap, g, Js):
         a = tap.a.to(torch.float32)
         if tap.kind == "linear" and a.ndim == 2:
-            K.jac_linear(a.contiguous(), g.contiguous(), Js, tap.w_off, tap.b_off)
+            get_kernels().jac_linear(a.contiguous(), g.contiguous(), Js, tap.w_off, tap.b_off)
         else:
             a4, g5, ks, st, pd, dl = self._conv_view(tap, a, g)
-            K.jac_conv(a4, g5, ks, st, pd, dl, Js, tap.w_off, tap.b_off)
+            get_kernels().jac_conv(a4, g5, ks, st, pd, dl, Js, tap.w_off, tap.b_off)
+
+    def _jac_norm(self, tap, g, Js):
+        self._norm_columns(tap, g, Js, tap.w_off, tap.b_off)
+
+    def _jac_gconv(self, tap, g, Js):
+        m = tap.module
+        get_kernels().jac_gconv(tap.a.to(torch.float32).contiguous(), g.contiguous(), m.kernel_size, m.stride, m.padding,
+                                m.dilation, m.groups, Js, tap.w_off, tap.b_off)
+
+    def _jac_embed(self, tap, g, Js):  # (Js arrives zeroed: the kernel writes the columns of the ids that occur, csrc/lk_embed.hip)
+        m = tap.module
+        get_kernels().jac_embed(g.contiguous(), self._embed_ids(tap), m.num_embeddings, m.padding_idx, Js, tap.w_off)
+
+    def _jac_param(self, tap, g, Js):  # (the per-sample cotangent IS the block: a strided copy, no reduction)
+        Jl = self._param_block(g)
+        Js[:, :, tap.w_off:tap.w_off + Jl.shape[-1]] = Jl
+
+    _JAC_WRITERS = {"linear": _jac_dense, "conv2d": _jac_dense, "norm": _jac_norm, "gconv": _jac_gconv, "embed": _jac_embed,
+                    "param": _jac_param}
+
+    def _layer_jacobian(self, tap, g, Js):
+        """Writes this module's columns of ``Js[B, S, P]``; ``g`` is ``[S, B, ...]``."""
+        self._JAC_WRITERS[tap.kind](self, tap, g, Js)
 
     def _rows(self, x, seeds_fn):
         """``Z[B, S, P]`` = seed-contracted per-sample Jacobians (all tracked params must be covered)."""
-        f, tape, grad_fn = self._forward(x, norm=True)
-        if self._unserved(tape):
+        f, tape, grad_fn = self._forward(x, extra=True)
+        if tape.unserved_by(tape.route):
             tape.release()
             raise Unserved("parameters outside nn.Linear / nn.Conv2d / the affine normalisation layers are not covered "
                            "by the HIP kernels")
@@ -668,44 +666,43 @@ class _HipCurvatureMixin:
     def _supported(self) -> bool:
         return not self._unserved(self._tape())
 
-    # ---- normalisation layers -----------------------------------------------------------------------------------------
-    def _norm_route(self, tape) -> bool:
-        """Are the tracked norm parameters served by the device kernel in THIS call?  Needs the switch, a kernel object that
-        provides the entry point (the emulation of the CPU test tier may not), and every norm tap servable as it stands
-        (``model.train()`` between two calls changes that)."""
-        return bool(tape.norm_taps and self.use_norm_kernels and not getattr(tape, "norm_off", False)
-                    and getattr(get_kernels(), "jac_norm_affine", None) is not None
-                    and all(norm_servable(t.module) for t in tape.norm_taps))
+    # ---- the extra tap kinds: normalisation layers, grouped convolutions, embeddings, lone parameters -----------------------
+    def _param_sweep_ok(self, tape, route) -> bool:
+        """Only the seed-batched sweep delivers a lone parameter's per-sample cotangent (autograd alone yields the batch sum), so:
+        ``use_sweep``, and a sweep for the resulting route whose rules accept every consumer of every such parameter - decided
+        on the traced graph, before any forward."""
+        return bool(self.use_sweep and tape.taps and not self.last_layer
+                    and self._sweep_for(tape, route | {"param"}) is not False)
 
-    def _gconv_route(self, tape) -> bool:
-        """Are the tracked grouped convolutions served by csrc/lk_gconv.hip?  Needs a kernel object with the entry point
-        (the stock emulation of the CPU test tier has none: such a model then takes the generic route)."""
-        return bool(tape.gconv_taps and self.use_gconv_kernels and getattr(get_kernels(), "jac_gconv", None) is not None)
+    def _norm_taps_servable(self, tape, route) -> bool:
+        """every norm tap is servable as it stands (``model.train()`` between two calls changes that)"""
+        return all(norm_servable(t.module) for t in tape.norm_taps)
 
-    def _embed_route(self, tape) -> bool:
-        """Are the tracked nn.Embedding weights served by csrc/lk_embed.hip?  Needs the switch and a kernel object with the
-        entry point (the emulations below tests/emulated_embed_kernels.py have none)."""
-        return bool(tape.embed_taps and self.use_embed_kernels and not getattr(tape, "embed_off", False)
-                    and getattr(get_kernels(), "jac_embed", None) is not None)
+    #: kind -> (switch, entry point the kernel object must provide, further condition on ``(self, tape, the route so far)``), in
+    #: the order of `capture.EXTRA_KINDS`.  A kernel object may lack an entry (the emulations of the CPU test tier do): such a
+    #: model then takes the generic route
+    _ROUTES = {"gconv": ("use_gconv_kernels", "jac_gconv", None),
+               "norm": ("use_norm_kernels", "jac_norm_affine", _norm_taps_servable),
+               "embed": ("use_embed_kernels", "jac_embed", None),
+               "param": ("use_embed_kernels", "jac_embed", _param_sweep_ok)}
 
-    def _param_route(self, tape) -> bool:
-        """Are the tracked lone parameters (class token, position table) served?  Only the seed-batched sweep delivers their
-        per-sample cotangent (autograd alone yields the batch sum), so: the same switch, ``use_sweep``, and a sweep whose rules
-        accept every consumer of every such parameter - decided on the traced graph, before any forward."""
-        if not (tape.param_taps and self.use_embed_kernels and self.use_sweep and tape.taps and not self.last_layer
-                and not getattr(tape, "param_off", False) and getattr(get_kernels(), "jac_embed", None) is not None):
-            return False
-        return self._sweep_for(tape, self._norm_route(tape), self._gconv_route(tape), self._embed_route(tape), True) is not False
+    def _route(self, tape) -> frozenset:
+        """the extra kinds whose tracked parameters the device kernels serve in THIS call"""
+        route = frozenset()
+        for kind, (switch, entry, cond) in self._ROUTES.items():
+            if (tape.extra_taps[kind] and getattr(self, switch) and kind not in tape.disabled
+                    and getattr(get_kernels(), entry, None) is not None and (cond is None or cond(self, tape, route))):
+                route |= {kind}
+        return route
 
     def _unserved(self, tape):
-        """tracked parameters that no device rule serves in this call (``tape.uncovered`` when the norm, grouped-convolution,
-        embedding and lone-parameter routes are off)"""
-        return tape.unserved_by(self._norm_route(tape), self._gconv_route(tape), self._embed_route(tape), self._param_route(tape))
+        """tracked parameters that no device rule would serve in a call made now (``tape.uncovered`` when every extra route is
+        off).  For use BEFORE a forward; after one, ``tape.route`` holds the decision."""
+        return tape.unserved_by(self._route(tape))
 
     def _served_taps(self, tape):
-        if self.last_layer:
-            return tape.taps
-        return tape.active_taps(self._norm_route(tape), self._gconv_route(tape), self._embed_route(tape), self._param_route(tape))
+        """the taps of the latest forward"""
+        return tape.active_taps(tape.route)
 
     @staticmethod
     def _embed_ids(tap):
@@ -720,20 +717,33 @@ class _HipCurvatureMixin:
     #: bytes a grouped convolution's own Jacobian block ``[b, S, width]`` may take; larger minibatches are cut along the batch
     gconv_block_bytes = 256 << 20
 
-    def _gconv_blocks(self, tap, g):
-        """yields ``(n0, Jl [b, S, width + n_b], width, n_b)`` over batch chunks of a grouped convolution's Jacobian block,
-        each within ``gconv_block_bytes`` and the tile path's ``b * S <= 65535``"""
-        m = tap.module
-        S, B = g.shape[0], g.shape[1]
-        width, n_b = m.weight.numel(), (m.out_channels if tap.has_bias else 0)
-        step = max(1, min(int(self.gconv_block_bytes) // (4 * S * (width + n_b)), 65535 // S, B))
-        a = tap.a.to(torch.float32)
-        for n0 in range(0, B, step):
-            b = min(step, B - n0)
-            Jl = torch.zeros(b, S, width + n_b, dtype=torch.float32, device=g.device)
-            get_kernels().jac_gconv(a[n0:n0 + b].contiguous(), g[:, n0:n0 + b].contiguous(), m.kernel_size, m.stride,
-                                    m.padding, m.dilation, m.groups, Jl, 0, width if n_b else -1)
-            yield n0, Jl, width, n_b
+    #: the kinds whose own small Jacobian block is formed and then reduced by a generic kernel (:meth:`_tap_blocks`)
+    BLOCK_KINDS = ("norm", "param", "gconv")
+
+    def _tap_blocks(self, tap, g):
+        """yields ``(n0, Jl [b, S, n], spans)`` for a tap of `BLOCK_KINDS`: the layer's own Jacobian block of the samples from
+        ``n0`` on, and where its columns belong: ``spans`` lists ``(column in Jl, width, offset in the parameter vector)`` - the
+        weight's and the bias's for a layer (width 0: not tracked), one for a lone parameter.  A norm layer's block is tiny (two
+        values per channel) and a lone parameter's cotangent IS the block; a grouped convolution's (a depthwise 3x3 layer has 9
+        columns per channel) comes in batch chunks, each within ``gconv_block_bytes`` and the tile path's ``b * S <= 65535``"""
+        if tap.kind == "param":
+            Jl = self._param_block(g)
+            yield 0, Jl, [(0, Jl.shape[-1], tap.w_off)]
+        elif tap.kind == "norm":
+            Jl, n_w, n_b = self._norm_block(tap, g)
+            yield 0, Jl, [(0, n_w, tap.w_off), (n_w, n_b, tap.b_off)]
+        else:
+            m = tap.module
+            S, B = g.shape[0], g.shape[1]
+            width, n_b = m.weight.numel(), (m.out_channels if tap.has_bias else 0)
+            step = max(1, min(int(self.gconv_block_bytes) // (4 * S * (width + n_b)), 65535 // S, B))
+            a = tap.a.to(torch.float32)
+            for n0 in range(0, B, step):
+                b = min(step, B - n0)
+                Jl = torch.zeros(b, S, width + n_b, dtype=torch.float32, device=g.device)
+                get_kernels().jac_gconv(a[n0:n0 + b].contiguous(), g[:, n0:n0 + b].contiguous(), m.kernel_size, m.stride,
+                                        m.padding, m.dilation, m.groups, Jl, 0, width if n_b else -1)
+                yield n0, Jl, [(0, width, tap.w_off), (width, n_b, tap.b_off)]
 
     @staticmethod
     def _norm_xhat(tap):
@@ -841,8 +851,8 @@ class _HipCurvatureMixin:
 
     def _diag_impl(self, x, y, seeds_fn, alpha):
         K = get_kernels()
-        f, tape, grad_fn = self._forward(x, norm=True)
-        if self._unserved(tape):
+        f, tape, grad_fn = self._forward(x, extra=True)
+        if tape.unserved_by(tape.route):
             tape.release()
             return None
         loss = torch.zeros(1, dtype=torch.float32, device=f.device)
@@ -851,29 +861,16 @@ class _HipCurvatureMixin:
         h = torch.zeros(tape.n_params, dtype=torch.float32, device=f.device)
         B, S = f.shape[0], seeds.shape[0]
         for tap, g in zip(self._served_taps(tape), grads):
-            if tap.kind == "norm":
-                # the layer's block [B, S, 2 Ch] is tiny: write it and square-sum its columns (as the narrow convolutions)
-                Jl, n_w, n_b = self._norm_block(tap, g)
-                if n_w:
-                    K.sq_colsum(Jl, 0, n_w, alpha, h[tap.w_off:tap.w_off + n_w])
-                if n_b:
-                    K.sq_colsum(Jl, n_w, n_b, alpha, h[tap.b_off:tap.b_off + n_b])
+            if tap.kind in self.BLOCK_KINDS:  # the layer's own block, its columns square-summed (as the narrow convolutions)
+                for _, Jl, spans in self._tap_blocks(tap, g):
+                    for col, n, off in spans:
+                        if n:
+                            K.sq_colsum(Jl, col, n, alpha, h[off:off + n])
                 continue
             if tap.kind == "embed":  # straight into h: the [B, S, V*D] block is never formed
                 m = tap.module
                 K.diag_embed(g.contiguous(), self._embed_ids(tap), m.num_embeddings, m.padding_idx, alpha,
                              h[tap.w_off:tap.w_off + m.weight.numel()])
-                continue
-            if tap.kind == "param":
-                Jl = self._param_block(g)
-                K.sq_colsum(Jl, 0, Jl.shape[-1], alpha, h[tap.w_off:tap.w_off + Jl.shape[-1]])
-                continue
-            if tap.kind == "gconv":
-                # the layer's own block (a depthwise 3x3 layer has 9 columns per channel), its columns square-summed
-                for _, Jl, n_w, n_b in self._gconv_blocks(tap, g):
-                    K.sq_colsum(Jl, 0, n_w, alpha, h[tap.w_off:tap.w_off + n_w])
-                    if n_b:
-                        K.sq_colsum(Jl, n_w, n_b, alpha, h[tap.b_off:tap.b_off + n_b])
                 continue
             a = tap.a.to(torch.float32)
             m = tap.module

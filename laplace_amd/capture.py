@@ -20,6 +20,9 @@ from torch import nn
 SUPPORTED = (nn.Linear, nn.Conv2d)
 #: affine normalisation layers: their weight / bias Jacobian is a per-channel reduction of ``g * xhat`` (csrc/lk_norm.hip)
 NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm, nn.RMSNorm)
+#: the tap kinds beyond Linear / dense Conv2d, in the order in which `Tape.active_taps` appends them (= the order of `grad_fn`'s
+#: gradients).  A ROUTE is a frozenset of these kinds: what one call taps beside `Tape.taps`
+EXTRA_KINDS = ("gconv", "norm", "embed", "param")
 
 
 @dataclass
@@ -145,6 +148,10 @@ class Tape:
             if id(p) in offsets and isinstance(p, nn.Parameter) and self._is_lone(model, name):
                 self.param_taps.append(Tap(name, None, "param", offsets[id(p)], -1))
         self._lone = {t.name: p for t in self.param_taps for n, p in model.named_parameters() if n == t.name}
+        self.extra_taps = {"gconv": self.gconv_taps, "norm": self.norm_taps, "embed": self.embed_taps, "param": self.param_taps}
+        self.route = frozenset()  # the route of the latest forward
+        self.disabled: set[str] = set()  # kinds that a forward of this model found it cannot tap: off from then on
+        self.sweeps: dict = {}  # route -> the reverse sweep that taps it (False: the model has none, `sweep_reason` says why)
 
     @staticmethod
     def _is_lone(model, path) -> bool:
@@ -156,15 +163,23 @@ class Tape:
         return not type(owner).__module__.startswith("torch.nn.")
 
     @property
+    def sweep(self):
+        """the sweep of the empty route (Linear / Conv2d taps only); ``None`` before one was built"""
+        return self.sweeps.get(frozenset())
+
+    def owned(self, kind: str):
+        """the parameters that the taps of one extra kind own - decided per call for ``norm``: a BatchNorm switched to training
+        mode (or one without running statistics) is not served"""
+        if kind == "param":
+            return list(self._lone.values())
+        # (nn.RMSNorm and nn.Embedding have no bias attribute)
+        return [p for t in self.extra_taps[kind] if kind != "norm" or norm_servable(t.module)
+                for p in (t.module.weight, getattr(t.module, "bias", None)) if p is not None]
+
+    @property
     def unserved(self):
-        """``uncovered`` minus what the norm taps own — decided per call: a BatchNorm switched to training mode (or one
-        without running statistics) is not served, and neither are embeddings, lone parameters, ..."""
-        owned = set()
-        for t in self.norm_taps:
-            if norm_servable(t.module):
-                # (nn.RMSNorm has no bias attribute)
-                owned.update(id(p) for p in (t.module.weight, getattr(t.module, "bias", None)) if p is not None)
-        return [p for p in self.uncovered if id(p) not in owned]
+        """``uncovered`` minus what the norm taps own: embeddings, lone parameters, ... are not served"""
+        return self.unserved_by(frozenset({"norm"}))
 
     def refuse_kfac(self):
         """KFAC (the accumulator, ``kron``, the Kron predictive) has no rule for a grouped convolution: what the reference's
@@ -174,32 +189,21 @@ class Tape:
             raise NotImplementedError(f"{t.name}: KFAC has no rule for a grouped convolution (groups={t.module.groups}); "
                                       "freeze the layer (requires_grad=False) or use hessian_structure 'diag' or 'full'")
 
-    def unserved_by(self, norm: bool, gconv: bool, embed: bool = False, param: bool = False):
-        """``uncovered`` minus what the norm taps (``norm``), the grouped-convolution taps (``gconv``), the embedding taps
-        (``embed``) and the lone-parameter taps (``param``) own"""
-        left = self.unserved if norm else self.uncovered
-        if gconv:
-            owned = {id(p) for t in self.gconv_taps for p in (t.module.weight, t.module.bias) if p is not None}
-            left = [p for p in left if id(p) not in owned]
-        if embed:
-            owned = {id(t.module.weight) for t in self.embed_taps}
-            left = [p for p in left if id(p) not in owned]
-        if param:
-            owned = {id(p) for p in self._lone.values()}
-            left = [p for p in left if id(p) not in owned]
-        return left
+    def unserved_by(self, route):
+        """``uncovered`` minus what the taps of the kinds in ``route`` own"""
+        owned = {id(p) for kind in route for p in self.owned(kind)}
+        return [p for p in self.uncovered if id(p) not in owned]
 
-    def active_taps(self, norm: bool = False, gconv: bool = False, embed: bool = False, param: bool = False):
+    def active_taps(self, route=frozenset()):
         """the taps of one call, in the order in which ``grad_fn`` returns their gradients"""
-        return (self.taps + (self.gconv_taps if gconv else []) + (self.norm_taps if norm else [])
-                + (self.embed_taps if embed else []) + (self.param_taps if param else []))
+        return self.taps + [t for kind in EXTRA_KINDS if kind in route for t in self.extra_taps[kind]]
 
-    def forward(self, x, norm: bool = False, gconv: bool = False, embed: bool = False):
-        """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph).  ``norm``: tap the norm layers too;
-        ``gconv``: and the grouped convolutions; ``embed``: and the embeddings (``tap.a``: the token ids).  Lone parameters
-        have no module to hook: the seed-batched sweep alone serves them."""
+    def forward(self, x, route=frozenset()):
+        """Run ``model(x)`` with hooks; returns ``f`` (attached to the graph).  ``route``: the extra kinds tapped too (an
+        embedding's ``tap.a``: the token ids).  Lone parameters have no module to hook (``"param"`` is ignored): the seed-batched
+        sweep alone serves them."""
         handles, seen = [], set()
-        self._active = self.active_taps(norm, gconv, embed)
+        self._active = self.active_taps(route - {"param"})
         for tap in self._active:
             def hook(m, inp, out, tap=tap):
                 if id(m) in seen:
@@ -262,10 +266,10 @@ class Tape:
         return result
 
     def release(self):
-        for t in self.taps + self.gconv_taps + self.norm_taps + self.embed_taps + self.param_taps:
+        for t in self.active_taps(frozenset(EXTRA_KINDS)):
             t.a = None
             t.a_split = None
             t.out = None
-        for attr, sweep in list(vars(self).items()):
-            if (attr == "sweep" or attr.endswith("_sweep")) and sweep:
+        for sweep in [*self.sweeps.values(), getattr(self, "feature_sweep", None)]:
+            if sweep:
                 sweep.release()

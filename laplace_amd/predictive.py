@@ -198,8 +198,8 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
     """``(f_mu, f_var)`` under a diagonal posterior with variances ``post_var[P]``."""
     _fp32_only(backend)
     K = get_kernels()
-    f, tape, grad_fn = backend._forward(x, norm=True)
-    if backend._unserved(tape):
+    f, tape, grad_fn = backend._forward(x, extra=True)
+    if tape.unserved_by(tape.route):
         tape.release()
         raise NotImplementedError("fused diagonal predictive needs Linear / Conv2d / affine normalisation layers only")
     B, C = f.shape
@@ -207,24 +207,16 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
     post_var = post_var.detach().to(torch.float32).contiguous()
     fvar = torch.zeros(B, C, C, dtype=torch.float32, device=f.device)
     for tap, g in zip(backend._served_taps(tape), grads):
-        if tap.kind == "norm":  # the layer's [B, C, 2 Ch] Jacobian block against its slice of the posterior variance
-            Jl, n_w, n_b = backend._norm_block(tap, g)
-            var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])
-            fvar += K.diag_quadform_js(Jl, var.contiguous())
+        if tap.kind in backend.BLOCK_KINDS:  # the layer's own Jacobian block against its slices of the posterior variance
+            for n0, Jl, spans in backend._tap_blocks(tap, g):
+                var = [post_var[off:off + n] for _, n, off in spans]
+                var = torch.cat(var) if len(var) > 1 else var[0]
+                fvar[n0:n0 + Jl.shape[0]].add_(K.diag_quadform_js(Jl, var.contiguous()))
             continue
         if tap.kind == "embed":  # run sums against the rows of the posterior variance, no Jacobian block (csrc/lk_embed.hip)
             m = tap.module
             K.diag_quadform_embed(g.contiguous(), backend._embed_ids(tap), m.num_embeddings, m.padding_idx,
                                   post_var[tap.w_off:tap.w_off + m.weight.numel()].contiguous(), fvar)
-            continue
-        if tap.kind == "param":  # the cotangent is the block
-            Jl = backend._param_block(g)
-            fvar += K.diag_quadform_js(Jl, post_var[tap.w_off:tap.w_off + Jl.shape[-1]].contiguous())
-            continue
-        if tap.kind == "gconv":  # likewise, in batch chunks of a bounded block
-            for n0, Jl, n_w, n_b in backend._gconv_blocks(tap, g):
-                var = torch.cat([post_var[tap.w_off:tap.w_off + n_w], post_var[tap.b_off:tap.b_off + n_b]])
-                fvar[n0:n0 + Jl.shape[0]] += K.diag_quadform_js(Jl, var.contiguous())
             continue
         m = tap.module
         n_w = m.weight.numel()

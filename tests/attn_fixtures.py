@@ -354,7 +354,7 @@ def run_curvature_checks(dev, name, lik, configure=None):
     def swept(backend):
         tape = backend._tape()
         assert getattr(tape, "sweep_reason", None) is None, tape.sweep_reason
-        assert any(getattr(tape, slot, None) not in (None, False) for slot in ("sweep", "norm_sweep")), "no sweep was built"
+        assert any(tape.sweeps.get(r) not in (None, False) for r in (frozenset(), frozenset({"norm"}))), "no sweep was built"
 
     backend = HipGGN(model, lik)
     configure(backend)

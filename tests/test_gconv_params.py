@@ -178,16 +178,17 @@ def test_sweep_delivers_the_tape_s_gradients(gconv_kernels, name):
     for use_sweep in (True, False):
         b = HipGGN(model, "classification")
         b.use_sweep = use_sweep
-        f, tape, grad_fn = b._forward(X, norm=True)
+        f, tape, grad_fn = b._forward(X, extra=True)
         taps = b._served_taps(tape)
         assert [t.name for t in taps if t.kind == "gconv"] == GROUPED[name]
         grads = grad_fn(seeds)
         assert len(grads) == len(taps)
         got[use_sweep] = {t.name: (t.a.clone(), gr.clone()) for t, gr in zip(taps, grads)}
-        sweep = getattr(tape, "gconv_norm_sweep" if name == "gcres" else "gconv_sweep", None)
+        assert tape.route == (frozenset({"gconv", "norm"}) if name == "gcres" else frozenset({"gconv"}))
+        sweep = tape.sweeps.get(tape.route)
         if use_sweep:
             assert isinstance(sweep, SeedBatchedSweep) and not getattr(sweep, "split_ok", False)
-            assert getattr(tape, "sweep", None) is None and getattr(tape, "norm_sweep", None) is None
+            assert set(tape.sweeps) == {tape.route}  # (only the sweep of this route was built)
         else:
             assert sweep is None
         tape.release()
@@ -247,7 +248,7 @@ def test_dense_models_keep_their_tape_and_sweep(gconv_kernels):
     b = HipGGN(model, "classification")
     b.jacobians(X), b.diag(X, y)
     tape = b._tape()
-    assert tape.gconv_taps == [] and tape.sweep and getattr(tape, "gconv_sweep", None) is None
+    assert tape.gconv_taps == [] and tape.sweep and set(tape.sweeps) == {frozenset()}
 
 
 def test_emulation_agrees_with_autograd_on_an_asymmetric_grouped_layer(gconv_kernels):

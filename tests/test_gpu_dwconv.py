@@ -217,7 +217,7 @@ def _split_sweeps(b):
     from laplace_amd.sweep_nhwc import SplitSweep
 
     tape = b._tape()
-    sweeps = [s for s in (getattr(tape, a, None) for a in ("sweep", "norm_sweep", "gconv_sweep", "gconv_norm_sweep")) if s]
+    sweeps = [s for s in tape.sweeps.values() if s]
     assert sweeps, getattr(tape, "sweep_reason", None)
     for s in sweeps:
         assert isinstance(s, SplitSweep) and s.split_reason is None, getattr(s, "split_reason", None)
@@ -319,7 +319,7 @@ def test_the_switch_gives_the_default_results(e2e, monkeypatch):
     monkeypatch.setattr(SplitSweep, "nhwc_depthwise", False)
     old = HipGGN(copy.deepcopy(e2e["m64"]).float().to(DEV), "classification")
     Js_old, f_old, h_old = _in_two_batches(old, Xd, yd)
-    sweep = old._tape().gconv_sweep
+    sweep = old._tape().sweeps[frozenset({"gconv"})]
     assert isinstance(sweep, SplitSweep) and not sweep.split_ok and "foreign to the NHWC kernels" in sweep.split_reason
     check(f_old, e2e["f"], what="f (nhwc_depthwise = False)")
     for n, lo, hi in _blocks(model):

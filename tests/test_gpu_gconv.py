@@ -246,7 +246,7 @@ def test_mobilenet_diag_against_its_own_jacobians():
     other_cols = others[torch.randperm(others.numel(), generator=gen)[:4096]]
 
     _, h = b.diag(X, y)
-    sweep = tape.gconv_norm_sweep
+    sweep = tape.sweeps[frozenset({"gconv", "norm"})]
     assert sweep, getattr(tape, "sweep_reason", None)  # (one seed-batched reverse pass, not one autograd pass per seed)
     Js, f = b.jacobians(X)
     assert Js.shape == (nb, 10, tape.n_params)

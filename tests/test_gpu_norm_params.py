@@ -214,7 +214,7 @@ def test_resnet18_unfrozen_batchnorm_diag_against_its_own_jacobians():
     other_cols = others[torch.randperm(others.numel(), generator=gen)[:4096]]
 
     _, h = b.diag(X, y)
-    sweep = tape.norm_sweep
+    sweep = tape.sweeps[frozenset({"norm"})]
     # which sweep served the model: the NCHW rules of the parent class (a tapped BatchNorm makes the split sweep ineligible)
     assert isinstance(sweep, SplitSweep) and not sweep.split_ok and "tapped BatchNorm" in sweep.split_reason
     print(f"sweep: {type(sweep).__name__}, split_ok={sweep.split_ok}, split_reason={sweep.split_reason!r}")

@@ -174,7 +174,7 @@ def test_backend_on_the_sweep_against_reference_golden(monkeypatch, name, lik):
     monkeypatch.setattr(torch.autograd, "grad", real)
     tape = b._tape()
     # the route: the seed-batched sweep with the norm layers tapped, one VJP launch per norm node and call, no autograd pass
-    assert isinstance(tape.norm_sweep, SeedBatchedSweep), getattr(tape, "sweep_reason", None)
+    assert isinstance(tape.sweeps.get(frozenset({"norm"})), SeedBatchedSweep), getattr(tape, "sweep_reason", None)
     assert len(calls) == 2 and not passes, (calls, passes)
     check(Js, g["Js"], what="jacobians")
     check(f, g["f"], what="f")

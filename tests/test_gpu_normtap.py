@@ -226,7 +226,7 @@ def _norm_sweep(b):
     from laplace_amd.sweep_nhwc import SplitSweep
 
     tape = b._tape()
-    sweep = getattr(tape, "norm_sweep", None)
+    sweep = tape.sweeps.get(frozenset({"norm"}))
     assert isinstance(sweep, SplitSweep), getattr(tape, "sweep_reason", None)
     assert sweep.split_ok and sweep.split_reason is None, sweep.split_reason
     return sweep
@@ -292,7 +292,7 @@ def test_the_golden_model_keeps_its_numbers_with_the_switch_on(lik):
     b = HipGGN(model, lik)
     Js, f = b.jacobians(X)
     _, h = b.diag(X, y)
-    sweep = b._tape().norm_sweep
+    sweep = b._tape().sweeps[frozenset({"norm"})]
     assert not sweep.split_ok and sweep.split_reason == "0: convolution outside the implicit-GEMM kernel's coverage"
     check(Js, torch.as_tensor(g["Js"]), what="jacobians")
     check(h, torch.as_tensor(g["h_ggn"]), what="diag GGN")
@@ -313,7 +313,7 @@ def test_resnet18_norm_columns_with_the_switch_on_equal_those_with_it_off():
     off.nhwc_norm_taps = False
     Js0, _ = off.jacobians(Xd)
     _, h0 = off.diag(Xd, yd)
-    sweep = off._tape().norm_sweep
+    sweep = off._tape().sweeps[frozenset({"norm"})]
     assert isinstance(sweep, SplitSweep) and not sweep.split_ok and "tapped BatchNorm" in sweep.split_reason
     names = set(nf.norm_names(m))
     n_norm = 0

@@ -181,15 +181,16 @@ def test_nchw_sweep_delivers_the_cotangent_of_a_tapped_batchnorm(norm_kernels):
     for use_sweep in (True, False):
         b = HipGGN(model, "classification")
         b.use_sweep = use_sweep
-        f, tape, grad_fn = b._forward(X, norm=True)
+        f, tape, grad_fn = b._forward(X, extra=True)
         taps = tape.taps + tape.norm_taps
         grads = grad_fn(seeds)
         assert len(grads) == len(taps) == 6
         got[use_sweep] = {t.name: (t.a.clone(), gr.clone()) for t, gr in zip(taps, grads)}
-        sweep = getattr(tape, "norm_sweep", None)
+        assert tape.route == frozenset({"norm"})
+        sweep = tape.sweeps.get(tape.route)
         if use_sweep:
             assert isinstance(sweep, SplitSweep) and not sweep.split_ok and "tapped BatchNorm" in sweep.split_reason
-            assert getattr(tape, "sweep", None) is None  # (the Linear / Conv2d sweep is a separate object, not built here)
+            assert set(tape.sweeps) == {tape.route}  # (the Linear / Conv2d sweep is a separate object, not built here)
         else:
             assert sweep is None
         tape.release()
@@ -208,7 +209,7 @@ def test_models_without_norm_taps_build_the_sweep_they_built_before(norm_kernels
     b = HipGGN(model, "classification")
     b.jacobians(X), b.diag(X, y)
     tape = b._tape()
-    assert tape.norm_taps == [] and getattr(tape, "norm_sweep", None) is None and tape.sweep
+    assert tape.norm_taps == [] and set(tape.sweeps) == {frozenset()} and tape.sweep
 
 
 def test_stock_emulation_without_the_entry_point_takes_the_generic_route(stock_kernels, monkeypatch):

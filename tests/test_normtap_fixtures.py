@@ -273,11 +273,11 @@ def test_jacobians_and_diag_equal_those_of_the_nchw_sweep(nt_kernels, name):
     on = HipGGN(model, "classification")
     on.nhwc_norm_taps = True
     Js, f, h = _in_two_batches(on, X, y)
-    sweep = on._tape().norm_sweep
+    sweep = on._tape().sweeps[frozenset({"norm"})]
     assert isinstance(sweep, SplitSweep) and sweep.split_ok, getattr(sweep, "split_reason", None)
     off = HipGGN(copy.deepcopy(m64).float(), "classification")
     Js0, f0, h0 = _in_two_batches(off, X, y)
-    sweep0 = off._tape().norm_sweep
+    sweep0 = off._tape().sweeps[frozenset({"norm"})]
     assert isinstance(sweep0, SplitSweep) and not sweep0.split_ok and "delivered by the NCHW sweep" in sweep0.split_reason
     assert _rel(f, f0) < 1e-4
     for n, lo, hi in nf.blocks(model):
@@ -302,7 +302,7 @@ def test_the_golden_model_keeps_its_numbers_with_the_switch_on(nt_kernels, lik):
     b.nhwc_norm_taps = True
     Js, f = b.jacobians(X)
     _, h = b.diag(X, y)
-    sweep = b._tape().norm_sweep
+    sweep = b._tape().sweeps[frozenset({"norm"})]
     assert not sweep.split_ok and sweep.split_reason == "0: convolution outside the implicit-GEMM kernel's coverage"
     assert _rel(Js, torch.as_tensor(g["Js"])) < 1e-4 and _rel(h, torch.as_tensor(g["h_ggn"])) < 1e-4
 

@@ -306,7 +306,7 @@ def test_tracked_rmsnorm_weights_are_served_by_the_norm_taps(emulated):
     for t in tape.norm_taps:  # (the layer's own columns, which are small beside the Linear layers')
         cols = slice(t.w_off, t.w_off + 32)
         assert rf.rel(Js[..., cols], Js64[..., cols]) < 1e-4, t.name
-    assert getattr(tape, "sweep_reason", None) is None and getattr(tape, "norm_sweep", None) not in (None, False)
+    assert getattr(tape, "sweep_reason", None) is None and tape.sweeps.get(frozenset({"norm"})) not in (None, False)
     _, h = backend.diag(X, y)
     assert rf.rel(h, co.ggn_diag(Js64, co.functional_hessian(f64, "classification"))) < 1e-4
     with pytest.raises(NotImplementedError, match="KFAC supports nn.Linear / nn.Conv2d parameters only"):

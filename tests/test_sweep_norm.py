@@ -177,8 +177,8 @@ def test_forward_without_vjp_keeps_nothing(emulated, request):
 @pytest.mark.parametrize("lik", ("classification", "regression"))
 @pytest.mark.parametrize("name", ("normgn", "normln"))
 def test_backend_sweeps_the_norm_models_and_meets_the_goldens(normvjp_kernels, monkeypatch, name, lik):
-    """``jacobians`` and ``diag`` at the ``TOL`` of tests/test_norm_params.py, on the sweep: ``tape.norm_sweep`` is a sweep object
-    (it was ``False``: the model dropped to one autograd pass per seed) and ``torch.autograd.grad`` is never called"""
+    """``jacobians`` and ``diag`` at the ``TOL`` of tests/test_norm_params.py, on the sweep: the sweep of route ``{"norm"}`` is a
+    sweep object (it was ``False``: the model dropped to one autograd pass per seed) and ``torch.autograd.grad`` is never called"""
     from laplace_amd import HipGGN
 
     g = load_golden(name, lik)
@@ -191,7 +191,7 @@ def test_backend_sweeps_the_norm_models_and_meets_the_goldens(normvjp_kernels, m
     monkeypatch.setattr(torch.autograd, "grad", real)
     assert not calls, f"{len(calls)} autograd passes"
     tape = b._tape()
-    assert isinstance(tape.norm_sweep, SeedBatchedSweep), getattr(tape, "sweep_reason", None)
+    assert isinstance(tape.sweeps.get(frozenset({"norm"})), SeedBatchedSweep), getattr(tape, "sweep_reason", None)
     for got, want, what in ((Js, g["Js"], "jacobians"), (f, g["f"], "f"), (h, g["h_ggn"], "diag GGN"), (loss, g["loss"], "loss")):
         e = rel(got, want)
         print(f"{name} {lik} {what}: {e:.3e}")

@@ -164,7 +164,7 @@ def leg_e2e(args, what):
            "tracked": "all but BatchNorm and the depthwise weights" if what == "kron" else "all but BatchNorm"}
     for route, b in backends.items():
         tape = b._tape()
-        sweep = getattr(tape, "sweep" if what == "kron" else "gconv_sweep", None)
+        sweep = tape.sweeps.get(frozenset() if what == "kron" else frozenset({"gconv"}))
         assert sweep not in (None, False), getattr(tape, "sweep_reason", None)
         out[route] = {"ms": _median(rounds[route]), "ms_rounds": rounds[route], "sweep": type(sweep).__name__,
                       "split_ok": bool(getattr(sweep, "split_ok", False)), "split_reason": getattr(sweep, "split_reason", None)}

@@ -178,7 +178,7 @@ def leg_device(args):
         b.diag(X, y)
     rounds = [timer(lambda i: b.diag(X, y), 1 if args.rehearse else 5) for _ in range(1 if args.rehearse else 3)]
     tape = b._tape()
-    sweep = getattr(tape, "gconv_norm_sweep", None)
+    sweep = tape.sweeps.get(frozenset({"gconv", "norm"}))
     return {"batch": B, "diag_ms": sorted(rounds)[len(rounds) // 2], "diag_ms_rounds": rounds,
             "ms_per_sample": sorted(rounds)[len(rounds) // 2] / B, "n_params": tape.n_params,
             "grouped_taps": len(tape.gconv_taps), "norm_taps": len(tape.norm_taps), "sweep": type(sweep).__name__,

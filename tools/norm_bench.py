@@ -143,7 +143,7 @@ def leg_diag(args, freeze_bn):
         b.diag(X, y)
     rounds = [timer(lambda i: b.diag(X, y), 1 if args.rehearse else 5) for _ in range(1 if args.rehearse else 3)]
     tape = b._tape()
-    sweep = getattr(tape, "sweep" if freeze_bn else "norm_sweep", None)
+    sweep = tape.sweeps.get(frozenset() if freeze_bn else frozenset({"norm"}))
     assert b._supported()
     return {"batch": B, "diag_ms": sorted(rounds)[len(rounds) // 2], "diag_ms_rounds": rounds,
             "ms_per_sample": sorted(rounds)[len(rounds) // 2] / B, "n_params": tape.n_params,

@@ -144,7 +144,7 @@ def leg_e2e(args, leg):
            "class_default": HipGGN.nhwc_norm_taps}
     for route, b in backends.items():
         tape = b._tape()
-        sweep = getattr(tape, "norm_sweep", None)
+        sweep = tape.sweeps.get(frozenset({"norm"}))
         assert sweep not in (None, False), getattr(tape, "sweep_reason", None)
         out[route] = {"ms": _median(rounds[route]), "ms_rounds": rounds[route], "sweep": type(sweep).__name__,
                       "split_ok": bool(getattr(sweep, "split_ok", False)), "split_reason": getattr(sweep, "split_reason", None)}
