@@ -287,6 +287,31 @@ def _one_scale(x: "SplitTensor", what: str) -> "SplitTensor":
     return x
 
 
+def _split_half(x: "SplitTensor", what: str, name: str, chunked: Optional[str]):
+    """``(hi, lo, sexp)`` addresses of a one-scale split operand.  ``chunked``: what a chunk-major one is to the caller, for its
+    refusal (``None``: the caller refuses it itself, with its shape)"""
+    _one_scale(x, what)
+    if chunked is not None and x.chunked:
+        raise LaplaceHipError(f"{what}: a chunk-major split tensor is {chunked}")
+    _check(x.planes, f"{name}.planes", torch.float16)
+    _check(x.sexp, f"{name}.sexp", torch.int32)
+    return x.planes[0].data_ptr(), x.planes[1].data_ptr(), x.sexp.data_ptr()
+
+
+def _split_operand(x, what: str, name: str, chunked: str):
+    """``(f32, hi, lo, sexp), shape, device`` of an operand that is an fp32 tensor or a one-scale :class:`SplitTensor` read as it
+    lies: the addresses of the form it has, ``None`` for the other"""
+    if isinstance(x, SplitTensor):
+        return (None, *_split_half(x, what, name, chunked)), x.shape, x.planes.device
+    _check(x, name)
+    return (x.data_ptr(), None, None, None), x.shape, x.device
+
+
+def _amax_word(amax, what: str):
+    if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
+        raise LaplaceHipError(f"{what}: amax is one 32-bit device word")
+
+
 def is_channels_last(x) -> bool:
     """logical [B, C, H, W] tensor whose memory is dense NHWC (and not also dense NCHW)"""
     return torch.is_tensor(x) and x.dim() == 4 and not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous()
@@ -1322,11 +1347,9 @@ class HipKernels:
         """the same columns from the NHWC sweep's own cotangent (csrc/lk_normtap.hip): ``g`` the one-scale split tensor
         ``[S*B, .., Ch]``, ``x`` ``[B, .., Ch]`` fp32, ``xhat = (x - mu) * rstd`` formed in registers (``mu``, ``rstd`` ``[Ch]``, or
         both ``None``: ``x`` is ``xhat``)."""
-        _one_scale(g, "jac_norm_affine_nhwc")
-        if g.chunked:
-            raise LaplaceHipError("jac_norm_affine_nhwc: a chunk-major split tensor is an operand of the weight-sharing "
-                                  "predictive; this kernel reads position-major planes [S*B, .., Ch]")
-        _check(g.planes, "g.planes", torch.float16), _check(g.sexp, "g.sexp", torch.int32), _check(x, "x"), _check(Js, "Js")
+        g_ptrs = _split_half(g, "jac_norm_affine_nhwc", "g", "an operand of the weight-sharing predictive; this kernel reads "
+                             "position-major planes [S*B, .., Ch]")
+        _check(x, "x"), _check(Js, "Js")
         S = int(S)
         if x.dim() < 2 or g.planes.dim() != x.dim() + 1 or S < 1 or g.planes.shape[1] != S * x.shape[0] \
                 or tuple(g.planes.shape[2:]) != tuple(x.shape[1:]) or Js.dim() != 3 or tuple(Js.shape[:2]) != (x.shape[0], S):
@@ -1339,7 +1362,7 @@ class HipKernels:
                 raise LaplaceHipError(f"jac_norm_affine_nhwc: {name} must be [Ch]")
         L = x.numel() // max(B * Ch, 1)
         self._rc(
-            self.lib.lk_jac_norm_affine_nhwc_f16x2(_ptr(g.planes[0]), _ptr(g.planes[1]), _ptr(g.sexp), _ptr(x), _ptr(mu), _ptr(rstd),
+            self.lib.lk_jac_norm_affine_nhwc_f16x2(*g_ptrs, _ptr(x), _ptr(mu), _ptr(rstd),
                                                    S, B, max(L, 1), Ch, _ptr(Js), Js.shape[-1], int(wcol0), int(bcol0),
                                                    self._stream(x.device)),
             "lk_jac_norm_affine_nhwc_f16x2",
@@ -1396,8 +1419,7 @@ class HipKernels:
             _check(w, "w")
             if w.numel() != Ch:
                 raise LaplaceHipError(f"norm_vjp: w must have {Ch} elements")
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("norm_vjp: amax is one 32-bit device word")
+        _amax_word(amax, "norm_vjp")
         dx = torch.empty_like(g)
         self._rc(self.lib.lk_norm_vjp_f32(_ptr(g), _ptr(xhat), _ptr(rstd), _ptr(w), int(S), B, L, Ch, int(G), int(layout),
                                           _ptr(dx), _ptr(amax), self._stream(g.device)), "lk_norm_vjp_f32")
@@ -1448,8 +1470,7 @@ class HipKernels:
             _check(w, "w")
             if w.numel() != D:
                 raise LaplaceHipError(f"rmsnorm_vjp: w must have {D} elements")
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("rmsnorm_vjp: amax is one 32-bit device word")
+        _amax_word(amax, "rmsnorm_vjp")
         dx = torch.empty_like(g)
         if rows == 0:
             return dx
@@ -1582,8 +1603,7 @@ class HipKernels:
                 raise LaplaceHipError("pool_vjp: arg must be [B, OH, OW, C]")
         elif arg is not None:
             raise LaplaceHipError("pool_vjp: the average takes no arg")
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("pool_vjp: amax is one 32-bit device word")
+        _amax_word(amax, "pool_vjp")
         dx = torch.empty(S * B, H, W, C, dtype=torch.float32, device=g.device)
         self._rc(self.lib.lk_pool_vjp_nhwc_f32(int(kind), _ptr(g), _ptr(arg), S, B, H, W, C, kh, kw, sh, sw, ph, pw,
                                                int(bool(count_include_pad)), int(divisor_override or 0), _ptr(dx), _ptr(amax),
@@ -1637,26 +1657,17 @@ class HipKernels:
         shape, dev = tuple(parts[0].shape), None
         arrays = [(ctypes.c_void_p * len(parts))() for _ in range(4)]  # f32, hi, lo, sexp
         for j, p in enumerate(parts):
-            if isinstance(p, SplitTensor):
-                _one_scale(p, "cat_vjp")
-                if p.chunked:
-                    raise LaplaceHipError("cat_vjp: a chunk-major split tensor is no NHWC map")
-                _check(p.planes, f"parts[{j}].planes", torch.float16)
-                _check(p.sexp, f"parts[{j}].sexp", torch.int32)
-                arrays[1][j], arrays[2][j], arrays[3][j] = p.planes[0].data_ptr(), p.planes[1].data_ptr(), p.sexp.data_ptr()
-                pdev = p.planes.device
-            else:
-                _check(p, f"parts[{j}]")
-                arrays[0][j], pdev = p.data_ptr(), p.device
-            if len(shape) != 4 or tuple(p.shape) != shape or (dev is not None and pdev != dev):
+            ptrs, pshape, pdev = _split_operand(p, "cat_vjp", f"parts[{j}]", "no NHWC map")
+            for a, ptr in zip(arrays, ptrs):
+                a[j] = ptr
+            if len(shape) != 4 or pshape != shape or (dev is not None and pdev != dev):
                 raise LaplaceHipError(f"cat_vjp: part {j} {tuple(p.shape)} is not an NHWC map [N, H, W, Ct] like part 0 {shape}")
             dev = pdev
         c0, Cs = int(c0), int(Cs)
         N, H, W, Ct = (int(d) for d in shape)
         if Cs < 1 or c0 < 0 or c0 + Cs > Ct:
             raise LaplaceHipError(f"cat_vjp: channels [{c0}, {c0 + Cs}) are no slice of {Ct} channels")
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("cat_vjp: amax is one 32-bit device word")
+        _amax_word(amax, "cat_vjp")
         dx = torch.empty(N, H, W, Cs, dtype=torch.float32, device=dev)
         self._rc(self.lib.lk_cat_vjp_nhwc_f32(len(parts), *(ctypes.addressof(a) for a in arrays), N * H * W, Ct, c0, Cs, _ptr(dx),
                                               _ptr(amax), self._stream(dev)), "lk_cat_vjp_nhwc_f32")
@@ -1702,22 +1713,13 @@ class HipKernels:
             c0, cs = int(c0), int(cs)
             if cs < 1 or c0 < 0 or c0 + cs > Ct:
                 raise LaplaceHipError(f"slice_vjp: piece {j}: columns [{c0}, {c0 + cs}) are no slice of {Ct} columns")
-            if isinstance(p, SplitTensor):
-                _one_scale(p, "slice_vjp")
-                if p.chunked:
-                    raise LaplaceHipError("slice_vjp: a chunk-major split tensor is no row matrix")
-                _check(p.planes, f"pieces[{j}].planes", torch.float16)
-                _check(p.sexp, f"pieces[{j}].sexp", torch.int32)
-                arrays[1][j], arrays[2][j], arrays[3][j] = p.planes[0].data_ptr(), p.planes[1].data_ptr(), p.sexp.data_ptr()
-                pdev, numel = p.planes.device, p.planes[0].numel()
-            else:
-                _check(p, f"pieces[{j}]")
-                arrays[0][j], pdev, numel = p.data_ptr(), p.device, p.numel()
-            if numel != R * cs or (dev is not None and pdev != dev):
+            ptrs, pshape, pdev = _split_operand(p, "slice_vjp", f"pieces[{j}]", "no row matrix")
+            for a, ptr in zip(arrays, ptrs):
+                a[j] = ptr
+            if pshape.numel() != R * cs or (dev is not None and pdev != dev):
                 raise LaplaceHipError(f"slice_vjp: piece {j} {tuple(p.shape)} is no row matrix [{R}, {cs}]")
             c0s[j], css[j], dev = c0, cs, pdev
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("slice_vjp: amax is one 32-bit device word")
+        _amax_word(amax, "slice_vjp")
         dx = torch.empty(R, Ct, dtype=torch.float32, device=dev)
         self._rc(self.lib.lk_slice_vjp_f32(n, *(ctypes.addressof(a) for a in arrays), ctypes.addressof(c0s), ctypes.addressof(css),
                                            R, Ct, _ptr(dx), _ptr(amax), self._stream(dev)), "lk_slice_vjp_f32")
@@ -1771,19 +1773,10 @@ class HipKernels:
     def _gate_g(g, what):
         """the four pointer arguments ``(g, g_h, g_l, sexp)`` of the gate kernels for a cotangent ``[N, H, W, C]`` - an fp32 NHWC
         tensor or a one-scale :class:`SplitTensor` read as it lies - with its shape and device"""
-        if isinstance(g, SplitTensor):
-            _one_scale(g, what)
-            if g.chunked:
-                raise LaplaceHipError(f"{what}: a chunk-major split tensor is no NHWC map")
-            _check(g.planes, "g.planes", torch.float16)
-            _check(g.sexp, "g.sexp", torch.int32)
-            ptrs, dev = (None, g.planes[0].data_ptr(), g.planes[1].data_ptr(), g.sexp.data_ptr()), g.planes.device
-        else:
-            _check(g, "g")
-            ptrs, dev = (g.data_ptr(), None, None, None), g.device
-        if len(g.shape) != 4:
-            raise LaplaceHipError(f"{what}: g {tuple(g.shape)} is no NHWC map [N, H, W, C]")
-        return ptrs, tuple(int(d) for d in g.shape), dev
+        ptrs, shape, dev = _split_operand(g, what, "g", "no NHWC map")
+        if len(shape) != 4:
+            raise LaplaceHipError(f"{what}: g {tuple(shape)} is no NHWC map [N, H, W, C]")
+        return ptrs, tuple(int(d) for d in shape), dev
 
     def gate_reduce(self, g, x, S):
         """``ds`` ``[S * B, C]``: ``ds[s B + b, c] = sum_hw g[s B + b, h, w, c] * x[b, h, w, c]`` for the ``S`` seeds stacked in the
@@ -1813,8 +1806,7 @@ class HipKernels:
             _check(r, "r")
             if tuple(r.shape) != (N, C) or r.device != dev:
                 raise LaplaceHipError(f"gate_vjp: r {tuple(r.shape)} is not [{N}, {C}]")
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("gate_vjp: amax is one 32-bit device word")
+        _amax_word(amax, "gate_vjp")
         dx = torch.empty(N, H, W, C, dtype=torch.float32, device=dev)
         self._rc(self.lib.lk_gate_vjp_nhwc_f32(*ptrs, _ptr(gate), _ptr(r), S, N // S, H * W, C, _ptr(dx), _ptr(amax),
                                                self._stream(dev)), "lk_gate_vjp_nhwc_f32")
@@ -1917,8 +1909,8 @@ class HipKernels:
     def dwconv_backward(self, g: "SplitTensor", w_tap, S, in_hw, kernel, stride, padding, amax=None):
         """``dx`` ``[S*B, H, W, C]`` (fp32) of a depthwise convolution for the ``S`` seeds stacked in the one-scale split cotangent
         ``g`` ``[S*B, OH, OW, C]``; ``in_hw`` = ``(H, W)``.  ``amax``: zeroed device word that receives the bit pattern of max|dx|."""
-        _one_scale(g, "dwconv_backward")
-        _check(g.planes, "g.planes", torch.float16), _check(g.sexp, "g.sexp", torch.int32), _check(w_tap, "w_tap")
+        g_ptrs = _split_half(g, "dwconv_backward", "g", None)  # (a chunk-major g is refused below, with its shape)
+        _check(w_tap, "w_tap")
         S, (H, W) = int(S), (int(in_hw[0]), int(in_hw[1]))
         if g.chunked or g.planes.dim() != 5 or S < 1 or g.planes.shape[1] % S:
             raise LaplaceHipError("dwconv_backward: g must be a split tensor [S*B, OH, OW, C]")
@@ -1929,10 +1921,9 @@ class HipKernels:
                                   f"({sh}, {sw}), padding ({ph}, {pw}) on a {H} x {W} map")
         if tuple(w_tap.shape) != (kh * kw, C):
             raise LaplaceHipError(f"dwconv_backward: w_tap {tuple(w_tap.shape)} is not [kh * kw, C] = [{kh * kw}, {C}]")
-        if amax is not None and (amax.numel() != 1 or amax.element_size() != 4):
-            raise LaplaceHipError("dwconv_backward: amax is one 32-bit device word")
+        _amax_word(amax, "dwconv_backward")
         dx = torch.empty(S * B, H, W, C, dtype=torch.float32, device=g.planes.device)
-        self._rc(self.lib.lk_dwconv_bwd_nhwc_f16x2(_ptr(g.planes[0]), _ptr(g.planes[1]), _ptr(g.sexp), _ptr(w_tap), S, B, H, W, C,
+        self._rc(self.lib.lk_dwconv_bwd_nhwc_f16x2(*g_ptrs, _ptr(w_tap), S, B, H, W, C,
                                                    kh, kw, sh, sw, ph, pw, _ptr(dx), _ptr(amax), self._stream(dx.device)),
                  "lk_dwconv_bwd_nhwc_f16x2")
         return dx

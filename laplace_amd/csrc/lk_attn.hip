@@ -25,7 +25,7 @@
 // delta is accumulated in the order of the DOT chain (d = 16 c + 4 g + e over c, e, g), so that with T == 1, where O == V and
 // P == 1, dP - delta is exactly 0.
 // Minimal traffic of a VJP call: 4 S B H T D (2 reads of gO + 3 writes) + 8 S B H T (delta) + the per-sample operands.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 #include <math.h>
 
@@ -400,11 +400,6 @@ static int attn_check_shape(const char* fn, int64_t S, int64_t B, int64_t H, int
   return LK_OK;
 }
 
-static bool attn_apart(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x + na <= y || y + nb <= x;
-}
-
 static int attn_check(const char* fn, const void* const* in, const size_t* in_bytes, int n_in, const void* const* out,
                       const size_t* out_bytes, int n_out, float scale) {
   uintptr_t bits = 0;
@@ -420,7 +415,7 @@ static int attn_check(const char* fn, const void* const* in, const size_t* in_by
   LK_REQUIRE(isfinite(scale), "%s: scale must be finite", fn);
   for (int i = 0; i < n_out; ++i)
     for (int j = 0; j < n_in; ++j)
-      LK_REQUIRE(attn_apart(out[i], out_bytes[i], in[j], in_bytes[j]), "%s: an output overlaps an input", fn);
+      LK_REQUIRE(disjoint(out[i], out_bytes[i], in[j], in_bytes[j]), "%s: an output overlaps an input", fn);
   return LK_OK;
 }
 

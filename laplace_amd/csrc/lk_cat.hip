@@ -13,15 +13,11 @@
 // 8-byte loads of four halves) where Ct, c0 and Cs are multiples of 4 and the pointers are aligned, one element per lane
 // otherwise; a grid of at most 256 CUs x 8 workgroups strides over the lanes.  Only the slice of every part is read.  Every dst
 // element has one owner, stores are plain, repeated runs give the same bits.  `amax` receives max|dst| as the bit pattern of a
-// non-negative float through atomicMax, one atomic per wave (as lk_pool_vjp_nhwc_f32).
+// non-negative float through atomicMax, one atomic per wave (wave_amax of lk_stream.h).
 // Minimal traffic of the VJP: R Cs (4 + 4 n_f32 + 4 n_split) bytes; of the forward: 8 R Cs bytes.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
-
-typedef _Float16 cat_f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int64_t CAT_MAX_BLOCKS = 256 * 8;  // 256 CUs x 8 workgroups of 256 threads
 
 struct CatParts {  // by value: device pointers of the parts (f32[p] non-null: an fp32 map; else planes h[p], l[p] and sexp[p])
   const float* f32[LK_CAT_MAX_PARTS];
@@ -30,84 +26,22 @@ struct CatParts {  // by value: device pointers of the parts (f32[p] non-null: a
   const int* sexp[LK_CAT_MAX_PARTS];
 };
 
-struct CatGeom {
-  int64_t Ct, c0, Cs, lanes;
-  int CV;   // lanes per row
-  int big;  // the lane index does not fit 31 bits: 64-bit division
-  FastDiv cv_div;
-};
-
-// lane index -> (row, first channel of the lane inside the slice)
-template <int VEC>
-__device__ __forceinline__ void cat_where(const CatGeom& q, int64_t t, int64_t& r, int& c) {
-  if (!q.big) {
-    const int ri = fdiv((int)t, q.cv_div);
-    r = ri;
-    c = ((int)t - ri * q.CV) * VEC;
-  } else {
-    r = t / q.CV;
-    c = (int)(t - r * q.CV) * VEC;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void cat_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void cat_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-
-// (float(h) + float(l)) * scale of VEC adjacent channels; scale is a power of two, so the product is exact
-template <int VEC>
-__device__ __forceinline__ void cat_ld_split(const _Float16* __restrict__ h, const _Float16* __restrict__ l, float scale,
-                                             float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const cat_f16x4 a = *reinterpret_cast<const cat_f16x4*>(h), b = *reinterpret_cast<const cat_f16x4*>(l);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = ((float)a[e] + (float)b[e]) * scale;
-  } else {
-    v[0] = ((float)*h + (float)*l) * scale;
-  }
-}
-
-// one atomic per wave: the lanes' maxima of |dst| (non-negative floats order like their bit patterns)
-__device__ __forceinline__ void cat_wave_amax(float m, unsigned* __restrict__ amax) {
-  unsigned b = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
-  if (amax != nullptr && (threadIdx.x & 63) == 0 && b) atomicMax(amax, b);
-}
-
 // ---- forward: a lane per VEC channels of a source row ---------------------------------------------------------------------------
 template <int VEC>
-__global__ __launch_bounds__(256) void cat_fwd_kernel(const float* __restrict__ src, CatGeom q, float* __restrict__ dst) {
+__global__ __launch_bounds__(256) void cat_fwd_kernel(const float* __restrict__ src, ColSliceGeom q, float* __restrict__ dst) {
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < q.lanes; t += (int64_t)gridDim.x * 256) {
     int64_t r;
     int c;
-    cat_where<VEC>(q, t, r, c);
+    col_where<VEC>(q, t, r, c);
     float v[VEC];
-    cat_ld<VEC>(src + t * VEC, v);  // (the source is the contiguous [R][Cs] map: its lanes lie in order)
-    cat_st<VEC>(dst + r * q.Ct + q.c0 + c, v);
+    ld<VEC>(src + t * VEC, v);  // (the source is the contiguous [R][Cs] map: its lanes lie in order)
+    st<VEC>(dst + r * q.Ct + q.c0 + c, v);
   }
 }
 
 // ---- VJP: a lane per VEC channels of a dst row; NP parts, summed left to right --------------------------------------------------
 template <int VEC, int NP>
-__global__ __launch_bounds__(256) void cat_vjp_kernel(CatParts P, CatGeom q, float* __restrict__ dst,
+__global__ __launch_bounds__(256) void cat_vjp_kernel(CatParts P, ColSliceGeom q, float* __restrict__ dst,
                                                       unsigned* __restrict__ amax) {
   float scale[NP];
 #pragma unroll
@@ -116,13 +50,13 @@ __global__ __launch_bounds__(256) void cat_vjp_kernel(CatParts P, CatGeom q, flo
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < q.lanes; t += (int64_t)gridDim.x * 256) {
     int64_t r;
     int c;
-    cat_where<VEC>(q, t, r, c);
+    col_where<VEC>(q, t, r, c);
     const int64_t at = r * q.Ct + q.c0 + c;
     float v[NP][VEC];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {  // (which kind a part is is the same in every lane; all loads are issued before the sum)
-      if (P.f32[p] != nullptr) cat_ld<VEC>(P.f32[p] + at, v[p]);
-      else cat_ld_split<VEC>(P.h[p] + at, P.l[p] + at, scale[p], v[p]);
+      if (P.f32[p] != nullptr) ld<VEC>(P.f32[p] + at, v[p]);
+      else ld_split<VEC>(P.h[p] + at, P.l[p] + at, scale[p], v[p]);
     }
     float acc[VEC];
 #pragma unroll
@@ -132,9 +66,9 @@ __global__ __launch_bounds__(256) void cat_vjp_kernel(CatParts P, CatGeom q, flo
       for (int p = 1; p < NP; ++p) acc[e] = acc[e] + v[p][e];
       vmax = fmaxf(vmax, fabsf(acc[e]));
     }
-    cat_st<VEC>(dst + t * VEC, acc);
+    st<VEC>(dst + t * VEC, acc);
   }
-  cat_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- host: the contract and the path of a shape ----------------------------------------------------------------------------------
@@ -151,13 +85,12 @@ static int cat_check_shape(const char* fn, int64_t R, int64_t Ct, int64_t c0, in
              "%s: extent out of range (0 <= R, R * Ct < 2^40)", fn);
   p->vec = aligned && Ct % 4 == 0 && c0 % 4 == 0 && Cs % 4 == 0;
   p->lanes = R * (p->vec ? Cs / 4 : Cs);
-  const int64_t need = (p->lanes + 255) / 256;
-  p->blocks = need < CAT_MAX_BLOCKS ? need : CAT_MAX_BLOCKS;
+  p->blocks = grid_blocks(p->lanes);
   return LK_OK;
 }
 
-static CatGeom cat_geometry(const CatPlan& p, int64_t Ct, int64_t c0, int64_t Cs) {
-  CatGeom q;
+static ColSliceGeom cat_geometry(const CatPlan& p, int64_t Ct, int64_t c0, int64_t Cs) {
+  ColSliceGeom q;
   q.Ct = Ct, q.c0 = c0, q.Cs = Cs, q.lanes = p.lanes;
   q.CV = (int)(p.vec ? Cs / 4 : Cs);
   q.big = p.lanes >= (1ll << 31);
@@ -165,17 +98,12 @@ static CatGeom cat_geometry(const CatPlan& p, int64_t Ct, int64_t c0, int64_t Cs
   return q;
 }
 
-static bool cat_disjoint(const void* a, unsigned __int128 a_bytes, const void* b, unsigned __int128 b_bytes) {
-  const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 + a_bytes <= b0 || b0 + b_bytes <= a0;
-}
-
 static int cat_check_fwd(const float* src, int64_t R, int64_t Cs, const float* dst, int64_t Ct, int64_t c0, CatPlan* p) {
   LK_REQUIRE(src && dst, "lk_cat_fwd_nhwc_f32: null pointer");
   const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
   const int rc = cat_check_shape("lk_cat_fwd_nhwc_f32", R, Ct, c0, Cs, aligned, p);
   if (rc != LK_OK) return rc;
-  LK_REQUIRE(cat_disjoint(src, (unsigned __int128)R * Cs * 4, dst, (unsigned __int128)R * Ct * 4),
+  LK_REQUIRE(disjoint(src, (unsigned __int128)R * Cs * 4, dst, (unsigned __int128)R * Ct * 4),
              "lk_cat_fwd_nhwc_f32: dst overlaps src");
   return LK_OK;
 }
@@ -204,8 +132,8 @@ static int cat_check_vjp(int nparts, const float* const* f32, const void* const*
   const unsigned __int128 db = (unsigned __int128)R * Cs * 4, pe = (unsigned __int128)R * Ct;
   bool clear = true;
   for (int i = 0; i < nparts; ++i) {
-    if (f32[i]) clear = clear && cat_disjoint(dst, db, f32[i], pe * 4);
-    else clear = clear && cat_disjoint(dst, db, hi[i], pe * 2) && cat_disjoint(dst, db, lo[i], pe * 2);
+    if (f32[i]) clear = clear && disjoint(dst, db, f32[i], pe * 4);
+    else clear = clear && disjoint(dst, db, hi[i], pe * 2) && disjoint(dst, db, lo[i], pe * 2);
   }
   LK_REQUIRE(clear, "lk_cat_vjp_nhwc_f32: dst overlaps a part");
   return LK_OK;
@@ -220,7 +148,7 @@ extern "C" int lk_cat_fwd_nhwc_f32(const float* src, int64_t R, int64_t Cs, floa
   const int rc = cat_check_fwd(src, R, Cs, dst, Ct, c0, &p);
   if (rc != LK_OK) return rc;
   if (R == 0) return LK_OK;
-  const CatGeom q = cat_geometry(p, Ct, c0, Cs);
+  const ColSliceGeom q = cat_geometry(p, Ct, c0, Cs);
   hipStream_t st = (hipStream_t)stream;
   if (p.vec) hipLaunchKernelGGL((cat_fwd_kernel<4>), dim3((unsigned)p.blocks), dim3(256), 0, st, src, q, dst);
   else hipLaunchKernelGGL((cat_fwd_kernel<1>), dim3((unsigned)p.blocks), dim3(256), 0, st, src, q, dst);
@@ -235,7 +163,7 @@ extern "C" int lk_cat_vjp_nhwc_f32(int nparts, const float* const* f32, const vo
   const int rc = cat_check_vjp(nparts, f32, hi, lo, sexp, R, Ct, c0, Cs, dst, &p, &split_mask);
   if (rc != LK_OK) return rc;
   if (R == 0) return LK_OK;
-  const CatGeom q = cat_geometry(p, Ct, c0, Cs);
+  const ColSliceGeom q = cat_geometry(p, Ct, c0, Cs);
   CatParts P;
   for (int i = 0; i < LK_CAT_MAX_PARTS; ++i) {
     const bool split = i < nparts && f32[i] == nullptr;

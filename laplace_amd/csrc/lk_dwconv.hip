@@ -17,15 +17,13 @@
 // weights are indexed statically; the tap's (dy, dx), dy / sh and dy % sh are wave-uniform counters, and the lane's own
 // (h + ph) / sh and % sh are taken once per pixel, so no tap costs a division.  8-byte loads of the planes and 16-byte loads /
 // stores of w_tap and dx where C % 4 == 0 and the pointers are aligned, else one channel per lane.  `amax` receives max|dx| as
-// the bit pattern of a non-negative float through atomicMax, one atomic per wave (as lk_pool_vjp_nhwc_f32).
+// the bit pattern of a non-negative float through atomicMax, one atomic per wave (wave_amax of lk_stream.h).
 // Minimal traffic of the backward: 4 S B C (OH OW + H W) + 4 kh kw C bytes.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
 constexpr int DW_SC = 4;  // seeds per pass of the backward (their plane loads are in flight together)
-
-typedef _Float16 dw_f16x4 __attribute__((ext_vector_type(4)));
 
 struct DwGeom {
   int H, W, C, OH, OW, CV;  // CV: channel vectors per pixel
@@ -34,65 +32,6 @@ struct DwGeom {
   FastDiv cv_div, w_div, h_div;  // by CV, by the width and the height of the map the lanes run over
   FastDiv sh_div, sw_div;
 };
-
-template <int VEC>
-__device__ __forceinline__ void dw_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void dw_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-
-// float(h) + float(l) of VEC adjacent channels (the power-of-two scale is applied once, to the sum over the taps)
-template <int VEC>
-__device__ __forceinline__ void dw_ld_split(const _Float16* __restrict__ h, const _Float16* __restrict__ l, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const dw_f16x4 a = *reinterpret_cast<const dw_f16x4*>(h), b = *reinterpret_cast<const dw_f16x4*>(l);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (float)a[e] + (float)b[e];
-  } else {
-    v[0] = (float)*h + (float)*l;
-  }
-}
-
-// one atomic per wave: the lanes' maxima of |dx| (non-negative floats order like their bit patterns)
-__device__ __forceinline__ void dw_wave_amax(float m, unsigned* __restrict__ amax) {
-  unsigned b = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
-  if (amax != nullptr && (threadIdx.x & 63) == 0 && b) atomicMax(amax, b);
-}
-
-// lane index -> (channel vector, column, row, image) of a [.., rows, cols, CV] map
-__device__ __forceinline__ void dw_where(const DwGeom& q, int64_t t, int rows, int cols, int& cv, int& col, int& row,
-                                         int64_t& n) {
-  if (!q.big) {
-    const int ti = (int)t, pix = fdiv(ti, q.cv_div), r = fdiv(pix, q.w_div), ni = fdiv(r, q.h_div);
-    cv = ti - pix * q.CV;
-    col = pix - r * cols;
-    row = r - ni * rows;
-    n = ni;
-  } else {
-    const int64_t pix = t / q.CV, r = pix / cols;
-    cv = (int)(t - pix * q.CV);
-    col = (int)(pix - r * cols);
-    n = r / rows;
-    row = (int)(r - n * rows);
-  }
-}
 
 // ---- forward: a lane per output element (x VEC channels) ----------------------------------------------------------------------
 template <int VEC, int TC>
@@ -103,13 +42,13 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const float* __restrict
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
     int cv, ow, oh;
     int64_t n;
-    dw_where(q, t, q.OH, q.OW, cv, ow, oh, n);
+    map_where(q, t, q.OH, q.OW, cv, ow, oh, n);
     const int h0 = oh * q.sh - q.ph, w0 = ow * q.sw - q.pw;
     const float* xn = x + n * q.H * q.W * q.C + cv * VEC;
     const float* wp = w_tap + cv * VEC;
     float acc[VEC];
     if (bias != nullptr) {
-      dw_ld<VEC>(bias + cv * VEC, acc);
+      ld<VEC>(bias + cv * VEC, acc);
     } else {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
@@ -121,15 +60,15 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const float* __restrict
         const int ih = h0 + dy, iw = w0 + dx;
         if ((unsigned)ih < (unsigned)q.H && (unsigned)iw < (unsigned)q.W) {
           float xv[VEC], wv[VEC];
-          dw_ld<VEC>(xn + ((int64_t)ih * q.W + iw) * q.C, xv);
-          dw_ld<VEC>(wp + (int64_t)tt * q.C, wv);
+          ld<VEC>(xn + ((int64_t)ih * q.W + iw) * q.C, xv);
+          ld<VEC>(wp + (int64_t)tt * q.C, wv);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) acc[e] += wv[e] * xv[e];
         }
         if (++dx == q.kw) dx = 0, ++dy;
       }
     }
-    dw_st<VEC>(y + ((n * q.OH + oh) * q.OW + ow) * q.C + cv * VEC, acc);
+    st<VEC>(y + ((n * q.OH + oh) * q.OW + ow) * q.C + cv * VEC, acc);
   }
 }
 
@@ -148,7 +87,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const _Float16* __restr
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
     int cv, w, h;
     int64_t n;
-    dw_where(q, t, q.H, q.W, cv, w, h, n);
+    map_where(q, t, q.H, q.W, cv, w, h, n);
     // h + ph = qh sh + rh: tap row dy reaches this pixel from output row qh - dy / sh when dy % sh == rh (columns likewise)
     int qh = h + q.ph, rh = 0, qw = w + q.pw, rw = 0;
     if constexpr (STRIDED) {
@@ -160,7 +99,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const _Float16* __restr
 #pragma unroll
     for (int tt = 0; tt < TMAX; ++tt) {
       if (tt < q.T) {
-        dw_ld<VEC>(w_tap + (int64_t)tt * q.C + cv * VEC, wr[tt]);
+        ld<VEC>(w_tap + (int64_t)tt * q.C + cv * VEC, wr[tt]);
       } else {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) wr[tt][e] = 0.f;
@@ -187,7 +126,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const _Float16* __restr
             float gv[DW_SC][VEC];
 #pragma unroll
             for (int k = 0; k < DW_SC; ++k)
-              if (s0 + k < s_end) dw_ld_split<VEC>(gh + o + (int64_t)(s0 + k) * g_seed, gl + o + (int64_t)(s0 + k) * g_seed, gv[k]);
+              if (s0 + k < s_end) ld_split<VEC>(gh + o + (int64_t)(s0 + k) * g_seed, gl + o + (int64_t)(s0 + k) * g_seed, gv[k]);
 #pragma unroll
             for (int k = 0; k < DW_SC; ++k)
               if (s0 + k < s_end) {
@@ -210,11 +149,11 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const _Float16* __restr
             acc[k][e] *= scale;
             vmax = fmaxf(vmax, fabsf(acc[k][e]));
           }
-          dw_st<VEC>(dp + (int64_t)(s0 + k) * dx_seed, acc[k]);
+          st<VEC>(dp + (int64_t)(s0 + k) * dx_seed, acc[k]);
         }
     }
   }
-  dw_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- host: the contract and the path of a shape ----------------------------------------------------------------------------------

@@ -13,30 +13,9 @@
 //
 // Lanes run across d (a row of g is D contiguous floats): 16-byte accesses where D % 4 == 0 and every pointer / row pitch is
 // 16-byte aligned, 4-byte otherwise.  These are streaming kernels: bytes that must move = 4 * S*B*T*D of g once.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
-
-template <int VEC>
-__device__ __forceinline__ void emb_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void emb_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
 
 // a token id the kernels write for: inside the table and not the padding row (the host never sees the ids)
 __device__ __forceinline__ bool emb_live(int64_t id, int V, int64_t pad) { return id >= 0 && id < V && id != pad; }
@@ -81,7 +60,7 @@ __global__ __launch_bounds__(256) void jac_embed_kernel(const float* __restrict_
         const float* gq = g + order[q] * D + d;
         float v[EMB_SC][VEC];
 #pragma unroll
-        for (int u = 0; u < EMB_SC; ++u) emb_ld<VEC>(gq + min(s0 + u, s_end - 1) * seed, v[u]);
+        for (int u = 0; u < EMB_SC; ++u) ld<VEC>(gq + min(s0 + u, s_end - 1) * seed, v[u]);
 #pragma unroll
         for (int u = 0; u < EMB_SC; ++u)
 #pragma unroll
@@ -89,7 +68,7 @@ __global__ __launch_bounds__(256) void jac_embed_kernel(const float* __restrict_
       }
 #pragma unroll
       for (int u = 0; u < EMB_SC; ++u)
-        if (s0 + u < s_end) emb_st<VEC>(out + (int64_t)(s0 + u) * P + d, acc[u]);
+        if (s0 + u < s_end) st<VEC>(out + (int64_t)(s0 + u) * P + d, acc[u]);
     }
   }
 }
@@ -146,7 +125,7 @@ __global__ __launch_bounds__(EMB_DIAG_THREADS) void diag_embed_kernel(const floa
           const float* gx = g + order[x] * D + d;
           float v[EMB_SC][VEC];
 #pragma unroll
-          for (int u = 0; u < EMB_SC; ++u) emb_ld<VEC>(gx + min(s0 + u, S - 1) * seed, v[u]);
+          for (int u = 0; u < EMB_SC; ++u) ld<VEC>(gx + min(s0 + u, S - 1) * seed, v[u]);
 #pragma unroll
           for (int u = 0; u < EMB_SC; ++u)
 #pragma unroll
@@ -172,10 +151,10 @@ __global__ __launch_bounds__(EMB_DIAG_THREADS) void diag_embed_kernel(const floa
 #pragma unroll
       for (int k = 0; k < VEC; ++k) tot[k] += red[(rr * DL + l) * VEC + k];
     float* hp = h + id * D + d;
-    emb_ld<VEC>(hp, old);
+    ld<VEC>(hp, old);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) old[k] += alpha * tot[k];
-    emb_st<VEC>(hp, old);
+    st<VEC>(hp, old);
   }
 }
 
@@ -226,7 +205,7 @@ __global__ __launch_bounds__(256) void diag_quadform_embed_kernel(const float* _
             for (int i = 0; i < EMB_QC; ++i) {
               if (c0 + i < C) {
                 float v[VEC];
-                emb_ld<VEC>(gt + (c0 + i) * cls, v);
+                ld<VEC>(gt + (c0 + i) * cls, v);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) rc[i][e] += v[e];
               }
@@ -235,13 +214,13 @@ __global__ __launch_bounds__(256) void diag_quadform_embed_kernel(const float* _
             for (int jj = 0; jj < EMB_QK; ++jj) {
               if (k0 + jj < C) {
                 float v[VEC];
-                emb_ld<VEC>(gt + (k0 + jj) * cls, v);
+                ld<VEC>(gt + (k0 + jj) * cls, v);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) rk[jj][e] += v[e];
               }
             }
           }
-          emb_ld<VEC>(var + id * D + d, vv);
+          ld<VEC>(var + id * D + d, vv);
 #pragma unroll
           for (int e = 0; e < VEC; ++e)
 #pragma unroll

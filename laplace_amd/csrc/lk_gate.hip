@@ -22,15 +22,12 @@
 // Every output element has one owner, stores are plain vector stores, the sums run in a fixed order, no atomic touches data:
 // repeated runs give the same bits.  With r null dx is the fp32 product (one rounding).  Offsets are 64-bit throughout.
 // Minimal traffic: g once, x / gate (and r) once per sample (map), the outputs once.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
-typedef _Float16 gate_f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GATE_NV = 16;                   // positions of x a thread keeps in registers (RESIDENT)
-constexpr int GATE_PP = 8;                    // positions a thread of the VJP walks per unit
-constexpr int64_t GATE_MAX_BLOCKS = 256 * 8;  // 256 CUs x 8 workgroups of 256 threads
+constexpr int GATE_NV = 16;  // positions of x a thread keeps in registers (RESIDENT)
+constexpr int GATE_PP = 8;   // positions a thread of the VJP walks per unit
 
 struct GateG {  // the cotangent: f32 non-null, or the planes with their scale word
   const float* f32;
@@ -39,38 +36,13 @@ struct GateG {  // the cotangent: f32 non-null, or the planes with their scale w
   const int* sexp;
 };
 
-template <int VEC>
-__device__ __forceinline__ void gate_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void gate_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-
 // VEC adjacent channels of g at element offset `at`; scale is a power of two, so the product is exact
 template <int VEC, bool SPLIT>
 __device__ __forceinline__ void gate_ld_g(const GateG& G, int64_t at, float scale, float (&v)[VEC]) {
   if constexpr (!SPLIT) {
-    gate_ld<VEC>(G.f32 + at, v);
-  } else if constexpr (VEC == 4) {
-    const gate_f16x4 a = *reinterpret_cast<const gate_f16x4*>(G.h + at), b = *reinterpret_cast<const gate_f16x4*>(G.l + at);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = ((float)a[e] + (float)b[e]) * scale;
+    ld<VEC>(G.f32 + at, v);
   } else {
-    v[0] = ((float)G.h[at] + (float)G.l[at]) * scale;
+    ld_split<VEC>(G.h + at, G.l + at, scale, v);
   }
 }
 
@@ -101,7 +73,7 @@ __global__ __launch_bounds__(256) void gate_reduce_kernel(GateG G, const float* 
         const int p = pg + k * PG;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) xv[k][e] = 0.f;
-        if (p < np) gate_ld<VEC>(x + xo + (int64_t)p * C, xv[k]);
+        if (p < np) ld<VEC>(x + xo + (int64_t)p * C, xv[k]);
       }
     }
     for (int64_t s = s_begin; s < s_end; ++s) {
@@ -125,7 +97,7 @@ __global__ __launch_bounds__(256) void gate_reduce_kernel(GateG G, const float* 
         for (int p = pg; p < np; p += PG) {  // (P < 2^30 and PG <= 256: no overflow)
           float gv[VEC], xw[VEC];
           gate_ld_g<VEC, SPLIT>(G, go + (int64_t)p * C, scale, gv);
-          gate_ld<VEC>(x + xo + (int64_t)p * C, xw);
+          ld<VEC>(x + xo + (int64_t)p * C, xw);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) acc[e] += gv[e] * xw[e];
         }
@@ -144,7 +116,7 @@ __global__ __launch_bounds__(256) void gate_reduce_kernel(GateG G, const float* 
       if (pg == 0 && live) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] = red[e * 256 + threadIdx.x];
-        gate_st<VEC>(ds + (s * B + b) * C + (int64_t)cvi * VEC, acc);
+        st<VEC>(ds + (s * B + b) * C + (int64_t)cvi * VEC, acc);
       }
       __syncthreads();  // (red is written again by the next seed)
     }
@@ -157,9 +129,7 @@ __global__ __launch_bounds__(256) void gate_reduce_kernel(GateG G, const float* 
 // waves of a launch, which finish together, queue up on one address for longer than the kernel streams its data.
 __device__ __forceinline__ void gate_block_amax(float m, unsigned* __restrict__ amax) {
   __shared__ unsigned wmax[4];
-  unsigned b = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
+  unsigned b = wave_max_bits(m);
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = b;
   __syncthreads();
   if (threadIdx.x == 0 && amax != nullptr) {
@@ -187,8 +157,8 @@ __global__ __launch_bounds__(256) void gate_vjp_kernel(GateG G, const float* __r
     if (cvi >= nvc) continue;
     const int64_t b = n % B;
     float gt[VEC], rv[VEC];
-    gate_ld<VEC>(gate + b * C + (int64_t)cvi * VEC, gt);
-    if constexpr (HAS_R) gate_ld<VEC>(r + n * C + (int64_t)cvi * VEC, rv);
+    ld<VEC>(gate + b * C + (int64_t)cvi * VEC, gt);
+    if constexpr (HAS_R) ld<VEC>(r + n * C + (int64_t)cvi * VEC, rv);
     const int64_t o = n * map + (int64_t)cvi * VEC;
     const int64_t p0 = (int64_t)chunk * PG * GATE_PP + pg;  // (< P + 2048 < 2^31)
 #pragma unroll
@@ -203,7 +173,7 @@ __global__ __launch_bounds__(256) void gate_vjp_kernel(GateG G, const float* __r
           else d[e] = gv[e] * gt[e];
           vmax = fmaxf(vmax, fabsf(d[e]));
         }
-        gate_st<VEC>(dx + o + p * C, d);
+        st<VEC>(dx + o + p * C, d);
       }
     }
   }
@@ -223,11 +193,6 @@ struct GatePlan {
   int64_t units, blocks;
 };
 
-static bool gate_disjoint(const void* p, unsigned __int128 p_bytes, const void* q, unsigned __int128 q_bytes) {
-  const unsigned __int128 p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-  return p0 + p_bytes <= q0 || q0 + q_bytes <= p0;
-}
-
 // the shape part of the contract (shared with lk_gate_variant), with the messages under the caller's name
 static int gate_check_shape(const char* fn, bool vjp, int64_t S, int64_t B, int64_t P, int64_t C, bool aligned, GatePlan* p) {
   LK_REQUIRE(S >= 1 && B >= 0 && P >= 1 && P < (1ll << 30) && C >= 1 && C < (1ll << 30),
@@ -244,13 +209,13 @@ static int gate_check_shape(const char* fn, bool vjp, int64_t S, int64_t B, int6
     p->chunks = (int)((P + PG * GATE_PP - 1) / (PG * GATE_PP));
     p->resident = 0;
     p->units = S * B * p->tiles * p->chunks;  // (< 2^40: a unit holds at least one element)
-    p->blocks = p->units < GATE_MAX_BLOCKS ? p->units : GATE_MAX_BLOCKS;
+    p->blocks = p->units < STREAM_MAX_BLOCKS ? p->units : STREAM_MAX_BLOCKS;
     p->s_per = S;
   } else {
     p->chunks = 1;
     p->resident = P <= PG * GATE_NV;
     p->units = B * p->tiles;
-    p->blocks = p->units < GATE_MAX_BLOCKS ? p->units : GATE_MAX_BLOCKS;
+    p->blocks = p->units < STREAM_MAX_BLOCKS ? p->units : STREAM_MAX_BLOCKS;
     p->s_per = seeds_per_slice(S, p->blocks * 4);
   }
   return LK_OK;
@@ -268,9 +233,9 @@ static int gate_check_g(const char* fn, const float* g, const void* g_h, const v
 
 static bool gate_clear_of_g(const void* out, unsigned __int128 out_bytes, const float* g, const void* g_h, const void* g_l,
                             const int* sexp, unsigned __int128 elems) {
-  if (g) return gate_disjoint(out, out_bytes, g, elems * 4);
-  return gate_disjoint(out, out_bytes, g_h, elems * 2) && gate_disjoint(out, out_bytes, g_l, elems * 2) &&
-         gate_disjoint(out, out_bytes, sexp, 4);
+  if (g) return disjoint(out, out_bytes, g, elems * 4);
+  return disjoint(out, out_bytes, g_h, elems * 2) && disjoint(out, out_bytes, g_l, elems * 2) &&
+         disjoint(out, out_bytes, sexp, 4);
 }
 
 static int gate_check_reduce(const float* g, const void* g_h, const void* g_l, const int* sexp, const float* x, int64_t S,
@@ -283,7 +248,7 @@ static int gate_check_reduce(const float* g, const void* g_h, const void* g_l, c
   rc = gate_check_shape("lk_gate_reduce_nhwc_f32", false, S, B, P, C, aligned, p);
   if (rc != LK_OK) return rc;
   const unsigned __int128 xe = (unsigned __int128)B * P * C, ob = (unsigned __int128)S * B * C * 4;
-  LK_REQUIRE(gate_clear_of_g(ds, ob, g, g_h, g_l, sexp, xe * S) && gate_disjoint(ds, ob, x, xe * 4),
+  LK_REQUIRE(gate_clear_of_g(ds, ob, g, g_h, g_l, sexp, xe * S) && disjoint(ds, ob, x, xe * 4),
              "lk_gate_reduce_nhwc_f32: ds overlaps an input");
   return LK_OK;
 }
@@ -298,9 +263,9 @@ static int gate_check_vjp(const float* g, const void* g_h, const void* g_l, cons
   rc = gate_check_shape("lk_gate_vjp_nhwc_f32", true, S, B, P, C, aligned, p);
   if (rc != LK_OK) return rc;
   const unsigned __int128 ge = (unsigned __int128)S * B * P * C, ob = ge * 4;
-  bool clear = gate_clear_of_g(dx, ob, g, g_h, g_l, sexp, ge) && gate_disjoint(dx, ob, gate, (unsigned __int128)B * C * 4);
-  if (r) clear = clear && gate_disjoint(dx, ob, r, (unsigned __int128)S * B * C * 4);
-  if (amax) clear = clear && gate_disjoint(dx, ob, amax, 4);
+  bool clear = gate_clear_of_g(dx, ob, g, g_h, g_l, sexp, ge) && disjoint(dx, ob, gate, (unsigned __int128)B * C * 4);
+  if (r) clear = clear && disjoint(dx, ob, r, (unsigned __int128)S * B * C * 4);
+  if (amax) clear = clear && disjoint(dx, ob, amax, 4);
   LK_REQUIRE(clear, "lk_gate_vjp_nhwc_f32: dx overlaps an input or the amax word");
   return LK_OK;
 }

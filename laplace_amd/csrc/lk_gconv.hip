@@ -17,7 +17,7 @@
 //
 // Everything else (Cig > 1, or more than 49 taps) goes through the tile scheme of jac_conv_kernel with the group's channel
 // offset; 16-row output tiles do not straddle groups.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
@@ -25,16 +25,6 @@ struct GConvGeom {
   int Cin, H, W, OH, OW, kh, kw, sh, sw, ph, pw, dh, dw;
   int Cig, Dog;  // input / output channels per group
 };
-
-template <int VEC>
-__device__ __forceinline__ void gconv_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
 
 // Depthwise: g [Cc][rows][L] with rows = B * Do (n, o); x [B][Cin][H][W], row (n, o) reads plane n*Cin + o / Dog.
 // KKT >= kh*kw: accumulators per seed; SC: seeds per pass; WL lanes per row; 256 / WL rows per workgroup.
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(256) void jac_dwconv_kernel(const float* __restrict
           float gv[VEC];
 #pragma unroll
           for (int e = 0; e < VEC; ++e) gv[e] = 0.f;
-          if (on) gconv_ld<VEC>(gr + (int64_t)(s0 + s) * seed_stride + l, gv);
+          if (on) ld<VEC>(gr + (int64_t)(s0 + s) * seed_stride + l, gv);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
             bs[s] += gv[e];

@@ -18,7 +18,7 @@
 // float's is asked for.  The seeds are split over grid.y when the tiles alone leave the device short of waves.  One launch per
 // requested output.  Nothing assumes packed fp32.
 // Minimal traffic: g once per requested output, a / b once, the outputs once.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
@@ -118,11 +118,6 @@ struct MatmulPlan {
   int64_t s_per;           // seeds per grid.y slice (one value for both launches)
 };
 
-static bool mm_disjoint(const void* p, unsigned __int128 p_bytes, const void* q, unsigned __int128 q_bytes) {
-  const unsigned __int128 p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-  return p0 + p_bytes <= q0 || q0 + q_bytes <= p0;
-}
-
 // the shape part of the contract (shared with lk_matmul_vjp_variant), with the messages under the caller's name
 static int matmul_check_shape(const char* fn, int64_t S, int64_t NB, int64_t M, int64_t K, int64_t N, bool want_da, bool want_db,
                               MatmulPlan* p) {
@@ -156,10 +151,10 @@ static int matmul_check(const float* g, const float* a, const float* b, int64_t 
   const unsigned __int128 ab = (unsigned __int128)NB * M * K * 4, bb = (unsigned __int128)NB * K * N * 4;
   const unsigned __int128 gb = (unsigned __int128)S * NB * M * N * 4, dab = ab * S, dbb = bb * S;
   bool clear = true;
-  if (da) clear = clear && mm_disjoint(da, dab, g, gb) && mm_disjoint(da, dab, a, ab) && mm_disjoint(da, dab, b, bb);
-  if (db) clear = clear && mm_disjoint(db, dbb, g, gb) && mm_disjoint(db, dbb, a, ab) && mm_disjoint(db, dbb, b, bb);
+  if (da) clear = clear && disjoint(da, dab, g, gb) && disjoint(da, dab, a, ab) && disjoint(da, dab, b, bb);
+  if (db) clear = clear && disjoint(db, dbb, g, gb) && disjoint(db, dbb, a, ab) && disjoint(db, dbb, b, bb);
   LK_REQUIRE(clear, "lk_matmul_vjp_f32: an output overlaps an input");
-  LK_REQUIRE(!(da && db) || mm_disjoint(da, dab, db, dbb), "lk_matmul_vjp_f32: da overlaps db");
+  LK_REQUIRE(!(da && db) || disjoint(da, dab, db, dbb), "lk_matmul_vjp_f32: da overlaps db");
   return LK_OK;
 }
 

@@ -8,44 +8,22 @@
 // one launch serves all seeds, g is read ONCE for both outputs, and a and b are read once per sample row and stay in registers
 // across the seed loop.
 //
-// One kernel template (after the ROW kernel of lk_normvjp.hip), two bodies:
+// One kernel template (vector access, grid cap and overlap check: lk_stream.h), two bodies:
 //   * row gate: a group of W lanes (a power of two <= 64, so a group never leaves its wave) owns one row; the row sum is a fixed
 //     xor-shuffle tree over the group, lane 0 of the group stores it.  a of the row stays in registers while the row fits
 //     (MUL_NV vectors per lane: RESIDENT); longer rows re-read it per seed.  The grid strides over the rows with at most
-//     MUL_MAX_BLOCKS workgroups.
+//     STREAM_MAX_BLOCKS workgroups.
 //   * full form: the same without the tree - a lane owns one vector of the flattened [R * L] and keeps its a and b.
 // 16-byte loads and stores where L % 4 == 0 and every pointer is 16-byte aligned, 4-byte ones otherwise.  Few rows: the seeds
 // are split over grid.y (a and b are then read once per slice).  Every output element has one owner, stores are plain vector
 // stores, there is no atomic: repeated runs give the same bits.  Plain fp32: one rounding per product (da, and db of the full
 // form, equal the fp32 product exactly); the row sum adds in a fixed order.  Nothing assumes packed fp32.
 // Minimal traffic: g once (4 S R L bytes), a and b once, and the outputs asked for.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
-constexpr int MUL_NV = 8;                    // vectors of a row a lane keeps in registers (RESIDENT)
-constexpr int64_t MUL_MAX_BLOCKS = 256 * 8;  // 256 CUs x 8 workgroups of 256 threads
-
-template <int VEC>
-__device__ __forceinline__ void mul_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void mul_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
+constexpr int MUL_NV = 8;  // vectors of a row a lane keeps in registers (RESIDENT)
 
 // da / db may be null (uniform over the grid); `seed_stride` = R * L; `units`: rows (ROW) or vectors of the flattened [R * L]
 template <int VEC, bool ROW, bool RESIDENT>
@@ -62,21 +40,21 @@ __global__ __launch_bounds__(256) void mul_vjp_kernel(const float* __restrict__ 
       float av[VEC], bv[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) av[e] = bv[e] = 0.f;
-      if (db != nullptr) mul_ld<VEC>(a + o, av);
-      if (da != nullptr) mul_ld<VEC>(b + o, bv);
+      if (db != nullptr) ld<VEC>(a + o, av);
+      if (da != nullptr) ld<VEC>(b + o, bv);
 #pragma unroll 2
       for (int64_t s = s_begin; s < s_end; ++s) {
         float gv[VEC], d[VEC];
-        mul_ld<VEC>(g + s * seed_stride + o, gv);
+        ld<VEC>(g + s * seed_stride + o, gv);
         if (da != nullptr) {
 #pragma unroll
           for (int e = 0; e < VEC; ++e) d[e] = gv[e] * bv[e];
-          mul_st<VEC>(da + s * seed_stride + o, d);
+          st<VEC>(da + s * seed_stride + o, d);
         }
         if (db != nullptr) {
 #pragma unroll
           for (int e = 0; e < VEC; ++e) d[e] = gv[e] * av[e];
-          mul_st<VEC>(db + s * seed_stride + o, d);
+          st<VEC>(db + s * seed_stride + o, d);
         }
       }
     }
@@ -98,7 +76,7 @@ __global__ __launch_bounds__(256) void mul_vjp_kernel(const float* __restrict__ 
           const int i = k * W + lane;
 #pragma unroll
           for (int e = 0; e < VEC; ++e) av[k][e] = 0.f;
-          if (db != nullptr && i < nvec) mul_ld<VEC>(a + base + (int64_t)i * VEC, av[k]);
+          if (db != nullptr && i < nvec) ld<VEC>(a + base + (int64_t)i * VEC, av[k]);
         }
         for (int64_t s = s_begin; s < s_end; ++s) {
           const float* gs = g + s * seed_stride + base;
@@ -108,13 +86,13 @@ __global__ __launch_bounds__(256) void mul_vjp_kernel(const float* __restrict__ 
             const int i = k * W + lane;
             if (i < nvec) {
               float gv[VEC], d[VEC];
-              mul_ld<VEC>(gs + (int64_t)i * VEC, gv);
+              ld<VEC>(gs + (int64_t)i * VEC, gv);
 #pragma unroll
               for (int e = 0; e < VEC; ++e) {
                 d[e] = gv[e] * bv;
                 acc += gv[e] * av[k][e];
               }
-              if (da != nullptr) mul_st<VEC>(da + s * seed_stride + base + (int64_t)i * VEC, d);
+              if (da != nullptr) st<VEC>(da + s * seed_stride + base + (int64_t)i * VEC, d);
             }
           }
           if (db != nullptr) {
@@ -129,16 +107,16 @@ __global__ __launch_bounds__(256) void mul_vjp_kernel(const float* __restrict__ 
 #pragma unroll 4
           for (int i = lane; i < nvec; i += W) {  // (nvec < 2^30 and W <= 64: no overflow)
             float gv[VEC], av[VEC], d[VEC];
-            mul_ld<VEC>(gs + (int64_t)i * VEC, gv);
+            ld<VEC>(gs + (int64_t)i * VEC, gv);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) av[e] = 0.f;
-            if (db != nullptr) mul_ld<VEC>(a + base + (int64_t)i * VEC, av);
+            if (db != nullptr) ld<VEC>(a + base + (int64_t)i * VEC, av);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               d[e] = gv[e] * bv;
               acc += gv[e] * av[e];
             }
-            if (da != nullptr) mul_st<VEC>(da + s * seed_stride + base + (int64_t)i * VEC, d);
+            if (da != nullptr) st<VEC>(da + s * seed_stride + base + (int64_t)i * VEC, d);
           }
           if (db != nullptr) {
             for (int o = W >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
@@ -161,11 +139,6 @@ struct MulPlan {
   int64_t units; // rows, or vectors of the flattened [R * L]
   int64_t blocks;
 };
-
-static bool mul_disjoint(const void* p, unsigned __int128 p_bytes, const void* q, unsigned __int128 q_bytes) {
-  const unsigned __int128 p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-  return p0 + p_bytes <= q0 || q0 + q_bytes <= p0;
-}
 
 // the shape part of the contract (shared with lk_mul_variant), with the messages under the caller's name
 static int mul_check_shape(const char* fn, int64_t S, int64_t R, int64_t L, int b_row, bool want_da, bool want_db, bool aligned,
@@ -191,7 +164,7 @@ static int mul_check_shape(const char* fn, int64_t S, int64_t R, int64_t L, int 
     p->units = R * nvec;
     p->blocks = (p->units + 255) / 256;
   }
-  if (p->blocks > MUL_MAX_BLOCKS) p->blocks = MUL_MAX_BLOCKS;
+  if (p->blocks > STREAM_MAX_BLOCKS) p->blocks = STREAM_MAX_BLOCKS;
   p->s_per = seeds_per_slice(S, p->blocks * 4);
   return LK_OK;
 }
@@ -205,10 +178,10 @@ static int mul_check(const float* g, const float* a, const float* b, int64_t S, 
   const unsigned __int128 rl = (unsigned __int128)R * L * 4, gb = rl * S, bb = b_row ? (unsigned __int128)R * 4 : rl;
   const unsigned __int128 dbb = b_row ? (unsigned __int128)S * R * 4 : gb;
   bool clear = true;
-  if (da) clear = clear && mul_disjoint(da, gb, g, gb) && mul_disjoint(da, gb, a, rl) && mul_disjoint(da, gb, b, bb);
-  if (db) clear = clear && mul_disjoint(db, dbb, g, gb) && mul_disjoint(db, dbb, a, rl) && mul_disjoint(db, dbb, b, bb);
+  if (da) clear = clear && disjoint(da, gb, g, gb) && disjoint(da, gb, a, rl) && disjoint(da, gb, b, bb);
+  if (db) clear = clear && disjoint(db, dbb, g, gb) && disjoint(db, dbb, a, rl) && disjoint(db, dbb, b, bb);
   LK_REQUIRE(clear, "lk_mul_vjp_f32: an output overlaps an input");
-  LK_REQUIRE(!(da && db) || mul_disjoint(da, gb, db, dbb), "lk_mul_vjp_f32: da overlaps db");
+  LK_REQUIRE(!(da && db) || disjoint(da, gb, db, dbb), "lk_mul_vjp_f32: da overlaps db");
   return LK_OK;
 }
 

@@ -13,23 +13,13 @@
 // halving tree); plain vector stores.  Parallelism comes from the rows (n, ch) and, when those are few, from splitting
 // the SEEDS over grid.y (every split re-reads xhat, 1/s_per of its cotangent traffic) - not from splitting L, so no
 // second stage is needed.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
 constexpr int NORM_SC = 16;    // seeds per pass of the channels-first kernel (2 accumulators each, in registers)
 constexpr int NORM_NV = 4;     // vectors of xhat a lane holds per tile of the reduced extent
 constexpr int NORM_SC_CL = 8;  // seeds per pass of the channels-last kernel (2 * VEC accumulators each)
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
 
 // Channels first: g [S][R][L], xhat [R][L] with R = B * Ch rows (n, ch).  A group of W lanes (W a power of two <= 64,
 // W * VEC >= min(L, 64 * VEC)) owns one row; a workgroup of 256 lanes owns 256 / W consecutive rows; grid.y splits seeds.
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(256) void jac_norm_cf_kernel(const float* __restric
         const int l = l0 + (v * W + lane) * VEC;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) xv[v][e] = 0.f;
-        if (live && l < L) ldv<VEC>(xhat + row_off + l, xv[v]);
+        if (live && l < L) ld<VEC>(xhat + row_off + l, xv[v]);
       }
 #pragma unroll
       for (int k = 0; k < NORM_SC; ++k) {
@@ -68,7 +58,7 @@ __global__ __launch_bounds__(256) void jac_norm_cf_kernel(const float* __restric
             const int l = l0 + (v * W + lane) * VEC;
             if (live && l < L) {
               float gv[VEC];
-              ldv<VEC>(gr + l, gv);
+              ld<VEC>(gr + l, gv);
 #pragma unroll
               for (int e = 0; e < VEC; ++e) {
                 aw[k] += gv[e] * xv[v][e];
@@ -125,12 +115,12 @@ __global__ __launch_bounds__(256) void jac_norm_cl_kernel(const float* __restric
     if (live) {
       for (int l = ty; l < L; l += TL) {
         float xv[VEC];
-        ldv<VEC>(xn + (int64_t)l * Ch, xv);
+        ld<VEC>(xn + (int64_t)l * Ch, xv);
 #pragma unroll
         for (int k = 0; k < NORM_SC_CL; ++k) {
           if (s0 + k < s_end) {
             float gv[VEC];
-            ldv<VEC>(g + (((int64_t)(s0 + k) * B + n) * L + l) * Ch + (int64_t)cv * VEC, gv);
+            ld<VEC>(g + (((int64_t)(s0 + k) * B + n) * L + l) * Ch + (int64_t)cv * VEC, gv);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               aw[k][e] += gv[e] * xv[e];

@@ -15,7 +15,7 @@
 // element has one owner and a plain store, no atomics: repeated runs give the same bits.  Few (sample, channel tile) pairs:
 // the SEEDS are split over grid.y (every slice re-reads x); L is never split.
 // Minimal traffic: 4 S B L Ch (planes) + 4 B L Ch (x) + 8 B S Ch (out) bytes.
-#include "lk_split16.h"
+#include "lk_stream.h"
 
 namespace lk {
 
@@ -29,19 +29,6 @@ template <int VEC>
 struct NtCap {
   static constexpr int value = VEC == 1 ? 64 : 32;
 };
-
-template <int VEC>
-__device__ __forceinline__ void nt_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 1) {
-    v[0] = *p;
-  } else {
-#pragma unroll
-    for (int q = 0; q < VEC / 4; ++q) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * q);
-      v[4 * q] = t[0], v[4 * q + 1] = t[1], v[4 * q + 2] = t[2], v[4 * q + 3] = t[3];
-    }
-  }
-}
 
 template <int VEC>
 struct NtPlanes;  // the raw halves of VEC adjacent channels of both planes (one load each)
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(256) void jac_normtap_kernel(const _Float16* __rest
   float m[VEC], r[VEC];
 #pragma unroll
   for (int e = 0; e < VEC; ++e) m[e] = 0.f, r[e] = 1.f;  // (x - 0) * 1 is x, bit for bit
-  if (live && mu != nullptr) nt_ld<VEC>(mu + c0, m), nt_ld<VEC>(rstd + c0, r);
+  if (live && mu != nullptr) ld<VEC>(mu + c0, m), ld<VEC>(rstd + c0, r);
   const float* xn = x + (int64_t)n * L * Ch + c0;
   const int64_t seed_stride = (int64_t)B * L * Ch;
   const int64_t gn = (int64_t)n * L * Ch + c0;
@@ -115,7 +102,7 @@ __global__ __launch_bounds__(256) void jac_normtap_kernel(const _Float16* __rest
         for (int k = 0; k < SC; ++k)
           if (s0 + k < s_end) nt_ld_planes<VEC>(gh + o + (s0 + k) * seed_stride, gl + o + (s0 + k) * seed_stride, pv[k]);  // (uniform)
         float xh[VEC];
-        nt_ld<VEC>(xn + (int64_t)l * Ch, xh);
+        ld<VEC>(xn + (int64_t)l * Ch, xh);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) xh[e] = (xh[e] - m[e]) * r[e];
 #pragma unroll

@@ -16,9 +16,8 @@
 // fits (NVJP_NV vectors per lane); longer rows read g twice.  16-byte loads where the contiguous extent is a multiple of 4
 // floats and the pointers are 16-byte aligned, 4-byte loads otherwise.  Deterministic: every dx element has one owner, plain
 // vector stores, no atomics on data; `amax` receives max|dx| as the bit pattern of a non-negative float through atomicMax, which
-// is order-independent (lk_conv.hip does the same for amax_out).  Few rows: the seeds are split over grid.y.
-#include "lk_common.h"
-#include "lk_rowvec.h"  // nv_ld, nv_st, nv_wave_amax
+// is order-independent (wave_amax of lk_stream.h).  Few rows: the seeds are split over grid.y.
+#include "lk_stream.h"
 
 namespace lk {
 
@@ -75,7 +74,7 @@ __global__ __launch_bounds__(256) void norm_fwd_row_kernel(const float* __restri
     const int i = (int)iw;
     int cv;
     float v[VEC];
-    nv_ld<VEC>(x + base + row_off<VEC>(q, i, cv), v);
+    ld<VEC>(x + base + row_off<VEC>(q, i, cv), v);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) sum += v[e];
   }
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(256) void norm_fwd_row_kernel(const float* __restri
     const int i = (int)iw;
     int cv;
     float v[VEC];
-    nv_ld<VEC>(x + base + row_off<VEC>(q, i, cv), v);
+    ld<VEC>(x + base + row_off<VEC>(q, i, cv), v);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) sq += (v[e] - mu) * (v[e] - mu);
   }
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(256) void norm_fwd_row_kernel(const float* __restri
     int cv;
     float v[VEC], wv[VEC], bv[VEC], xh[VEC], yv[VEC];
     const int64_t o = base + row_off<VEC>(q, i, cv);
-    nv_ld<VEC>(x + o, v);
+    ld<VEC>(x + o, v);
     row_affine<VEC>(q, w, 1.f, grp, i, cv, wv);
     row_affine<VEC>(q, b, 0.f, grp, i, cv, bv);
 #pragma unroll
@@ -105,8 +104,8 @@ __global__ __launch_bounds__(256) void norm_fwd_row_kernel(const float* __restri
       xh[e] = (v[e] - mu) * rs;
       yv[e] = wv[e] * xh[e] + bv[e];
     }
-    nv_st<VEC>(xhat + o, xh);
-    nv_st<VEC>(y + o, yv);
+    st<VEC>(xhat + o, xh);
+    st<VEC>(y + o, yv);
   }
   if (live && lane == 0) rstd[row] = rs;
 }
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(256) void norm_vjp_row_kernel(const float* __restri
       if (i < nvec) {
         int cv;
         off[k] = base + row_off<VEC>(q, i, cv);
-        nv_ld<VEC>(xhat + off[k], xv[k]);
+        ld<VEC>(xhat + off[k], xv[k]);
         row_affine<VEC>(q, w, 1.f, grp, i, cv, wv[k]);
       }
     }
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(256) void norm_vjp_row_kernel(const float* __restri
 #pragma unroll
           for (int e = 0; e < VEC; ++e) t[j][k][e] = 0.f;
           if (on && off[k] >= 0) {
-            nv_ld<VEC>(gs + off[k], t[j][k]);
+            ld<VEC>(gs + off[k], t[j][k]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               t[j][k][e] *= wv[k][e];
@@ -188,7 +187,7 @@ __global__ __launch_bounds__(256) void norm_vjp_row_kernel(const float* __restri
               d[e] = rs * (t[j][k][e] - m1 - xv[k][e] * m2);
               vmax = fmaxf(vmax, fabsf(d[e]));
             }
-            nv_st<VEC>(ds + off[k], d);
+            st<VEC>(ds + off[k], d);
           }
         }
       }
@@ -204,8 +203,8 @@ __global__ __launch_bounds__(256) void norm_vjp_row_kernel(const float* __restri
         int cv;
         float gv[VEC], xv[VEC], wv[VEC];
         const int64_t o = base + row_off<VEC>(q, i, cv);
-        nv_ld<VEC>(gs + o, gv);
-        nv_ld<VEC>(xhat + o, xv);
+        ld<VEC>(gs + o, gv);
+        ld<VEC>(xhat + o, xv);
         row_affine<VEC>(q, w, 1.f, grp, i, cv, wv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
@@ -225,19 +224,19 @@ __global__ __launch_bounds__(256) void norm_vjp_row_kernel(const float* __restri
         int cv;
         float gv[VEC], xv[VEC], wv[VEC], d[VEC];
         const int64_t o = base + row_off<VEC>(q, i, cv);
-        nv_ld<VEC>(gs + o, gv);
-        nv_ld<VEC>(xhat + o, xv);
+        ld<VEC>(gs + o, gv);
+        ld<VEC>(xhat + o, xv);
         row_affine<VEC>(q, w, 1.f, grp, i, cv, wv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           d[e] = rs * (gv[e] * wv[e] - m1 - xv[e] * m2);
           vmax = fmaxf(vmax, fabsf(d[e]));
         }
-        nv_st<VEC>(ds + o, d);
+        st<VEC>(ds + o, d);
       }
     }
   }
-  nv_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- VJP, TILE kernel: g [S][B][L][Ch], fewer than NVJP_WIDE channels per group ---------------------------------------------------
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(256) void norm_vjp_tile_kernel(const float* __restr
       const int l = ty + k * TL;
 #pragma unroll
       for (int e = 0; e < VEC; ++e) xv[k][e] = 0.f;
-      if (live && l < L) nv_ld<VEC>(xhat + mine + (int64_t)l * Ch, xv[k]);
+      if (live && l < L) ld<VEC>(xhat + mine + (int64_t)l * Ch, xv[k]);
     }
   }
   float vmax = 0.f;
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(256) void norm_vjp_tile_kernel(const float* __restr
 #pragma unroll
           for (int e = 0; e < VEC; ++e) t[j][k][e] = 0.f;
           if (on && live && l < L) {
-            nv_ld<VEC>(gs + (int64_t)l * Ch, t[j][k]);
+            ld<VEC>(gs + (int64_t)l * Ch, t[j][k]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               t[j][k][e] *= wv[e];
@@ -310,8 +309,8 @@ __global__ __launch_bounds__(256) void norm_vjp_tile_kernel(const float* __restr
 #pragma unroll 4
         for (int l = ty; l < L; l += TL) {
           float gv[VEC], xl[VEC];
-          nv_ld<VEC>(gs + (int64_t)l * Ch, gv);
-          nv_ld<VEC>(xhat + mine + (int64_t)l * Ch, xl);
+          ld<VEC>(gs + (int64_t)l * Ch, gv);
+          ld<VEC>(xhat + mine + (int64_t)l * Ch, xl);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
             const float tt = gv[e] * wv[e];
@@ -366,27 +365,27 @@ __global__ __launch_bounds__(256) void norm_vjp_tile_kernel(const float* __restr
               d[e] = rsv[e] * (t[j][k][e] - m1[e] - xv[k][e] * m2[e]);
               vmax = fmaxf(vmax, fabsf(d[e]));
             }
-            nv_st<VEC>(ds + (int64_t)l * Ch, d);
+            st<VEC>(ds + (int64_t)l * Ch, d);
           }
         }
       } else {
 #pragma unroll 4
         for (int l = ty; l < L; l += TL) {
           float gv[VEC], xl[VEC], d[VEC];
-          nv_ld<VEC>(gs + (int64_t)l * Ch, gv);
-          nv_ld<VEC>(xhat + mine + (int64_t)l * Ch, xl);
+          ld<VEC>(gs + (int64_t)l * Ch, gv);
+          ld<VEC>(xhat + mine + (int64_t)l * Ch, xl);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
             d[e] = rsv[e] * (gv[e] * wv[e] - m1[e] - xl[e] * m2[e]);
             vmax = fmaxf(vmax, fabsf(d[e]));
           }
-          nv_st<VEC>(ds + (int64_t)l * Ch, d);
+          st<VEC>(ds + (int64_t)l * Ch, d);
         }
       }
     }
     // (the next pass writes `red` only after every lane has left the group sums above, and `stat` only after its own barriers)
   }
-  nv_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- host: which kernel a shape takes -------------------------------------------------------------------------------------------

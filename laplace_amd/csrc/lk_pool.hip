@@ -15,9 +15,9 @@
 // ceil(kh / sh) * ceil(kw / sw) <= 64 windows) and then loops over the seeds, POOL_SC of them in flight per pass.  SELECTION
 // (kh <= sh and kw <= sw: no two windows share a pixel) is a copy or a zero; SUMMING walks the covering windows and skips the
 // loads of a window none of the lane's channels won.  Few pixels: the seeds are split over grid.y.  `amax` receives max|dx| as
-// the bit pattern of a non-negative float through atomicMax, which is order-independent (as lk_norm_vjp_f32).
+// the bit pattern of a non-negative float through atomicMax, which is order-independent (wave_amax of lk_stream.h).
 // Minimal traffic of the VJP: 4 S B C (OH OW + H W) + B C OH OW bytes.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
@@ -31,58 +31,11 @@ struct PoolGeom {
   FastDiv cv_div, w_div, h_div;  // by CV, by the width and the height of the map the lanes run over
 };
 
-template <int VEC>
-__device__ __forceinline__ void pool_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void pool_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-
 // the codes of VEC adjacent channels, one per byte
 template <int VEC>
 __device__ __forceinline__ unsigned pool_ld_codes(const uint8_t* __restrict__ p) {
   if constexpr (VEC == 4) return *reinterpret_cast<const unsigned*>(p);
   else return *p;
-}
-
-// one atomic per wave: the lanes' maxima of |dx| (non-negative floats order like their bit patterns)
-__device__ __forceinline__ void pool_wave_amax(float m, unsigned* __restrict__ amax) {
-  unsigned b = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
-  if (amax != nullptr && (threadIdx.x & 63) == 0 && b) atomicMax(amax, b);
-}
-
-// lane index -> (channel vector, column, row, image) of a [.., rows, cols, CV] map
-__device__ __forceinline__ void pool_where(const PoolGeom& q, int64_t t, int rows, int cols, int& cv, int& col, int& row,
-                                           int64_t& n) {
-  if (!q.big) {
-    const int ti = (int)t, pix = fdiv(ti, q.cv_div), r = fdiv(pix, q.w_div), ni = fdiv(r, q.h_div);
-    cv = ti - pix * q.CV;
-    col = pix - r * cols;
-    row = r - ni * rows;
-    n = ni;
-  } else {
-    const int64_t pix = t / q.CV, r = pix / cols;
-    cv = (int)(t - pix * q.CV);
-    col = (int)(pix - r * cols);
-    n = r / rows;
-    row = (int)(r - n * rows);
-  }
 }
 
 // the divisor of the average over the window at (h0, w0)
@@ -99,7 +52,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
     int cv, ow, oh;
     int64_t n;
-    pool_where(q, t, q.OH, q.OW, cv, ow, oh, n);
+    map_where(q, t, q.OH, q.OW, cv, ow, oh, n);
     const int h0 = oh * q.sh - q.ph, w0 = ow * q.sw - q.pw;
     const int dy_lo = max(0, -h0), dy_hi = min(q.kh, q.H - h0), dx_lo = max(0, -w0), dx_hi = min(q.kw, q.W - w0);
     const float* xn = x + n * q.H * q.W * q.C + cv * VEC;
@@ -113,7 +66,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
     for (int dy = dy_lo; dy < dy_hi; ++dy)
       for (int dx = dx_lo; dx < dx_hi; ++dx) {
         float v[VEC];
-        pool_ld<VEC>(xn + ((int64_t)(h0 + dy) * q.W + (w0 + dx)) * q.C, v);
+        ld<VEC>(xn + ((int64_t)(h0 + dy) * q.W + (w0 + dx)) * q.C, v);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           if constexpr (KIND == LK_POOL_MAX) {
@@ -136,7 +89,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
     } else {
       arg[o] = (uint8_t)code[0];
     }
-    pool_st<VEC>(y + o, acc);
+    st<VEC>(y + o, acc);
   }
 }
 
@@ -152,7 +105,7 @@ __global__ __launch_bounds__(256) void pool_vjp_kernel(const float* __restrict__
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
     int cv, w, h;
     int64_t n;
-    pool_where(q, t, q.H, q.W, cv, w, h, n);
+    map_where(q, t, q.H, q.W, cv, w, h, n);
     // the windows that cover (h, w): oh * sh - ph <= h < oh * sh - ph + kh
     const int nh = h + q.ph - q.kh + 1, nw = w + q.pw - q.kw + 1;
     // (SELECT: at most one per axis, so the loops below end after their first turn)
@@ -195,7 +148,7 @@ __global__ __launch_bounds__(256) void pool_vjp_kernel(const float* __restrict__
             float gv[POOL_SC][VEC];
 #pragma unroll
             for (int k = 0; k < POOL_SC; ++k)
-              if (s0 + k < s_end) pool_ld<VEC>(gp + (int64_t)(s0 + k) * g_seed, gv[k]);
+              if (s0 + k < s_end) ld<VEC>(gp + (int64_t)(s0 + k) * g_seed, gv[k]);
 #pragma unroll
             for (int k = 0; k < POOL_SC; ++k)
               if (s0 + k < s_end) {
@@ -215,11 +168,11 @@ __global__ __launch_bounds__(256) void pool_vjp_kernel(const float* __restrict__
         if (s0 + k < s_end) {
 #pragma unroll
           for (int e = 0; e < VEC; ++e) vmax = fmaxf(vmax, fabsf(acc[k][e]));
-          pool_st<VEC>(dp + (int64_t)(s0 + k) * dx_seed, acc[k]);
+          st<VEC>(dp + (int64_t)(s0 + k) * dx_seed, acc[k]);
         }
     }
   }
-  pool_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- host: the contract and the path of a shape ----------------------------------------------------------------------------------

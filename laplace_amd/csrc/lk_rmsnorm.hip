@@ -6,14 +6,13 @@
 // only, there is no mean_row(t) term, and xhat is one multiply away from x, so the forward stores y and rstd [rows] alone and
 // the VJP forms xh from x and rstd.
 //
-// The ROW kernel of lk_normvjp.hip on a plain [rows][D] matrix: a group of W lanes (a power of two <= 64) owns a row and
+// A row kernel (lk_stream.h) on a plain [rows][D] matrix: a group of W lanes (a power of two <= 64) owns a row and
 // reduces with a fixed xor-shuffle tree; xh and w of the row stay in registers across the seed loop while the row fits
 // (RMS_NV vectors per lane) with two seeds' g in flight; longer rows read g twice.  16-byte loads where D % 4 == 0 and the
 // pointers are 16-byte aligned, 4-byte loads otherwise.  Deterministic: every element has one owner, plain vector stores, no
 // atomics on data; `amax` receives max|dx| as a bit pattern through atomicMax (order-independent).  Few rows: the seeds are split
 // over grid.y.
-#include "lk_common.h"
-#include "lk_rowvec.h"
+#include "lk_stream.h"
 
 namespace lk {
 
@@ -24,7 +23,7 @@ constexpr int RMS_NV = 8;  // vectors of a row a lane keeps on chip
 template <int VEC>
 __device__ __forceinline__ void rms_weight(const float* __restrict__ w, int i, float (&v)[VEC]) {
   if (w != nullptr) {
-    nv_ld<VEC>(w + (int64_t)i * VEC, v);
+    ld<VEC>(w + (int64_t)i * VEC, v);
   } else {
 #pragma unroll
     for (int e = 0; e < VEC; ++e) v[e] = 1.f;
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const float* __restric
   float sq = 0.f;
   for (int i = lane; i < nvec; i += W) {  // (D < 2^30: i + W stays below 2^31)
     float v[VEC];
-    nv_ld<VEC>(x + base + (int64_t)i * VEC, v);
+    ld<VEC>(x + base + (int64_t)i * VEC, v);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) sq += v[e] * v[e];
   }
@@ -53,11 +52,11 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const float* __restric
   for (int i = lane; i < nvec; i += W) {
     float v[VEC], wv[VEC], yv[VEC];
     const int64_t o = base + (int64_t)i * VEC;
-    nv_ld<VEC>(x + o, v);
+    ld<VEC>(x + o, v);
     rms_weight<VEC>(w, i, wv);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) yv[e] = wv[e] * (v[e] * rs);
-    nv_st<VEC>(y + o, yv);
+    st<VEC>(y + o, yv);
   }
   if (live && lane == 0) rstd[row] = rs;
 }
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(256) void rmsnorm_vjp_kernel(const float* __restric
       for (int e = 0; e < VEC; ++e) xh[k][e] = wv[k][e] = 0.f;
       if (i < nvec) {
         off[k] = base + (int64_t)i * VEC;
-        nv_ld<VEC>(x + off[k], xh[k]);
+        ld<VEC>(x + off[k], xh[k]);
         rms_weight<VEC>(w, i, wv[k]);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) xh[k][e] *= rs;
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(256) void rmsnorm_vjp_kernel(const float* __restric
 #pragma unroll
           for (int e = 0; e < VEC; ++e) t[j][k][e] = 0.f;
           if (on && off[k] >= 0) {
-            nv_ld<VEC>(gs + off[k], t[j][k]);
+            ld<VEC>(gs + off[k], t[j][k]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               t[j][k][e] *= wv[k][e];
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(256) void rmsnorm_vjp_kernel(const float* __restric
               d[e] = rs * (t[j][k][e] - xh[k][e] * m2);
               vmax = fmaxf(vmax, fabsf(d[e]));
             }
-            nv_st<VEC>(ds + off[k], d);
+            st<VEC>(ds + off[k], d);
           }
         }
       }
@@ -147,8 +146,8 @@ __global__ __launch_bounds__(256) void rmsnorm_vjp_kernel(const float* __restric
       for (int i = lane; i < nvec; i += W) {
         float gv[VEC], xv[VEC], wv[VEC];
         const int64_t o = base + (int64_t)i * VEC;
-        nv_ld<VEC>(gs + o, gv);
-        nv_ld<VEC>(x + o, xv);
+        ld<VEC>(gs + o, gv);
+        ld<VEC>(x + o, xv);
         rms_weight<VEC>(w, i, wv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) a2 += (gv[e] * wv[e]) * (xv[e] * rs);
@@ -159,19 +158,19 @@ __global__ __launch_bounds__(256) void rmsnorm_vjp_kernel(const float* __restric
       for (int i = lane; i < nvec; i += W) {
         float gv[VEC], xv[VEC], wv[VEC], d[VEC];
         const int64_t o = base + (int64_t)i * VEC;
-        nv_ld<VEC>(gs + o, gv);
-        nv_ld<VEC>(x + o, xv);
+        ld<VEC>(gs + o, gv);
+        ld<VEC>(x + o, xv);
         rms_weight<VEC>(w, i, wv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           d[e] = rs * (gv[e] * wv[e] - (xv[e] * rs) * m2);
           vmax = fmaxf(vmax, fabsf(d[e]));
         }
-        nv_st<VEC>(ds + o, d);
+        st<VEC>(ds + o, d);
       }
     }
   }
-  nv_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- host: which path a shape takes ---------------------------------------------------------------------------------------------

@@ -14,15 +14,11 @@
 // and stores of fp32, 8-byte loads of four halves) where Ct and every c0 and cs are multiples of 4 and the pointers are aligned -
 // a vector then never straddles a piece boundary -, one element per lane otherwise; a grid of at most 256 CUs x 8 workgroups
 // strides over the lanes.  Every dst element has one owner, stores are plain, repeated runs give the same bits.  `amax` receives
-// max|dst| as the bit pattern of a non-negative float through atomicMax, one atomic per wave (as lk_cat_vjp_nhwc_f32).
+// max|dst| as the bit pattern of a non-negative float through atomicMax, one atomic per wave (wave_amax of lk_stream.h).
 // Minimal traffic of the VJP: 4 R Ct bytes written plus every piece read once; of the forward: 8 R Cs bytes.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
-
-typedef _Float16 slice_f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int64_t SLICE_MAX_BLOCKS = 256 * 8;  // 256 CUs x 8 workgroups of 256 threads
 
 struct SlicePieces {  // by value: device pointers and column ranges of the pieces (f32[p] non-null: an fp32 map; else planes)
   const float* f32[LK_SLICE_MAX_PIECES];
@@ -33,84 +29,22 @@ struct SlicePieces {  // by value: device pointers and column ranges of the piec
   int cs[LK_SLICE_MAX_PIECES];
 };
 
-struct SliceGeom {
-  int64_t Ct, c0, Cs, lanes;
-  int CV;   // lanes per row
-  int big;  // the lane index does not fit 31 bits: 64-bit division
-  FastDiv cv_div;
-};
-
-// lane index -> (row, first column of the lane)
-template <int VEC>
-__device__ __forceinline__ void slice_where(const SliceGeom& q, int64_t t, int64_t& r, int& c) {
-  if (!q.big) {
-    const int ri = fdiv((int)t, q.cv_div);
-    r = ri;
-    c = ((int)t - ri * q.CV) * VEC;
-  } else {
-    r = t / q.CV;
-    c = (int)(t - r * q.CV) * VEC;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void slice_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void slice_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-
-// (float(h) + float(l)) * scale of VEC adjacent columns; scale is a power of two, so the product is exact
-template <int VEC>
-__device__ __forceinline__ void slice_ld_split(const _Float16* __restrict__ h, const _Float16* __restrict__ l, float scale,
-                                               float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const slice_f16x4 a = *reinterpret_cast<const slice_f16x4*>(h), b = *reinterpret_cast<const slice_f16x4*>(l);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = ((float)a[e] + (float)b[e]) * scale;
-  } else {
-    v[0] = ((float)*h + (float)*l) * scale;
-  }
-}
-
-// one atomic per wave: the lanes' maxima of |dst| (non-negative floats order like their bit patterns)
-__device__ __forceinline__ void slice_wave_amax(float m, unsigned* __restrict__ amax) {
-  unsigned b = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
-  if (amax != nullptr && (threadIdx.x & 63) == 0 && b) atomicMax(amax, b);
-}
-
 // ---- forward: a lane per VEC columns of a dst row ---------------------------------------------------------------------------------
 template <int VEC>
-__global__ __launch_bounds__(256) void slice_fwd_kernel(const float* __restrict__ src, SliceGeom q, float* __restrict__ dst) {
+__global__ __launch_bounds__(256) void slice_fwd_kernel(const float* __restrict__ src, ColSliceGeom q, float* __restrict__ dst) {
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < q.lanes; t += (int64_t)gridDim.x * 256) {
     int64_t r;
     int c;
-    slice_where<VEC>(q, t, r, c);
+    col_where<VEC>(q, t, r, c);
     float v[VEC];
-    slice_ld<VEC>(src + r * q.Ct + q.c0 + c, v);
-    slice_st<VEC>(dst + t * VEC, v);  // (dst is the contiguous [R][Cs] map: its lanes lie in order)
+    ld<VEC>(src + r * q.Ct + q.c0 + c, v);
+    st<VEC>(dst + t * VEC, v);  // (dst is the contiguous [R][Cs] map: its lanes lie in order)
   }
 }
 
 // ---- VJP: a lane per VEC columns of a dst row [R][Ct]; NP pieces, the covering ones summed in the listed order --------------------
 template <int VEC, int NP>
-__global__ __launch_bounds__(256) void slice_vjp_kernel(SlicePieces P, SliceGeom q, float* __restrict__ dst,
+__global__ __launch_bounds__(256) void slice_vjp_kernel(SlicePieces P, ColSliceGeom q, float* __restrict__ dst,
                                                         unsigned* __restrict__ amax) {
   float scale[NP];
 #pragma unroll
@@ -119,7 +53,7 @@ __global__ __launch_bounds__(256) void slice_vjp_kernel(SlicePieces P, SliceGeom
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < q.lanes; t += (int64_t)gridDim.x * 256) {
     int64_t r;
     int c;
-    slice_where<VEC>(q, t, r, c);
+    col_where<VEC>(q, t, r, c);
     float acc[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
@@ -130,8 +64,8 @@ __global__ __launch_bounds__(256) void slice_vjp_kernel(SlicePieces P, SliceGeom
       if (cp >= 0 && cp < P.cs[p]) {
         const int64_t at = r * P.cs[p] + cp;
         float v[VEC];
-        if (P.f32[p] != nullptr) slice_ld<VEC>(P.f32[p] + at, v);
-        else slice_ld_split<VEC>(P.h[p] + at, P.l[p] + at, scale[p], v);
+        if (P.f32[p] != nullptr) ld<VEC>(P.f32[p] + at, v);
+        else ld_split<VEC>(P.h[p] + at, P.l[p] + at, scale[p], v);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] = have ? acc[e] + v[e] : v[e];
         have = true;
@@ -139,9 +73,9 @@ __global__ __launch_bounds__(256) void slice_vjp_kernel(SlicePieces P, SliceGeom
     }
 #pragma unroll
     for (int e = 0; e < VEC; ++e) vmax = fmaxf(vmax, fabsf(acc[e]));
-    slice_st<VEC>(dst + t * VEC, acc);  // (dst is the contiguous [R][Ct] map: its lanes lie in order)
+    st<VEC>(dst + t * VEC, acc);  // (dst is the contiguous [R][Ct] map: its lanes lie in order)
   }
-  slice_wave_amax(vmax, amax);
+  wave_amax(vmax, amax);
 }
 
 // ---- host: the contract and the path of a shape ----------------------------------------------------------------------------------
@@ -149,11 +83,6 @@ struct SlicePlan {
   int vec;
   int64_t lanes, blocks;
 };
-
-static bool slice_disjoint(const void* a, unsigned __int128 a_bytes, const void* b, unsigned __int128 b_bytes) {
-  const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 + a_bytes <= b0 || b0 + b_bytes <= a0;
-}
 
 // the extent both entry points share, with the messages under the caller's name
 static int slice_check_extent(const char* fn, int64_t R, int64_t Ct) {
@@ -171,12 +100,11 @@ static int slice_check_range(const char* fn, int64_t Ct, int64_t c0, int64_t cs)
 static void slice_plan(SlicePlan* p, int64_t R, int64_t width, bool vec) {
   p->vec = vec;
   p->lanes = R * (vec ? width / 4 : width);
-  const int64_t need = (p->lanes + 255) / 256;
-  p->blocks = need < SLICE_MAX_BLOCKS ? need : SLICE_MAX_BLOCKS;
+  p->blocks = grid_blocks(p->lanes);
 }
 
-static SliceGeom slice_geometry(const SlicePlan& p, int64_t Ct, int64_t c0, int64_t Cs, int64_t width) {
-  SliceGeom q;
+static ColSliceGeom slice_geometry(const SlicePlan& p, int64_t Ct, int64_t c0, int64_t Cs, int64_t width) {
+  ColSliceGeom q;
   q.Ct = Ct, q.c0 = c0, q.Cs = Cs, q.lanes = p.lanes;
   q.CV = (int)(p.vec ? width / 4 : width);
   q.big = p.lanes >= (1ll << 31);
@@ -205,7 +133,7 @@ static int slice_check_fwd(const float* src, int64_t R, int64_t Ct, int64_t c0, 
   if (rc != LK_OK) return rc;
   rc = slice_check_range("lk_slice_fwd_f32", Ct, c0, Cs);
   if (rc != LK_OK) return rc;
-  LK_REQUIRE(slice_disjoint(dst, (unsigned __int128)R * Cs * 4, src, (unsigned __int128)R * Ct * 4),
+  LK_REQUIRE(disjoint(dst, (unsigned __int128)R * Cs * 4, src, (unsigned __int128)R * Ct * 4),
              "lk_slice_fwd_f32: dst overlaps src");
   const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
   slice_plan(p, R, Cs, aligned && Ct % 4 == 0 && c0 % 4 == 0 && Cs % 4 == 0);
@@ -231,8 +159,8 @@ static int slice_check_vjp(int npieces, const float* const* f32, const void* con
   bool clear = true;
   for (int i = 0; i < npieces; ++i) {
     const unsigned __int128 pe = (unsigned __int128)R * cs[i];
-    if (f32[i]) clear = clear && slice_disjoint(dst, db, f32[i], pe * 4);
-    else clear = clear && slice_disjoint(dst, db, hi[i], pe * 2) && slice_disjoint(dst, db, lo[i], pe * 2);
+    if (f32[i]) clear = clear && disjoint(dst, db, f32[i], pe * 4);
+    else clear = clear && disjoint(dst, db, hi[i], pe * 2) && disjoint(dst, db, lo[i], pe * 2);
   }
   LK_REQUIRE(clear, "lk_slice_vjp_f32: dst overlaps a piece");
   return LK_OK;
@@ -247,7 +175,7 @@ extern "C" int lk_slice_fwd_f32(const float* src, int64_t R, int64_t Ct, int64_t
   const int rc = slice_check_fwd(src, R, Ct, c0, Cs, dst, &p);
   if (rc != LK_OK) return rc;
   if (R == 0) return LK_OK;
-  const SliceGeom q = slice_geometry(p, Ct, c0, Cs, Cs);
+  const ColSliceGeom q = slice_geometry(p, Ct, c0, Cs, Cs);
   hipStream_t st = (hipStream_t)stream;
   if (p.vec) hipLaunchKernelGGL((slice_fwd_kernel<4>), dim3((unsigned)p.blocks), dim3(256), 0, st, src, q, dst);
   else hipLaunchKernelGGL((slice_fwd_kernel<1>), dim3((unsigned)p.blocks), dim3(256), 0, st, src, q, dst);
@@ -261,7 +189,7 @@ extern "C" int lk_slice_vjp_f32(int npieces, const float* const* f32, const void
   const int rc = slice_check_vjp(npieces, f32, hi, lo, sexp, c0, cs, R, Ct, dst, &p);
   if (rc != LK_OK) return rc;
   if (R == 0) return LK_OK;
-  const SliceGeom q = slice_geometry(p, Ct, 0, Ct, Ct);
+  const ColSliceGeom q = slice_geometry(p, Ct, 0, Ct, Ct);
   SlicePieces P;
   for (int i = 0; i < LK_SLICE_MAX_PIECES; ++i) {
     const bool used = i < npieces, split = used && f32[i] == nullptr;

@@ -7,40 +7,18 @@
 // runs it once per seed: `_softmax_backward_data` / `_log_softmax_backward_data` on [B, ...], S launches that each read y again.
 // Here one launch serves all seeds and y (for the log form exp(y), computed ONCE) of a row stays in registers across the seed loop.
 //
-// One kernel template after the ROW body of lk_mul.hip / lk_normvjp.hip: a group of W lanes (a power of two <= 64, so a group never
+// One kernel template (lk_stream.h; the ROW body of lk_mul.hip): a group of W lanes (a power of two <= 64, so a group never
 // leaves its wave) owns one row; the row sum is a fixed xor-shuffle tree over the group.  While the row fits (SMX_NV vectors per
 // lane: RESIDENT) y and the seed's g stay in registers between the sum and the store; longer rows re-read both per seed.  16-byte
 // loads and stores where L % 4 == 0 and every pointer is 16-byte aligned, 4-byte ones otherwise.  Few rows: the seeds are split
 // over grid.y.  Every output element has one owner, stores are plain vector stores, there is no atomic: repeated runs give the same
 // bits.  A probability that is exactly zero (a masked key) gives dx = 0 * (finite) = 0 exactly.  Nothing assumes packed fp32.
 // Minimal traffic: g once and dx once (8 S R L bytes), y once.
-#include "lk_common.h"
+#include "lk_stream.h"
 
 namespace lk {
 
-constexpr int SMX_NV = 8;                    // vectors of a row a lane keeps in registers (RESIDENT)
-constexpr int64_t SMX_MAX_BLOCKS = 256 * 8;  // 256 CUs x 8 workgroups of 256 threads
-
-template <int VEC>
-__device__ __forceinline__ void smx_ld(const float* __restrict__ p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void smx_st(float* __restrict__ p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    f32x4 t;
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
+constexpr int SMX_NV = 8;  // vectors of a row a lane keeps in registers (RESIDENT)
 
 // what the row sum adds (g y / g) and what the element gets from it
 template <bool LOG>
@@ -75,7 +53,7 @@ __global__ __launch_bounds__(256) void softmax_vjp_kernel(const float* __restric
 #pragma unroll
         for (int e = 0; e < VEC; ++e) pv[k][e] = 0.f;
         if (i < nvec) {
-          smx_ld<VEC>(y + base + (int64_t)i * VEC, pv[k]);
+          ld<VEC>(y + base + (int64_t)i * VEC, pv[k]);
           if constexpr (LOG) {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) pv[k][e] = expf(pv[k][e]);
@@ -92,7 +70,7 @@ __global__ __launch_bounds__(256) void softmax_vjp_kernel(const float* __restric
 #pragma unroll
           for (int e = 0; e < VEC; ++e) gv[k][e] = 0.f;
           if (i < nvec) {
-            smx_ld<VEC>(gs + (int64_t)i * VEC, gv[k]);
+            ld<VEC>(gs + (int64_t)i * VEC, gv[k]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) acc += smx_term<LOG>(gv[k][e], pv[k][e]);
           }
@@ -105,7 +83,7 @@ __global__ __launch_bounds__(256) void softmax_vjp_kernel(const float* __restric
             float d[VEC];
 #pragma unroll
             for (int e = 0; e < VEC; ++e) d[e] = smx_out<LOG>(gv[k][e], pv[k][e], acc);
-            smx_st<VEC>(dx + s * seed_stride + base + (int64_t)i * VEC, d);
+            st<VEC>(dx + s * seed_stride + base + (int64_t)i * VEC, d);
           }
         }
       }
@@ -115,21 +93,21 @@ __global__ __launch_bounds__(256) void softmax_vjp_kernel(const float* __restric
         float acc = 0.f;
         for (int i = lane; i < nvec; i += W) {  // (nvec < 2^30 and W <= 64: no overflow)
           float gv[VEC], pv[VEC];
-          smx_ld<VEC>(gs + (int64_t)i * VEC, gv);
+          ld<VEC>(gs + (int64_t)i * VEC, gv);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) pv[e] = 0.f;
-          if constexpr (!LOG) smx_ld<VEC>(y + base + (int64_t)i * VEC, pv);  // (the log form sums g alone)
+          if constexpr (!LOG) ld<VEC>(y + base + (int64_t)i * VEC, pv);  // (the log form sums g alone)
 #pragma unroll
           for (int e = 0; e < VEC; ++e) acc += smx_term<LOG>(gv[e], pv[e]);
         }
         for (int o = W >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
         for (int i = lane; i < nvec; i += W) {
           float gv[VEC], pv[VEC], d[VEC];
-          smx_ld<VEC>(gs + (int64_t)i * VEC, gv);
-          smx_ld<VEC>(y + base + (int64_t)i * VEC, pv);
+          ld<VEC>(gs + (int64_t)i * VEC, gv);
+          ld<VEC>(y + base + (int64_t)i * VEC, pv);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) d[e] = smx_out<LOG>(gv[e], LOG ? expf(pv[e]) : pv[e], acc);
-          smx_st<VEC>(dx + s * seed_stride + base + (int64_t)i * VEC, d);
+          st<VEC>(dx + s * seed_stride + base + (int64_t)i * VEC, d);
         }
       }
     }
@@ -146,11 +124,6 @@ struct SoftmaxPlan {
   int64_t blocks;
 };
 
-static bool smx_disjoint(const void* p, unsigned __int128 p_bytes, const void* q, unsigned __int128 q_bytes) {
-  const unsigned __int128 p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-  return p0 + p_bytes <= q0 || q0 + q_bytes <= p0;
-}
-
 // the shape part of the contract (shared with lk_softmax_vjp_variant), with the messages under the caller's name
 static int softmax_check_shape(const char* fn, int64_t S, int64_t R, int64_t L, int is_log, bool aligned, SoftmaxPlan* p) {
   LK_REQUIRE(is_log == 0 || is_log == 1, "%s: is_log must be 0 (y = softmax) or 1 (y = log_softmax)", fn);
@@ -164,7 +137,7 @@ static int softmax_check_shape(const char* fn, int64_t S, int64_t R, int64_t L, 
   p->resident = nvec <= (int64_t)p->W * SMX_NV;
   const int rpb = 256 / p->W;
   p->blocks = (R + rpb - 1) / rpb;
-  if (p->blocks > SMX_MAX_BLOCKS) p->blocks = SMX_MAX_BLOCKS;
+  if (p->blocks > STREAM_MAX_BLOCKS) p->blocks = STREAM_MAX_BLOCKS;
   p->s_per = seeds_per_slice(S, p->blocks * 4);
   return LK_OK;
 }
@@ -176,7 +149,7 @@ static int softmax_check(const float* g, const float* y, int64_t S, int64_t R, i
   const int rc = softmax_check_shape("lk_softmax_vjp_f32", S, R, L, is_log, (bits & 15) == 0, p);
   if (rc != LK_OK) return rc;
   const unsigned __int128 rl = (unsigned __int128)R * L * 4, gb = rl * S;
-  LK_REQUIRE(smx_disjoint(dx, gb, g, gb) && smx_disjoint(dx, gb, y, rl), "lk_softmax_vjp_f32: dx overlaps an input");
+  LK_REQUIRE(disjoint(dx, gb, g, gb) && disjoint(dx, gb, y, rl), "lk_softmax_vjp_f32: dx overlaps an input");
   return LK_OK;
 }
 

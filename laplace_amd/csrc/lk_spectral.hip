@@ -29,7 +29,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "lk_common.h"
+#include "lk_stream.h"
 #include "lk_quadtile.h"
 
 namespace lk {
@@ -316,11 +316,6 @@ static bool sp_plan(int form, int64_t N, int64_t C, int64_t DP, int64_t G, SpPla
   return true;
 }
 
-static bool sp_disjoint(const void* p, unsigned __int128 p_bytes, const void* q, unsigned __int128 q_bytes) {
-  const unsigned __int128 p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-  return p0 + p_bytes <= q0 || q0 + q_bytes <= p0;
-}
-
 // the whole contract of the four entry points, with the messages under the caller's name
 static int spectral_check_args(const char* fn, int form, const float* X, const float* Q, const float* lam, float hfac,
                                const float* deltas, int64_t G, int64_t N, int64_t C, int64_t DP, const float* out,
@@ -349,9 +344,9 @@ static int spectral_check_args(const char* fn, int form, const float* X, const f
   }
   const unsigned __int128 ob = (unsigned __int128)N * C * 4 * (p->grid ? (unsigned __int128)G : (unsigned __int128)C);
   const unsigned __int128 xb = ll ? (unsigned __int128)N * DP * 4 : (unsigned __int128)N * C * p->P * 4;
-  bool clear = sp_disjoint(out, ob, X, xb) && sp_disjoint(out, ob, lam, (unsigned __int128)p->P * 4) &&
-               sp_disjoint(out, ob, deltas, (unsigned __int128)G * 4) && sp_disjoint(out, ob, ws, p->ws);
-  if (ll) clear = clear && sp_disjoint(out, ob, Q, (unsigned __int128)p->P * p->P * 4);
+  bool clear = disjoint(out, ob, X, xb) && disjoint(out, ob, lam, (unsigned __int128)p->P * 4) &&
+               disjoint(out, ob, deltas, (unsigned __int128)G * 4) && disjoint(out, ob, ws, p->ws);
+  if (ll) clear = clear && disjoint(out, ob, Q, (unsigned __int128)p->P * p->P * 4);
   LK_REQUIRE(clear, "%s: the output overlaps an input or the workspace", fn);
   return LK_OK;
 }

@@ -35,7 +35,7 @@ from tests.mul_fixtures import full_mantissa
 from tests.slice_fixtures import E2E_CLASSES, _seeded, rel, run_curvature_checks, taps  # noqa: F401  (shared with the slicing tests)
 
 U = 2.0 ** -24
-SMX_MAX_BLOCKS = 2048  # SMX_MAX_BLOCKS of csrc/lk_softmax.hip
+SMX_MAX_BLOCKS = 2048  # STREAM_MAX_BLOCKS of csrc/lk_stream.h
 MM_RES_DEPTH = 128  # MM_RES_DEPTH of csrc/lk_matmul.hip
 #: twice the measured relative error, in units of u, of torch's CPU fp32 exp against fp64 on the log cases (see the docstring)
 MEASURED_EXP_ERROR = 1.03

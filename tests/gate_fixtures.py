@@ -21,7 +21,7 @@ from torch import nn
 
 from tests.mul_fixtures import E2E_CLASSES, _seeded, full_mantissa, rel, run_curvature_checks, se_fixture, taps  # noqa: F401
 
-MAX_BLOCKS = 2048  # GATE_MAX_BLOCKS of csrc/lk_gate.hip
+MAX_BLOCKS = 2048  # STREAM_MAX_BLOCKS of csrc/lk_stream.h
 RESIDENT_POSITIONS = 16  # GATE_NV: positions of x a thread keeps in registers
 VJP_POSITIONS = 8  # GATE_PP: positions a thread of the VJP walks per unit
 

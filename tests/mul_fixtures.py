@@ -17,7 +17,7 @@ from torch import nn
 
 from tests.slice_fixtures import E2E_CLASSES, _seeded, rel, run_curvature_checks, taps  # noqa: F401  (shared with the slicing tests)
 
-MAX_BLOCKS = 2048  # MUL_MAX_BLOCKS of csrc/lk_mul.hip
+MAX_BLOCKS = 2048  # STREAM_MAX_BLOCKS of csrc/lk_stream.h
 RESIDENT_VECTORS = 64 * 8  # vectors of a row that stay in registers (64 lanes x MUL_NV)
 
 

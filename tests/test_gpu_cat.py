@@ -199,6 +199,8 @@ def test_the_bindings():
             K.cat_vjp([ops[1], ops[1][:, :, :, :40].contiguous()], 8, 4)
         with pytest.raises(LaplaceHipError):
             K.cat_vjp([SplitTensor(ops[0].planes, torch.zeros(2, dtype=torch.int32, device=DEV))], 8, 4)  # (one scale per image)
+        with pytest.raises(LaplaceHipError, match="chunk-major split tensor is no NHWC map"):
+            K.cat_vjp([SplitTensor(ops[0].planes, ops[0].sexp, chunked=True)], 8, 4)
         with pytest.raises(LaplaceHipError):
             K.cat_forward([srcs[0], srcs[1][:, :2].contiguous()])
         with pytest.raises(LaplaceHipError):

@@ -174,6 +174,10 @@ def test_the_binding_allocates_checks_and_refuses():
     if DEV != "cpu":
         with pytest.raises(LaplaceHipError):
             K.dwconv_backward(g, w.to(DEV), c["S"], (c["H"] + 2, c["W"]), c["k"], c["s"], c["p"])
+        with pytest.raises(LaplaceHipError, match="amax is one 32-bit device word"):
+            K.dwconv_backward(g, w.to(DEV), c["S"], (c["H"], c["W"]), c["k"], c["s"], c["p"], amax=torch.zeros(2, device=DEV))
+        with pytest.raises(LaplaceHipError, match="g must be a split tensor"):  # (chunk-major planes are no NHWC map)
+            K.dwconv_backward(SplitTensor(g.planes, g.sexp, chunked=True), w.to(DEV), c["S"], (c["H"], c["W"]), c["k"], c["s"], c["p"])
         with pytest.raises(LaplaceHipError):
             K.dwconv_forward(x.to(DEV), w.to(DEV)[:4], None, c["k"], c["s"], c["p"])
         with pytest.raises(LaplaceHipError):

@@ -145,6 +145,11 @@ def test_vjp_without_an_amax_word_and_the_binding():
     want, bound = nf.vjp_reference(g.reshape(3, 2, 16, 64), xhat, rstd, w, c)
     assert _ratio(nf.to_rows(dx.reshape(3, 2, 16, 64), 32, 1), want, bound)[1] <= 0.0
     assert rel(y, torch.nn.functional.group_norm(x.movedim(-1, 1).double(), 32, w.double(), b.double(), EPS).movedim(1, -1)) < 1e-5
+    if DEV != "cpu":
+        from laplace_amd._lib import LaplaceHipError
+
+        with pytest.raises(LaplaceHipError, match="amax is one 32-bit device word"):
+            K.norm_vjp(g, xhat, rstd, w, 3, 32, 1, amax=torch.zeros(2, device=DEV))
 
 
 # ---- 2. the backend against the goldens of the reference --------------------------------------------------------------------------

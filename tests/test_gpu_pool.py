@@ -174,6 +174,8 @@ def test_vjp_without_an_amax_word_and_the_binding():
     if DEV != "cpu":
         with pytest.raises(LaplaceHipError):
             K.pool_vjp(g.reshape(-1, *y.shape[1:]), arg, c["S"], (c["H"] + 2, c["W"]), K.POOL_MAX, 3, 2, 1)
+        with pytest.raises(LaplaceHipError, match="amax is one 32-bit device word"):
+            K.pool_vjp(g.reshape(-1, *y.shape[1:]), arg, c["S"], (c["H"], c["W"]), K.POOL_MAX, 3, 2, 1, amax=torch.zeros(2, device=DEV))
         with pytest.raises(LaplaceHipError):
             K.pool_forward(x, K.POOL_MAX, 9, 1, 4)  # (the C ABI's own refusal reaches the caller)
 

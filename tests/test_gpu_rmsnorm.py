@@ -158,6 +158,11 @@ def test_no_rows_return_clean_and_the_binding():
     for s in range(3):
         (want,) = torch.autograd.grad(out, xr, g0[s].double(), retain_graph=True)
         assert rf.rel(dx.reshape(3, 10, 192)[s], want) < 1e-5
+    if DEV != "cpu":
+        from laplace_amd._lib import LaplaceHipError
+
+        with pytest.raises(LaplaceHipError, match="amax is one 32-bit device word"):
+            K.rmsnorm_vjp(g.reshape(-1, 192), x, rstd, w, 3, amax=torch.zeros(2, device=DEV))
 
 
 # ---- 2. end to end -----------------------------------------------------------------------------------------------------------------

@@ -205,6 +205,8 @@ def test_the_bindings():
             K.slice_vjp([(ops[1][0], 0, 40)], 30, 48)  # (the tensor holds 48 columns, not 40)
         with pytest.raises(LaplaceHipError):
             K.slice_vjp([(SplitTensor(ops[0][0].planes, torch.zeros(2, dtype=torch.int32, device=DEV)), 8, 4)], 30, 48)
+        with pytest.raises(LaplaceHipError, match="chunk-major split tensor is no row matrix"):
+            K.slice_vjp([(SplitTensor(ops[0][0].planes, ops[0][0].sexp, chunked=True), 8, 4)], 30, 48)
         with pytest.raises(LaplaceHipError):
             K.slice_forward(x.to(DEV), 30, 48, 40, 9)
         with pytest.raises(LaplaceHipError):
