@@ -682,6 +682,35 @@ int lk_slice_vjp_f32(int npieces, const float* const* f32, const void* const* hi
                      unsigned* amax, void* stream);
 int lk_slice_variant(int npieces, int split_mask, const int64_t* c0, const int64_t* cs, int64_t R, int64_t Ct, int aligned);
 
+/* Maximum over positions (x.amax(2), x.max(2)[0], AdaptiveMaxPool1d(1): what 1-D ResNets, text CNNs and PointNets end in) for
+ * the seed-batched reverse sweep.  The operand is a contiguous fp32 [outer][L][inner], L the product of the reduced dims.  They
+ * replace, in the reverse pass of laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through such a reduction, a
+ * zero fill of the whole [S][outer][L][inner] tensor and a scatter per seed.
+ *
+ * lk_maxred_fwd_f32: y[o][i] = max_l x[o][l][i]; idx[o][i] (int32) = the first l that holds it; cnt[o][i] (int32) = how many l
+ *   compare equal to it (0.0 == -0.0, as torch compares).  A row with a NaN gives NaN in y; its idx and cnt are unspecified.
+ *   inner == 1: a group of 1 .. 64 lanes per row and a fixed xor-shuffle tree on (value, index, count) items ordered "larger
+ *   value, then smaller index" (the result does not depend on the tree); inner > 1: a lane per (outer, inner vector) that walks
+ *   l.  A reduction is never split over workgroups.
+ * lk_maxred_vjp_f32: g is [S][outer][inner], dx [S][outer][L][inner], all seeds in one launch.  With idx alone (x, y, cnt null)
+ *   dx = (l == idx) ? g : +0.0f (max(dim), the adaptive max pools: the first maximum); with x, y and cnt (idx is ignored)
+ *   dx = (x == y) ? g / cnt : +0.0f (amax: an even split over the maxima; one fp32 division).  Every element of dx is written:
+ *   the caller fills nothing.  One owner per element, plain stores, no atomics: deterministic.  idx / x, y, cnt of an element
+ *   are read once for all seeds.  Minimal traffic: 4 S (outer inner)(L + 1) bytes.
+ * Contract of both: pointers non-null where used; 1 <= S < 2^31 (the forward has S = 1), 0 <= outer, 1 <= L < 2^30,
+ *   1 <= inner < 2^30, outer * inner < 2^31, S * outer * L * inner < 2^40; the outputs overlap no operand (nor, in the forward,
+ *   each other).  outer == 0 returns LK_OK.  Errors: "<entry>: bad arguments (...)".
+ * lk_reduce_variant (host only): the path a shape takes in the forward (vjp == 0) or the VJP (vjp != 0; `even`: x, y, cnt are
+ * given); `aligned`: every pointer is 16-byte aligned.  Returns
+ *   row | vec << 1 | even << 2 | 64-bit lane index << 3 | log2(lanes per row) << 4 | seed-split << 7 | workgroups << 8
+ *   row: inner == 1; vec: 16-byte accesses (forward: inner % 4 == 0; VJP: inner % 4 == 0, or L % 4 == 0 where inner == 1; and
+ *   aligned); seed-split: the seeds are split over grid.y; workgroups: at most 2048 of 256 threads stride over the work
+ * or a negative value for a shape the entry points refuse. */
+int lk_maxred_fwd_f32(const float* x, int64_t outer, int64_t L, int64_t inner, float* y, int* idx, int* cnt, void* stream);
+int lk_maxred_vjp_f32(const float* g, const int* idx, const float* x, const float* y, const int* cnt, int64_t S, int64_t outer,
+                      int64_t L, int64_t inner, float* dx, void* stream);
+int lk_reduce_variant(int vjp, int64_t S, int64_t outer, int64_t L, int64_t inner, int even, int aligned);
+
 /* Element-wise product of two traced tensors (squeeze-and-excitation gates, GLU / SwiGLU / GeGLU, self-gating) for the
  * seed-batched reverse sweep.  It replaces, in the reverse pass of laplace/curvature/curvlinops.py:87-100 and
  * curvature.py:88-129 through out = a * b as stock torch runs it once per seed, g * b, g * a and - for a gate - a sum over the

@@ -138,6 +138,9 @@ SIGNATURES = {
     "lk_slice_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_slice_vjp_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "lk_slice_variant": (_int, [_int, _int, _vp, _vp, _i64, _i64, _int]),
+    "lk_maxred_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "lk_maxred_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "lk_reduce_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int, _int]),
     "lk_mul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_mul_variant": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
     "lk_gate_reduce_nhwc_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
@@ -1736,6 +1739,61 @@ class HipKernels:
             return None
         return {"vec": bool(r & 1), "npieces": (r >> 1) & 15, "split_mask": (r >> 5) & 255, "wide_index": bool(r & (1 << 13)),
                 "blocks": r >> 14}
+
+    def maxred_forward(self, x, outer, L, inner):
+        """``(y, idx, cnt)``, each ``[outer, inner]``, of the contiguous fp32 ``x`` read as ``[outer, L, inner]``: the maximum over
+        ``L``, the first position that holds it and how many positions compare equal to it (int32), in one launch of
+        lk_maxred_fwd_f32 (csrc/lk_reduce.hip)"""
+        _check(x, "x")
+        outer, L, inner = int(outer), int(L), int(inner)
+        if outer < 0 or L < 1 or inner < 1 or x.numel() != outer * L * inner:
+            raise LaplaceHipError(f"maxred_forward: x {tuple(x.shape)} is no [{outer}, {L}, {inner}] operand")
+        y = torch.empty(outer, inner, dtype=torch.float32, device=x.device)
+        idx = torch.empty(outer, inner, dtype=torch.int32, device=x.device)
+        cnt = torch.empty(outer, inner, dtype=torch.int32, device=x.device)
+        if outer == 0:  # (an empty tensor has no address to hand over)
+            return y, idx, cnt
+        self._rc(self.lib.lk_maxred_fwd_f32(_ptr(x), outer, L, inner, _ptr(y), _ptr(idx), _ptr(cnt), self._stream(x.device)),
+                 "lk_maxred_fwd_f32")
+        return y, idx, cnt
+
+    def maxred_vjp(self, g, S, outer, L, inner, idx=None, x=None, y=None, cnt=None):
+        """``dx`` ``[S, outer, L, inner]`` of a maximum over ``L`` for the ``S`` seeds stacked in ``g`` ``[S, outer, inner]``, in ONE
+        launch of lk_maxred_vjp_f32 that writes every element: with ``idx`` alone the cotangent goes to the first maximum
+        (``max(dim)``, the adaptive max pools), with ``x``, ``y`` and ``cnt`` it is split evenly over the maxima (``amax``)"""
+        _check(g, "g")
+        S, outer, L, inner = int(S), int(outer), int(L), int(inner)
+        even = x is not None or y is not None or cnt is not None
+        if even:
+            if x is None or y is None or cnt is None:
+                raise LaplaceHipError("maxred_vjp: the even split needs x, y and cnt")
+            _check(x, "x"), _check(y, "y"), _check(cnt, "cnt", torch.int32)
+            idx = None
+        else:
+            if idx is None:
+                raise LaplaceHipError("maxred_vjp: give idx (first maximum) or x, y and cnt (even split)")
+            _check(idx, "idx", torch.int32)
+        if S < 1 or outer < 0 or L < 1 or inner < 1 or g.numel() != S * outer * inner:
+            raise LaplaceHipError(f"maxred_vjp: g {tuple(g.shape)} is no [{S}, {outer}, {inner}] cotangent")
+        for t, n, name in ((idx, outer * inner, "idx"), (y, outer * inner, "y"), (cnt, outer * inner, "cnt"), (x, outer * L * inner, "x")):
+            if t is not None and t.numel() != n:
+                raise LaplaceHipError(f"maxred_vjp: {name} has {t.numel()} elements, expected {n}")
+        dx = torch.empty(S, outer, L, inner, dtype=torch.float32, device=g.device)
+        if outer == 0:
+            return dx
+        self._rc(self.lib.lk_maxred_vjp_f32(_ptr(g), _ptr(idx), _ptr(x), _ptr(y), _ptr(cnt), S, outer, L, inner, _ptr(dx),
+                                            self._stream(g.device)), "lk_maxred_vjp_f32")
+        return dx
+
+    def reduce_variant(self, vjp, S, outer, L, inner, even=False, aligned=True):
+        """lk_reduce_variant: the path ``lk_maxred_fwd_f32`` (``vjp`` false) or ``lk_maxred_vjp_f32`` takes for a shape (host only,
+        no device call), or ``None`` for a shape they refuse."""
+        r = int(self.lib.lk_reduce_variant(int(bool(vjp)), int(S), int(outer), int(L), int(inner), int(bool(even)),
+                                           int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vjp": bool(vjp), "row": bool(r & 1), "vec": bool(r & 2), "even": bool(r & 4), "wide_index": bool(r & 8),
+                "lanes": 1 << ((r >> 4) & 7), "seed_split": bool(r & 128), "blocks": r >> 8}
 
     def mul_vjp(self, g, a, b, S, b_row, want=(True, True)):
         """``(da, db)`` of ``out = a * b`` for the ``S`` seeds stacked in the cotangent ``g`` (``S * a.numel()`` elements, seed-major)

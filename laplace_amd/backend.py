@@ -35,6 +35,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor, get_kernels, is_channels_last, keep_layout
 from laplace_amd.capture import EmbedTapForeign, NormTapReused, Tape, norm_servable
 from laplace_amd.sweep import SeedBatchedSweep, SweepUnsupported
@@ -54,11 +55,9 @@ def shared_operands(tap, g, B, C, Q1=None, Q2=None, bounds=None, planes: bool = 
     output gradient ``[C, B, Do]`` for the bias.  ``bounds``: a dict that receives the FORM the operands come back in —
     ``planes``: both are SplitTensors (lk_conv_nhwc_f16x2_planes: ``u [C * B, Do, L]`` seed-major with one scale, ``v [B, Dk, L]``
     with one scale per sample), ``u_seed_major``: fp32 with ``u [C, B, Do, L]``.  ``planes=False`` keeps both operands fp32."""
-    m = tap.module
+    m = cv.lift(tap.module)
     a = tap.a.to(torch.float32)
     if tap.kind == "conv2d":
-        from laplace_amd import conv as cv
-
         K = get_kernels()
         Do = m.out_channels
         Dk = m.weight[0].numel()
@@ -401,9 +400,11 @@ class _HipCurvatureMixin:
             f = f.unsqueeze(-1)
         if f.ndim != 2:
             raise NotImplementedError(f"model output must be [batch, outputs]; got {tuple(f.shape)}")
-        for t in taps:
-            t.a = sweep.taps[t.name]["a"]
+        for t in taps:  # (an nn.Conv1d tap: lifted to the unit-height Conv2d it is served as, here and in `grad_fn`)
+            t.a = cv.lift_maps(t.module, sweep.taps[t.name]["a"])[0]
             t.a_split = getattr(sweep, "tap_splits", {}).get(t.name)  # NHWC SplitTensor of the same activation, if any
+
+        lifted = {t.name: t.module for t in taps if isinstance(t.module, nn.Conv1d)}
 
         def grad_fn(seeds, stack=True, on_tap=None, defer_bn_scale=False, keep_split=False):
             """All seeds in one sweep while ``S*B`` stays below ``sweep_max_rows`` images; many-output models
@@ -411,6 +412,9 @@ class _HipCurvatureMixin:
             are handed over layer by layer (additive consumers such as the KFAC accumulator) and nothing is returned."""
             seeds = seeds.reshape(seeds.shape[0], seeds.shape[1], *sweep.out_shape)
             S, B = seeds.shape[0], seeds.shape[1]
+            if on_tap is not None and lifted:
+                user_tap = on_tap
+                on_tap = lambda name, g: user_tap(name, cv.lift_maps(lifted[name], g=g)[1] if name in lifted else g)
             # a few cotangents of the largest activation are alive at once: keep them inside the memory budget
             rows = min(int(self.sweep_max_rows), int(self.sweep_mem_bytes) // (16 * max(sweep.max_act_numel, 1)))
             chunk = max(1, rows // max(B, 1))
@@ -419,7 +423,7 @@ class _HipCurvatureMixin:
                     grads = sweep.backward(seeds, on_tap=on_tap, defer_bn_scale=defer_bn_scale, keep_split=True)
                 else:
                     grads = sweep.backward(seeds, on_tap=on_tap, defer_bn_scale=defer_bn_scale)
-                return [grads[t.name] for t in taps]
+                return [cv.lift_maps(t.module, g=grads[t.name])[1] for t in taps]
             parts = []
             for s0 in range(0, S, chunk):
                 grads = sweep.backward(seeds[s0:s0 + chunk].contiguous(), on_tap=on_tap, defer_bn_scale=defer_bn_scale)
@@ -431,7 +435,7 @@ class _HipCurvatureMixin:
                                   if isinstance(grads[t.name], (SplitTensor, NhwcNormGrad)) else grads[t.name] for t in taps])
             if on_tap is not None:
                 return None
-            return [torch.cat([p[i] for p in parts]) for i in range(len(taps))]
+            return [cv.lift_maps(t.module, g=torch.cat([p[i] for p in parts]))[1] for i, t in enumerate(taps)]
 
         grad_fn.streams_taps = True  # accepts on_tap: gradients are delivered layer by layer
         grad_fn.accepts_keep_split = True  # can hand conv-tap gradients back as NHWC SplitTensors
@@ -508,7 +512,7 @@ class _HipCurvatureMixin:
     @staticmethod
     def _positions(tap, a) -> int:
         if tap.kind == "conv2d":
-            m = tap.module
+            m = cv.lift(tap.module)
             H, W = a.shape[-2:]
             oh = (H + 2 * m.padding[0] - m.dilation[0] * (m.kernel_size[0] - 1) - 1) // m.stride[0] + 1
             ow = (W + 2 * m.padding[1] - m.dilation[1] * (m.kernel_size[1] - 1) - 1) // m.stride[1] + 1
@@ -516,7 +520,7 @@ class _HipCurvatureMixin:
         return int(a[0].numel() // a.shape[-1])
 
     def _factor_shapes(self, tap):
-        m = tap.module
+        m = cv.lift(tap.module)
         if tap.kind == "linear":
             return m.out_features, m.in_features
         return m.out_channels, m.in_channels * m.kernel_size[0] * m.kernel_size[1]
@@ -525,7 +529,7 @@ class _HipCurvatureMixin:
         """``A += alpha/(N L) * sum a a^T`` (input side; needs only the forward activations)."""
         K = get_kernels()
         a = tap.a.to(torch.float32)
-        m = tap.module
+        m = cv.lift(tap.module)
         L = self._positions(tap, a)
         if tap.kind == "linear":
             Di = m.in_features
@@ -566,7 +570,7 @@ class _HipCurvatureMixin:
     def _factor_G(self, tap, g, alpha_g, kfac_approx, G, fused=False, persist=None):
         """``G += alpha * sum g g^T`` (output side; ``g`` is ``[S, B, ...]`` or the unstacked per-seed list)."""
         K = get_kernels()
-        m = tap.module
+        m = cv.lift(tap.module)
         if isinstance(g, SplitTensor):  # NHWC split cotangent [S*B, H, W, Do] of the split-fp16 sweep
             Do = g.shape[-1]
             if kfac_approx == "expand" and (Do == 64 or Do % 128 == 0):
@@ -607,7 +611,7 @@ class _HipCurvatureMixin:
         """``(a, g, kernel_size, stride, padding, dilation)`` of a weight-sharing tap as a convolution: a Conv2d as it
         is; an ``nn.Linear`` applied along extra dims (``a [B, ..., Di]``, ``g [S, B, ..., Do]``) is the 1x1
         convolution over its ``T`` shared positions, whose ``[Do, Di, 1, 1]`` weight flattens like the Linear's."""
-        m = tap.module
+        m = cv.lift(tap.module)
         if tap.kind == "conv2d":
             return a.contiguous(), g.contiguous(), m.kernel_size, m.stride, m.padding, m.dilation
         B, S = a.shape[0], g.shape[0]
@@ -628,7 +632,7 @@ class _HipCurvatureMixin:
         self._norm_columns(tap, g, Js, tap.w_off, tap.b_off)
 
     def _jac_gconv(self, tap, g, Js):
-        m = tap.module
+        m = cv.lift(tap.module)
         get_kernels().jac_gconv(tap.a.to(torch.float32).contiguous(), g.contiguous(), m.kernel_size, m.stride, m.padding,
                                 m.dilation, m.groups, Js, tap.w_off, tap.b_off)
 
@@ -733,7 +737,7 @@ class _HipCurvatureMixin:
             Jl, n_w, n_b = self._norm_block(tap, g)
             yield 0, Jl, [(0, n_w, tap.w_off), (n_w, n_b, tap.b_off)]
         else:
-            m = tap.module
+            m = cv.lift(tap.module)
             S, B = g.shape[0], g.shape[1]
             width, n_b = m.weight.numel(), (m.out_channels if tap.has_bias else 0)
             step = max(1, min(int(self.gconv_block_bytes) // (4 * S * (width + n_b)), 65535 // S, B))
@@ -873,7 +877,7 @@ class _HipCurvatureMixin:
                              h[tap.w_off:tap.w_off + m.weight.numel()])
                 continue
             a = tap.a.to(torch.float32)
-            m = tap.module
+            m = cv.lift(tap.module)
             if tap.kind == "linear" and a.ndim == 2:
                 n_w = m.out_features * m.in_features
                 K.diag_ggn_linear(a.contiguous(), g.contiguous(), alpha, h[tap.w_off:tap.w_off + n_w],
@@ -1033,7 +1037,7 @@ class KronAccumulator:
         self.factors, self._taps_meta = [], []
         shapes = []
         for tap in tape.taps:
-            m = tap.module
+            m = cv.lift(tap.module)
             if tap.kind == "linear":
                 do, di = m.out_features, m.in_features
                 native = None
@@ -1083,7 +1087,7 @@ class KronAccumulator:
 
         Both pixel-pair forms are linear in the data: one small product per minibatch, the 81 patch blocks are
         assembled once per fit."""
-        m = tap.module
+        m = cv.lift(tap.module)
         if tap.kind != "conv2d" or self.kfac_approx != "expand" or not self.use_pixgram:
             return None
         if (tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation)) != ((3, 3), (1, 1), (1, 1), (1, 1)):
@@ -1911,6 +1915,13 @@ class HipGGN(_HipCurvatureMixin, GGNInterface):
 
     # KFAC — replaces CurvlinopsInterface.kron (laplace/curvature/curvlinops.py:77-108)
     def kron(self, x, y, N, **kwargs):
+        """``(loss, HipKron)`` of one minibatch, as ``CurvlinopsInterface.kron``.  Factors exist for tracked ``nn.Linear`` and dense
+        ``nn.Conv2d`` layers, and for a dense ``nn.Conv1d``, which is served AS the ``nn.Conv2d`` with a unit-height window that it
+        equals (``Conv1d(k, s, p, d)`` on ``[B, C, L]`` = ``Conv2d((1, k), (1, s), (0, p), (1, d))`` on ``[B, C, 1, L]``,
+        `laplace_amd.conv.lift`): the same function of the same parameter vector in the same order, so its factors are the
+        reference's Conv2d factors of that layer - what the oracle computes on the model's 2-D twin - and nothing is guessed.
+        Grouped convolutions of either rank are refused (`Tape.refuse_kfac`: the reference's rule for them is unknown), as is
+        every other tracked parameter."""
         twin, dt = self._twin()
         if twin is not None:
             return self._cast(twin.kron(self._to32(x), self._to32(y), N, **kwargs), dt)

@@ -17,7 +17,12 @@ from typing import Sequence
 import torch
 from torch import nn
 
-SUPPORTED = (nn.Linear, nn.Conv2d)
+from laplace_amd.conv import lift_maps
+
+SUPPORTED = (nn.Linear, nn.Conv2d, nn.Conv1d)
+#: convolution modules: an nn.Conv1d is served AS the unit-height nn.Conv2d it equals (`laplace_amd.conv.lift`): its taps carry the
+#: kinds of a Conv2d ('conv2d', 'gconv'), their ``a`` and output gradients arrive lifted to ``[B, C, 1, L]`` / ``[S, B, C, 1, L']``
+CONV = (nn.Conv2d, nn.Conv1d)
 #: affine normalisation layers: their weight / bias Jacobian is a per-channel reduction of ``g * xhat`` (csrc/lk_norm.hip)
 NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.LayerNorm, nn.GroupNorm, nn.RMSNorm)
 #: the tap kinds beyond Linear / dense Conv2d, in the order in which `Tape.active_taps` appends them (= the order of `grad_fn`'s
@@ -58,7 +63,7 @@ def norm_servable(m: nn.Module) -> bool:
     return True
 
 
-def _conv_checks(m: nn.Conv2d, name: str):
+def _conv_checks(m, name: str):
     if isinstance(m.padding, str):
         raise NotImplementedError(f"{name}: string padding ('{m.padding}') not supported")
     if m.padding_mode != "zeros":
@@ -81,7 +86,7 @@ class Tape:
         for name, mod in model.named_modules():
             if not isinstance(mod, SUPPORTED) or id(mod.weight) not in offsets:
                 continue
-            if isinstance(mod, nn.Conv2d):
+            if isinstance(mod, CONV):
                 _conv_checks(mod, name)
                 if mod.groups != 1:
                     continue  # (a tap list of its own, below)
@@ -99,7 +104,7 @@ class Tape:
         # Linear / dense Conv2d owns it" (what the KFAC accumulator, the Kron predictive and the batched grids refuse on).
         self.gconv_taps: list[Tap] = []
         for name, mod in model.named_modules():
-            if isinstance(mod, nn.Conv2d) and mod.groups != 1 and id(mod.weight) in offsets:
+            if isinstance(mod, CONV) and mod.groups != 1 and id(mod.weight) in offsets:
                 b_off = offsets[id(mod.bias)] if mod.bias is not None and id(mod.bias) in offsets else -1
                 self.gconv_taps.append(Tap(name, mod, "gconv", offsets[id(mod.weight)], b_off))
         # affine normalisation layers with a tracked weight and / or bias, in a list of their own: `taps` stays the list
@@ -183,7 +188,10 @@ class Tape:
 
     def refuse_kfac(self):
         """KFAC (the accumulator, ``kron``, the Kron predictive) has no rule for a grouped convolution: what the reference's
-        KFAC (curvlinops) does with ``groups > 1`` is not pinned by any golden here, so nothing is guessed"""
+        KFAC (curvlinops) does with ``groups > 1`` is not pinned by any golden here, so nothing is guessed.  A dense nn.Conv1d is
+        NOT refused and nothing is guessed for it either: it is served as the nn.Conv2d with a unit-height window that computes
+        the same function of the same parameter vector in the same order, and its factors are the reference's Conv2d factors of
+        that layer (the oracle computes them on the model's 2-D twin); a grouped Conv1d is refused like a grouped Conv2d"""
         if self.gconv_taps:
             t = self.gconv_taps[0]
             raise NotImplementedError(f"{t.name}: KFAC has no rule for a grouped convolution (groups={t.module.groups}); "
@@ -213,7 +221,7 @@ class Tape:
                 seen.add(id(m))
                 if tap.kind == "embed" and inp[0] is not x:
                     raise EmbedTapForeign(f"{tap.name}: the Embedding does not read the model's input")
-                tap.a = inp[0].detach()
+                tap.a = lift_maps(m, inp[0].detach())[0]
                 # the gradient EDGE of the output as it is now: models that go on to modify the tensor in place
                 # (torchvision's `out += identity; relu_(out)`) would otherwise hand back the gradient w.r.t. the
                 # mutated tensor — the reference's curvlinops hooks see the pre-mutation gradient as well
@@ -248,7 +256,8 @@ class Tape:
         S = seeds.shape[0]
         has_conv = any(t.kind in ("conv2d", "gconv") for t in taps)
         if S == 1:
-            return [g.unsqueeze(0).contiguous() for g in torch.autograd.grad(f, outs, grad_outputs=seeds[0])]
+            return [lift_maps(t.module, g=g.unsqueeze(0).contiguous())[1]
+                    for t, g in zip(taps, torch.autograd.grad(f, outs, grad_outputs=seeds[0]))]
         if not has_conv:
             try:
                 grads = torch.autograd.grad(f, outs, grad_outputs=seeds, is_grads_batched=True, retain_graph=True)
@@ -260,9 +269,9 @@ class Tape:
         for i, tap in enumerate(taps):
             gs = [ps[i].contiguous() for ps in per_seed]
             if tap.kind == "conv2d" and not stack:  # (dense convolutions only: a grouped one is always stacked)
-                result.append(gs)
+                result.append(lift_maps(tap.module, g=gs)[1])
             else:
-                result.append(torch.stack(gs))
+                result.append(lift_maps(tap.module, g=torch.stack(gs))[1])
         return result
 
     def release(self):

@@ -8,11 +8,53 @@ seeds at once through :func:`conv_backward_data`.
 from __future__ import annotations
 
 import functools
+import weakref
 
 import torch
 from torch import nn
 
 from laplace_amd._lib import SplitTensor, get_kernels
+
+
+_LIFTED: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # nn.Conv1d -> its unit-height nn.Conv2d (`lift`)
+
+
+def lift(m):
+    """The ``nn.Conv2d`` a convolution module IS: an ``nn.Conv2d`` itself; for ``nn.Conv1d(k, s, p, d)`` on ``[B, C, L]`` the
+    ``nn.Conv2d((1, k), (1, s), (0, p), (1, d))`` on ``[B, C, 1, L]`` (a unit height makes one output row whatever its stride).
+    The lifted layer's weight ``[Co, Ci, 1, k]`` is a VIEW of the real one - same storage, same ``_version``, flattening in the
+    same order - and its bias is the real parameter, so every reader of a convolution's geometry (``kernel_size``, ``stride``,
+    ``padding``, ``dilation`` as pairs, ``groups``, the 4-D weight) reads it here and every kernel that takes a Conv2d serves
+    the Conv1d.  Any other module comes back as it is.  Hooks stay on the real module, offsets come from its parameters."""
+    if not isinstance(m, nn.Conv1d):
+        return m
+    w, hit = m.weight, _LIFTED.get(m)
+    if (hit is None or hit.weight.data_ptr() != w.data_ptr() or hit.weight.dtype != w.dtype or hit.bias is not m.bias
+            or hit.weight.requires_grad != w.requires_grad or hit.weight.shape[-1] != w.shape[-1]):
+        if isinstance(m.padding, str) or m.padding_mode != "zeros":
+            raise NotImplementedError(f"Conv1d with padding {m.padding!r} / padding_mode {m.padding_mode!r} has no unit-height view")
+        hit = nn.Conv2d(m.in_channels, m.out_channels, (1, m.kernel_size[0]), (1, m.stride[0]), (0, m.padding[0]),
+                        (1, m.dilation[0]), m.groups, bias=False, device="meta")
+        hit.weight = nn.Parameter(w.detach().unsqueeze(2), requires_grad=w.requires_grad)
+        hit.bias = m.bias
+        hit.lifted_from_1d = True  # (`_geometry_ok`: the own implicit-GEMM kernels are not offered a lifted layer)
+        _LIFTED[m] = hit
+    hit.training = m.training
+    return hit
+
+
+def lift_maps(m, a=None, g=None):
+    """``(a, g)`` of a tap of the module ``m`` as its :func:`lift` reads them - views, no copies.  For an ``nn.Conv1d``: the input
+    ``a [B, Ci, L] -> [B, Ci, 1, L]`` and the output cotangent ``g [S, B, Co, L'] -> [S, B, Co, 1, L']`` (or the list of the
+    per-seed ``[B, Co, L']`` tensors, each lifted); for every other module both come back as they are."""
+    if isinstance(m, nn.Conv1d):
+        if torch.is_tensor(a) and a.dim() == 3:
+            a = a.unsqueeze(2)
+        if isinstance(g, (list, tuple)):
+            g = [t.unsqueeze(2) if t.dim() == 3 else t for t in g]
+        elif torch.is_tensor(g) and g.dim() == 4:
+            g = g.unsqueeze(3)
+    return a, g
 
 
 def supported(m: nn.Conv2d) -> bool:
@@ -22,8 +64,9 @@ def supported(m: nn.Conv2d) -> bool:
 
 
 def _geometry_ok(m) -> bool:
-    return (isinstance(m, nn.Conv2d) and m.groups == 1 and tuple(m.dilation) == (1, 1) and not isinstance(m.padding, str)
-            and m.padding_mode == "zeros" and m.kernel_size[0] * m.kernel_size[1] <= 9 and m.stride[0] == m.stride[1])
+    # (a lifted nn.Conv1d stays on the library routes: its unit-height window on the implicit-GEMM kernels is a feature of its own)
+    return (isinstance(m, nn.Conv2d) and not getattr(m, "lifted_from_1d", False) and m.groups == 1
+            and tuple(m.dilation) == (1, 1) and not isinstance(m.padding, str) and m.padding_mode == "zeros" and m.kernel_size[0] * m.kernel_size[1] <= 9 and m.stride[0] == m.stride[1])
 
 
 def forward_supported(m: nn.Conv2d) -> bool:

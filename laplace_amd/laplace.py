@@ -23,6 +23,7 @@ from torch.nn.utils import parameters_to_vector, vector_to_parameters
 
 from laplace_amd import predictive as _pred
 from laplace_amd.backend import HipGGN
+from laplace_amd.conv import lift
 from laplace_amd.kron import HipKron
 
 
@@ -168,7 +169,8 @@ def expected_exchange_bytes(model_or_shapes) -> int:
         for m in model_or_shapes.modules():
             if isinstance(m, nn.Linear) and m.weight.requires_grad:
                 sizes += [m.out_features, m.in_features]
-            elif isinstance(m, nn.Conv2d) and m.weight.requires_grad:
+            elif isinstance(m, (nn.Conv2d, nn.Conv1d)) and m.weight.requires_grad:
+                m = lift(m)
                 sizes += [m.out_channels, m.in_channels * m.kernel_size[0] * m.kernel_size[1]]
     else:
         sizes = list(model_or_shapes)

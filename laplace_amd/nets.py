@@ -757,3 +757,93 @@ class ViTLlama(nn.Module):
         for blk in self.blocks:
             x = blk(x)
         return self.head(self.norm(x).mean(1))
+
+
+# ---- 1-D convolutional networks (``dims=2``: the unit-height 2-D twin, the same function of the same state dict with the conv
+# weights unsqueezed at dim 2; it exists so that an oracle that knows nn.Conv2d only can be run on the model) ----------------------
+def _conv_nd(dims: int, cin: int, cout: int, k: int, stride: int = 1, padding: int = 0, dilation: int = 1, groups: int = 1,
+             bias: bool = False) -> nn.Module:
+    if dims == 1:
+        return nn.Conv1d(cin, cout, k, stride, padding, dilation, groups, bias)
+    if dims == 2:
+        return nn.Conv2d(cin, cout, (1, k), (1, stride), (0, padding), (1, dilation), groups, bias)
+    raise ValueError(f"dims must be 1 or 2, got {dims!r}")
+
+
+class BasicBlock1d(nn.Module):
+    """The basic residual block on ``[B, C, L]`` maps: two ``k = 3`` convolutions (the first carries the stride and the dilation,
+    the second may be depthwise) with BatchNorm, a strided 1x1 shortcut where the shape changes."""
+
+    def __init__(self, cin: int, cout: int, stride: int, act=nn.ReLU, dims: int = 1, dilation: int = 1, depthwise: bool = False):
+        super().__init__()
+        bn = nn.BatchNorm1d if dims == 1 else nn.BatchNorm2d
+        self.conv1, self.bn1, self.act1 = _conv_nd(dims, cin, cout, 3, stride, dilation, dilation), bn(cout), act()
+        self.conv2, self.bn2 = _conv_nd(dims, cout, cout, 3, 1, 1, groups=cout if depthwise else 1), bn(cout)
+        self.act2 = act()
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(_conv_nd(dims, cin, cout, 1, stride), bn(cout))
+
+    def forward(self, x):
+        out = self.bn2(self.conv2(self.act1(self.bn1(self.conv1(x)))))
+        return self.act2(out + (x if self.downsample is None else self.downsample(x)))
+
+
+class ResNet1d(nn.Module):
+    """A 1-D ResNet-18 as used on ECG, audio and sensor data: stem ``Conv1d(k=7, s=2)``, BatchNorm1d, activation,
+    ``MaxPool1d(3, 2, 1)``; four stages of ``depth`` :class:`BasicBlock1d` each (``widths``; every stage after the first halves the
+    length); ``AdaptiveAvgPool1d(1)``, flatten, ``Linear``.  Input ``[B, in_channels, L]``.  ``freeze_norm``: the BatchNorm
+    affine parameters are not tracked, so that KFAC runs (the Conv1d layers are served as the unit-height Conv2d they equal,
+    `laplace_amd.conv.lift`).  ``dilation``: of the strided convolution that opens stages two to four; ``depthwise``: the second
+    convolution of every block is depthwise (``freeze_depthwise``: and not tracked - KFAC has no rule for grouped layers).
+    ``dims=2``: the unit-height twin on ``[B, in_channels, 1, L]``."""
+
+    def __init__(self, num_classes: int = 10, in_channels: int = 12, widths=(64, 128, 256, 512), depth: int = 2, act=nn.ReLU,
+                 freeze_norm: bool = True, dims: int = 1, dilation: int = 1, depthwise: bool = False, freeze_depthwise: bool = False):
+        super().__init__()
+        bn = nn.BatchNorm1d if dims == 1 else nn.BatchNorm2d
+        self.conv1, self.bn1, self.act1 = _conv_nd(dims, in_channels, widths[0], 7, 2, 3), bn(widths[0]), act()
+        self.maxpool = nn.MaxPool1d(3, 2, 1) if dims == 1 else nn.MaxPool2d((1, 3), (1, 2), (0, 1))
+        blocks, cin = [], widths[0]
+        for i, cout in enumerate(widths):
+            for j in range(depth):
+                first = i > 0 and j == 0
+                blocks.append(BasicBlock1d(cin, cout, 2 if first else 1, act, dims, dilation if first else 1, depthwise))
+                cin = cout
+        self.layers = nn.Sequential(*blocks)
+        self.pool = nn.AdaptiveAvgPool1d(1) if dims == 1 else nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+        for m in self.modules():
+            if freeze_norm and isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d)):
+                m.weight.requires_grad_(False), m.bias.requires_grad_(False)
+            if freeze_depthwise and isinstance(m, (nn.Conv1d, nn.Conv2d)) and m.groups != 1:
+                m.weight.requires_grad_(False)
+
+    def forward(self, x):
+        x = self.maxpool(self.act1(self.bn1(self.conv1(x))))
+        return self.fc(torch.flatten(self.pool(self.layers(x)), 1))
+
+
+class TextCNN(nn.Module):
+    """The text CNN with max-over-time pooling (Kim 2014): token ids ``[B, T]`` through an embedding, ``transpose(1, 2)`` to
+    ``[B, E, T]``, parallel ``Conv1d`` s of widths ``widths`` each followed by an activation and ``amax(2)`` (the maximum over the
+    positions: csrc/lk_reduce.hip in the reverse sweep), ``cat``, ``Linear``.  ``freeze_embed``: the embedding table is not tracked,
+    so that KFAC runs (a tracked one is served through ``use_embed_kernels``).  ``dims=2``: the unit-height twin."""
+
+    def __init__(self, num_classes: int = 4, vocab: int = 2000, embed_dim: int = 128, channels: int = 100, widths=(3, 4, 5),
+                 act=nn.ReLU, freeze_embed: bool = True, dims: int = 1):
+        super().__init__()
+        self.dims = dims
+        self.embed = nn.Embedding(vocab, embed_dim)
+        self.convs = nn.ModuleList(_conv_nd(dims, embed_dim, channels, k, bias=True) for k in widths)
+        self.acts = nn.ModuleList(act() for _ in widths)
+        self.fc = nn.Linear(channels * len(widths), num_classes)
+        if freeze_embed:
+            self.embed.weight.requires_grad_(False)
+
+    def forward(self, x):
+        e = self.embed(x).transpose(1, 2)
+        if self.dims == 2:
+            e = e.unsqueeze(2)
+        feats = [act(conv(e)).amax(2 if self.dims == 1 else (2, 3)) for conv, act in zip(self.convs, self.acts)]
+        return self.fc(torch.cat(feats, 1))

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import torch
 
+from laplace_amd import conv as cv
 from laplace_amd._lib import get_kernels
 from laplace_amd.backend import shared_operands as _shared_operands
 
@@ -64,7 +65,7 @@ def _as_nchw(g, B, C):
 def _conv_block_jacobian(tap, g, B, C):
     g = _as_nchw(g, B, C)
     K = get_kernels()
-    m = tap.module
+    m = cv.lift(tap.module)  # (an nn.Conv1d: the unit-height Conv2d it is served as; `tap.a` and `g` arrive lifted)
     width = m.weight.numel()
     nb = m.out_channels if tap.has_bias else 0
     Jl = torch.zeros(B, C, width + nb, dtype=torch.float32, device=g.device)

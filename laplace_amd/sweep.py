@@ -57,6 +57,10 @@ NEG, SUB = "negation", "difference"
 # NHWC walk never meets - `SplitSweep._split_eligible` sends such a model to the NCHW walk - so they are no part of the public kind list
 # that the two walks' tables are held against)
 _EMBED, _PARAM, _EXPAND = "embedding", "parameter", "batch-expansion"
+# _MAXRED: the maximum along one static non-batch dim or along adjacent ones (``amax``, ``max(dim)[0]``, ``AdaptiveMaxPool1d(1)``:
+# what 1-D convolutional networks end in; csrc/lk_reduce.hip); _SUMRED: ``sum`` along static non-batch dims (an ``expand``, as
+# MEAN's).  (Module-private names: the NHWC walk sends a model that holds one to the NCHW walk, `SplitSweep._split_eligible`)
+_MAXRED, _SUMRED = "max-reduction", "sum-reduction"
 
 
 class Rule(NamedTuple):
@@ -88,18 +92,24 @@ _GENERIC_ACT_FN = (F.gelu, F.silu, F.leaky_relu, F.elu, F.softplus, F.hardtanh, 
 
 # the three spellings of an operation -> (kind, activation flavour); adding an operation starts here
 _MODULE_KINDS = (
-    ((nn.Conv2d,), CONV, None), ((nn.Linear,), LINEAR, None), ((nn.BatchNorm2d, nn.BatchNorm1d), BN, None),
+    ((nn.Conv2d, nn.Conv1d), CONV, None), ((nn.Linear,), LINEAR, None), ((nn.BatchNorm2d, nn.BatchNorm1d), BN, None),
     # (normalisation with per-sample statistics; the functional spellings read their weights through `get_attr` and stay refused)
     ((nn.GroupNorm, nn.LayerNorm, nn.RMSNorm), NORM, None),
     ((nn.ReLU,), ACT, "relu"), ((nn.Tanh,), ACT, "tanh"), ((nn.Sigmoid,), ACT, "sigmoid"),
     (_GENERIC_ACT_MODULES, ACT, "generic"), ((nn.Identity, nn.Dropout), IDENTITY, None), ((nn.Flatten,), RESHAPE, None),
     ((nn.AdaptiveAvgPool2d,), GPOOL, None), ((nn.AvgPool2d,), AVGPOOL, None), ((nn.MaxPool2d,), MAXPOOL, None),
+    # (the 1-D pools are the unit-height window of the 2-D rules, lifted at the node: flavour "1d")
+    ((nn.AdaptiveAvgPool1d,), GPOOL, "1d"), ((nn.AvgPool1d,), AVGPOOL, "1d"), ((nn.MaxPool1d,), MAXPOOL, "1d"),
+    ((nn.AdaptiveMaxPool1d, nn.AdaptiveMaxPool2d), _MAXRED, None),
     ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None), ((nn.Embedding,), _EMBED, None))
 _FUNCTION_KINDS = {
     torch.relu: (ACT, "relu"), F.relu: (ACT, "relu"), torch.tanh: (ACT, "tanh"), F.tanh: (ACT, "tanh"),
     torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
     operator.add: (ADD, None), torch.add: (ADD, None), operator.iadd: (ADD, None), torch.flatten: (RESHAPE, None),
     F.adaptive_avg_pool2d: (GPOOL, None), F.avg_pool2d: (AVGPOOL, None), F.max_pool2d: (MAXPOOL, None),
+    F.adaptive_avg_pool1d: (GPOOL, "1d"), F.avg_pool1d: (AVGPOOL, "1d"), F.max_pool1d: (MAXPOOL, "1d"),
+    torch.amax: (_MAXRED, None), torch.max: (_MAXRED, None), F.adaptive_max_pool1d: (_MAXRED, None),
+    F.adaptive_max_pool2d: (_MAXRED, None), torch.sum: (_SUMRED, None),
     torch.mean: (MEAN, None), operator.getitem: (GETITEM, None), F.scaled_dot_product_attention: (ATTN, None),
     torch.transpose: (PERMUTE, None), torch.permute: (PERMUTE, None),
     torch.cat: (CAT, None), torch.concat: (CAT, None), torch.concatenate: (CAT, None),
@@ -114,6 +124,7 @@ _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
     "size": (SIZE, None), "transpose": (PERMUTE, None), "permute": (PERMUTE, None),
+    "amax": (_MAXRED, None), "max": (_MAXRED, None), "sum": (_SUMRED, None),
     "chunk": (SPLIT, None), "split": (SPLIT, None), "narrow": (SLICE, None), "expand": (CONST, None), "expand_as": (CONST, None),
     "mul": (MUL, None), "multiply": (MUL, None), "mul_": (MUL, None),
     "matmul": (MATMUL, None), "bmm": (MATMUL, None), "softmax": (SOFTMAX, None), "log_softmax": (SOFTMAX, None),
@@ -131,6 +142,14 @@ _POOL_PARAMS = {  # names and defaults of the functional form; the modules carry
     MAXPOOL: (("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices"), (None, None, 0, 1, False, False)),
     AVGPOOL: (("kernel_size", "stride", "padding", "ceil_mode", "count_include_pad", "divisor_override"),
               (None, None, 0, False, True, None))}
+
+
+def _unit_height(name, v):
+    """a 1-D pool's parameter as that of the 2-D pool with a unit-height window that it equals on ``[B, C, 1, L]``"""
+    if name not in ("kernel_size", "stride", "padding", "dilation") or v is None or (isinstance(v, (tuple, list)) and not v):
+        return v
+    v = v[0] if isinstance(v, (tuple, list)) else v
+    return (0 if name == "padding" else 1, v)
 
 
 def _bind(node, names, defaults):
@@ -526,12 +545,137 @@ def _classify_sub(node, modules):
     return tuple(node.args)
 
 
+def _same(t):
+    """the forward of a node that hands its source on (the ``[0]`` / ``.values`` of a ``max(dim)``, whose node holds the values)"""
+    return t
+
+
+_ADAPTIVE_MAX = {nn.AdaptiveMaxPool1d: 1, nn.AdaptiveMaxPool2d: 2, F.adaptive_max_pool1d: 1, F.adaptive_max_pool2d: 2}
+# relatives of the reduction rules that have none: refused by name
+_NO_REDUCE_RULE = {torch.min: "min", torch.amin: "amin", torch.logsumexp: "logsumexp", torch.topk: "topk", "min": "min", "amin": "amin",
+                   "logsumexp": "logsumexp", "topk": "topk", F.adaptive_max_pool1d_with_indices: "adaptive_max_pool1d(return_indices=True)",
+                   F.adaptive_max_pool2d_with_indices: "adaptive_max_pool2d(return_indices=True)",
+                   F.max_pool1d_with_indices: "max_pool1d(return_indices=True)"}
+
+
+def _classify_reduce(node, m, kind):
+    """``(src, (name, dims as written, keepdim, tie, is_tuple))`` of a maximum or a sum over static non-batch dims - ``amax``,
+    ``max(dim)``, ``sum(dim)`` (functions and methods), the adaptive max pools to ONE cell - or the refusal that names the
+    operation.  ``tie``: ``"first"`` (``max(dim)`` and the pools send the cotangent to the first maximum, as autograd does),
+    ``"even"`` (``amax`` splits it evenly over the maxima), ``None`` for a sum; ``is_tuple``: the node is the (values, indices)
+    pair of a ``max(dim)``, whose ``[0]`` / ``.values`` hands the values on.  The dims are resolved on the value (`reduce_geometry`)."""
+    key = type(m) if m is not None else node.target
+    if key in _ADAPTIVE_MAX:
+        nd = _ADAPTIVE_MAX[key]
+        name = f"adaptive_max_pool{nd}d"
+        if m is not None:
+            size, ret = m.output_size, m.return_indices
+        else:
+            kwargs = dict(node.kwargs)
+            kwargs.pop("input", None)
+            size = node.args[1] if len(node.args) > 1 else kwargs.pop("output_size", None)
+            ret = node.args[2] if len(node.args) > 2 else kwargs.pop("return_indices", False)
+            if kwargs or len(node.args) > 3:
+                raise SweepUnsupported(f"{name}: unknown argument {sorted(kwargs) or node.args[3:]}")
+        if isinstance(ret, fx.Node) or ret:
+            raise SweepUnsupported(f"{name}(return_indices=True): the indices of a maximum have no cotangent and no rule")
+        cells = tuple(size) if isinstance(size, (tuple, list)) else (size,) * nd
+        if any(isinstance(c, fx.Node) for c in cells):
+            raise SweepUnsupported(f"{name} with a data-dependent output size")
+        if len(cells) != nd or any(c != 1 for c in cells):
+            raise SweepUnsupported(f"{name} to {size} cells (only the maximum over all positions, output size 1, is served)")
+        x = node.args[0] if node.args else node.kwargs.get("input")
+        if not isinstance(x, fx.Node):
+            raise SweepUnsupported(f"{name}: the input must be a traced tensor")
+        return (x,), (name, tuple(range(-nd, 0)), True, "first", False)
+    name = str(getattr(node.target, "__name__", node.target))
+    kwargs = dict(node.kwargs)
+    x = node.args[0] if node.args else kwargs.pop("input", None)
+    kwargs.pop("input", None)
+    if not isinstance(x, fx.Node):
+        raise SweepUnsupported(f"{name}: the tensor must be a traced tensor")
+    if kwargs.pop("out", None) is not None:
+        raise SweepUnsupported(f"{name} with an out= argument (the sweep keeps its own values)")
+    if kwargs.pop("dtype", None) is not None:
+        raise SweepUnsupported(f"{name} with dtype= (the sweep keeps the dtype of the traced value)")
+    rest = list(node.args[1:])
+    if name == "max" and ((rest and isinstance(rest[0], fx.Node)) or isinstance(kwargs.get("other"), fx.Node)):
+        raise SweepUnsupported("max(x, other): the element-wise maximum of two tensors has no rule (only max over a dim is served)")
+    dim = rest.pop(0) if rest else kwargs.pop("dim", kwargs.pop("axis", None))
+    keepdim = rest.pop(0) if rest else kwargs.pop("keepdim", False)
+    if name == "sum" and rest:  # (the method's third positional argument)
+        raise SweepUnsupported("sum with dtype= (the sweep keeps the dtype of the traced value)")
+    if rest or kwargs:
+        raise SweepUnsupported(f"{name}: unknown argument {sorted(kwargs) or rest}")
+    if dim is None or (isinstance(dim, (tuple, list)) and not dim):
+        raise SweepUnsupported(f"{name}() without a dim reduces the batch dim too (name the dims: dim 0 must stay)")
+    if isinstance(keepdim, fx.Node) or not isinstance(keepdim, bool):
+        raise SweepUnsupported(f"{name} with a data-dependent keepdim")
+    dims = tuple(dim) if isinstance(dim, (tuple, list)) else (dim,)
+    if name == "max" and isinstance(dim, (tuple, list)):
+        raise SweepUnsupported("max over a tuple of dims (max takes one dim; amax takes several)")
+    dims = tuple(_static_int(d, name, "dim") for d in dims)
+    if 0 in dims:
+        raise SweepUnsupported(f"{name} over {_BATCH_SLICE}")
+    tie = None if kind == _SUMRED else "first" if name == "max" else "even"
+    return (x,), (name, dims, keepdim, tie, name == "max")
+
+
+def reduce_geometry(dims, shape, what="reduction"):
+    """``(dims, outer, L, inner)`` of a _MAXRED / _SUMRED rule resolved on a value of ``shape``: the sorted non-batch dims (a
+    maximum: adjacent ones) and the view ``[outer][L][inner]`` of the contiguous value in which they are one dim"""
+    ndim = len(shape)
+    for d in dims:
+        if not -ndim <= d < ndim:
+            raise SweepUnsupported(f"{what} along dim {d} of a value with {ndim} dims")
+    res = sorted({d % ndim for d in dims})
+    if len(res) != len(dims):
+        raise SweepUnsupported(f"{what}: dim listed twice in {tuple(dims)}")
+    if res[0] == 0:
+        raise SweepUnsupported(f"{what} over {_BATCH_SLICE}")
+    outer = L = inner = 1
+    for i, d in enumerate(shape):
+        if i < res[0]:
+            outer *= int(d)
+        elif i <= res[-1]:
+            L *= int(d)
+        else:
+            inner *= int(d)
+    return res, outer, L, inner
+
+
+def reduce_forward_math(x3):
+    """``(y, idx, cnt)`` of csrc/lk_reduce.hip's forward in plain torch (any dtype): ``x3`` is ``[outer, L, inner]``; the maximum
+    over ``L``, the FIRST position that holds it and how many positions compare equal to it (int32; ``0.0 == -0.0``)"""
+    L = x3.shape[1]
+    y = x3.amax(1)
+    eq = x3 == y.unsqueeze(1)
+    pos = torch.arange(L, device=x3.device, dtype=torch.int32).reshape(1, L, 1)
+    idx = torch.where(eq, pos, torch.full_like(pos, L)).amin(1)
+    return y, idx, eq.sum(1, dtype=torch.int32)
+
+
+def reduce_vjp_math(g, L, idx=None, x=None, y=None, cnt=None):
+    """``dx`` ``[S, outer, L, inner]`` for the ``S`` seeds in ``g`` ``[S, outer, inner]`` - the formulas of lk_maxred_vjp_f32 in plain
+    torch (any dtype): with ``idx`` the cotangent goes to the first maximum, ``(l == idx) ? g : 0``; with ``x``, ``y``, ``cnt`` it is
+    split evenly over the maxima, ``(x == y) ? g / cnt : 0``"""
+    if x is not None:
+        hit, q = x == y.unsqueeze(1), g / cnt.to(g.dtype)
+    else:
+        pos = torch.arange(L, device=g.device, dtype=idx.dtype).reshape(1, L, 1)
+        hit, q = pos == idx.unsqueeze(1), g
+    return torch.where(hit.unsqueeze(0), q.unsqueeze(2), q.new_zeros(()))
+
+
 def _no_slice_rule(target):
     """what a refusal adds for a relative of the slicing rules (``unbind``, ``tensor_split``, ``stack``) or of the matrix product
     (``einsum``, ``baddbmm``)"""
     name = _NO_MATMUL_RULE.get(target)
     if name is not None:
         return f" ({name} is out of scope: matmul, @ and bmm are what the sweep serves)"
+    name = _NO_REDUCE_RULE.get(target)
+    if name is not None:
+        return f" ({name} is out of scope: amax, max(dim)[0], sum(dim) and the adaptive max pools to one cell are what the sweep serves)"
     name = _NO_SLICE_RULE.get(target)
     if name is None:
         return ""
@@ -575,9 +719,17 @@ def classify(node: fx.Node, modules: dict) -> Rule:
         if hit is None:
             raise SweepUnsupported(f"no VJP rule for module {what} ({node.target})")
         # (grouped convolutions: forward is the module itself, backward-data `_conv_input_grad`, which passes `groups`)
-        if isinstance(m, nn.Conv2d) and (isinstance(m.padding, str) or m.padding_mode != "zeros"):
+        # (nn.Conv1d: the same rule - the module runs the forward, `_conv_input_grad` passes geometry tuples of any length)
+        if isinstance(m, (nn.Conv2d, nn.Conv1d)) and (isinstance(m.padding, str) or m.padding_mode != "zeros"):
             raise SweepUnsupported(f"{node.target}: unsupported convolution variant")
     elif node.op == "call_function":
+        if node.target in (operator.getitem, getattr) and args and isinstance(args[0], fx.Node):
+            up = classify(args[0], modules)
+            if up.kind == _MAXRED and up.args[4]:  # (an item of the pair a `max(dim)` returns: the node itself holds the values)
+                if len(args) > 1 and not isinstance(args[1], (fx.Node, bool)) and args[1] in (0, "values"):
+                    return Rule(IDENTITY, (args[0],), _same, ((args[0],), {}), f"values of {up.what}")
+                raise SweepUnsupported(f"{up.what}: its indices ({args[1] if len(args) > 1 else None!r}) have no cotangent and no rule "
+                                       "(take the values with [0] or .values)")
         fn, hit, what = node.target, _FUNCTION_KINDS.get(node.target), getattr(node.target, "__name__", node.target)
         if hit is None:
             raise SweepUnsupported(f"no VJP rule for function {what}" + _no_slice_rule(node.target))
@@ -624,18 +776,27 @@ def classify(node: fx.Node, modules: dict) -> Rule:
         kwargs.pop("inplace", None)  # (the derivative is taken by autograd on a leaf)
     elif kind in _POOL_PARAMS:
         names, defaults = _POOL_PARAMS[kind]
-        p = {n: getattr(m, n) for n in names} if m is not None else _bind(node, names, defaults)
+        # (nn.AvgPool1d has no divisor_override: the default)
+        p = {n: getattr(m, n, d) for n, d in zip(names, defaults)} if m is not None else _bind(node, names, defaults)
         if p.pop("return_indices", False):
-            raise SweepUnsupported("max_pool2d(return_indices=True)")
+            raise SweepUnsupported("max_pool1d(return_indices=True)" if flavour == "1d" else "max_pool2d(return_indices=True)")
+        if flavour == "1d":  # (the unit-height window: the node lifts its input to [B, C, 1, L], `_run_pool`)
+            p = {n: _unit_height(n, v) for n, v in p.items()}
         if kind == MAXPOOL:  # always evaluated with indices: they are what its VJP scatters by
             fn, args, kwargs = F.max_pool2d, (args[0], *p.values(), True), {}
         else:
             static = tuple(p.values())
+            if flavour == "1d":  # (one spelling of the lifted window)
+                fn, args, kwargs = F.avg_pool2d, (args[0], *static), {}
     elif kind == GPOOL:
         static = (m.output_size if m is not None else kwargs.get("output_size", args[1] if len(args) > 1 else None),)
     elif kind == MEAN:
         static = (kwargs.get("dim", args[1] if len(args) > 1 else None),
                   kwargs.get("keepdim", args[2] if len(args) > 2 else False))
+    elif kind in (_MAXRED, _SUMRED):
+        src, static = _classify_reduce(node, m, kind)
+        what = static[0] if m is None else f"{what} ({node.target})"
+        fn, args, kwargs, m = None, src, {}, None  # (evaluated by `SeedBatchedSweep._run_reduce`)
     elif kind == ATTN:
         src, static = _classify_attn(node)
     elif kind == PERMUTE:
@@ -934,6 +1095,8 @@ class SeedBatchedSweep:
         for node, r in self.rule.items():  # (a tuple of parts has no cotangent: only its items do)
             if r.kind == SPLIT and any(self.rule[u].kind != SLICE for u in node.users):
                 raise SweepUnsupported(f"{r.what}: its parts must be taken one by one with a static integer index")
+            if r.kind == _MAXRED and r.args[4] and any(self.rule[u].fn is not _same for u in node.users):
+                raise SweepUnsupported(f"{r.what}(dim) returns (values, indices): take the values with [0] or .values")
         self.out_node = next(reversed(self.rule)).args[0]
         if not isinstance(self.out_node, fx.Node):
             raise SweepUnsupported("model must return a single tensor")
@@ -1045,6 +1208,9 @@ class SeedBatchedSweep:
             elif kind in (MAXPOOL, AVGPOOL):
                 out, keep = self._run_pool(node, r, args, kwargs)
                 keep = keep if need_vjp else None
+            elif kind in (_MAXRED, _SUMRED):
+                out, keep = self._run_reduce(r, inp)
+                keep = keep if need_vjp else None
             elif kind == ATTN:
                 out, keep = self._run_attn(r, *(env[n] for n in r.src))
                 keep = keep if need_vjp else None
@@ -1132,10 +1298,16 @@ class SeedBatchedSweep:
     def _run_pool(self, node, r, args, kwargs):
         """max / average pooling forward -> ``(out, keep)``: a max pool is evaluated with indices (`classify`), which are what
         its VJP scatters by; the average's VJP needs the input's shape only"""
+        if r.flavour == "1d":  # (lifted at the node: [B, C, L] -> [B, C, 1, L] in, the height squeezed out; the VJP lifts back)
+            if not torch.is_tensor(args[0]) or args[0].dim() != 3:
+                raise SweepUnsupported(f"{r.what}: a 1-D pool on a value that is not [B, C, L]")
+            args = (args[0].unsqueeze(2), *args[1:])
         if r.kind == MAXPOOL:
             out, idx = r.fn(*args)
-            return out, (idx, args[0].shape)
-        return r.fn(*args, **kwargs), args[0].shape
+            keep = (idx, args[0].shape)
+        else:
+            out, keep = r.fn(*args, **kwargs), args[0].shape
+        return (out.squeeze(2) if r.flavour == "1d" else out), keep
 
     def _run_cat(self, node, r, tensors, dim):
         """concatenation forward along the resolved ``dim`` (the VJP needs the sources' sizes along it only)"""
@@ -1499,6 +1671,53 @@ class SeedBatchedSweep:
             return K.softmax_vjp(g.contiguous(), y.contiguous(), S, is_log)
         return softmax_vjp_math(g, y, S, dim, is_log, self.attn_mem_bytes)
 
+    #: ``False``: a maximum over positions stays on the torch math of its rule (`reduce_forward_math`, `reduce_vjp_math`) whatever
+    #: the kernel object offers
+    use_reduce_kernels = True
+
+    def _reduce_kernels(self, t, S, outer, L, inner):
+        """the kernel object when csrc/lk_reduce.hip serves a maximum over ``L`` of ``t`` read as ``[outer, L, inner]`` (an object
+        with the entry points - the stock emulation has none -, fp32, a shape inside the contract), else ``None``: the same
+        formulas in torch"""
+        K = self.kernels() if self.kernels is not None and self.use_reduce_kernels else None
+        if K is None or not hasattr(K, "maxred_forward") or t.dtype != torch.float32 or outer == 0:
+            return None
+        return K if K.reduce_variant(True, S, outer, L, inner) is not None else None
+
+    def _run_reduce(self, r, inp):
+        """maximum / sum over static non-batch dims, forward -> ``(out, keep)``.  A maximum keeps what belongs to the sample, not to
+        the seed: the first position of the maximum (``tie`` "first") or the input, the maximum and the number of positions that
+        hold it ("even"); a sum keeps the shape only."""
+        name, dims, keepdim, tie, _ = r.args
+        if not torch.is_tensor(inp):
+            raise SweepUnsupported(f"{r.what}: the input is not a tensor")
+        dims, outer, L, inner = reduce_geometry(dims, inp.shape, r.what)
+        if tie is None:
+            return inp.sum(dims, keepdim=keepdim), (inp.shape, keepdim, dims)
+        if dims != list(range(dims[0], dims[-1] + 1)):
+            raise SweepUnsupported(f"{r.what} over the non-adjacent dims {tuple(dims)} (reduce one run of adjacent dims at a time)")
+        if L == 0:
+            raise SweepUnsupported(f"{r.what} over an empty dim")
+        x3 = inp.contiguous().reshape(outer, L, inner)
+        K = self._reduce_kernels(x3, 1, outer, L, inner)
+        y, idx, cnt = K.maxred_forward(x3, outer, L, inner) if K is not None else reduce_forward_math(x3)
+        shape = [1 if i in dims else int(d) for i, d in enumerate(inp.shape)] if keepdim else \
+            [int(d) for i, d in enumerate(inp.shape) if i not in dims]
+        return y.reshape(shape), (inp.shape, L, idx if tie == "first" else None, *((x3, y, cnt) if tie == "even" else (None,) * 3))
+
+    def _reduce_vjp(self, saved, g, S):
+        """input cotangent of a maximum over positions for all seeds, ``g`` ``[S*B, ...]``: ONE launch of lk_maxred_vjp_f32, which
+        writes every element (no zero fill, no scatter), or the same formula in torch (`reduce_vjp_math`)"""
+        shp, L, idx, x3, y, cnt = saved
+        outer, inner = (idx if idx is not None else y).shape
+        gv = g.contiguous().reshape(S, outer, inner)
+        K = self._reduce_kernels(gv, S, outer, L, inner) if (idx is not None or x3.dtype == torch.float32) else None
+        if K is not None:
+            dx = K.maxred_vjp(gv, S, outer, L, inner, idx=idx, x=x3, y=y, cnt=cnt)
+        else:
+            dx = reduce_vjp_math(gv, L, idx, x3, y, cnt)
+        return dx.reshape(S * shp[0], *shp[1:])
+
     def _add_const(self, r, args, kwargs):
         """``x + constant``: the constant must broadcast to exactly the other operand's shape (the other way round the VJP is
         a reduction, which has no rule)"""
@@ -1571,7 +1790,7 @@ class SeedBatchedSweep:
         key = (m.weight._version, m.weight.data_ptr(), id(scale))
         hit = self._w_cache.get(name)
         if hit is None or hit[0] != key:
-            hit = (key, (m.weight.detach() * scale.reshape(-1, 1, 1, 1)).contiguous(), scale)
+            hit = (key, (m.weight.detach() * scale.reshape(-1, *([1] * (m.weight.dim() - 1)))).contiguous(), scale)
             self._w_cache[name] = hit
         return hit[1]
 
@@ -1702,7 +1921,7 @@ class SeedBatchedSweep:
             RESHAPE: "_vjp_reshape", GPOOL: "_vjp_gpool", AVGPOOL: "_vjp_avgpool", MAXPOOL: "_vjp_maxpool", MEAN: "_vjp_mean",
             ATTN: "_vjp_attn", PERMUTE: "_vjp_permute", ADD: "_vjp_add", MUL: "_vjp_mul", MATMUL: "_vjp_matmul",
             SOFTMAX: "_vjp_softmax", SCALE: "_vjp_scale", NEG: "_vjp_neg", SUB: "_vjp_sub", CAT: "_vjp_cat", SLICE: "_vjp_slice",
-            _EXPAND: "_vjp_identity", _EMBED: "_vjp_leaf", _PARAM: "_vjp_leaf",
+            _EXPAND: "_vjp_identity", _EMBED: "_vjp_leaf", _PARAM: "_vjp_leaf", _MAXRED: "_vjp_maxred", _SUMRED: "_vjp_sumred",
             SIZE: None, GETITEM: None, SPLIT: None, CONST: None, "placeholder": None, "output": None}
 
     def _vjp_rule(self, r):
@@ -1747,15 +1966,35 @@ class SeedBatchedSweep:
         g = g.reshape((walk.S * walk.B,) + tuple(self.saved[node][1:]))
         walk.push(r.src[0], as_map(g) if as_map is not None and g.dim() == 4 else g)
 
+    # (a 1-D pool, flavour "1d": the cotangent is lifted to the unit-height map at the node and the height squeezed out again)
     def _vjp_gpool(self, walk, node, r, g, g2):
-        walk.push(r.src[0], self._adaptive_avgpool_vjp(g, self.saved[node], walk.S * walk.B))
+        shp = self.saved[node]
+        if r.flavour == "1d":
+            d = self._adaptive_avgpool_vjp(g.unsqueeze(2), (shp[0], shp[1], 1, shp[2]), walk.S * walk.B).squeeze(2)
+        else:
+            d = self._adaptive_avgpool_vjp(g, shp, walk.S * walk.B)
+        walk.push(r.src[0], d)
 
     def _vjp_avgpool(self, walk, node, r, g, g2):
-        walk.push(r.src[0], self._avgpool_vjp(g, self.saved[node], walk.S * walk.B, *r.args))
+        lift = r.flavour == "1d"  # (the forward kept the lifted shape)
+        d = self._avgpool_vjp(g.unsqueeze(2) if lift else g, self.saved[node], walk.S * walk.B, *r.args)
+        walk.push(r.src[0], d.squeeze(2) if lift else d)
 
     def _vjp_maxpool(self, walk, node, r, g, g2):
         idx, shp = self.saved[node]
-        walk.push(r.src[0], self._maxpool_vjp(g, idx, shp, walk.S, walk.B))
+        lift = r.flavour == "1d"
+        d = self._maxpool_vjp(g.unsqueeze(2) if lift else g, idx, shp, walk.S, walk.B)
+        walk.push(r.src[0], d.squeeze(2) if lift else d)
+
+    def _vjp_maxred(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._reduce_vjp(self.saved[node], g, walk.S))
+
+    def _vjp_sumred(self, walk, node, r, g, g2):
+        shp, keep, dims = self.saved[node]
+        if not keep:
+            for d in dims:
+                g = g.unsqueeze(d)
+        walk.push(r.src[0], g.expand(walk.S * walk.B, *shp[1:]))
 
     def _vjp_mean(self, walk, node, r, g, g2):
         walk.push(r.src[0], self._mean_vjp(g, self.saved[node], walk.S * walk.B))
