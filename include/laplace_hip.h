@@ -550,6 +550,26 @@ int lk_attn_vjp_f32(const float* go, const float* q, const float* k, const float
                     float* dv, void* ws, size_t ws_bytes, void* stream);
 int lk_attn_variant(int64_t S, int64_t B, int64_t H, int64_t T, int64_t D, int layout, int causal);
 
+/* The same attention with STRIDED operands, for a packed projection (nn.MultiheadAttention's in_proj, a fused qkv Linear): the
+ * operands are read where the projection left them and the cotangent is written where the projection's VJP reads it, so
+ * neither the three slice copies nor the concatenation of dq, dk, dv exist.
+ *   q, k, v: [B][T][H][D] with a row stride of ldq floats; for one [B][T][3 H D] projection q = qkv, k = qkv + H D,
+ *     v = qkv + 2 H D, ldq = 3 H D.
+ *   dq, dk, dv: [S][B][T][H][D] with a row stride of ldd floats; the three may interleave in one [S][B][T][3 H D] buffer.
+ *     Every element of all three is written (no zero fill needed); what lies between the rows is not touched.
+ *   o, go: layout 1 ([B][T][H][D], go with a leading [S]); lse [B][H][T].
+ * The same kernels and the same arithmetic in the same order as layout 1: with ldq = ldd = H D the results are bit-equal to
+ * lk_attn_fwd_f32 / lk_attn_vjp_f32 with layout = 1.  One owner per element, no atomics, two equal calls are bit-equal.  The
+ * workspace is that of lk_attn_vjp_workspace_bytes, the path what lk_attn_variant(S, B, H, T, D, 1, causal) names.
+ * Contract: that of the layout-1 entry points, and: ldq >= H D, ldd >= H D, both multiples of 4; B T ldq < 2^40,
+ * S B T ldd < 2^40; no output overlaps an input (extents from the first to the last element); dq, dk, dv may interleave but
+ * share no element.  The forward has no ldd. */
+int lk_attn_fwd_strided_f32(const float* q, const float* k, const float* v, int64_t ldq, int64_t B, int64_t H, int64_t T, int64_t D,
+                            float scale, int causal, float* o, float* lse, void* stream);
+int lk_attn_vjp_strided_f32(const float* go, const float* q, const float* k, const float* v, int64_t ldq, const float* o,
+                            const float* lse, int64_t S, int64_t B, int64_t H, int64_t T, int64_t D, float scale, int causal,
+                            float* dq, float* dk, float* dv, int64_t ldd, void* ws, size_t ws_bytes, void* stream);
+
 /* Max and average pooling (nn.MaxPool2d / nn.AvgPool2d, ceil_mode false, no dilation) on fp32 NHWC feature maps for the NHWC
  * reverse sweep; they replace, there, max_pool2d(return_indices=True) / avg_pool2d and the seed-expanded scatter_add_ of the
  * NCHW sweep (the reverse passes of laplace/curvature/curvlinops.py:87-100 and curvature.py:88-129 through a pooling layer).

@@ -129,6 +129,9 @@ SIGNATURES = {
     "lk_attn_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp, _vp,
                                _sz, _vp]),
     "lk_attn_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
+    "lk_attn_fwd_strided_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp, _vp, _vp]),
+    "lk_attn_vjp_strided_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp, _vp, _vp,
+                                       _i64, _vp, _sz, _vp]),
     "lk_pool_fwd_nhwc_f32": (_int, [_int, _vp, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_vjp_nhwc_f32": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _i64] + [_int] * 8 + [_vp, _vp, _vp]),
     "lk_pool_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64] + [_int] * 7),
@@ -1542,6 +1545,57 @@ class HipKernels:
                                           float(scale), int(bool(causal)), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), ws.numel(),
                                           self._stream(go.device)), "lk_attn_vjp_f32")
         return dq, dk, dv
+
+    @staticmethod
+    def _attn_strided(what, shape, *named):
+        """the common row stride (in floats) of ``[N, T, H, D]`` fp32 device views whose rows of ``H D`` floats are contiguous and
+        ``ld`` apart - the slices of a packed ``[N, T, 3 H D]`` projection, or contiguous tensors (``ld = H D``)"""
+        N, T, H, D = shape
+        lds = set()
+        for t, name in named:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+                raise LaplaceHipError(f"{what}: {name} must be a fp32 tensor {tuple(shape)} on a ROCm device (no CPU path)")
+            sn, st, sh, sd = t.stride()
+            if (D > 1 and sd != 1) or (H > 1 and sh != D) or (N > 1 and T > 0 and sn != T * st):
+                raise LaplaceHipError(f"{what}: {name} must be a [N, T, H, D] view with contiguous rows of H * D floats and "
+                                      f"a batch stride of T rows (strides {t.stride()})")
+            lds.add(int(st) if T > 1 or N > 1 else H * D)
+        if len(lds) != 1:
+            raise LaplaceHipError(f"{what}: {', '.join(n for _, n in named)} must share one row stride (got {sorted(lds)})")
+        return lds.pop()
+
+    def attn_forward_strided(self, q, k, v, scale, causal):
+        """``(o, lse)`` of lk_attn_fwd_strided_f32 on ``q``, ``k``, ``v`` ``[B, T, H, D]``: views with one row stride, such as
+        ``qkv.view(B, T, 3, H, D).unbind(2)`` of a packed projection - read where they lie, no copy.  ``o``: ``[B, T, H, D]``
+        contiguous (``o.view(B, T, H * D)`` feeds the output projection), ``lse``: ``[B, H, T]``."""
+        B, T, H, D = q.shape
+        ldq = self._attn_strided("attn_forward_strided", q.shape, (q, "q"), (k, "k"), (v, "v"))
+        o = torch.empty(B, T, H, D, dtype=torch.float32, device=q.device)
+        lse = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+        self._rc(self.lib.lk_attn_fwd_strided_f32(_ptr(q), _ptr(k), _ptr(v), ldq, B, H, T, D, float(scale), int(bool(causal)),
+                                                  _ptr(o), _ptr(lse), self._stream(q.device)), "lk_attn_fwd_strided_f32")
+        return o, lse
+
+    def attn_vjp_strided(self, go, q, k, v, o, lse, S, scale, causal, dq, dk, dv):
+        """lk_attn_vjp_strided_f32: writes the cotangents of all ``S`` seeds into the caller's ``dq``, ``dk``, ``dv``
+        ``[S*B, T, H, D]`` - views with one row stride, such as ``dqkv.view(S * B, T, 3, H, D).unbind(2)`` of the ``[S*B, T, 3 H D]``
+        buffer that the packed projection's VJP reads (every element of the three is written).  ``go`` ``[S*B, T, H, D]`` and ``o``
+        ``[B, T, H, D]`` contiguous, ``q``, ``k``, ``v`` as `attn_forward_strided` takes them, ``lse`` ``[B, H, T]``."""
+        B, T, H, D = q.shape
+        S = int(S)
+        what = "attn_vjp_strided"
+        ldq = self._attn_strided(what, q.shape, (q, "q"), (k, "k"), (v, "v"))
+        ldd = self._attn_strided(what, (S * B, T, H, D), (dq, "dq"), (dk, "dk"), (dv, "dv"))
+        _check(lse, "lse")
+        if self._attn_strided(what, q.shape, (o, "o")) != H * D or self._attn_strided(what, (S * B, T, H, D), (go, "go")) != H * D:
+            raise LaplaceHipError(f"{what}: go and o must be contiguous")
+        if lse.numel() != B * H * T:
+            raise LaplaceHipError(f"{what}: lse must be [B, H, T]")
+        nbytes = int(self.lib.lk_attn_vjp_workspace_bytes(S, B, H, T, D))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=go.device)
+        self._rc(self.lib.lk_attn_vjp_strided_f32(_ptr(go), _ptr(q), _ptr(k), _ptr(v), ldq, _ptr(o), _ptr(lse), S, B, H, T, D,
+                                                  float(scale), int(bool(causal)), _ptr(dq), _ptr(dk), _ptr(dv), ldd, _ptr(ws),
+                                                  ws.numel(), self._stream(go.device)), "lk_attn_vjp_strided_f32")
 
     def attn_variant(self, S, B, H, T, D, layout=0, causal=False):
         """lk_attn_variant: the path ``lk_attn_vjp_f32`` takes for a shape (host only, no device call), or ``None`` for a

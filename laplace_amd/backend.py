@@ -37,7 +37,7 @@ from torch import nn
 
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor, get_kernels, is_channels_last, keep_layout
-from laplace_amd.capture import EmbedTapForeign, NormTapReused, Tape, norm_servable
+from laplace_amd.capture import EmbedTapForeign, MhaTapRefused, NormTapReused, Tape, norm_servable
 from laplace_amd.sweep import SeedBatchedSweep, SweepUnsupported
 from laplace_amd.sweep_nhwc import NhwcNormGrad, SplitSweep
 from laplace_amd.kron import HipKron
@@ -208,7 +208,7 @@ class _HipCurvatureMixin:
                     a.copy_(b)  # (casts)
             cur[0] = sig
         twin = cur[1]
-        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "use_attn_kernels", "nhwc_norm_taps", "use_gconv_kernels",
+        for k in ("use_sweep", "use_split_sweep", "use_norm_kernels", "use_attn_kernels", "use_strided_attn", "nhwc_norm_taps", "use_gconv_kernels",
                   "gconv_block_bytes", "use_embed_kernels",
                   "generator"):
             if k in self.__dict__:
@@ -283,6 +283,10 @@ class _HipCurvatureMixin:
         except EmbedTapForeign:
             tape.disabled.add("embed")  # (an embedding of something else than the input: its weight stays unserved)
             return self._forward(x, keep_tap_splits, extra=True)
+        except MhaTapRefused as e:
+            # (a masked / cross-attention call of an nn.MultiheadAttention: its parameters are `uncovered` from here on)
+            tape.drop_mha(e.name, str(e))
+            return self._forward(x, keep_tap_splits, extra)
         self._check_dtype(f)
         if f.ndim == 1:
             f = f.unsqueeze(-1)
@@ -297,6 +301,10 @@ class _HipCurvatureMixin:
     #: ``False``: an ``F.scaled_dot_product_attention`` node of the reverse sweep stays on the torch math of its rule
     #: (`sweep.attn_forward_math`, `sweep.attn_vjp_math`) instead of csrc/lk_attn.hip.  Read at every forward
     use_attn_kernels = True
+    #: ``False``: an nn.MultiheadAttention node of the reverse sweep makes contiguous copies of the three slices of its packed
+    #: projection and concatenates the three cotangents around the layout-1 entry points of csrc/lk_attn.hip, instead of handing
+    #: the strided entry points the packed buffers themselves.  Read at every forward
+    use_strided_attn = True
     #: ``True``: a model with tracked eval-mode BatchNorm2d / feature-map GroupNorm parameters stays on the NHWC split-fp16 sweep
     #: (`SplitSweep.nhwc_norm_taps`, csrc/lk_normtap.hip); ``False`` (the default): it runs through the NCHW sweep.  Read when the
     #: sweep is built
@@ -385,6 +393,7 @@ class _HipCurvatureMixin:
             return None
         try:
             sweep.use_attn_kernels = bool(self.use_attn_kernels)
+            sweep.use_strided_attn = bool(self.use_strided_attn)
             sweep.attn_mem_bytes = max(int(self.sweep_mem_bytes) // 4, 1)
             if isinstance(sweep, SplitSweep):
                 sweep.act_sink = getattr(self, "_act_sink", None)

@@ -17,6 +17,7 @@ from typing import Sequence
 import torch
 from torch import nn
 
+from laplace_amd import mha
 from laplace_amd.conv import lift_maps
 
 SUPPORTED = (nn.Linear, nn.Conv2d, nn.Conv1d)
@@ -40,10 +41,23 @@ class Tap:
     a: torch.Tensor | None = None  # module input (detached)
     a_split: object | None = None  # the same input as an NHWC SplitTensor, when the forward pass produced one
     out: object | None = None  # gradient edge of the module output in the autograd graph
+    # the nn.MultiheadAttention a 'linear' tap is one half of (`laplace_amd.mha.lift`: ``module`` is that half's nn.Linear view,
+    # which holds the real parameters and never runs itself); ``None`` for every other tap
+    owner: nn.Module | None = None
 
     @property
     def has_bias(self) -> bool:
         return self.b_off >= 0
+
+
+class MhaTapRefused(NotImplementedError):
+    """a tapped nn.MultiheadAttention was called in a way that is not served as Linear, attention, Linear (a mask,
+    cross-attention, ...: `laplace_amd.mha.refusal`); ``name``: the module.  The caller drops its taps (`Tape.drop_mha`): the
+    module's parameters are ``uncovered`` from then on"""
+
+    def __init__(self, name, why):
+        super().__init__(f"{name}: {why}")
+        self.name = name
 
 
 class NormTapReused(NotImplementedError):
@@ -76,6 +90,7 @@ class Tape:
 
     def __init__(self, model: nn.Module, params: Sequence[nn.Parameter]):
         self.model = model
+        self._params = list(params)
         offsets, off = {}, 0
         for p in params:
             offsets[id(p)] = off
@@ -83,8 +98,28 @@ class Tape:
         self.n_params = off
         self.taps: list[Tap] = []
         covered = set()
+        # nn.MultiheadAttention: served as the two nn.Linear layers around its attention core (`laplace_amd.mha.lift`), both
+        # 'linear' taps at the module's place in this order.  Its real ``out_proj`` is an nn.Linear that never runs (the
+        # module's forward reads the raw weights): never tapped itself.  What `mha.refusal` names stays in `uncovered`
+        self.mha_refused: dict[str, str] = {}
+        never_run = {id(m.out_proj) for m in model.modules() if isinstance(m, nn.MultiheadAttention)}
         for name, mod in model.named_modules():
-            if not isinstance(mod, SUPPORTED) or id(mod.weight) not in offsets:
+            if isinstance(mod, nn.MultiheadAttention):
+                why = mha.refusal(mod)
+                if why is not None:
+                    self.mha_refused[name] = f"{name}: {why}"
+                    continue
+                for half, lin in zip(("in_proj", "out_proj"), mha.lift(mod)):
+                    if id(lin.weight) not in offsets or id(lin.weight) in covered:
+                        continue
+                    b_off = -1
+                    if lin.bias is not None and id(lin.bias) in offsets:
+                        b_off = offsets[id(lin.bias)]
+                        covered.add(id(lin.bias))
+                    covered.add(id(lin.weight))
+                    self.taps.append(Tap(f"{name}.{half}", lin, "linear", offsets[id(lin.weight)], b_off, owner=mod))
+                continue
+            if not isinstance(mod, SUPPORTED) or id(mod.weight) not in offsets or id(mod) in never_run:
                 continue
             if isinstance(mod, CONV):
                 _conv_checks(mod, name)
@@ -212,7 +247,11 @@ class Tape:
         sweep alone serves them."""
         handles, seen = [], set()
         self._active = self.active_taps(route - {"param"})
+        for owner in {id(t.owner): t.owner for t in self._active if t.owner is not None}.values():
+            handles.append(owner.register_forward_hook(self._mha_hook(owner, seen), with_kwargs=True))
         for tap in self._active:
+            if tap.owner is not None:
+                continue
             def hook(m, inp, out, tap=tap):
                 if id(m) in seen:
                     if tap.kind == "norm":
@@ -237,6 +276,45 @@ class Tape:
             if tap.out is None:
                 raise RuntimeError(f"{tap.name}: module did not run in the forward pass")
         return f
+
+    def _mha_hook(self, owner, seen):
+        """the forward hook of a tapped nn.MultiheadAttention: evaluates what the module equals - ``F.linear``, scaled dot-product
+        attention, ``F.linear`` on the module's own parameters (`laplace_amd.mha.decomposed`) - from the module's input and
+        returns that value as the module's output, so that the inputs and the gradient edges of both halves exist"""
+        halves = {t.name.rsplit(".", 1)[1]: t for t in self._active if t.owner is owner}
+        name = next(iter(halves.values())).name.rsplit(".", 1)[0]
+
+        def hook(m, args, kwargs, out):
+            if id(m) in seen:
+                raise NotImplementedError(f"{name}: module is applied more than once per forward")
+            seen.add(id(m))
+            why = mha.refusal(m, (args, kwargs))
+            if why is not None:
+                raise MhaTapRefused(name, why)
+            y, qkv, ctx = mha.decomposed(m, args[0] if args else kwargs["query"])
+            for half, a, t in (("in_proj", args[0] if args else kwargs["query"], qkv), ("out_proj", ctx, y)):
+                if half in halves:
+                    halves[half].a = a.detach()
+                    halves[half].out = torch.autograd.graph.get_gradient_edge(t) if t.requires_grad else t
+            weights = out[1]
+            if weights is not None and weights.requires_grad:  # (the taps see the path through the output only)
+                def consumed(_):
+                    raise NotImplementedError(f"{name}: nn.MultiheadAttention whose attention weights are consumed is not served "
+                                              "(call it with need_weights=False, or freeze the module)")
+                weights.register_hook(consumed)
+            return y, weights
+
+        return hook
+
+    def drop_mha(self, name: str, why: str):
+        """stop serving the nn.MultiheadAttention ``name`` (a call of it was refused): its taps leave `taps`, its parameters are
+        `uncovered` from here on, and the sweeps built for the old tap list are forgotten"""
+        gone = [t for t in self.taps if t.owner is not None and t.name.rsplit(".", 1)[0] == name]
+        self.taps = [t for t in self.taps if t not in gone]
+        back = {id(p) for t in gone for p in (t.module.weight, t.module.bias) if p is not None}
+        self.uncovered = [p for p in self._params if id(p) in back or any(p is q for q in self.uncovered)]
+        self.mha_refused[name] = why
+        self.sweeps = {}
 
     def output_grads(self, f: torch.Tensor, seeds: torch.Tensor, stack: bool = True):
         """``seeds[s]`` is a cotangent of ``f``; returns, per tap, the gradients w.r.t. the module output

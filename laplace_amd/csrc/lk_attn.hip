@@ -25,6 +25,7 @@
 // delta is accumulated in the order of the DOT chain (d = 16 c + 4 g + e over c, e, g), so that with T == 1, where O == V and
 // P == 1, dP - delta is exactly 0.
 // Minimal traffic of a VJP call: 4 S B H T D (2 reads of gO + 3 writes) + 8 S B H T (delta) + the per-sample operands.
+#include "lk_attn_strided.h"
 #include "lk_stream.h"
 
 #include <math.h>
@@ -38,8 +39,13 @@ constexpr int ATTN_RESIDENT_MAX_T = 256;  // largest T whose [64][T] probability
 constexpr int ATTN_MAX_D = 128;
 
 struct AttnGeo {
-  int64_t row, head, batch, seed;  // strides in floats
+  int64_t row, head, batch, seed;  // strides in floats (of o and go)
   int B, H, T, D;
+};
+// the strides of another group of tensors of the same [S][B][H][T][D] extents: GI the operands q, k, v (no seed), GD the cotangents
+// dq, dk, dv.  Both equal the AttnGeo's own in layouts 0 and 1; the strided entry points set the row and batch strides
+struct AttnStride {
+  int64_t row, head, batch, seed;
 };
 
 template <int NC>
@@ -130,25 +136,25 @@ __device__ __forceinline__ float attn_colsum(float v) {
 // blockIdx.x = ((b * H + h) * nblk + block of 64 query rows)
 template <int NC>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                       const float* __restrict__ v, AttnGeo G, int nblk, float scale, int causal,
-                                                       float* __restrict__ o, float* __restrict__ lse) {
+                                                       const float* __restrict__ v, AttnGeo G, AttnStride GI, int nblk, float scale,
+                                                       int causal, float* __restrict__ o, float* __restrict__ lse) {
   constexpr int LD = AttnTile<NC>::LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *xk = smem, *xv = smem + ATTN_BN * LD;
   const int bh = blockIdx.x / nblk, blk = blockIdx.x - bh * nblk, b = bh / G.H, h = bh - b * G.H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   const int T = G.T, D = G.D, q0 = blk * ATTN_BM, myrow = q0 + 16 * wave + n;
-  const int64_t base = (int64_t)b * G.batch + (int64_t)h * G.head;
+  const int64_t base = (int64_t)b * G.batch + (int64_t)h * G.head, ibase = (int64_t)b * GI.batch + (int64_t)h * GI.head;
   f32x4 qf[NC], acc[NC];
-  attn_load_frag<NC>(myrow < T ? q + base + (int64_t)myrow * G.row : nullptr, D, g, qf);
+  attn_load_frag<NC>(myrow < T ? q + ibase + (int64_t)myrow * GI.row : nullptr, D, g, qf);
 #pragma unroll
   for (int c = 0; c < NC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
   const int kend = causal ? min(T, q0 + ATTN_BM) : T;
   for (int k0 = 0; k0 < kend; k0 += ATTN_BN) {
     __syncthreads();
-    attn_stage<NC>(xk, k + base, G.row, k0, T, D);
-    attn_stage<NC>(xv, v + base, G.row, k0, T, D);
+    attn_stage<NC>(xk, k + ibase, GI.row, k0, T, D);
+    attn_stage<NC>(xv, v + ibase, GI.row, k0, T, D);
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < ATTN_BN / ATTN_TILE; ++sub) {
@@ -194,18 +200,19 @@ template <int NC, bool RESIDENT>
 __global__ __launch_bounds__(256) void attn_vjp_q_kernel(const float* __restrict__ go, const float* __restrict__ q,
                                                          const float* __restrict__ k, const float* __restrict__ v,
                                                          const float* __restrict__ o, const float* __restrict__ lse, AttnGeo G,
-                                                         int S, int nblk, int s_per, float scale, int causal,
-                                                         float* __restrict__ dq, float* __restrict__ delta) {
+                                                         AttnStride GI, AttnStride GD, int S, int nblk, int s_per, float scale,
+                                                         int causal, float* __restrict__ dq, float* __restrict__ delta) {
   constexpr int LD = AttnTile<NC>::LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *xk = smem, *xv = smem + ATTN_BN * LD, *pres = smem + 2 * ATTN_BN * LD + threadIdx.x;  // pres[(tile * 4 + t) * 256]
   const int bh = blockIdx.x / nblk, blk = blockIdx.x - bh * nblk, b = bh / G.H, h = bh - b * G.H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   const int T = G.T, D = G.D, q0 = blk * ATTN_BM, myrow = q0 + 16 * wave + n;
-  const int64_t base = (int64_t)b * G.batch + (int64_t)h * G.head;
+  const int64_t base = (int64_t)b * G.batch + (int64_t)h * G.head, ibase = (int64_t)b * GI.batch + (int64_t)h * GI.head;
+  const int64_t dbase = (int64_t)b * GD.batch + (int64_t)h * GD.head + (int64_t)myrow * GD.row;
   const bool live = myrow < T;
   f32x4 qf[NC];
-  attn_load_frag<NC>(live ? q + base + (int64_t)myrow * G.row : nullptr, D, g, qf);
+  attn_load_frag<NC>(live ? q + ibase + (int64_t)myrow * GI.row : nullptr, D, g, qf);
   const float lse_i = live ? lse[(int64_t)bh * T + myrow] : 0.f;
   const int kend = causal ? min(T, q0 + ATTN_BM) : T;
   const int last_key = q0 + 16 * wave + 15;  // (causal: no key above it is visible to this wave)
@@ -224,7 +231,7 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(const float* __restrict
   if constexpr (RESIDENT) {
     for (int k0 = 0; k0 < kend; k0 += ATTN_BN) {
       __syncthreads();
-      attn_stage<NC>(xk, k + base, G.row, k0, T, D);
+      attn_stage<NC>(xk, k + ibase, GI.row, k0, T, D);
       __syncthreads();
 #pragma unroll
       for (int sub = 0; sub < ATTN_BN / ATTN_TILE; ++sub) {
@@ -248,8 +255,8 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(const float* __restrict
     for (int c = 0; c < NC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < kend; k0 += ATTN_BN) {
       __syncthreads();
-      attn_stage<NC>(xk, k + base, G.row, k0, T, D);
-      attn_stage<NC>(xv, v + base, G.row, k0, T, D);
+      attn_stage<NC>(xk, k + ibase, GI.row, k0, T, D);
+      attn_stage<NC>(xv, v + ibase, GI.row, k0, T, D);
       __syncthreads();
 #pragma unroll
       for (int sub = 0; sub < ATTN_BN / ATTN_TILE; ++sub) {
@@ -269,7 +276,7 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(const float* __restrict
         attn_acc<NC>(xk + sub * 16 * LD, ds, acc, n, g);
       }
     }
-    if (live) attn_store_frag<NC>(dq + sbase, D, g, acc, scale);
+    if (live) attn_store_frag<NC>(dq + (int64_t)s * GD.seed + dbase, D, g, acc, scale);
   }
 }
 
@@ -278,19 +285,21 @@ template <int NC, bool RESIDENT>
 __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(const float* __restrict__ go, const float* __restrict__ q,
                                                           const float* __restrict__ k, const float* __restrict__ v,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
-                                                          AttnGeo G, int S, int nblk, int s_per, float scale, int causal,
-                                                          float* __restrict__ dk, float* __restrict__ dv) {
+                                                          AttnGeo G, AttnStride GI, AttnStride GD, int S, int nblk, int s_per,
+                                                          float scale, int causal, float* __restrict__ dk,
+                                                          float* __restrict__ dv) {
   constexpr int LD = AttnTile<NC>::LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *xq = smem, *xg = smem + ATTN_BN * LD, *pres = smem + 2 * ATTN_BN * LD + threadIdx.x;
   const int bh = blockIdx.x / nblk, blk = blockIdx.x - bh * nblk, b = bh / G.H, h = bh - b * G.H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   const int T = G.T, D = G.D, k0blk = blk * ATTN_BM, myrow = k0blk + 16 * wave + n;
-  const int64_t base = (int64_t)b * G.batch + (int64_t)h * G.head;
+  const int64_t base = (int64_t)b * G.batch + (int64_t)h * G.head, ibase = (int64_t)b * GI.batch + (int64_t)h * GI.head;
+  const int64_t dbase = (int64_t)b * GD.batch + (int64_t)h * GD.head + (int64_t)myrow * GD.row;
   const bool live = myrow < T;
   f32x4 kf[NC], vf[NC];
-  attn_load_frag<NC>(live ? k + base + (int64_t)myrow * G.row : nullptr, D, g, kf);
-  attn_load_frag<NC>(live ? v + base + (int64_t)myrow * G.row : nullptr, D, g, vf);
+  attn_load_frag<NC>(live ? k + ibase + (int64_t)myrow * GI.row : nullptr, D, g, kf);
+  attn_load_frag<NC>(live ? v + ibase + (int64_t)myrow * GI.row : nullptr, D, g, vf);
   const int qstart = causal ? (k0blk / ATTN_BN) * ATTN_BN : 0;  // (causal: no query below the block's first key sees it)
   const int first_key = k0blk + 16 * wave;
   const float* lse_bh = lse + (int64_t)bh * T;
@@ -309,7 +318,7 @@ __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(const float* __restric
   if constexpr (RESIDENT) {
     for (int i0 = qstart; i0 < T; i0 += ATTN_BN) {
       __syncthreads();
-      attn_stage<NC>(xq, q + base, G.row, i0, T, D);
+      attn_stage<NC>(xq, q + ibase, GI.row, i0, T, D);
       __syncthreads();
 #pragma unroll
       for (int sub = 0; sub < ATTN_BN / ATTN_TILE; ++sub) {
@@ -330,7 +339,7 @@ __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(const float* __restric
     for (int c = 0; c < NC; ++c) acck[c] = accv[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int i0 = qstart; i0 < T; i0 += ATTN_BN) {
       __syncthreads();
-      attn_stage<NC>(xq, q + base, G.row, i0, T, D);
+      attn_stage<NC>(xq, q + ibase, GI.row, i0, T, D);
       attn_stage<NC>(xg, go + sbase, G.row, i0, T, D);
       __syncthreads();
 #pragma unroll
@@ -356,8 +365,8 @@ __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(const float* __restric
       }
     }
     if (live) {
-      attn_store_frag<NC>(dk + sbase + (int64_t)myrow * G.row, D, g, acck, scale);
-      attn_store_frag<NC>(dv + sbase + (int64_t)myrow * G.row, D, g, accv, 1.f);
+      attn_store_frag<NC>(dk + (int64_t)s * GD.seed + dbase, D, g, acck, scale);
+      attn_store_frag<NC>(dv + (int64_t)s * GD.seed + dbase, D, g, accv, 1.f);
     }
   }
 }
@@ -371,6 +380,7 @@ struct AttnPlan {
   int64_t blocks;  // grid.x
   size_t lds_fwd, lds_vjp;
   AttnGeo geo;
+  AttnStride in, out;  // (the strides of q, k, v and of dq, dk, dv: the geo's own unless a strided entry point sets them)
 };
 
 // the part of the contract the entry points and the variant query share, with the messages under the caller's name
@@ -397,6 +407,7 @@ static int attn_check_shape(const char* fn, int64_t S, int64_t B, int64_t H, int
   g.head = layout == 0 ? T * D : D;
   g.batch = H * T * D;
   g.seed = B * H * T * D;
+  p->in = p->out = AttnStride{g.row, g.head, g.batch, g.seed};
   return LK_OK;
 }
 
@@ -436,8 +447,8 @@ static void attn_allow_lds(Kern kern, size_t bytes) {  // (every launch: the att
 template <int NC>
 static void attn_launch_fwd(const AttnPlan& p, const float* q, const float* k, const float* v, float scale, int causal, float* o,
                             float* lse, hipStream_t st) {
-  hipLaunchKernelGGL((attn_fwd_kernel<NC>), dim3((unsigned)p.blocks), dim3(256), p.lds_fwd, st, q, k, v, p.geo, (int)p.nblk, scale,
-                     causal, o, lse);
+  hipLaunchKernelGGL((attn_fwd_kernel<NC>), dim3((unsigned)p.blocks), dim3(256), p.lds_fwd, st, q, k, v, p.geo, p.in, (int)p.nblk,
+                     scale, causal, o, lse);
 }
 
 template <int NC, bool RES>
@@ -446,11 +457,11 @@ static void attn_launch_vjp(const AttnPlan& p, const float* go, const float* q, 
                             hipStream_t st) {
   const dim3 grid((unsigned)p.blocks, (unsigned)((S + p.s_per - 1) / p.s_per));
   attn_allow_lds(attn_vjp_q_kernel<NC, RES>, p.lds_vjp);
-  hipLaunchKernelGGL((attn_vjp_q_kernel<NC, RES>), grid, dim3(256), p.lds_vjp, st, go, q, k, v, o, lse, p.geo, S, (int)p.nblk,
-                     p.s_per, scale, causal, dq, delta);
+  hipLaunchKernelGGL((attn_vjp_q_kernel<NC, RES>), grid, dim3(256), p.lds_vjp, st, go, q, k, v, o, lse, p.geo, p.in, p.out, S,
+                     (int)p.nblk, p.s_per, scale, causal, dq, delta);
   attn_allow_lds(attn_vjp_kv_kernel<NC, RES>, p.lds_vjp);
-  hipLaunchKernelGGL((attn_vjp_kv_kernel<NC, RES>), grid, dim3(256), p.lds_vjp, st, go, q, k, v, lse, delta, p.geo, S, (int)p.nblk,
-                     p.s_per, scale, causal, dk, dv);
+  hipLaunchKernelGGL((attn_vjp_kv_kernel<NC, RES>), grid, dim3(256), p.lds_vjp, st, go, q, k, v, lse, delta, p.geo, p.in, p.out, S,
+                     (int)p.nblk, p.s_per, scale, causal, dk, dv);
 }
 
 }  // namespace lk
@@ -510,6 +521,70 @@ extern "C" int lk_attn_vjp_f32(const float* go, const float* q, const float* k, 
   rc = attn_check_workspace(fn, need, ws_bytes);
   if (rc != LK_OK) return rc;
   if (B == 0) return LK_OK;
+  hipStream_t st = (hipStream_t)stream;
+#define LK_ATTN_VJP(N)                                                                                                    \
+  if (p.resident) attn_launch_vjp<N, true>(p, go, q, k, v, o, lse, (int)S, scale, causal != 0, dq, dk, dv, (float*)ws, st); \
+  else attn_launch_vjp<N, false>(p, go, q, k, v, o, lse, (int)S, scale, causal != 0, dq, dk, dv, (float*)ws, st)
+  LK_ATTN_BY_NC(LK_ATTN_VJP)
+#undef LK_ATTN_VJP
+  return check_launch("attn_vjp_kernel");
+}
+
+// The strided entry points: layout 1 with a row stride of ldq floats for q, k, v (the slices of a packed projection where it left
+// them) and of ldd floats for dq, dk, dv (one buffer that the projection's VJP reads); o, go and lse as in layout 1.  The same
+// kernels on the same plan: with ldq = ldd = H D bit-equal to the layout-1 entry points (csrc/lk_attn_strided.h: their contract)
+extern "C" int lk_attn_fwd_strided_f32(const float* q, const float* k, const float* v, int64_t ldq, int64_t B, int64_t H, int64_t T,
+                                       int64_t D, float scale, int causal, float* o, float* lse, void* stream) {
+  const char* fn = "lk_attn_fwd_strided_f32";
+  AttnPlan p;
+  int rc = attn_check_shape(fn, 1, B, H, T, D, 1, &p);
+  if (rc != LK_OK) return rc;
+  rc = attn_check_strides(fn, 1, B, H, T, D, ldq, ldq);
+  if (rc != LK_OK) return rc;
+  const size_t n1 = (size_t)B * H * T * D * sizeof(float), nl = (size_t)B * H * T * sizeof(float);
+  const size_t ni = attn_strided_bytes(B * T, ldq, H * D);
+  const void* in[3] = {q, k, v};
+  const size_t in_bytes[3] = {ni, ni, ni};
+  const void* out[2] = {o, lse};
+  const size_t out_bytes[2] = {n1, nl};
+  rc = attn_check(fn, in, in_bytes, 3, out, out_bytes, 2, scale);
+  if (rc != LK_OK) return rc;
+  if (B == 0) return LK_OK;
+  p.in.row = ldq, p.in.batch = T * ldq;
+  hipStream_t st = (hipStream_t)stream;
+#define LK_ATTN_FWD(N) attn_launch_fwd<N>(p, q, k, v, scale, causal != 0, o, lse, st)
+  LK_ATTN_BY_NC(LK_ATTN_FWD)
+#undef LK_ATTN_FWD
+  return check_launch("attn_fwd_kernel");
+}
+
+extern "C" int lk_attn_vjp_strided_f32(const float* go, const float* q, const float* k, const float* v, int64_t ldq, const float* o,
+                                       const float* lse, int64_t S, int64_t B, int64_t H, int64_t T, int64_t D, float scale,
+                                       int causal, float* dq, float* dk, float* dv, int64_t ldd, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  const char* fn = "lk_attn_vjp_strided_f32";
+  AttnPlan p;
+  int rc = attn_check_shape(fn, S, B, H, T, D, 1, &p);
+  if (rc != LK_OK) return rc;
+  rc = attn_check_strides(fn, S, B, H, T, D, ldq, ldd);
+  if (rc != LK_OK) return rc;
+  const size_t n1 = (size_t)B * H * T * D * sizeof(float), nS = (size_t)S * n1, nl = (size_t)B * H * T * sizeof(float);
+  const size_t ni = attn_strided_bytes(B * T, ldq, H * D), nd = attn_strided_bytes(S * B * T, ldd, H * D);
+  const size_t need = attn_delta_bytes(S, B, H, T);
+  const void* in[6] = {go, q, k, v, o, lse};
+  const size_t in_bytes[6] = {nS, ni, ni, ni, n1, nl};
+  const void* out[4] = {dq, dk, dv, ws};
+  const size_t out_bytes[4] = {nd, nd, nd, need};
+  rc = attn_check(fn, in, in_bytes, 6, out, out_bytes, 4, scale);
+  if (rc != LK_OK) return rc;
+  rc = attn_check_workspace(fn, need, ws_bytes);
+  if (rc != LK_OK) return rc;
+  const float* const outs[3] = {dq, dk, dv};
+  rc = attn_check_interleave(fn, outs, 3, S * B * T, ldd, H * D);
+  if (rc != LK_OK) return rc;
+  if (B == 0) return LK_OK;
+  p.in.row = ldq, p.in.batch = T * ldq;
+  p.out.row = ldd, p.out.batch = T * ldd, p.out.seed = B * T * ldd;
   hipStream_t st = (hipStream_t)stream;
 #define LK_ATTN_VJP(N)                                                                                                    \
   if (p.resident) attn_launch_vjp<N, true>(p, go, q, k, v, o, lse, (int)S, scale, causal != 0, dq, dk, dv, (float*)ws, st); \

@@ -326,6 +326,37 @@ class ViTSmall(nn.Module):
         return self.head(self.norm(x).mean(1))
 
 
+class ViTStock(nn.Module):
+    """:class:`ViTSmall`'s sizes built from PyTorch's own transformer: the patches (unfolded by a reshape) through a ``Linear``, a
+    fixed sin-cos positional buffer, ``nn.TransformerEncoder`` of ``depth`` pre-norm GELU ``nn.TransformerEncoderLayer`` s
+    (``batch_first``, dropout 0, no nested tensors) with a final LayerNorm, the mean over the positions and a ``Linear`` head.
+    Each layer's ``nn.MultiheadAttention`` is served as the two Linear layers around its attention core (`laplace_amd.mha`): its
+    packed projection is read where it lies (csrc/lk_attn.hip, the strided entry points).  ``freeze_norm=True`` freezes the
+    LayerNorm affines, which KFAC needs."""
+
+    def __init__(self, num_classes: int = 10, image: int = 32, patch: int = 4, dim: int = 192, depth: int = 6, heads: int = 3,
+                 freeze_norm: bool = True):
+        super().__init__()
+        if image % patch:
+            raise ValueError(f"patch ({patch}) must divide image ({image})")
+        self.patch, self.grid = patch, image // patch
+        self.embed = nn.Linear(3 * patch * patch, dim)
+        self.register_buffer("pos", sincos_positions(self.grid ** 2, dim))
+        layer = nn.TransformerEncoderLayer(dim, heads, 4 * dim, 0.0, "gelu", batch_first=True, norm_first=True)
+        self.encoder = nn.TransformerEncoder(layer, depth, norm=nn.LayerNorm(dim), enable_nested_tensor=False)
+        self.head = nn.Linear(dim, num_classes)
+        if freeze_norm:
+            for m in self.modules():
+                if isinstance(m, nn.LayerNorm):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+
+    def forward(self, x):
+        p, g = self.patch, self.grid
+        x = x.view(x.size(0), 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(x.size(0), g * g, 3 * p * p)
+        return self.head(self.encoder(self.embed(x) + self.pos).mean(1))
+
+
 class CSPBlock(nn.Module):
     """Residual block of a CSP stage: ``act(x + BN(conv3x3(act(BN(conv3x3(x))))))`` at constant width; no convolution has a bias"""
 

@@ -30,6 +30,8 @@ import torch.fx as fx
 import torch.nn.functional as F
 from torch import nn
 
+from laplace_amd import mha
+
 
 class SweepUnsupported(RuntimeError):
     pass
@@ -61,6 +63,11 @@ _EMBED, _PARAM, _EXPAND = "embedding", "parameter", "batch-expansion"
 # what 1-D convolutional networks end in; csrc/lk_reduce.hip); _SUMRED: ``sum`` along static non-batch dims (an ``expand``, as
 # MEAN's).  (Module-private names: the NHWC walk sends a model that holds one to the NCHW walk, `SplitSweep._split_eligible`)
 _MAXRED, _SUMRED = "max-reduction", "sum-reduction"
+# _MHA: an nn.MultiheadAttention called as unmasked self-attention - a tuple-valued node (output, attention weights) that is looked
+# through by its items, as SPLIT is; the node itself runs Linear, attention, Linear on the module's own parameters
+# (`laplace_amd.mha`) and fills the taps of both halves.  _MHAOUT: ``[0]`` of it, the output (``[1]``, the weights, is served only
+# when nothing consumes it).  (Module-private names: the NHWC walk sends a model that holds one to the NCHW walk)
+_MHA, _MHAOUT = "multi-head-attention", "attention-output"
 
 
 class Rule(NamedTuple):
@@ -101,7 +108,7 @@ _MODULE_KINDS = (
     # (the 1-D pools are the unit-height window of the 2-D rules, lifted at the node: flavour "1d")
     ((nn.AdaptiveAvgPool1d,), GPOOL, "1d"), ((nn.AvgPool1d,), AVGPOOL, "1d"), ((nn.MaxPool1d,), MAXPOOL, "1d"),
     ((nn.AdaptiveMaxPool1d, nn.AdaptiveMaxPool2d), _MAXRED, None),
-    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None), ((nn.Embedding,), _EMBED, None))
+    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None), ((nn.Embedding,), _EMBED, None), ((nn.MultiheadAttention,), _MHA, None))
 _FUNCTION_KINDS = {
     torch.relu: (ACT, "relu"), F.relu: (ACT, "relu"), torch.tanh: (ACT, "tanh"), F.tanh: (ACT, "tanh"),
     torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
@@ -199,6 +206,24 @@ def _classify_attn(node):
     if not all(isinstance(t, fx.Node) for t in src):
         raise SweepUnsupported("scaled_dot_product_attention: query, key and value must be traced tensors")
     return src, (bool(vals["is_causal"]), None if vals["scale"] is None else float(vals["scale"]))
+
+
+def _classify_mha(node, m):
+    """the source of an nn.MultiheadAttention call that is served as Linear, attention, Linear, or the refusal that names why it
+    is not (`laplace_amd.mha.refusal`; the attention weights count as consumed when ``[1]`` of the node has a user)"""
+    weights_used = False
+    for u in node.users:
+        item = u.args[1] if u.op == "call_function" and u.target is operator.getitem and len(u.args) == 2 else None
+        if isinstance(item, bool) or item not in (0, 1):
+            raise SweepUnsupported(f"{node.target}: the (output, weights) pair of nn.MultiheadAttention must be indexed with [0] or [1]")
+        weights_used |= item == 1 and bool(u.users)
+    try:
+        why = mha.refusal(m, (node.args, node.kwargs), weights_used)
+    except TypeError as e:
+        why = str(e)
+    if why is not None:
+        raise SweepUnsupported(f"{node.target}: {why}")
+    return (mha.bind_call(node.args, node.kwargs)["query"],)
 
 
 def _classify_permute(node, what):
@@ -730,6 +755,8 @@ def classify(node: fx.Node, modules: dict) -> Rule:
                     return Rule(IDENTITY, (args[0],), _same, ((args[0],), {}), f"values of {up.what}")
                 raise SweepUnsupported(f"{up.what}: its indices ({args[1] if len(args) > 1 else None!r}) have no cotangent and no rule "
                                        "(take the values with [0] or .values)")
+            if up.kind == _MHA:  # (an item of the pair an nn.MultiheadAttention returns: `_classify_mha` checked the index)
+                return Rule(_MHAOUT, (args[0],), None, ((args[0],), {}), f"item {args[1]} of {up.what}", args=(int(args[1]),))
         fn, hit, what = node.target, _FUNCTION_KINDS.get(node.target), getattr(node.target, "__name__", node.target)
         if hit is None:
             raise SweepUnsupported(f"no VJP rule for function {what}" + _no_slice_rule(node.target))
@@ -799,6 +826,9 @@ def classify(node: fx.Node, modules: dict) -> Rule:
         fn, args, kwargs, m = None, src, {}, None  # (evaluated by `SeedBatchedSweep._run_reduce`)
     elif kind == ATTN:
         src, static = _classify_attn(node)
+    elif kind == _MHA:
+        src = _classify_mha(node, m)
+        args, kwargs, what = src, {}, f"MultiheadAttention ({node.target})"
     elif kind == PERMUTE:
         static = _classify_permute(node, what)
     elif kind == CAT:
@@ -825,7 +855,7 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == SUB:
         src = _classify_sub(node, modules)
         fn, args, kwargs, what = operator.sub, src, {}, "sub"  # (`-=` / `sub_` must not write into a kept tensor)
-    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM, _EMBED) else None, static)
+    return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM, _EMBED, _MHA) else None, static)
 
 
 def norm_geometry(m, inp):
@@ -1072,6 +1102,7 @@ class SeedBatchedSweep:
             self.gm = fx.symbolic_trace(model)
         except Exception as e:  # data-dependent control flow, non-tensor inputs, ...
             raise SweepUnsupported(f"torch.fx cannot trace the model: {e}") from e
+        mha.expand_encoders(self.gm)  # (the stock encoder: a leaf of the tracer, rewritten into nodes for its sub-modules)
         self.modules = dict(self.gm.named_modules())
         self.tap_names = set(tap_modules)
         #: node -> :class:`Rule`, in graph order (the graph does not change after tracing)
@@ -1214,6 +1245,11 @@ class SeedBatchedSweep:
             elif kind == ATTN:
                 out, keep = self._run_attn(r, *(env[n] for n in r.src))
                 keep = keep if need_vjp else None
+            elif kind == _MHA:
+                out, keep = self._run_mha(node, r, inp)
+                keep = keep if need_vjp else None
+            elif kind == _MHAOUT:
+                out = inp[r.args[0]]
             elif kind == PERMUTE:
                 perm = permutation(*r.args, inp.dim())
                 out, keep = inp.permute(perm), [perm.index(i) for i in range(len(perm))]  # (keep: the inverse permutation)
@@ -1517,6 +1553,85 @@ class SeedBatchedSweep:
         if K is not None:
             return K.attn_vjp(g, q, k, v, o, aux, S, scale, causal)
         return attn_vjp_math(g, q, k, v, o, aux, S, scale, self.attn_mem_bytes)
+
+    #: ``False``: an nn.MultiheadAttention node hands the layout-1 entry points contiguous copies of the three slices of its packed
+    #: projection and concatenates the three cotangents, instead of giving the strided entry points the packed buffers themselves
+    use_strided_attn = True
+
+    def _mha_kernels(self, x, B, H, T, D):
+        """the kernel object when csrc/lk_attn.hip serves the attention core of an nn.MultiheadAttention node (as `_attn_kernels`;
+        a head dim that is no multiple of 4 falls to the torch math), else ``None``"""
+        K = self.kernels() if self.kernels is not None and self.use_attn_kernels else None
+        if K is None or not hasattr(K, "attn_forward") or x.dtype != torch.float32:
+            return None
+        return K if D % 4 == 0 and K.attn_variant(1, B, H, T, D, 1, False) is not None else None
+
+    def _run_mha(self, node, r, x):
+        """nn.MultiheadAttention forward as what it equals -> ``((out, None), keep)``: ``F.linear`` into ONE ``[B, T, 3 E]`` buffer,
+        the attention core on its three slices where they lie (lk_attn_fwd_strided_f32; contiguous copies and the layout-1 entry
+        point with ``use_strided_attn = False``; the torch math of the ATTN rule without kernels), ``F.linear``.  Fills the taps
+        of both halves: ``<target>.in_proj`` reads ``x``, ``<target>.out_proj`` the attention context ``[B, T, E]``"""
+        m = r.mod
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[-1] != m.embed_dim:
+            raise SweepUnsupported(f"{node.target}: nn.MultiheadAttention on an input that is not [B, T, {m.embed_dim}]")
+        B, T, E = x.shape
+        H, D = m.num_heads, m.head_dim
+        scale = float(D) ** -0.5
+        b_in = None if m.in_proj_bias is None else m.in_proj_bias.detach()
+        qkv = F.linear(x, m.in_proj_weight.detach(), b_in)
+        K = self._mha_kernels(x, B, H, T, D) if B > 0 else None
+        if K is not None and self.use_strided_attn and hasattr(K, "attn_forward_strided"):
+            q, k, v = qkv.view(B, T, 3, H, D).unbind(2)  # (views: rows of E floats, 3 E apart)
+            o, lse = K.attn_forward_strided(q, k, v, scale, False)
+            ctx, keep = o.view(B, T, E), ("strided", K, q, k, v, o, lse, scale)
+        elif K is not None:
+            q, k, v = (t.contiguous().transpose(1, 2) for t in qkv.view(B, T, 3, H, D).unbind(2))  # (copies, in layout 1)
+            o, lse = K.attn_forward(q, k, v, scale, False)
+            ctx, keep = o.transpose(1, 2).reshape(B, T, E), ("copies", K, q, k, v, o, lse, scale)
+        else:
+            q, k, v = mha.heads(qkv, H)
+            o, p = attn_forward_math(q, k, v, scale, False)
+            self._attn_math_numel = max(self._attn_math_numel, p.numel())
+            ctx, keep = o.transpose(1, 2).reshape(B, T, E), ("math", None, q, k, v, o, p, scale)
+        self.max_act_numel = max(self.max_act_numel, qkv.numel() // max(B, 1))
+        b_out = None if m.out_proj.bias is None else m.out_proj.bias.detach()
+        out = F.linear(ctx, m.out_proj.weight.detach(), b_out)
+        for half, a in (("in_proj", x), ("out_proj", ctx)):
+            name = f"{node.target}.{half}"
+            if name in self.tap_names:
+                if name in self.taps:
+                    raise SweepUnsupported(f"{name}: module is applied more than once per forward")
+                self.taps[name] = {"a": a, "node": node}
+        return (out, None), keep
+
+    def _vjp_mha(self, walk, node, r, g, g2):
+        """``g [S*B, T, E]``: the cotangent of the module's output, which is ``out_proj``'s tap; ``dctx = g W_out``; the attention
+        VJP of all seeds straight into ONE ``[S*B, T, 3 E]`` buffer (lk_attn_vjp_strided_f32), which is ``in_proj``'s tap;
+        ``dx = dqkv W_in``"""
+        m, S = r.mod, walk.S
+        how, K, q, k, v, o, aux, scale = self.saved[node]
+        SB, T, E = g.shape
+        H, D = m.num_heads, m.head_dim
+        done = f"{node.target}.out_proj" in self.tap_names and walk.tap(f"{node.target}.out_proj", g.reshape(S, SB // S, T, E))
+        if done:
+            return
+        dctx = g @ m.out_proj.weight.detach()
+        if how == "strided":
+            dqkv = g.new_empty(SB, T, 3 * E)
+            K.attn_vjp_strided(dctx.view(SB, T, H, D), q, k, v, o, aux, S, scale, False, *dqkv.view(SB, T, 3, H, D).unbind(2))
+        else:
+            go = dctx.view(SB, T, H, D).transpose(1, 2)
+            if how == "copies":
+                parts = K.attn_vjp(go, q, k, v, o, aux, S, scale, False)
+            else:
+                parts = attn_vjp_math(go, q, k, v, o, aux, S, scale, self.attn_mem_bytes)
+            dqkv = torch.cat([d.transpose(1, 2).reshape(SB, T, E) for d in parts], -1)
+        if f"{node.target}.in_proj" in self.tap_names and walk.tap(f"{node.target}.in_proj", dqkv.reshape(S, SB // S, T, 3 * E)):
+            return
+        walk.push(r.src[0], dqkv @ m.in_proj_weight.detach())
+
+    def _vjp_mhaout(self, walk, node, r, g, g2):
+        walk.push(r.src[0], g)
 
     #: ``False``: the VJP of a product stays on the torch math of its rule (``g * b``, ``(g * a).sum(...)``) whatever the kernel
     #: object offers
@@ -1922,6 +2037,7 @@ class SeedBatchedSweep:
             ATTN: "_vjp_attn", PERMUTE: "_vjp_permute", ADD: "_vjp_add", MUL: "_vjp_mul", MATMUL: "_vjp_matmul",
             SOFTMAX: "_vjp_softmax", SCALE: "_vjp_scale", NEG: "_vjp_neg", SUB: "_vjp_sub", CAT: "_vjp_cat", SLICE: "_vjp_slice",
             _EXPAND: "_vjp_identity", _EMBED: "_vjp_leaf", _PARAM: "_vjp_leaf", _MAXRED: "_vjp_maxred", _SUMRED: "_vjp_sumred",
+            _MHA: "_vjp_mha", _MHAOUT: "_vjp_mhaout",
             SIZE: None, GETITEM: None, SPLIT: None, CONST: None, "placeholder": None, "output": None}
 
     def _vjp_rule(self, r):
