@@ -731,6 +731,42 @@ int lk_maxred_vjp_f32(const float* g, const int* idx, const float* x, const floa
                       int64_t L, int64_t inner, float* dx, void* stream);
 int lk_reduce_variant(int vjp, int64_t S, int64_t outer, int64_t L, int64_t inner, int even, int aligned);
 
+/* Static, separable, linear resampling of the last two dims (nn.Upsample / F.interpolate: nearest, nearest-exact, linear,
+ * bilinear, bicubic, area, with or without antialias; F.pad and the padding modules: constant, reflect, replicate, circular,
+ * cropping pads included) for the seed-batched reverse sweep.  Per plane the operation is y = Mh x Mw^T + const with static sparse
+ * axis matrices Mh [OH][H], Mw [OW][W].  It replaces, in the reverse pass of laplace/curvature/curvlinops.py:87-100 and
+ * curvature.py:88-129 through such an operation as stock torch runs it once per seed, upsample_*_backward,
+ * reflection_pad*_backward and replication_pad*_backward, which accumulate with atomics (the bits change from run to run), or
+ * the zero fill and strided copy of a constant pad.
+ *
+ * lk_resample_vjp_f32: g is [P][OH][OW], dx [P][H][W], contiguous fp32, all seeds in one launch (P = S B C planes).
+ *   dx[p][h][w] = sum_{j in [ptr_h[h], ptr_h[h + 1])} sum_{i in [ptr_w[w], ptr_w[w + 1])} w_h[j] * w_w[i] * g[p][idx_h[j]][idx_w[i]]
+ *   in fp32, j ascending, then i, formed as acc += w_h[j] * (sum_i w_w[i] * g).  (ptr, idx, w) of an axis is the TRANSPOSE of
+ *   its matrix in CSR form: ptr [L + 1] int32, idx int32 ascending per entry, w float32, all on the device.  Every element of dx
+ *   is written: an input that no output reads (a cropped border) receives +0.0f; the caller fills nothing.  One owner per
+ *   element, plain stores, no atomics, a fixed tap order: deterministic.  A lane reads the taps of its pixels once for all
+ *   planes of its slice.  Minimal traffic: 4 P (OH OW + H W) bytes; the reuse of g among neighbouring lanes is left to the caches.
+ * Contract: pointers non-null; 1 <= P; 1 <= OH, OW, H, W < 2^30; P * max(OH * OW, H * W) < 2^40; ptr monotone from 0 with
+ *   ptr[L] = nnz; 0 <= idx_h < OH, 0 <= idx_w < OW; at most LK_RESAMPLE_MAX_TAPS taps per entry; dx overlaps no operand.  The
+ *   tables live on the device and are NOT validated by the entry point (the caller validates them when it builds them); what is
+ *   free is done there: a longer list is cut at LK_RESAMPLE_MAX_TAPS and an index is clamped into the plane, so that no table
+ *   content makes the kernel write outside dx.  The scalars, the pointers and the overlap (g and the ptr arrays in full, the tap
+ *   arrays by their first entry) are checked.  Errors: "lk_resample_vjp_f32: bad arguments (...)".
+ * lk_resample_variant (host only): the path a shape takes; taps_h / taps_w: the longest tap list of each axis; `aligned`: dx is
+ * 16-byte aligned.  Returns
+ *   vec | taps-in-registers << 1 | 64-bit lane index << 2 | plane-split << 3 | grid-stride << 4 | packed slices << 5 |
+ *   workgroups of grid.x << 8
+ *   vec: 16-byte stores (W % 4 == 0 and aligned), else one pixel per lane; taps-in-registers: both lists hold at most 4 taps
+ *   (decided per lane on the device: this is the answer for the longest lists); 64-bit lane index: H * W (/ 4 with vec) >= 2^31;
+ *   plane-split: the planes are split into slices over grid.y (one plane leaves the device short of waves); grid-stride: one
+ *   plane has more lanes than the at most 2048 workgroups of 256 threads of grid.x; packed slices: a plane has at most 128
+ *   lanes and a workgroup takes 256 / lanes slices side by side
+ * or a negative value for a shape the entry point refuses or a tap count outside 0 .. LK_RESAMPLE_MAX_TAPS. */
+#define LK_RESAMPLE_MAX_TAPS 16
+int lk_resample_vjp_f32(const float* g, int64_t P, int64_t OH, int64_t OW, int64_t H, int64_t W, const int* ptr_h, const int* idx_h,
+                        const float* w_h, const int* ptr_w, const int* idx_w, const float* w_w, float* dx, void* stream);
+int lk_resample_variant(int64_t P, int64_t OH, int64_t OW, int64_t H, int64_t W, int taps_h, int taps_w, int aligned);
+
 /* Element-wise product of two traced tensors (squeeze-and-excitation gates, GLU / SwiGLU / GeGLU, self-gating) for the
  * seed-batched reverse sweep.  It replaces, in the reverse pass of laplace/curvature/curvlinops.py:87-100 and
  * curvature.py:88-129 through out = a * b as stock torch runs it once per seed, g * b, g * a and - for a gate - a sum over the

@@ -144,6 +144,8 @@ SIGNATURES = {
     "lk_maxred_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "lk_maxred_vjp_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "lk_reduce_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int, _int]),
+    "lk_resample_vjp_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lk_resample_variant": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int, _int]),
     "lk_mul_vjp_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "lk_mul_variant": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
     "lk_gate_reduce_nhwc_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
@@ -1848,6 +1850,62 @@ class HipKernels:
             return None
         return {"vjp": bool(vjp), "row": bool(r & 1), "vec": bool(r & 2), "even": bool(r & 4), "wide_index": bool(r & 8),
                 "lanes": 1 << ((r >> 4) & 7), "seed_split": bool(r & 128), "blocks": r >> 8}
+
+    RESAMPLE_MAX_TAPS = 16  # (LK_RESAMPLE_MAX_TAPS of the header)
+
+    def resample_pack(self, ptr, idx, w, L, OL):
+        """the transposed tap lists of ONE axis of a static resampling (``sweep.resample_tables``: ``ptr`` ``[L + 1]`` int32, ``idx``
+        int32, ``w`` float32) as lk_resample_vjp_f32 reads them, validated here ONCE - the entry point does not look into device
+        tables: ``ptr`` rises from 0 to ``nnz``, at most ``RESAMPLE_MAX_TAPS`` taps per input, every ``idx`` an output ``0 <= idx <
+        OL``, ascending within a list.  Returns ``(ptr, idx, w, L, OL, longest list)`` with contiguous device tensors (an axis with
+        no tap at all carries one unused entry: an empty tensor has no address to hand over)."""
+        L, OL = int(L), int(OL)
+        for t, name, dt in ((ptr, "ptr", torch.int32), (idx, "idx", torch.int32), (w, "w", torch.float32)):
+            _check(t, name, dt)
+        p = ptr.to("cpu", torch.int64)
+        nnz = int(idx.numel())
+        if L < 1 or OL < 1 or p.numel() != L + 1 or w.numel() != nnz:
+            raise LaplaceHipError(f"resample_pack: ptr [{p.numel()}], idx [{nnz}], w [{w.numel()}] are no tap lists of {L} inputs")
+        cnt = p[1:] - p[:-1]
+        if int(p[0]) != 0 or int(p[-1]) != nnz or bool((cnt < 0).any()):
+            raise LaplaceHipError("resample_pack: ptr must rise from 0 to the number of taps")
+        taps = int(cnt.max())
+        if taps > self.RESAMPLE_MAX_TAPS:
+            raise LaplaceHipError(f"resample_pack: {taps} taps for one input exceed LK_RESAMPLE_MAX_TAPS = {self.RESAMPLE_MAX_TAPS}")
+        if nnz:
+            i = idx.to("cpu", torch.int64)
+            first = torch.zeros(nnz, dtype=torch.bool)
+            first[p[:-1][cnt > 0]] = True
+            if bool((i < 0).any()) or bool((i >= OL).any()) or bool(((i[1:] <= i[:-1]) & ~first[1:]).any()):
+                raise LaplaceHipError(f"resample_pack: idx must lie in [0, {OL}) and ascend within the list of an input")
+        else:
+            idx, w = idx.new_zeros(1), w.new_zeros(1)
+        return ptr, idx, w, L, OL, taps
+
+    def resample_vjp(self, g, axis_h, axis_w):
+        """``dx`` ``[P, H, W]`` of a static separable resampling for the ``P = S B C`` planes of the contiguous fp32 cotangent ``g``
+        ``[P, OH, OW]``, in ONE launch of lk_resample_vjp_f32 (csrc/lk_resample.hip) that writes every element: ``axis_h`` /
+        ``axis_w`` are what :meth:`resample_pack` returned for the two axes"""
+        _check(g, "g")
+        (ph, ih, wh, H, OH, _), (pw, iw, ww, W, OW, _) = axis_h, axis_w
+        if g.dim() != 3 or tuple(g.shape[1:]) != (OH, OW) or g.shape[0] < 1:
+            raise LaplaceHipError(f"resample_vjp: g {tuple(g.shape)} is no [P >= 1, {OH}, {OW}] cotangent")
+        if any(t.device != g.device for t in (ph, ih, wh, pw, iw, ww)):
+            raise LaplaceHipError("resample_vjp: the tap lists are on another device than g")
+        P = int(g.shape[0])
+        dx = torch.empty(P, H, W, dtype=torch.float32, device=g.device)
+        self._rc(self.lib.lk_resample_vjp_f32(_ptr(g), P, OH, OW, H, W, _ptr(ph), _ptr(ih), _ptr(wh), _ptr(pw), _ptr(iw), _ptr(ww),
+                                              _ptr(dx), self._stream(g.device)), "lk_resample_vjp_f32")
+        return dx
+
+    def resample_variant(self, P, OH, OW, H, W, taps_h, taps_w, aligned=True):
+        """lk_resample_variant: the path ``lk_resample_vjp_f32`` takes for a shape and the longest tap list of each axis (host only,
+        no device call), or ``None`` for what it refuses."""
+        r = int(self.lib.lk_resample_variant(int(P), int(OH), int(OW), int(H), int(W), int(taps_h), int(taps_w), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "taps_in_registers": bool(r & 2), "wide_index": bool(r & 4), "plane_split": bool(r & 8),
+                "grid_stride": bool(r & 16), "packed_slices": bool(r & 32), "blocks": r >> 8}
 
     def mul_vjp(self, g, a, b, S, b_row, want=(True, True)):
         """``(da, db)`` of ``out = a * b`` for the ``S`` seeds stacked in the cotangent ``g`` (``S * a.numel()`` elements, seed-major)

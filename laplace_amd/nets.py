@@ -10,6 +10,7 @@ from __future__ import annotations
 import math
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 
@@ -878,3 +879,91 @@ class TextCNN(nn.Module):
             e = e.unsqueeze(2)
         feats = [act(conv(e)).amax(2 if self.dims == 1 else (2, 3)) for conv, act in zip(self.convs, self.acts)]
         return self.fc(torch.cat(feats, 1))
+
+
+# ---- networks that change the resolution of a map by something other than a convolution or a pool (csrc/lk_resample.hip) -----------
+class FPNSmall(nn.Module):
+    """A CIFAR-sized feature pyramid used as a classifier: three levels (a 3x3 stem and two stride-2 3x3 convolutions, each with
+    BatchNorm and an activation; ``widths`` are multiples of 32), 1x1 laterals to ``fpn`` channels, a top-down path that upsamples
+    the coarser level by two and adds it to the lateral, a 3x3 smoothing convolution and a global average pool per level, ``cat``,
+    ``Linear``.  ``mode="nearest"``: the top-down path is ``nn.Upsample(scale_factor=2, mode="nearest")``; ``mode="bilinear"``: it is
+    ``F.interpolate(size=y.size()[2:], mode="bilinear", align_corners=False)`` with ``y`` the lateral it joins.  ``freeze_norm``:
+    the BatchNorm affine parameters are not tracked, so that KFAC runs."""
+
+    def __init__(self, num_classes: int = 10, widths=(32, 64, 128), fpn: int = 64, mode: str = "nearest", act=nn.ReLU,
+                 freeze_norm: bool = True):
+        super().__init__()
+        if mode not in ("nearest", "bilinear"):
+            raise ValueError(f"mode must be 'nearest' or 'bilinear', got {mode!r}")
+        self.mode = mode
+        cin, stages = 3, []
+        for i, w in enumerate(widths):
+            stages.append(nn.Sequential(nn.Conv2d(cin, w, 3, 1 if i == 0 else 2, 1, bias=False), nn.BatchNorm2d(w), act()))
+            cin = w
+        self.stages = nn.ModuleList(stages)
+        self.laterals = nn.ModuleList(nn.Conv2d(w, fpn, 1) for w in widths)
+        self.smooth = nn.ModuleList(nn.Conv2d(fpn, fpn, 3, 1, 1) for _ in widths)
+        self.up = nn.Upsample(scale_factor=2, mode="nearest")
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(fpn * len(widths), num_classes)
+        for m in self.modules():
+            if freeze_norm and isinstance(m, nn.BatchNorm2d):
+                m.weight.requires_grad_(False), m.bias.requires_grad_(False)
+
+    def forward(self, x):
+        feats = []
+        for stage in self.stages:
+            x = stage(x)
+            feats.append(x)
+        top, levels = None, []
+        for f, lateral in zip(reversed(feats), reversed(self.laterals)):  # (coarse to fine)
+            y = lateral(f)
+            if top is not None:
+                if self.mode == "nearest":
+                    y = y + self.up(top)
+                else:
+                    y = y + F.interpolate(top, size=y.size()[2:], mode="bilinear", align_corners=False)
+            top = y
+            levels.append(y)
+        pooled = [torch.flatten(self.pool(s(p)), 1) for s, p in zip(self.smooth, reversed(levels))]
+        return self.fc(torch.cat(pooled, 1))
+
+
+class TCNBlock(nn.Module):
+    """One causal block of a temporal convolution network on ``[B, C, L]`` maps: a left pad of ``dilation * (k - 1)`` positions
+    (``F.pad`` with zeros, or ``nn.ReflectionPad1d`` where ``reflect``), a dilated ``Conv1d``, an activation, a residual add (through
+    a 1x1 convolution where the channel count changes).  ``dims=2``: the unit-height twin."""
+
+    def __init__(self, cin: int, cout: int, k: int, dilation: int, act=nn.ReLU, reflect: bool = False, dims: int = 1):
+        super().__init__()
+        self.left = dilation * (k - 1)
+        self.reflect = None
+        if reflect:
+            self.reflect = nn.ReflectionPad1d((self.left, 0)) if dims == 1 else nn.ReflectionPad2d((self.left, 0, 0, 0))
+        self.conv, self.act = _conv_nd(dims, cin, cout, k, dilation=dilation, bias=True), act()
+        self.short = None if cin == cout else _conv_nd(dims, cin, cout, 1)
+
+    def forward(self, x):
+        y = self.reflect(x) if self.reflect is not None else F.pad(x, (self.left, 0))
+        return self.act(self.conv(y)) + (x if self.short is None else self.short(x))
+
+
+class TCNSmall(nn.Module):
+    """A causal temporal convolution network (Bai et al. 2018) as a sequence classifier: :class:`TCNBlock` s of ``channels`` with
+    kernel ``k`` and the ``dilations`` (the block ``reflect_block`` pads by reflection, the others with zeros), the mean over time,
+    ``Linear``.  Input ``[B, in_channels, L]``.  ``dims=2``: the unit-height twin on ``[B, in_channels, 1, L]``."""
+
+    def __init__(self, num_classes: int = 10, in_channels: int = 8, channels: int = 64, k: int = 3, dilations=(1, 2, 4, 8),
+                 act=nn.ReLU, reflect_block: int = 1, dims: int = 1):
+        super().__init__()
+        self.dims = dims
+        blocks, cin = [], in_channels
+        for i, d in enumerate(dilations):
+            blocks.append(TCNBlock(cin, channels, k, d, act, i == reflect_block, dims))
+            cin = channels
+        self.blocks = nn.Sequential(*blocks)
+        self.fc = nn.Linear(channels, num_classes)
+
+    def forward(self, x):
+        x = self.blocks(x)
+        return self.fc(x.mean(2) if self.dims == 1 else x.mean((2, 3)))

@@ -68,6 +68,11 @@ _MAXRED, _SUMRED = "max-reduction", "sum-reduction"
 # (`laplace_amd.mha`) and fills the taps of both halves.  _MHAOUT: ``[0]`` of it, the output (``[1]``, the weights, is served only
 # when nothing consumes it).  (Module-private names: the NHWC walk sends a model that holds one to the NCHW walk)
 _MHA, _MHAOUT = "multi-head-attention", "attention-output"
+# _RESAMPLE: a static, separable, linear resampling of the last one or two dims - nn.Upsample / F.interpolate in every 1-D and 2-D
+# mode, F.pad and the padding modules in every mode.  Per plane ``y = Mh x Mw^T + const`` with axis matrices read off torch's own
+# operator (`resample_tables`); the VJP of all seeds is one launch of csrc/lk_resample.hip.  (A module-private name: the NHWC walk
+# sends a model that holds one to the NCHW walk)
+_RESAMPLE = "static-resampling"
 
 
 class Rule(NamedTuple):
@@ -108,7 +113,11 @@ _MODULE_KINDS = (
     # (the 1-D pools are the unit-height window of the 2-D rules, lifted at the node: flavour "1d")
     ((nn.AdaptiveAvgPool1d,), GPOOL, "1d"), ((nn.AvgPool1d,), AVGPOOL, "1d"), ((nn.MaxPool1d,), MAXPOOL, "1d"),
     ((nn.AdaptiveMaxPool1d, nn.AdaptiveMaxPool2d), _MAXRED, None),
-    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None), ((nn.Embedding,), _EMBED, None), ((nn.MultiheadAttention,), _MHA, None))
+    ((nn.Softmax, nn.LogSoftmax), SOFTMAX, None), ((nn.Embedding,), _EMBED, None), ((nn.MultiheadAttention,), _MHA, None),
+    # (nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d are nn.Upsample; nn.ZeroPad1d / 2d are nn.ConstantPad1d / 2d)
+    ((nn.Upsample,), _RESAMPLE, "interpolate"),
+    ((nn.ConstantPad1d, nn.ConstantPad2d, nn.ReflectionPad1d, nn.ReflectionPad2d, nn.ReplicationPad1d, nn.ReplicationPad2d,
+      nn.CircularPad1d, nn.CircularPad2d), _RESAMPLE, "pad"))
 _FUNCTION_KINDS = {
     torch.relu: (ACT, "relu"), F.relu: (ACT, "relu"), torch.tanh: (ACT, "tanh"), F.tanh: (ACT, "tanh"),
     torch.sigmoid: (ACT, "sigmoid"), F.sigmoid: (ACT, "sigmoid"), **{f: (ACT, "generic") for f in _GENERIC_ACT_FN},
@@ -126,7 +135,8 @@ _FUNCTION_KINDS = {
     F.softmax: (SOFTMAX, None), torch.softmax: (SOFTMAX, None), F.log_softmax: (SOFTMAX, None), torch.log_softmax: (SOFTMAX, None),
     operator.truediv: (SCALE, None), operator.itruediv: (SCALE, None), torch.div: (SCALE, None), torch.true_divide: (SCALE, None),
     operator.neg: (NEG, None), torch.neg: (NEG, None), torch.negative: (NEG, None),
-    operator.sub: (SUB, None), operator.isub: (SUB, None), torch.sub: (SUB, None), torch.subtract: (SUB, None)}
+    operator.sub: (SUB, None), operator.isub: (SUB, None), torch.sub: (SUB, None), torch.subtract: (SUB, None),
+    F.interpolate: (_RESAMPLE, "interpolate"), F.pad: (_RESAMPLE, "pad")}
 _METHOD_KINDS = {
     "relu": (ACT, "relu"), "tanh": (ACT, "tanh"), "sigmoid": (ACT, "sigmoid"), "contiguous": (IDENTITY, None),
     "view": (RESHAPE, None), "reshape": (RESHAPE, None), "flatten": (RESHAPE, None), "mean": (MEAN, None),
@@ -570,6 +580,217 @@ def _classify_sub(node, modules):
     return tuple(node.args)
 
 
+_RESAMPLE_PARAMS = {  # names and defaults of the functional forms (the input excluded)
+    "interpolate": (("size", "scale_factor", "mode", "align_corners", "recompute_scale_factor", "antialias"),
+                    (None, None, "nearest", None, None, False)),
+    "pad": (("pad", "mode", "value"), (None, "constant", None))}
+_PAD_MODULE_MODES = ((nn.ConstantPad1d, "constant"), (nn.ConstantPad2d, "constant"), (nn.ReflectionPad1d, "reflect"),
+                     (nn.ReflectionPad2d, "reflect"), (nn.ReplicationPad1d, "replicate"), (nn.ReplicationPad2d, "replicate"),
+                     (nn.CircularPad1d, "circular"), (nn.CircularPad2d, "circular"))
+
+
+def _holds_node(v):
+    return isinstance(v, fx.Node) or (isinstance(v, (tuple, list)) and any(_holds_node(e) for e in v))
+
+
+def _classify_resample(node, m, op, modules):
+    """``(x, keyword arguments of the functional form, what)`` of an ``F.interpolate`` / ``F.pad`` call or of a module that makes
+    one (nn.Upsample and its two subclasses, the eight padding modules): every argument bound by name, the mode and the pad static,
+    ``size`` / ``scale_factor`` static or made of values the sweep evaluates to ints (``y.size(2)``, items of ``y.size()``), or the
+    refusal that names the operation and the reason"""
+    names, defaults = _RESAMPLE_PARAMS[op]
+    vals = dict(zip(names, defaults))
+    if m is not None:
+        what = f"{type(m).__name__} ({node.target})"
+        if op == "interpolate":
+            vals.update(size=m.size, scale_factor=m.scale_factor, mode=m.mode, align_corners=m.align_corners,
+                        recompute_scale_factor=m.recompute_scale_factor)
+        else:
+            vals.update(pad=tuple(m.padding), mode=next(md for t, md in _PAD_MODULE_MODES if isinstance(m, t)),
+                        value=getattr(m, "value", None))
+        extra = list(node.args[1:]) + sorted(node.kwargs)
+        if extra and set(node.kwargs) != {"input"}:
+            raise SweepUnsupported(f"{what}: unknown argument {extra}")
+    else:
+        what = op
+        kwargs = dict(node.kwargs)
+        if kwargs.pop("out", None) is not None:
+            raise SweepUnsupported(f"{what} with an out= argument (the sweep keeps its own values)")
+        for n, a in zip(names, node.args[1:]):
+            vals[n] = a
+        for k in list(kwargs):
+            if k in vals:
+                vals[k] = kwargs.pop(k)
+        kwargs.pop("input", None)
+        if kwargs or len(node.args) > 1 + len(names):
+            raise SweepUnsupported(f"{what}: unknown argument {sorted(kwargs) or node.args[1 + len(names):]}")
+    x = node.args[0] if node.args else node.kwargs.get("input")
+    if not isinstance(x, fx.Node):
+        raise SweepUnsupported(f"{what}: the operand must be a traced tensor")
+    for n in ("mode", "align_corners", "recompute_scale_factor", "antialias", "pad"):
+        if n in vals and _holds_node(vals[n]):
+            raise SweepUnsupported(f"{what} with a data-dependent {n}")
+    if not isinstance(vals["mode"], str):
+        raise SweepUnsupported(f"{what}: mode must be a string, got {type(vals['mode']).__name__}")
+    if op == "interpolate":
+        if vals["mode"] == "trilinear":
+            raise SweepUnsupported(f"{what} in mode trilinear (3-D resampling is out of scope: the last two dims are what the rule serves)")
+        for n in ("size", "scale_factor"):
+            for e in (vals[n] if isinstance(vals[n], (tuple, list)) else (vals[n],)):
+                if isinstance(e, fx.Node) and classify(e, modules).kind not in (SIZE, GETITEM):
+                    raise SweepUnsupported(f"{what} with a data-dependent {n} ({e.name}: only values of a size() are resolved)")
+                if torch.is_tensor(e):
+                    raise SweepUnsupported(f"{what} with a tensor {n}")
+        if isinstance(vals["scale_factor"], fx.Node) or _holds_node(vals["scale_factor"]):
+            raise SweepUnsupported(f"{what} with a data-dependent scale_factor")
+    else:
+        if isinstance(vals["value"], fx.Node) or torch.is_tensor(vals["value"]):
+            raise SweepUnsupported(f"{what} with a traced value (the constant of a pad must be a Python number)")
+        pad = vals["pad"]
+        if not isinstance(pad, (tuple, list)) or len(pad) % 2 or not pad or \
+                not all(isinstance(v, int) and not isinstance(v, bool) for v in pad):
+            raise SweepUnsupported(f"{what}: pad must be a non-empty tuple of static integers of even length, got {pad!r}")
+        vals["pad"] = tuple(int(v) for v in pad)
+    return x, vals, what
+
+
+def resample_dims(op, vals, shape, what):
+    """how many of the LAST dims (1 or 2) a _RESAMPLE rule resamples on a value of ``shape``, never dim 0 (the seeds are stacked
+    there), or the refusal that names the reason"""
+    ndim = len(shape)
+    if op == "interpolate":
+        if ndim == 5:
+            raise SweepUnsupported(f"{what} of a 5-D value (3-D resampling is out of scope)")
+        if ndim not in (3, 4):
+            raise SweepUnsupported(f"{what} of a value with {ndim} dims (expected [B, C, L] or [B, C, H, W])")
+        return ndim - 2
+    pad = list(vals["pad"])
+    while len(pad) > 2 and pad[-2:] == [0, 0]:
+        del pad[-2:]
+    k = len(pad) // 2
+    if k >= ndim:
+        raise SweepUnsupported(f"{what}{tuple(vals['pad'])} of a value with {ndim} dims pads {_BATCH_SLICE}")
+    if k > 2:
+        raise SweepUnsupported(f"{what}{tuple(vals['pad'])} pads more than the last two dims")
+    if ndim < 3:
+        raise SweepUnsupported(f"{what} of a value with {ndim} dims (the operand must have at least 3: [B, C, L], [B, T, D], [B, C, H, W])")
+    return k
+
+
+class ResampleTables(NamedTuple):
+    """the two axis matrices of a static separable resampling and their transposes in CSR form (`resample_tables`)"""
+
+    Mh: torch.Tensor  # [OH, H], the dtype of the value
+    Mw: torch.Tensor  # [OW, W]
+    csr_h: tuple  # (ptr [H + 1] int32, idx int32 ascending per entry, w float32): per input row the outputs that read it
+    csr_w: tuple
+    taps: tuple  # (longest list of csr_h, of csr_w)
+
+
+def _axis_matrix(axis_op, L, width, like):
+    """``M`` ``[OL, L]`` of one axis, read off torch's own operator: ``axis_op(basis) - axis_op(zeros)`` on the ``L`` unit vectors
+    (the difference removes the constant of a pad), the other axis at extent ``width`` and constant along it"""
+    eye = torch.eye(L, dtype=like.dtype, device=like.device)
+    return (axis_op(eye, width) - axis_op(torch.zeros_like(eye), width)).t().contiguous()
+
+
+def _csr_transposed(M):
+    """the transpose of the dense ``M`` ``[OL, L]`` in CSR form: per input ``l`` the outputs ``o`` with ``M[o, l] != 0``, ascending"""
+    Mt = M.t()
+    nz = Mt.nonzero()  # (row-major: by l, then o ascending)
+    cnt = torch.bincount(nz[:, 0], minlength=M.shape[1])
+    ptr = torch.zeros(M.shape[1] + 1, dtype=torch.int64, device=M.device)
+    ptr[1:] = torch.cumsum(cnt, 0)
+    return (ptr.to(torch.int32), nz[:, 1].to(torch.int32).contiguous(), Mt[nz[:, 0], nz[:, 1]].float().contiguous()), \
+        int(cnt.max()) if cnt.numel() else 0
+
+
+def resample_tables(op, vals, in_hw, out_hw, k, like):
+    """:class:`ResampleTables` of the operation ``op`` ("interpolate" / "pad") with the resolved keyword arguments ``vals`` on a
+    plane of extent ``in_hw`` = ``(H, W)`` that it maps to ``out_hw``; ``k``: the number of resampled dims (1: ``H = OH = 1`` and
+    the height's matrix is the identity).  Nothing is assumed about torch's index arithmetic: each axis matrix is the operator
+    itself on a basis (`_axis_matrix`), in the dtype and on the device of ``like``."""
+    (H, W), (OH, OW) = in_hw, out_hw
+
+    def run(t, axis, width):
+        """the operator on ``t`` ``[n, L]`` read as ``n`` planes whose axis ``axis`` (0: rows, 1: columns) has extent ``L`` and whose
+        other axis has extent ``width`` (constant along it) -> ``[n, OL]`` (the first position of the other axis)"""
+        n, L = t.shape
+        if k == 1:
+            x = t.reshape(n, 1, L)
+        elif axis == 0:
+            x = t.reshape(n, 1, L, 1).expand(n, 1, L, width)
+        else:
+            x = t.reshape(n, 1, 1, L).expand(n, 1, width, L)
+        x = x.contiguous()
+        if op == "pad":
+            pad = list(vals["pad"][:2 * k]) + [0] * (2 * k - len(vals["pad"][:2 * k]))
+            if k == 2:  # (the other axis is not padded)
+                pad = [0, 0, pad[2], pad[3]] if axis == 0 else [pad[0], pad[1], 0, 0]
+            y = F.pad(x, tuple(pad), mode=vals["mode"], value=vals["value"])
+        else:
+            kw = {n_: vals[n_] for n_ in ("mode", "align_corners", "recompute_scale_factor", "antialias")}
+            if vals["size"] is not None:  # (as resolved by the forward: the output's extent)
+                kw["size"] = (OW,) if k == 1 else ((OH, width) if axis == 0 else (width, OW))
+            else:
+                sf = vals["scale_factor"]
+                sf = tuple(float(v) for v in sf) if isinstance(sf, (tuple, list)) else (float(sf),) * k
+                kw["scale_factor"] = sf if k == 1 else ((sf[0], 1.0) if axis == 0 else (1.0, sf[1]))
+            y = F.interpolate(x, **kw)
+        if k == 1:
+            return y.reshape(n, -1)
+        return y[:, 0, :, 0] if axis == 0 else y[:, 0, 0, :]
+
+    def whole(x):
+        """the operator itself on ``x`` ``[n, 1, H, W]`` (``k = 1``: ``[n, 1, W]``), its constant removed"""
+        fn = F.pad if op == "pad" else F.interpolate
+        kw = vals if op == "pad" else {**vals, "size": None if vals["size"] is None else ((OW,) if k == 1 else (OH, OW))}
+        return fn(x, **kw) - fn(torch.zeros_like(x), **kw)
+
+    with torch.no_grad():
+        # the other axis at unit extent with its argument neutral (size 1, scale 1.0, pad 0); the pair is then held against the
+        # operator itself on one random plane.  Where it misses - the operator does not map a unit axis by exactly 1 (a bicubic
+        # ``1 -> 1`` may sum its four clamped coefficients to ``1 +- ulp``; the antialias filters mishandle a unit extent) - the
+        # other axis is tried at extent 2 and at full width, constant along it.  A mode that no derivation fits is not separable.
+        one = torch.ones(1, 1, dtype=like.dtype, device=like.device)
+        probe = torch.rand((1, 1, W) if k == 1 else (1, 1, H, W), generator=torch.Generator().manual_seed(H * 7919 + W),
+                           dtype=torch.float64).to(like)
+        want, err = whole(probe).reshape(OH, OW), None
+        for width_h, width_w in dict.fromkeys(((1, 1), (min(2, W), min(2, H)), (W, H))):
+            if k == 1:
+                Mh = one.clone()
+            else:
+                Mh = _axis_matrix(lambda t, width: run(t, 0, width), H, width_h, like)
+            Mw = _axis_matrix(lambda t, width: run(t, 1, width), W, width_w, like)
+            if tuple(Mh.shape) != (OH, H) or tuple(Mw.shape) != (OW, W):
+                continue
+            if k == 2 and op == "interpolate":  # (what a unit / constant other axis is mapped by: exactly 1, or the next derivation)
+                kw = {n_: vals[n_] for n_ in ("mode", "align_corners", "recompute_scale_factor", "antialias")}
+                kw.update({"size": (width_w, width_h)} if vals["size"] is not None else {"scale_factor": (1.0, 1.0)})
+                if not bool((F.interpolate(one.reshape(1, 1, 1, 1).expand(1, 1, width_w, width_h).contiguous(), **kw) == 1).all()):
+                    continue
+            got = Mh @ probe.reshape(H, W) @ Mw.t()
+            err = (got - want).abs().max()
+            scale = (Mh.abs() @ probe.reshape(H, W).abs() @ Mw.abs().t()).max()
+            if bool(err <= 64 * torch.finfo(like.dtype).eps * scale + torch.finfo(like.dtype).tiny):
+                break
+        else:
+            raise SweepUnsupported(f"{op} in mode {vals.get('mode')!r} is not a separable linear map of the last {k} dims of a "
+                                   f"{(H, W)} plane" + ("" if err is None else f" (|y - Mh x Mw^T| = {float(err):.2e})"))
+        (csr_h, th), (csr_w, tw) = _csr_transposed(Mh), _csr_transposed(Mw)
+    return ResampleTables(Mh, Mw, csr_h, csr_w, (th, tw))
+
+
+def resample_vjp_math(g, Mh, Mw, S=None):
+    """``dx = Mh^T g Mw`` ``[..., H, W]`` for the seeds stacked in ``g`` ``[..., OH, OW]`` - the sum of lk_resample_vjp_f32 as two
+    dense matrix products (any dtype; deterministic: no atomics, unlike stock ``upsample_*_backward`` / ``*_pad*_backward``)"""
+    OH, OW = g.shape[-2:]
+    t = (g.reshape(-1, OW) @ Mw.to(g.dtype)).reshape(*g.shape[:-1], Mw.shape[1])  # (one GEMM over all rows of all planes)
+    if tuple(Mh.shape) == (1, 1) and bool(Mh[0, 0] == 1):  # (a 1-D operation: the height's matrix is the identity)
+        return t
+    return torch.matmul(Mh.t().to(g.dtype), t)
+
+
 def _same(t):
     """the forward of a node that hands its source on (the ``[0]`` / ``.values`` of a ``max(dim)``, whose node holds the values)"""
     return t
@@ -855,6 +1076,12 @@ def classify(node: fx.Node, modules: dict) -> Rule:
     elif kind == SUB:
         src = _classify_sub(node, modules)
         fn, args, kwargs, what = operator.sub, src, {}, "sub"  # (`-=` / `sub_` must not write into a kept tensor)
+    elif kind == _RESAMPLE:
+        x, vals, what = _classify_resample(node, m, flavour, modules)
+        # (one spelling: the modules make exactly this call; every argument by name, resolved on the values in the forward)
+        fn, src, args, kwargs, static = (F.interpolate if flavour == "interpolate" else F.pad), (x,), (x,), vals, (flavour,)
+        if classify(x, modules).kind == CONST:  # (a resampled frozen buffer: a constant of the sweep, evaluated in the forward)
+            return Rule(CONST, (), fn, ((x,), vals), f"constant {what} of {x.name}")
     return Rule(kind, src, fn, (tuple(args), kwargs), what, flavour, m if kind in (CONV, LINEAR, BN, NORM, _EMBED, _MHA) else None, static)
 
 
@@ -1287,6 +1514,8 @@ class SeedBatchedSweep:
                 out = torch.neg(inp)
             elif kind == SUB:
                 out = self._run_sub(r, args)
+            elif kind == _RESAMPLE:
+                out, keep = self._run_resample(node, r, inp, kwargs, need_vjp)
             elif kind == ADD and any(isinstance(a, fx.Node) and self.rule[a].kind == CONST for a in r.src):
                 out = self._add_const(r, args, kwargs)
             elif r.flavour == "generic" and need_vjp:
@@ -1833,6 +2062,75 @@ class SeedBatchedSweep:
             dx = reduce_vjp_math(gv, L, idx, x3, y, cnt)
         return dx.reshape(S * shp[0], *shp[1:])
 
+    #: ``False``: a static resampling stays on the torch math of its rule (`resample_vjp_math`: two dense matrix products)
+    #: whatever the kernel object offers
+    use_resample_kernels = True
+
+    def _resample_kernels(self, g, entry, P):
+        """``(kernel object, None)`` when csrc/lk_resample.hip serves the cotangent ``g`` of a resampling with the cached ``entry``
+        (an object with the entry points - the stock emulation has none -, fp32, tap lists inside the kernel's cap, a shape inside
+        the contract), else ``(None, why)``: the same sum in torch.  The tables are packed for the device (and validated) once."""
+        tables = entry[0]
+        if not self.use_resample_kernels:
+            return None, "use_resample_kernels is off"
+        K = self.kernels() if self.kernels is not None else None
+        if K is None or not hasattr(K, "resample_vjp"):
+            return None, "the kernel object has no resample_vjp"
+        if g.dtype != torch.float32:
+            return None, f"dtype {g.dtype}"
+        if max(tables.taps) > K.RESAMPLE_MAX_TAPS:
+            return None, f"{max(tables.taps)} taps per input exceed the kernel's cap of {K.RESAMPLE_MAX_TAPS}"
+        (OH, H), (OW, W) = tables.Mh.shape, tables.Mw.shape
+        if P < 1 or K.resample_variant(P, OH, OW, H, W, *tables.taps) is None:
+            return None, "a shape outside the kernel's contract"
+        if entry[1] is None:
+            entry[1] = (K.resample_pack(*tables.csr_h, H, OH), K.resample_pack(*tables.csr_w, W, OW))
+        return K, None
+
+    def _run_resample(self, node, r, x, kw, need_vjp=True):
+        """static resampling forward -> ``(out, (cache entry, input shape, k))``: torch's own call on the ``[B, ...]`` value (bit-equal
+        to the model's); the axis matrices of the resolved geometry are derived once (`resample_tables`, which holds them against the
+        operator itself: a mode that is not separable is refused by name) and cached on the sweep"""
+        op, kw = r.args[0], dict(kw)
+        if not torch.is_tensor(x):
+            raise SweepUnsupported(f"{r.what}: the operand is not a tensor ({type(x).__name__})")
+        if not x.is_floating_point():
+            raise SweepUnsupported(f"{r.what}: the operand is the integer input (a resampling of token ids has no cotangent)")
+        if op == "interpolate" and kw["size"] is not None:  # (values of a size(): plain ints for torch and for the cache key)
+            kw["size"] = tuple(int(v) for v in kw["size"]) if isinstance(kw["size"], (tuple, list)) else int(kw["size"])
+        k = resample_dims(op, kw, x.shape, r.what)
+        try:
+            out = r.fn(x, **kw)
+        except (RuntimeError, ValueError, TypeError, NotImplementedError, AssertionError) as e:  # (torch's own words)
+            raise SweepUnsupported(f"{r.what}: {e}") from e
+        if out.dim() != x.dim() or tuple(out.shape[:-k]) != tuple(x.shape[:-k]):
+            raise SweepUnsupported(f"{r.what}: {tuple(x.shape)} -> {tuple(out.shape)} changes more than the last {k} dims")
+        if not need_vjp:
+            return out, None
+        in_hw = (1 if k == 1 else int(x.shape[-2]), int(x.shape[-1]))
+        out_hw = (1 if k == 1 else int(out.shape[-2]), int(out.shape[-1]))
+        key = (op, repr(sorted(kw.items())), in_hw, out_hw, k, x.dtype, str(x.device))
+        cache = self.__dict__.setdefault("_resample_cache", {})
+        entry = cache.get(key)
+        if entry is None:
+            tables = resample_tables(op, kw, in_hw, out_hw, k, x)
+            entry = cache[key] = [tables, None]  # ([1]: the tables as the kernel object packed them)
+        return out, (entry, tuple(x.shape), k)
+
+    def _resample_vjp(self, node, saved, g, S):
+        """input cotangent of a static resampling for all seeds, ``g`` ``[S*B, ...]``: ONE launch of lk_resample_vjp_f32 over the
+        ``S B C`` planes, which writes every element, or ``Mh^T g Mw`` in torch (`resample_vjp_math`); both deterministic.
+        ``self.resample_route[node name]`` says which one ran, and why"""
+        entry, shp, k = saved
+        tables = entry[0]
+        (OH, H), (OW, W) = tables.Mh.shape, tables.Mw.shape
+        P = g.numel() // (OH * OW)
+        gv = g.contiguous().reshape(P, OH, OW)
+        K, why = self._resample_kernels(gv, entry, P)
+        self.__dict__.setdefault("resample_route", {})[node.name] = "kernel" if K is not None else f"torch math: {why}"
+        dx = K.resample_vjp(gv, *entry[1]) if K is not None else resample_vjp_math(gv, tables.Mh, tables.Mw, S)
+        return dx.reshape(g.shape[0], *shp[1:])
+
     def _add_const(self, r, args, kwargs):
         """``x + constant``: the constant must broadcast to exactly the other operand's shape (the other way round the VJP is
         a reduction, which has no rule)"""
@@ -2037,7 +2335,7 @@ class SeedBatchedSweep:
             ATTN: "_vjp_attn", PERMUTE: "_vjp_permute", ADD: "_vjp_add", MUL: "_vjp_mul", MATMUL: "_vjp_matmul",
             SOFTMAX: "_vjp_softmax", SCALE: "_vjp_scale", NEG: "_vjp_neg", SUB: "_vjp_sub", CAT: "_vjp_cat", SLICE: "_vjp_slice",
             _EXPAND: "_vjp_identity", _EMBED: "_vjp_leaf", _PARAM: "_vjp_leaf", _MAXRED: "_vjp_maxred", _SUMRED: "_vjp_sumred",
-            _MHA: "_vjp_mha", _MHAOUT: "_vjp_mhaout",
+            _MHA: "_vjp_mha", _MHAOUT: "_vjp_mhaout", _RESAMPLE: "_vjp_resample",
             SIZE: None, GETITEM: None, SPLIT: None, CONST: None, "placeholder": None, "output": None}
 
     def _vjp_rule(self, r):
@@ -2104,6 +2402,9 @@ class SeedBatchedSweep:
 
     def _vjp_maxred(self, walk, node, r, g, g2):
         walk.push(r.src[0], self._reduce_vjp(self.saved[node], g, walk.S))
+
+    def _vjp_resample(self, walk, node, r, g, g2):
+        walk.push(r.src[0], self._resample_vjp(node, self.saved[node], g, walk.S))
 
     def _vjp_sumred(self, walk, node, r, g, g2):
         shp, keep, dims = self.saved[node]

@@ -40,7 +40,7 @@ from torch import nn
 from laplace_amd import conv as cv
 from laplace_amd._lib import SplitTensor
 from laplace_amd.sweep import (ACT, ADD, ATTN, AVGPOOL, BN, CAT, CONST, CONV, _EMBED, _EXPAND, GETITEM, GPOOL, IDENTITY, LINEAR, MATMUL, MAXPOOL, MEAN, MUL, NEG, NORM,
-                               _MAXRED, _MHA, _MHAOUT, _PARAM, PERMUTE, RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SUB, _SUMRED, SeedBatchedSweep, SweepUnsupported, _sum, _Walk)
+                               _MAXRED, _MHA, _MHAOUT, _PARAM, PERMUTE, _RESAMPLE, RESHAPE, SCALE, SIZE, SLICE, SOFTMAX, SPLIT, SUB, _SUMRED, SeedBatchedSweep, SweepUnsupported, _sum, _Walk)
 
 # node kinds by what the NHWC walk does with them
 _LAZY = {CONV, BN, ACT, IDENTITY}  # hand all incoming cotangent parts to ``_to_split`` (which can fuse a pending convolution)
@@ -54,7 +54,7 @@ _FEATURE = {CONV, BN, GPOOL, GN_MAP, CAT_MAP, SLICE_MAP, GATE_MAP} | _POOL  # pr
 _MAP_SOURCES = {CONV, BN, GN_MAP, CAT_MAP, SLICE_MAP, GATE_MAP, "placeholder"} | _POOL  # what a node that sits on a feature map has upstream
 # a graph with one of these runs through the NCHW sweep (MUL: unless ``nhwc_mul`` serves it as a squeeze-and-excitation gate on
 # csrc/lk_gate.hip, or both its operands lie in the head region)
-_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE, NEG, SUB, _EMBED, _PARAM, _EXPAND, _MAXRED, _SUMRED, _MHA, _MHAOUT}
+_NO_RULE = {MEAN, SIZE, GETITEM, ATTN, PERMUTE, CONST, MUL, MATMUL, SOFTMAX, SCALE, NEG, SUB, _EMBED, _PARAM, _EXPAND, _MAXRED, _SUMRED, _MHA, _MHAOUT, _RESAMPLE}
 _GATE_CHAIN = {CONV, LINEAR, ACT, IDENTITY, RESHAPE}  # what the branch from the pooled tensor to a served gate may hold
 # kinds the head region holds too (plain tensors after the flatten): a node of these whose parts are all plain tensors, and that is
 # no served gate, runs the parent's rule for its kind (`SplitSweep._head_vjp`).  The value: the refusal where another part reaches
@@ -251,6 +251,9 @@ class SplitSweep(SeedBatchedSweep):
             if r.kind == CONV and isinstance(r.mod, nn.Conv1d):
                 return f"{node.target}: Conv1d has no NHWC rule"
             if r.kind in (_MAXRED, _SUMRED) or r.flavour == "1d":
+                return f"{node.target if node.op == 'call_module' else node.name}: {r.what} has no NHWC rule"
+        for node, r in self.rule.items():  # (upsampling and padding: named before the ``size()`` a traced ``size=`` reads)
+            if r.kind == _RESAMPLE:
                 return f"{node.target if node.op == 'call_module' else node.name}: {r.what} has no NHWC rule"
         for node, r in self.rule.items():
             if r.kind == ATTN:  # (named first: it is what decides the walk of a transformer block)
