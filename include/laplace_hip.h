@@ -954,7 +954,10 @@ int lk_vjp_scale_mask_f32(const float* g, const float* g2, const void* m, int m_
  * Dense last-layer GGN.  Replaces last_layer_jacobians + GGNInterface.full for a Linear head
  * (curvature.py:131-167,375-411) without materialising Js, using J_n = I_C (x) [phi_n, 1]:
  *   H[(j,a),(k,b)] += alpha * sum_n (delta_jk p_nj - p_nj p_nk) pt_na pt_nb      pt = [phi, 1]
- *                   = alpha * ( blockdiag_j Gram(sqrt(p_j).Pt) - Gram(Y) ),  Y[n][(j,a)] = p_nj pt_na
+ *                   = alpha * ( blockdiag_j Gram(sqrt(p_j s_j).Pt) - offdiag_jk Gram(Y) ),
+ *                     s_nj = sum_{k != j} p_nk,  Y[n][(j,a)] = p_nj pt_na
+ * No class-diagonal block is formed as a difference, so rows with p_j within an ulp of 0 or 1 keep their
+ * digits and H stays positive semi-definite to rounding.
  * phi: [B][D]; probs: [B][C] softmax probabilities (NULL = regression, Lambda = I);
  * H: [P][P] in the reference's parameter order (weight [C][D] row-major, then bias [C]),
  * P = C*D (+C if has_bias).

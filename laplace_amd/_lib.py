@@ -2172,8 +2172,9 @@ class HipKernels:
         nb = self.lib.lk_ll_ggn_workspace_bytes(B, C, D)
         ws = self._workspace(nb, phi.device)
         Dt = D + (1 if has_bias else 0)
-        # structured form: C block-diagonal Grams of sqrt(p_j) phi~ minus the Gram of Y = [p_j phi~]_j — about 2 C^2 Dt^2 flop per
-        # sample against the 2 C^3 Dt^2 of J^T Lambda J as the reference writes it (curvature.py:375-411)
+        # structured form: C block-diagonal Grams of sqrt(p_j sum_{k != j} p_k) phi~ minus the off-diagonal blocks of the Gram of
+        # Y = [p_j phi~]_j — about 2 C^2 Dt^2 flop per sample against the 2 C^3 Dt^2 of J^T Lambda J as the reference writes it
+        # (curvature.py:375-411)
         self._rc(self._timed("llggn", 2.0 * B * C * C * Dt * Dt, phi.device, lambda: self.lib.lk_ll_ggn_full_f32(
             _ptr(phi), _ptr(probs), B, C, D, 1 if has_bias else 0, float(alpha), _ptr(H), _ptr(ws), ws.numel(),
             self._stream(phi.device)), nbytes=4.0 * (B * D + B * C + (C * Dt) ** 2)), "lk_ll_ggn_full_f32")

@@ -7,8 +7,12 @@
 //
 // GGN.  With pt = [phi, 1] (D~ = D + has_bias) and softmax probabilities p:
 //     H[(j,a),(k,b)] = sum_n (delta_jk p_nj - p_nj p_nk) pt_na pt_nb
-//                    = blockdiag_j Gram(sqrt(p_j) . Pt)  -  Gram(Y),    Y[n][(j,a)] = p_nj pt_na
+//                    = blockdiag_j Gram(sqrt(p_j s_j) . Pt)  -  offdiag_jk Gram(Y),
+//                      s_nj = sum_{k != j} p_nk,   Y[n][(j,a)] = p_nj pt_na
 //   i.e. C small Grams + ONE Gram with K = B rows (not B*C): 2 B C^2 D~^2 flop instead of 2 B C^3 D~^2.
+//   No class-diagonal block is a difference: p_j - p_j^2 as Gram(sqrt(p_j) Pt) - Gram(p_j Pt), two separately rounded
+//   fp32 Grams, loses every digit of p_j (1 - p_j) in the rows of a trained classifier, where p_j is within an ulp of 0
+//   or 1, and leaves H indefinite.  The class-diagonal blocks of Gram(Y) are computed and not used.
 //   Regression (probs == NULL): H = I_C (x) Gram(Pt).  All Grams run on the exact-fp32 MFMA engine
 //   of lk_gram.hip; the result is scattered from the "augmented" order (j, a) to the reference's
 //   parameter order (weight [C][D] row-major, then bias [C]).
@@ -27,7 +31,7 @@ __device__ __forceinline__ float phi_aug(const float* __restrict__ phi, int64_t 
 __device__ __forceinline__ int ref_index(int j, int a, int C, int D) { return a < D ? j * D + a : C * D + j; }
 
 // mode 0: out[n][j*Dt + a] = p[n][j] * pt[n][a]   (Y)
-// mode 1: out[n][a]        = sqrt(p[n][jsel]) * pt[n][a]
+// mode 1: out[n][a]        = sqrt(p[n][jsel] * sum_{k != jsel} p[n][k]) * pt[n][a]
 // mode 2: out[n][a]        = pt[n][a]
 __global__ __launch_bounds__(256) void ll_build_rows_kernel(const float* __restrict__ phi,
                                                             const float* __restrict__ probs, int64_t B, int C, int D,
@@ -42,7 +46,10 @@ __global__ __launch_bounds__(256) void ll_build_rows_kernel(const float* __restr
       const int j = col / Dt, a = col - j * Dt;
       v = probs[n * C + j] * phi_aug(phi, n, a, D);
     } else if (mode == 1) {
-      v = sqrtf(probs[n * C + jsel]) * phi_aug(phi, n, col, D);
+      float others = 0.f;  // (not 1 - p: that is the cancellation)
+      for (int k = 0; k < C; ++k)
+        if (k != jsel) others += probs[n * C + k];
+      v = sqrtf(probs[n * C + jsel] * others) * phi_aug(phi, n, col, D);
     } else {
       v = phi_aug(phi, n, col, D);
     }
@@ -50,8 +57,8 @@ __global__ __launch_bounds__(256) void ll_build_rows_kernel(const float* __restr
   }
 }
 
-// H[ref(j,a)][ref(k,b)] += src[(j,a)][(k,b)]  for the full augmented matrix (srcdim = C*Dt), or, with
-// block >= 0, add the Dt x Dt matrix `src` into diagonal block j = block (block == -2: into every block).
+// H[ref(j,a)][ref(k,b)] += src[(j,a)][(k,b)]  for the blocks j != k of the full augmented matrix (srcdim = C*Dt), or,
+// with block >= 0, add the Dt x Dt matrix `src` into diagonal block j = block (block == -2: into every block).
 __global__ __launch_bounds__(256) void ll_scatter_kernel(const float* __restrict__ src, int C, int D, int Dt,
                                                          int block, float* __restrict__ H, int64_t P) {
   if (block == -1) {
@@ -59,7 +66,7 @@ __global__ __launch_bounds__(256) void ll_scatter_kernel(const float* __restrict
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
       const int r = (int)(idx / n), c = (int)(idx - (int64_t)r * n);
       const int j = r / Dt, a = r - j * Dt, k = c / Dt, b = c - k * Dt;
-      H[(int64_t)ref_index(j, a, C, D) * P + ref_index(k, b, C, D)] += src[idx];
+      if (j != k) H[(int64_t)ref_index(j, a, C, D) * P + ref_index(k, b, C, D)] += src[idx];
     }
   } else {
     const int64_t total = (int64_t)Dt * Dt;
@@ -274,7 +281,7 @@ extern "C" int lk_ll_ggn_full_f32(const float* phi, const float* probs, int64_t 
                        -2, H, (int64_t)C * Dt);
     return check_launch("lk_ll_ggn_full_f32");
   }
-  // - Gram(Y)
+  // - Gram(Y), class pairs j != k
   hipLaunchKernelGGL(ll_build_rows_kernel, dim3(grid_for(B * p.P)), dim3(256), 0, stream, phi, probs, B, (int)C, (int)D,
                      Dt, 0, 0, Y);
   if (hipMemsetAsync(Haug, 0, (size_t)p.P * p.P * 4, stream) != hipSuccess) return LK_ELAUNCH;
@@ -282,7 +289,7 @@ extern "C" int lk_ll_ggn_full_f32(const float* phi, const float* probs, int64_t 
   if (rc) return rc;
   hipLaunchKernelGGL(ll_scatter_kernel, dim3(grid_for(p.P * p.P)), dim3(256), 0, stream, Haug, (int)C, (int)D, Dt, -1, H,
                      p.P);
-  // + blockdiag_j Gram(sqrt(p_j) . Pt)
+  // + blockdiag_j Gram(sqrt(p_j s_j) . Pt)
   for (int j = 0; j < C; ++j) {
     hipLaunchKernelGGL(ll_build_rows_kernel, dim3(grid_for(B * Dt)), dim3(256), 0, stream, phi, probs, B, (int)C, (int)D,
                        Dt, 1, j, X);
