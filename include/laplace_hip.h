@@ -1233,6 +1233,40 @@ int lk_spectral_grid_f32(const float* R, const float* lam, float hfac, const flo
                          int64_t P, float* var, void* ws, size_t ws_bytes, void* stream);
 int lk_spectral_variant(int form, int64_t N, int64_t C, int64_t D_or_P, int64_t G, int aligned);
 
+/* The link approximations of the GLM predictive for classification, fused: (f_mu [B][C], f_var) -> class probabilities
+ * probs [B][C] in one launch.  Replaces the torch sequences of baselaplace.py:598-695 (probit, the Laplace bridge, the mean over
+ * Monte-Carlo softmax samples) and utils/utils.py:337-378 (normal_samples: a batched Cholesky, a batched product with the shared
+ * draw and two [n_samples][B][C] tensors).
+ *   link   LK_LINK_PROBIT       softmax(f_mu / sqrt(1 + pi/8 var_diag))
+ *          LK_LINK_MC           L = chol(f_var_b) (lower, fp32);  f_s = f_mu + L z[:, s];  probs = (1 / n) sum_s softmax(f_s)
+ *                               with the maximum subtracted and the sum over s in ascending order
+ *          LK_LINK_BRIDGE       the Dirichlet mean of the Laplace bridge from the row sums, column sums, total and diagonal of
+ *          LK_LINK_BRIDGE_NORM  f_var_b (one streaming pass), the second with the variance rescaled to sqrt(C / 2); NaN -> 1
+ *   diag   non-zero: f_var is [B][C] (the marginal variances; mc then uses L = sqrt(f_var), the bridge a diagonal matrix);
+ *          zero: f_var is [B][C][C]; mc reads its lower triangle and diagonal only, the bridge all of it
+ *   z      [C][n_samples] standard-normal draws shared by all samples of the batch (mc only, may be null otherwise); the kernel
+ *          consumes them and draws nothing itself
+ *   info   [B]: 0, or j + 1 where mc met a pivot <= 0 or a non-finite pivot at column j; that sample's probs row is NaN, every
+ *          other row is unaffected.  The other links always write 0.
+ * Three regimes by C: C <= 64: a wave per sample, four samples per workgroup, the factorisation in registers a lane per row
+ * (the block staged through a wave-private padded LDS tile); 64 < C <= LK_LINK_MAX_C: a workgroup per sample, L resident in LDS
+ * (192 * 193 * 4 bytes = 148 KiB of the 160), a right-looking blocked Cholesky with 16-wide panels whose trailing update and
+ * L z run on the exact fp32 matrix instruction, z staged 16 draws at a time; C > LK_LINK_MAX_C: refused.  One owner per output
+ * element, a fixed reduction order, plain stores, no atomics: two equal calls are bit-equal.
+ * Contract: f_mu, f_var, probs, info non-null, z non-null for mc; every pointer given 16-byte aligned; 1 <= C <= LK_LINK_MAX_C;
+ *   0 <= B < 2^31; 1 <= n_samples < 2^20 for mc (ignored otherwise); link in 0..3; probs and info overlap neither an input nor
+ *   each other.  B == 0 returns LK_OK before any device call.
+ * lk_glm_link_variant (host only): 0 (wave per sample) or 1 (workgroup per sample), or a negative value for a shape the entry
+ * point refuses. */
+#define LK_LINK_MAX_C 192
+#define LK_LINK_PROBIT 0
+#define LK_LINK_MC 1
+#define LK_LINK_BRIDGE 2
+#define LK_LINK_BRIDGE_NORM 3
+int lk_glm_link_f32(const float* f_mu, const float* f_var, const float* z, int64_t B, int64_t C, int64_t n_samples, int link,
+                    int diag, float* probs, int32_t* info, void* stream);
+int lk_glm_link_variant(int64_t B, int64_t C, int64_t n_samples, int link, int diag);
+
 #ifdef __cplusplus
 }
 #endif

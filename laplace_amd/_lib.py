@@ -200,6 +200,8 @@ SIGNATURES = {
     "lk_spectral_quadform_f32": (_int, [_vp, _vp, _f32, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "lk_spectral_grid_f32": (_int, [_vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "lk_spectral_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int]),
+    "lk_glm_link_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
+    "lk_glm_link_variant": (_int, [_i64, _i64, _i64, _int, _int]),
 }
 
 
@@ -2583,6 +2585,45 @@ class HipKernels:
             return None
         return {"ct": r & 15, "grid": bool(r & 16), "pairs": bool(r & 32), "ll": bool(r & 64), "split": (r >> 8) & 4095,
                 "gc": r >> 20}
+
+    # ---- link approximations of the GLM predictive (csrc/lk_link.hip) -------------------------------------------
+    LINKS = {"probit": 0, "mc": 1, "bridge": 2, "bridge_norm": 3}
+    LINK_MAX_C = 192  # LK_LINK_MAX_C (include/laplace_hip.h)
+
+    def glm_link(self, f_mu, f_var, z, link, diag=False, probs=None, info=None):
+        """``(probs [B, C], info [B])`` of one link approximation of the classification GLM predictive, in one launch:
+        ``link`` 'probit', 'mc', 'bridge' or 'bridge_norm'; ``f_var`` is ``[B, C, C]``, or ``[B, C]`` with ``diag``; ``z [C, n]``
+        is the shared standard-normal draw of 'mc' (``None`` otherwise).  ``info[b] = j + 1`` where the Cholesky factorisation of
+        'mc' met a pivot that is not positive at column ``j`` (row ``b`` of ``probs`` is then NaN).  ``probs`` / ``info``: buffers
+        to write into (16-byte aligned)."""
+        code = self.LINKS[link] if isinstance(link, str) else int(link)
+        _check(f_mu, "f_mu"), _check(f_var, "f_var")
+        B, C = f_mu.shape
+        if f_var.shape != ((B, C) if diag else (B, C, C)):
+            raise LaplaceHipError(f"glm_link: f_var must be {'[B, C]' if diag else '[B, C, C]'} for f_mu [B, C]")
+        n = 0
+        if code == 1:
+            _check(z, "z")
+            if z.dim() != 2 or z.shape[0] != C:
+                raise LaplaceHipError("glm_link: z must be [C, n_samples]")
+            n = z.shape[1]
+        if probs is None:
+            probs = torch.empty(B, C, dtype=torch.float32, device=f_mu.device)
+        if info is None:
+            info = torch.empty(B, dtype=torch.int32, device=f_mu.device)
+        _check(probs, "probs"), _check(info, "info", torch.int32)
+        if probs.shape != (B, C) or info.shape != (B,):
+            raise LaplaceHipError("glm_link: probs must be [B, C] and info [B]")
+        self._rc(self.lib.lk_glm_link_f32(_ptr(f_mu), _ptr(f_var), _ptr(z) if code == 1 else None, B, C, n, code,
+                                          1 if diag else 0, _ptr(probs), _ptr(info), self._stream(f_mu.device)), "lk_glm_link_f32")
+        return probs, info
+
+    def glm_link_variant(self, B, C, n_samples=1, link="mc", diag=False):
+        """the regime ``lk_glm_link_f32`` takes for a shape (host only): 0 a wave per sample, 1 a workgroup per sample, ``None``
+        for a shape it refuses"""
+        code = self.LINKS[link] if isinstance(link, str) else int(link)
+        r = int(self.lib.lk_glm_link_variant(int(B), int(C), int(n_samples), code, 1 if diag else 0))
+        return None if r < 0 else r
 
 
 _KERNELS = None

@@ -446,6 +446,9 @@ class _HipLaplace:
         f_mu, f_var = self._glm_predictive_distribution(x, diagonal_output=diagonal_output)
         if self.likelihood == "regression":
             return f_mu, f_var
+        K = self._link_kernels(f_mu, f_var)
+        if K is not None:
+            return self._glm_link(K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator)
         if link_approx == "mc":
             fv = f_var if not diagonal_output else torch.diag_embed(f_var)
             return self._glm_predictive_samples(f_mu, fv, n_samples, diagonal_output, generator).mean(dim=0)
@@ -456,6 +459,34 @@ class _HipLaplace:
         var_diag = f_var if diagonal_output else torch.diagonal(f_var, dim1=1, dim2=2)
         kappa = 1 / torch.sqrt(1.0 + pi / 8 * var_diag)
         return torch.softmax(kappa * f_mu, dim=-1)
+
+    #: route the link approximation of the classification GLM predictive through the fused kernel (csrc/lk_link.hip) where it
+    #: applies: fp32 device tensors, C <= 192 outputs, a kernel provider that has ``glm_link``.  Off: the torch sequences below.
+    use_link_kernels = True
+
+    def _link_kernels(self, f_mu, f_var):
+        """the kernel provider when the fused link kernel serves ``(f_mu, f_var)``, else ``None`` (the torch path runs)"""
+        if not (self.use_link_kernels and f_mu.is_cuda and f_mu.dtype == f_var.dtype == torch.float32 and f_mu.dim() == 2):
+            return None
+        K = _pred.get_kernels()
+        return K if hasattr(K, "glm_link") and 1 <= f_mu.shape[1] <= getattr(K, "LINK_MAX_C", 0) else None
+
+    def _glm_link(self, K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator):
+        """``link_approx`` of ``(f_mu, f_var)`` in one launch; 'mc' consumes the draw ``_glm_functional_samples`` makes."""
+        z = None
+        if link_approx == "mc":
+            z = torch.randn(f_mu.shape[1], n_samples, device=f_mu.device, dtype=f_mu.dtype, generator=generator)
+        elif link_approx != "probit" and diagonal_output:
+            f_mu, f_var = self._glm_predictive_distribution(x)  # the bridge needs the full output covariance
+            diagonal_output = False
+        probs, info = K.glm_link(f_mu.contiguous(), f_var.contiguous(), z, link_approx, diag=diagonal_output)
+        if link_approx == "mc" and not diagonal_output:
+            status = info.cpu()  # (the one host read of the call, as torch.linalg.cholesky reads its status)
+            if bool(status.any()):
+                b = int(status.nonzero()[0])
+                raise torch.linalg.LinAlgError(f"glm_link: the predictive covariance of sample {b} is not positive-definite "
+                                               f"(pivot {int(status[b])} of its Cholesky factorisation)")
+        return probs
 
     def _laplace_bridge(self, f_mu, f_var, normalise: bool):
         """Dirichlet mean of the Laplace bridge (baselaplace.py:665-692): project the logit Gaussian onto the
