@@ -1267,6 +1267,49 @@ int lk_glm_link_f32(const float* f_mu, const float* f_var, const float* z, int64
                     int diag, float* probs, int32_t* info, void* stream);
 int lk_glm_link_variant(int64_t B, int64_t C, int64_t n_samples, int link, int diag);
 
+/* The two reductions of KFAC-reduce (csrc/lk_kfacreduce.hip): with kfac_approx="reduce" (laplace/curvature/curvlinops.py:95-98
+ * hands it to curvlinops' KFAC) a weight-sharing layer's output gradients are summed and its inputs averaged over the shared
+ * positions before the outer products.  They replace the torch sequences  g.float().sum((1, 2)),  g.reshape(S B, Do, L).sum(2),
+ * a.reshape(B, L, Di).mean(1)  and  F.unfold(a, ...).mean(2); the rows they write go to lk_gram_tn_f32.
+ *
+ * lk_possum_f32 / lk_possum_f16x2: y[r][d] = alpha * sum_l x[r][l][d] (layout 0: x [R][L][D], D contiguous - NHWC maps with
+ *   L = H W, sequences [B, T, D]) or alpha * sum_l x[r][d][l] (layout 1: x [R][D][L] - NCHW maps); y [R][D] fp32.  The source
+ *   is an fp32 tensor, or the two fp16 planes x_h, x_l of a ONE-scale split tensor read as they lie, value = (float(x_h) +
+ *   float(x_l)) * 2^-sexp[0] with sexp a device word (no host read, no fp32 copy).  Layout 0: lanes across D, the positions of a
+ *   row split over 256 / lanes groups of the workgroup (few rows: narrower lane groups, more tiles); layout 1: up to 256 lanes
+ *   a row.  Partial sums add in ascending order and meet in a fixed tree over LDS; one owner per output, plain stores, no
+ *   atomics: two equal calls are bit-equal.  16-byte fp32 (8-byte fp16) accesses where the contiguous extent is a multiple of
+ *   4 and x (the planes: 8 bytes) and y are 16-byte aligned, 4-byte (2-byte) ones otherwise.
+ *   Minimal traffic: x once plus 4 R D bytes.
+ * Contract: pointers non-null, fp32 and sexp 4-byte, planes 2-byte aligned; layout 0 or 1; 0 <= R, 1 <= L < 2^30,
+ *   1 <= D < 2^30, R * L * D < 2^40; y overlaps no input.  R == 0 returns LK_OK before any device call.
+ * lk_possum_variant (host only): vec | layout << 1 | log2(lanes) << 2 | workgroups << 8 for a shape (`aligned`: the bases allow
+ *   the wide accesses), or a negative value for a shape the entry points refuse.
+ *
+ * lk_patch_mean_f32: the rows of the input factor of a dense convolution under `reduce`, without the patch matrix:
+ *     out[b][col(kh, kw, ci)] = 1/(OH OW) sum_{oh, ow} x[b][ci][oh sh + kh dh - ph][ow sw + kw dw - pw]
+ *   with out-of-image taps adding zero.  x is the logical [B, C, H, W] map in NCHW memory (channels_last 0) or NHWC memory
+ *   (channels_last 1); out [B][C kh kw] fp32 with col = (kh kw_n + kw) C + ci (unfold_order 0, the accumulator's native order)
+ *   or ci kh_n kw_n + kh kw_n + kw (unfold_order 1, F.unfold's).  The sum is separable: a workgroup owns (sample, block of
+ *   channels), reads every element of its slab ONCE while it forms the sums over one axis's strided position sets in LDS
+ *   (lanes along memory: the columns' sets per row for NHWC, the rows' sets per column for NCHW), then a thread per output
+ *   sums those over the other axis's set.  Fixed orders, one owner per output, no atomics: bit-reproducible.
+ *   Minimal traffic: 4 B H W C + 4 B kh kw C bytes.
+ * Contract: x, out non-null and 4-byte aligned; 0 <= B; 1 <= C, H, W < 2^20; B C H W < 2^40; 1 <= kh, kw <= 16; 1 <= stride,
+ *   dilation < 65536; 0 <= padding < 65536; the dilated kernel fits the padded map; groups == 1; out does not overlap x; the
+ *   one-axis sums of the narrowest channel block (H kw, or kh W, floats a channel) fit the 160 KiB of LDS - a shape that does
+ *   not is refused with LK_EINVAL and stays with the caller.  B == 0 returns LK_OK before any device call.
+ * lk_patch_mean_variant (host only): vec | channels of a block << 1 | KiB of LDS << 12 (`aligned`: x is 16-byte aligned), or a
+ *   negative value for a shape lk_patch_mean_f32 refuses. */
+int lk_possum_f32(const float* x, int64_t R, int64_t L, int64_t D, int layout, float alpha, float* y, void* stream);
+int lk_possum_f16x2(const void* x_h, const void* x_l, const int* sexp, int64_t R, int64_t L, int64_t D, int layout, float alpha,
+                    float* y, void* stream);
+int lk_possum_variant(int64_t R, int64_t L, int64_t D, int layout, int aligned);
+int lk_patch_mean_f32(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, int channels_last, int kh, int kw, int sh, int sw,
+                      int ph, int pw, int dh, int dw, int unfold_order, float* out, void* stream);
+int lk_patch_mean_variant(int64_t B, int64_t C, int64_t H, int64_t W, int channels_last, int kh, int kw, int sh, int sw, int ph,
+                          int pw, int dh, int dw, int aligned);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ instance.  Tests that exercise *host logic* on a CPU-only box install a stand-in
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -202,6 +203,11 @@ SIGNATURES = {
     "lk_spectral_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int]),
     "lk_glm_link_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
     "lk_glm_link_variant": (_int, [_i64, _i64, _i64, _int, _int]),
+    "lk_possum_f32": (_int, [_vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
+    "lk_possum_f16x2": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
+    "lk_possum_variant": (_int, [_i64, _i64, _i64, _int, _int]),
+    "lk_patch_mean_f32": (_int, [_vp] + [_i64] * 4 + [_int] * 10 + [_vp, _vp]),
+    "lk_patch_mean_variant": (_int, [_i64] * 4 + [_int] * 10),
 }
 
 
@@ -1992,6 +1998,61 @@ class HipKernels:
             return None
         return {"vec": bool(r & 1), "resident": bool(r & 2), "seed_split": bool(r & 4), "wide_index": bool(r & 8),
                 "lanes": 1 << ((r >> 4) & 7), "blocks": r >> 8}
+
+    # ---- KFAC-reduce: the position sum and the patch mean (csrc/lk_kfacreduce.hip) --------------------------------------------
+    def possum(self, x, R, L, D, layout=0, alpha=1.0):
+        """``y`` ``[R, D]`` fp32: ``alpha * sum_l x[r, l, d]`` (``layout`` 0, ``x`` ``[R][L][D]``) or ``alpha * sum_l x[r, d, l]``
+        (``layout`` 1, ``x`` ``[R][D][L]``) of a contiguous fp32 tensor or a one-scale :class:`SplitTensor` read as it lies (no fp32
+        copy, the scale word stays on the device), in one launch of lk_possum_f32 / lk_possum_f16x2"""
+        ptrs, shape, dev = _split_operand(x, "possum", "x", "no [R][L][D] / [R][D][L] tensor")
+        R, L, D = int(R), int(L), int(D)
+        if R < 0 or L < 1 or D < 1 or math.prod(shape) != R * L * D:
+            raise LaplaceHipError(f"possum: x {tuple(shape)} does not hold R * L * D = {R} * {L} * {D} elements")
+        y = torch.empty(R, D, dtype=torch.float32, device=dev)
+        if ptrs[0] is not None:
+            self._rc(self.lib.lk_possum_f32(ptrs[0], R, L, D, int(layout), float(alpha), _ptr(y), self._stream(dev)), "lk_possum_f32")
+        else:
+            self._rc(self.lib.lk_possum_f16x2(*ptrs[1:], R, L, D, int(layout), float(alpha), _ptr(y), self._stream(dev)),
+                     "lk_possum_f16x2")
+        return y
+
+    def possum_variant(self, R, L, D, layout=0, aligned=True):
+        """lk_possum_variant: the path the position sum takes for a shape (host only), or ``None`` for a shape it refuses"""
+        r = int(self.lib.lk_possum_variant(int(R), int(L), int(D), int(layout), int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "layout": (r >> 1) & 1, "lanes": 1 << ((r >> 2) & 15), "blocks": r >> 8}
+
+    @staticmethod
+    def _patch_geometry(kernel_size, stride, padding, dilation):
+        return [int(v) for pair in (kernel_size, stride, padding, dilation) for v in pair]
+
+    def patch_mean(self, x, kernel_size, stride, padding, dilation, unfold_order=False):
+        """``out`` ``[B, C kh kw]`` fp32: the mean over the output positions of the patches of a dense convolution,
+        ``F.unfold(x, ...).mean(2)`` without the patch matrix (lk_patch_mean_f32).  ``x``: logical ``[B, C, H, W]`` fp32, dense NCHW
+        or channels-last memory.  Columns in the accumulator's native order ``(kh, kw, ci)``, or ``unfold_order``: ``(ci, kh, kw)``"""
+        if not (torch.is_tensor(x) and x.dim() == 4):
+            raise LaplaceHipError("patch_mean: x is no [B, C, H, W] map")
+        cl = is_channels_last(x)
+        _check(x.permute(0, 2, 3, 1) if cl else x, "x")
+        B, C, H, W = (int(d) for d in x.shape)
+        geo = self._patch_geometry(kernel_size, stride, padding, dilation)
+        out = torch.empty(B, C * geo[0] * geo[1], dtype=torch.float32, device=x.device)
+        self._rc(self.lib.lk_patch_mean_f32(_ptr(x), B, C, H, W, int(cl), *geo, int(bool(unfold_order)), _ptr(out),
+                                            self._stream(x.device)), "lk_patch_mean_f32")
+        return out
+
+    def patch_mean_variant(self, shape, channels_last, kernel_size, stride, padding, dilation, aligned=True):
+        """lk_patch_mean_variant: the channel block and LDS ``lk_patch_mean_f32`` takes for a map ``shape = (B, C, H, W)`` (host
+        only), or ``None`` for a shape it refuses (the caller then keeps the unfold)"""
+        try:
+            geo = self._patch_geometry(kernel_size, stride, padding, dilation)
+        except (TypeError, ValueError):
+            return None  # (padding given as a string: no geometry of this kernel)
+        r = int(self.lib.lk_patch_mean_variant(*(int(d) for d in shape), int(bool(channels_last)), *geo, int(bool(aligned))))
+        if r < 0:
+            return None
+        return {"vec": bool(r & 1), "channel_block": (r >> 1) & 2047, "lds_kib": r >> 12}
 
     def softmax_vjp(self, g, y, S, is_log=False):
         """``dx`` (the shape of ``g``) of ``y = softmax(x, -1)`` / ``log_softmax(x, -1)`` for the ``S`` seeds stacked in the

@@ -534,7 +534,45 @@ class _HipCurvatureMixin:
             return m.out_features, m.in_features
         return m.out_channels, m.in_channels * m.kernel_size[0] * m.kernel_size[1]
 
-    def _factor_A(self, tap, N, alpha_a_scale, kfac_approx, A, fused=False):
+    #: ``False``: under ``kfac_approx="reduce"`` the sums over the weight-sharing positions stay on torch (``F.unfold(...).mean(2)``,
+    #: ``g.float().sum((1, 2))``, ``reshape(...).sum(...)``) instead of csrc/lk_kfacreduce.hip, as they do with a kernel object
+    #: that lacks ``possum`` / ``patch_mean``, a tensor that is not fp32 (or a one-scale split tensor) on the device, or a geometry
+    #: the patch mean refuses.  `KronAccumulator.reduce_route` says per tap which one ran.  The default follows the gate of
+    #: tools/kfac_reduce_bench.py (profiles/kfac_reduce_bench.json)
+    use_kfac_reduce_kernels = True
+
+    def _reduce_kernels(self, *tensors):
+        """the kernel object when the position sum and the patch mean serve these operands, else the reason they do not"""
+        K = get_kernels()
+        if not self.use_kfac_reduce_kernels:
+            return None, "torch math: use_kfac_reduce_kernels is off"
+        if not (hasattr(K, "possum") and hasattr(K, "patch_mean") and hasattr(K, "patch_mean_variant")):
+            return None, "torch math: the kernel object has no possum / patch_mean"
+        for t in tensors:
+            if isinstance(t, SplitTensor):
+                if t.sexp.numel() != 1 or t.chunked or not t.planes.is_cuda:
+                    return None, "torch math: no one-scale split tensor in the sweep's own layout"
+            elif t.dtype != torch.float32 or not t.is_cuda:
+                return None, f"torch math: {t.dtype} on {t.device.type}"
+        return K, None
+
+    @staticmethod
+    def _note_reduce(route, tap, why):
+        """``route[tap name]``: "kernel" while both sides of the tap took the kernels, else the (latest) reason one did not"""
+        if route is not None:
+            if why is not None:
+                route[tap.name] = why
+            else:
+                route.setdefault(tap.name, "kernel")
+
+    @staticmethod
+    def _possum_map(K, t, R, Do, L):
+        """``[R, Do]``: the sum over the ``L`` positions of ``R`` feature maps of ``Do`` channels, read in the memory order they have"""
+        if t.dim() == 4 and is_channels_last(t):
+            return K.possum(t.permute(0, 2, 3, 1), R, L, Do, 0)
+        return K.possum(t.contiguous(), R, L, Do, 1)
+
+    def _factor_A(self, tap, N, alpha_a_scale, kfac_approx, A, fused=False, route=None):
         """``A += alpha/(N L) * sum a a^T`` (input side; needs only the forward activations)."""
         K = get_kernels()
         a = tap.a.to(torch.float32)
@@ -545,7 +583,13 @@ class _HipCurvatureMixin:
             if kfac_approx == "expand" or L == 1:
                 K.gram_tn(a.reshape(-1, Di).contiguous(), alpha_a_scale / (N * L), A, upper_only=fused)
             else:  # 'reduce': average inputs over the weight-sharing positions
-                K.gram_tn(a.reshape(a.shape[0], L, Di).mean(1).contiguous(), alpha_a_scale / N, A, upper_only=fused)
+                KR, why = self._reduce_kernels(tap.a)
+                self._note_reduce(route, tap, why)
+                if KR is not None:
+                    rows = KR.possum(a.contiguous(), a.shape[0], L, Di, 0, 1.0 / L)
+                else:
+                    rows = a.reshape(a.shape[0], L, Di).mean(1).contiguous()
+                K.gram_tn(rows, alpha_a_scale / N, A, upper_only=fused)
             return A
         if kfac_approx == "expand":
             ak = keep_layout(a)
@@ -569,6 +613,17 @@ class _HipCurvatureMixin:
             K.gram_conv(ak, m.kernel_size, m.stride, m.padding, m.dilation, alpha_a_scale / (N * L), A,
                         upper_only=fused, native=fused)
         else:
+            KR, why = self._reduce_kernels(tap.a)
+            if KR is not None:
+                ak = keep_layout(a)
+                if m.groups != 1 or KR.patch_mean_variant(ak.shape, is_channels_last(ak), m.kernel_size, m.stride, m.padding,
+                                                          m.dilation, ak.data_ptr() % 16 == 0) is None:
+                    KR, why = None, "torch math: a geometry lk_patch_mean_f32 refuses"
+            self._note_reduce(route, tap, why)
+            if KR is not None:  # the patch means straight from the map, in the accumulator's native column order when fused
+                K.gram_tn(KR.patch_mean(ak, m.kernel_size, m.stride, m.padding, m.dilation, unfold_order=not fused),
+                          alpha_a_scale / N, A, upper_only=fused)
+                return A
             cols = torch.nn.functional.unfold(a, m.kernel_size, dilation=m.dilation, padding=m.padding, stride=m.stride)
             if fused:  # keep the accumulator's native column order: (kh, kw, ci)
                 KK = m.kernel_size[0] * m.kernel_size[1]
@@ -576,7 +631,7 @@ class _HipCurvatureMixin:
             K.gram_tn(cols.mean(2).contiguous(), alpha_a_scale / N, A, upper_only=fused)
         return A
 
-    def _factor_G(self, tap, g, alpha_g, kfac_approx, G, fused=False, persist=None):
+    def _factor_G(self, tap, g, alpha_g, kfac_approx, G, fused=False, persist=None, route=None):
         """``G += alpha * sum g g^T`` (output side; ``g`` is ``[S, B, ...]`` or the unstacked per-seed list)."""
         K = get_kernels()
         m = cv.lift(tap.module)
@@ -587,6 +642,12 @@ class _HipCurvatureMixin:
                 if not fused:
                     K.symmetrize(G)
                 return G
+            if kfac_approx != "expand":
+                KR, why = self._reduce_kernels(g)
+                self._note_reduce(route, tap, why)
+                if KR is not None:  # the planes as the sweep left them: no fp32 copy of the map
+                    K.gram_tn(KR.possum(g, g.shape[0], g.shape[1] * g.shape[2], Do, 0), alpha_g, G, upper_only=fused)
+                    return G
             gf = g.float()
             rows = gf.reshape(-1, Do) if kfac_approx == "expand" else gf.sum((1, 2))
             K.gram_tn(rows.contiguous(), alpha_g, G, upper_only=fused)
@@ -601,7 +662,13 @@ class _HipCurvatureMixin:
             if kfac_approx == "expand" or L == 1:
                 K.gram_tn(g.reshape(-1, Do).contiguous(), alpha_g, G, upper_only=fused)
             else:
-                K.gram_tn(g.reshape(S, B, L, Do).sum(2).reshape(S * B, Do).contiguous(), alpha_g, G, upper_only=fused)
+                KR, why = self._reduce_kernels(g)
+                self._note_reduce(route, tap, why)
+                if KR is not None:
+                    rows = KR.possum(g.contiguous(), S * B, L, Do, 0)
+                else:
+                    rows = g.reshape(S, B, L, Do).sum(2).reshape(S * B, Do).contiguous()
+                K.gram_tn(rows, alpha_g, G, upper_only=fused)
             return G
         Do = m.out_channels
         if kfac_approx == "expand":
@@ -610,6 +677,15 @@ class _HipCurvatureMixin:
             else:
                 K.gram_nt(g.reshape(S * B, Do, L).contiguous(), alpha_g, G, upper_only=fused, persist=persist)
         else:
+            KR, why = self._reduce_kernels(*(g if isinstance(g, (list, tuple)) else [g]))
+            self._note_reduce(route, tap, why)
+            if KR is not None:  # per-seed maps are summed where they lie: the [S B, Do] rows are all that is stacked
+                if isinstance(g, (list, tuple)):
+                    rows = torch.cat([self._possum_map(KR, gs, B, Do, L) for gs in g])
+                else:
+                    rows = self._possum_map(KR, g.reshape(S * B, Do, *g.shape[3:]), S * B, Do, L)
+                K.gram_tn(rows, alpha_g, G, upper_only=fused)
+                return G
             if isinstance(g, (list, tuple)):
                 g = torch.stack(g)
             K.gram_tn(g.reshape(S * B, Do, L).sum(2).contiguous(), alpha_g, G, upper_only=fused)
@@ -843,6 +919,7 @@ class _HipCurvatureMixin:
         acc._persist_slabs = False
         acc.lanes = 1  # (one minibatch: nothing to run beside it)
         acc.coalesce = False  # (... and nothing to stack it with: its raw form is read right away)
+        self.reduce_route = acc.reduce_route  # (the latest minibatch's, for a caller that never sees the accumulator)
         try:
             acc.add_batch(x, y)
         except NotImplementedError as e:
@@ -1000,6 +1077,9 @@ class KronAccumulator:
             backend = twin
         self.backend, self.N, self.kfac_approx = backend, N, kfac_approx
         self.overlap = overlap
+        #: under ``kfac_approx="reduce"``: tap name -> "kernel" (csrc/lk_kfacreduce.hip formed the tap's rows on both sides) or the
+        #: reason the torch sums ran (`use_kfac_reduce_kernels`), as ``sweep.resample_route`` for the resampling nodes
+        self.reduce_route = {}
         self._side = None
         self._side_done = None  # event at the end of the previous minibatch's side-stream work (lagged join)
         self._side_older = []   # ... of the minibatches before that which the main stream has not waited for yet
@@ -1120,11 +1200,11 @@ class KronAccumulator:
                 t = K.nchw_to_nhwc(keep_layout(tap.a))  # (a copy: the sweep releases the activation)
                 self._pix_inputs.setdefault(idx, []).append((geo, rt / (self.N * geo[1] * geo[2]), t, tap.module))
                 return
-            self.backend._factor_A(tap, self.N, rt, self.kfac_approx, F[1], fused=True)
+            self.backend._factor_A(tap, self.N, rt, self.kfac_approx, F[1], fused=True, route=self.reduce_route)
             return
         acc = self._pix.get(idx)
         if acc is None:
-            self.backend._factor_A(tap, self.N, rt, self.kfac_approx, F[1], fused=True)
+            self.backend._factor_A(tap, self.N, rt, self.kfac_approx, F[1], fused=True, route=self.reduce_route)
             return
         geo, buf = acc
         alpha = rt / (self.N * geo[1] * geo[2])
@@ -1356,6 +1436,7 @@ class KronAccumulator:
                 sub.use_pixgram, sub.pix_group, sub.lag_join = self.use_pixgram, self.pix_group, self.lag_join
                 sub.lag_depth, sub.direct_stack = self.lag_depth, self.direct_stack
                 sub._defer_bn, sub._persist_slabs = self._defer_bn, self._persist_slabs
+                sub.reduce_route = self.reduce_route
                 self._lane_accs.append(sub)
         k = self._lane_next
         self._lane_next = (k + 1) % self.lanes
@@ -1674,13 +1755,13 @@ class KronAccumulator:
                 tap, F = by_name[name]
                 persist = None if isinstance(g, SplitTensor) else self._g_slabs(tap, g, rt * hs)
                 if side is None:
-                    b._factor_G(tap, g, rt * hs, self.kfac_approx, F[0], fused=True, persist=persist)
+                    b._factor_G(tap, g, rt * hs, self.kfac_approx, F[0], fused=True, persist=persist, route=self.reduce_route)
                     return
                 ev = torch.cuda.Event()
                 ev.record(main)
                 side.wait_event(ev)
                 with torch.cuda.stream(side):
-                    b._factor_G(tap, g, rt * hs, self.kfac_approx, F[0], fused=True, persist=persist)
+                    b._factor_G(tap, g, rt * hs, self.kfac_approx, F[0], fused=True, persist=persist, route=self.reduce_route)
                 (g.planes if isinstance(g, SplitTensor) else g).record_stream(side)  # allocated on main, read on side
                 if isinstance(g, SplitTensor) and torch.is_tensor(g.sexp):
                     g.sexp.record_stream(side)
@@ -1689,7 +1770,7 @@ class KronAccumulator:
         else:
             grads = grad_fn(seeds, stack=False)
             for tap, g, F in zip(tape.taps, grads, self.factors):
-                b._factor_G(tap, g, rt * hs, self.kfac_approx, F[0], fused=True)
+                b._factor_G(tap, g, rt * hs, self.kfac_approx, F[0], fused=True, route=self.reduce_route)
         if defer:
             self._note_grad_scales(tape, grad_fn.grad_scale())
         if side is not None:

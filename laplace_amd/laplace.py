@@ -730,16 +730,24 @@ class HipKronLaplace(_HipLaplace):
 
     """KFAC Laplace (KronLaplace, baselaplace.py:1704-1879) on the HIP kernels."""
 
-    def __init__(self, *args, damping: bool = False, **kwargs):
+    def __init__(self, *args, damping: bool = False, kfac_approx: str = "expand", **kwargs):
+        """``kfac_approx``: ``"expand"`` or ``"reduce"`` - the Kronecker approximation of layers that share weights over positions,
+        what the reference takes as ``asdl_fisher_kwargs={"kfac_approx": ...}`` (curvlinops.py:95-98)."""
+        if kfac_approx not in ("expand", "reduce"):
+            raise ValueError(f"kfac_approx must be 'expand' or 'reduce', got {kfac_approx!r}")
         self.damping = damping
+        self.kfac_approx = kfac_approx
         self.H_facs = None
         super().__init__(*args, **kwargs)
 
     def _init_H(self):
         self.H = HipKron.init_from_model(self.params, self._device, self._dtype)
 
+    def _kfac_kwargs(self):  # (nothing for the default: the call a backend without the argument has always seen)
+        return {} if self.kfac_approx == "expand" else {"kfac_approx": self.kfac_approx}
+
     def _curv_closure(self, X, y, N):
-        return self.backend.kron(X, y, N=N)
+        return self.backend.kron(X, y, N=N, **self._kfac_kwargs())
 
     def _curvature_tensors(self):
         return [Hi for F in self.H.kfacs for Hi in F]
@@ -769,7 +777,7 @@ class HipKronLaplace(_HipLaplace):
             self.model.eval()
             self.mean = parameters_to_vector(self.params).detach()
             N = len(train_loader.dataset)
-            acc = self.backend.kron_accumulator(N)
+            acc = self.backend.kron_accumulator(N, **self._kfac_kwargs())
             for data in train_loader:
                 if isinstance(data, dict) or hasattr(data, "keys"):
                     X, y = data, data[self.backend.dict_key_y].to(self._device)
