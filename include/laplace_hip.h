@@ -1150,6 +1150,44 @@ int lk_quadform_shared_grid_f32(const float* u, const float* v, const float* w0,
 #define LK_QF_DIAG_GGN 4       /* lk_diag_ggn_shared_f32 */
 #define LK_QF_GRID 5           /* lk_quadform_shared_grid_f32, all three modes, either layout of u */
 int lk_quadform_shared_variant(int form, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L, int aligned16);
+
+/* Diagonal-output forms (csrc/lk_quaddiag.hip): only the C per-output variances of a sample, fvar_diag [B][C] (+=), for up to
+ * LK_QUADDIAG_MAX_C outputs (LK_EINVAL beyond) — what `diagonal_output=True` and the probit link read of f_var.
+ * Weight-sharing layers, operands as for lk_kron_quadform_shared_f32 / lk_diag_quadform_shared_f32 (u [B][C][Do][L], or
+ * [C][B][Do][L] with seed_major != 0; v [B][Dk][L]):
+ *   fvar_diag[n][c] += sum_{o,i} (sum_l u[n][c][o][l] v[n][i][l])^2 w[o,i]
+ *   Kronecker posterior: w = 1 / (l1[o] l2[i] + delta[0]);   diagonal posterior: w = var_w[o][i]
+ * A workgroup owns (sample, split slot) and walks the 32 x 128 super-tiles; inside a super-tile the outputs go by in chunks of
+ * 8 through the tile products of the full form (three-piece bf16 with L % 4 == 0 and 16-byte aligned u, v, else
+ * v_mfma_f32_32x32x2_f32), each weighted tile is squared and summed to one number per output, and the running sums live in
+ * an LDS array [C] per wave.  The v panel of a super-tile stays in LDS across the chunks while L <= 64.  Waves, then split
+ * slots, are combined in fixed order through the workspace (lk_quaddiag_shared_workspace_bytes; a short one is LK_EINVAL):
+ * repeated calls give the same bits.  Requires C*L*Do < 2^29, L*Dk < 2^29 (seed_major: B*L*Do < 2^28; diagonal: Do*Dk < 2^31). */
+#define LK_QUADDIAG_MAX_C 4096
+size_t lk_quaddiag_shared_workspace_bytes(int64_t B, int64_t C, int64_t Do, int64_t Dk);
+int lk_kron_quaddiag_shared_f32(const float* u, const float* v, const float* l1, const float* l2, const float* delta, int64_t B,
+                                int64_t C, int64_t Do, int64_t Dk, int64_t L, int seed_major, float* fvar_diag, void* ws,
+                                size_t ws_bytes, void* stream);
+int lk_diag_quaddiag_shared_f32(const float* u, const float* v, const float* var_w, int64_t B, int64_t C, int64_t Do, int64_t Dk,
+                                int64_t L, int seed_major, float* fvar_diag, void* ws, size_t ws_bytes, void* stream);
+/* nn.Linear layers, operands as for lk_kron_quadform_linear_f32 / lk_diag_quadform_linear_f32 (u, ub, g [C][B][Do]; v, a [B][Di]):
+ *   Kronecker: fvar_diag[n][c] += sum_o u[c][n][o]^2 s[n][o] (+ sum_o ub[c][n][o]^2 / (lb_o + delta_b) if ub != NULL),
+ *              s[n][o] = sum_i v[n][i]^2 / (l1_o l2_i + delta)
+ *   diagonal:  fvar_diag[n][c] += sum_o g[c][n][o]^2 (sum_i a[n][i]^2 var_w[o][i] (+ var_b[o] if var_b != NULL))
+ * s is formed once per sample in LDS (Do <= 32768) and read by every output; nothing of size C^2 is written. */
+int lk_kron_quaddiag_linear_f32(const float* u, const float* v, const float* l1, const float* l2, const float* delta, int64_t B,
+                                int64_t C, int64_t Do, int64_t Di, const float* ub, const float* lb, const float* delta_b,
+                                float* fvar_diag, void* stream);
+int lk_diag_quaddiag_linear_f32(const float* a, const float* g, const float* var_w, const float* var_b, int64_t B, int64_t C,
+                                int64_t Do, int64_t Di, float* fvar_diag, void* stream);
+/* The path a shape takes through the weight-sharing diagonal-output kernel (pure host function, the launcher decides with
+ * the same helpers).  `form`: LK_QD_*.  Returns  arith | resident << 1 | rem << 2 | chunks << 5 | split << 15:
+ *   arith 1 = three-piece bf16 products, resident 1 = the v panel is staged once per super-tile (else it streams from memory
+ *   for every chunk), chunks = ceil(C / 8) output chunks per super-tile, rem = C % 8 (non-zero: with C > 8 the last chunk is
+ *   moved back to end at C), split = workgroups per sample; negative for a shape that is not served. */
+#define LK_QD_KRON 0 /* lk_kron_quaddiag_shared_f32 */
+#define LK_QD_DIAG 1 /* lk_diag_quaddiag_shared_f32 */
+int lk_quaddiag_variant(int form, int64_t B, int64_t C, int64_t Do, int64_t Dk, int64_t L, int aligned16);
 /* Which kernel, tile, epilogue and grid a launch of the split-fp16 convolution takes (pure host function except for the
  * device's CU count, 256 without a device: conv_dispatch and the launchers decide with the same helpers of csrc/lk_conv.hip).
  * `entry`: LK_CONV_*; the arguments are those of the entry point (the three dense entry points ignore Hc, Wc, out_step, oh0, ow0,

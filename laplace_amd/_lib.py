@@ -208,6 +208,12 @@ SIGNATURES = {
     "lk_possum_variant": (_int, [_i64, _i64, _i64, _int, _int]),
     "lk_patch_mean_f32": (_int, [_vp] + [_i64] * 4 + [_int] * 10 + [_vp, _vp]),
     "lk_patch_mean_variant": (_int, [_i64] * 4 + [_int] * 10),
+    "lk_quaddiag_shared_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "lk_kron_quaddiag_shared_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    "lk_diag_quaddiag_shared_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    "lk_kron_quaddiag_linear_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "lk_diag_quaddiag_linear_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "lk_quaddiag_variant": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _int]),
 }
 
 
@@ -2472,6 +2478,94 @@ class HipKernels:
             "lk_diag_quadform_linear_f32",
         )
         return fvar
+
+    # ---- diagonal-output predictive (csrc/lk_quaddiag.hip): fvar_diag [B, C] for any number of outputs -------------------
+    #: most outputs of the diagonal-output kernels (LK_QUADDIAG_MAX_C: the per-wave sums in LDS)
+    QUADDIAG_MAX_C = 4096
+    #: ``form`` of :meth:`quaddiag_variant` (LK_QD_* of include/laplace_hip.h)
+    QD_KRON, QD_DIAG = range(2)
+
+    def _quaddiag_shared_shapes(self, what, u, v, fvar_diag, seed_major):
+        if u.dim() != 4 or v.dim() != 3:
+            raise LaplaceHipError(f"{what}: u [B, C, Do, L] (seed_major: [C, B, Do, L]), v [B, Dk, L]")
+        C, B, Do, L = u.shape if seed_major else (u.shape[1], u.shape[0], u.shape[2], u.shape[3])
+        Dk = v.shape[1]
+        if v.shape != (B, Dk, L) or fvar_diag.shape != (B, C):
+            raise LaplaceHipError(f"{what}: v [B, Dk, L], fvar_diag [B, C]")
+        return B, C, Do, Dk, L
+
+    def kron_quaddiag_shared(self, u, v, l1, l2, delta, fvar_diag, seed_major=False):
+        """``fvar_diag [B, C] +=`` the per-output variances of a weight-sharing layer under the Kronecker posterior; operands
+        as :meth:`kron_quadform_shared`, any ``C <= QUADDIAG_MAX_C``"""
+        for t, nm in ((u, "u"), (v, "v"), (l1, "l1"), (l2, "l2"), (delta, "delta"), (fvar_diag, "fvar_diag")):
+            _check(t, nm)
+        B, C, Do, Dk, L = self._quaddiag_shared_shapes("kron_quaddiag_shared", u, v, fvar_diag, seed_major)
+        if l1.numel() != Do or l2.numel() != Dk or delta.numel() != 1:
+            raise LaplaceHipError("kron_quaddiag_shared: l1 [Do], l2 [Dk], delta a scalar tensor")
+        ws = self._workspace(self.lib.lk_quaddiag_shared_workspace_bytes(B, C, Do, Dk), u.device)
+        self._rc(self._timed("quaddiag", 2.0 * B * C * L * Do * Dk, u.device, lambda: self.lib.lk_kron_quaddiag_shared_f32(
+            _ptr(u), _ptr(v), _ptr(l1), _ptr(l2), _ptr(delta), B, C, Do, Dk, L, int(bool(seed_major)), _ptr(fvar_diag), _ptr(ws),
+            ws.numel(), self._stream(u.device))), "lk_kron_quaddiag_shared_f32")
+        return fvar_diag
+
+    def diag_quaddiag_shared(self, u, v, var_w, fvar_diag, seed_major=False):
+        """:meth:`kron_quaddiag_shared` under the diagonal posterior ``var_w [Do, Dk]``"""
+        for t, nm in ((u, "u"), (v, "v"), (var_w, "var_w"), (fvar_diag, "fvar_diag")):
+            _check(t, nm)
+        B, C, Do, Dk, L = self._quaddiag_shared_shapes("diag_quaddiag_shared", u, v, fvar_diag, seed_major)
+        if var_w.numel() != Do * Dk:
+            raise LaplaceHipError("diag_quaddiag_shared: var_w [Do, Dk]")
+        ws = self._workspace(self.lib.lk_quaddiag_shared_workspace_bytes(B, C, Do, Dk), u.device)
+        self._rc(self._timed("quaddiag", 2.0 * B * C * L * Do * Dk, u.device, lambda: self.lib.lk_diag_quaddiag_shared_f32(
+            _ptr(u), _ptr(v), _ptr(var_w), B, C, Do, Dk, L, int(bool(seed_major)), _ptr(fvar_diag), _ptr(ws), ws.numel(),
+            self._stream(u.device))), "lk_diag_quaddiag_shared_f32")
+        return fvar_diag
+
+    def kron_quaddiag_linear(self, u, v, l1, l2, delta, fvar_diag, ub=None, lb=None, delta_b=None):
+        """nn.Linear layer, operands as :meth:`kron_quadform_linear` (``u, ub [C, B, Do]``, ``v [B, Di]``); ``fvar_diag [B, C] +=``"""
+        for t, nm in ((u, "u"), (v, "v"), (l1, "l1"), (l2, "l2"), (delta, "delta"), (fvar_diag, "fvar_diag")):
+            _check(t, nm)
+        if u.dim() != 3 or v.dim() != 2:
+            raise LaplaceHipError("kron_quaddiag_linear: u [C, B, Do], v [B, Di]")
+        C, B, Do = u.shape
+        Di = v.shape[1]
+        if v.shape[0] != B or fvar_diag.shape != (B, C) or l1.numel() != Do or l2.numel() != Di or delta.numel() != 1:
+            raise LaplaceHipError("kron_quaddiag_linear: v [B, Di], l1 [Do], l2 [Di], delta a scalar tensor, fvar_diag [B, C]")
+        if ub is not None:
+            _check(ub, "ub"), _check(lb, "lb"), _check(delta_b, "delta_b")
+            if ub.shape != u.shape or lb.numel() != Do or delta_b.numel() != 1:
+                raise LaplaceHipError("kron_quaddiag_linear: ub [C, B, Do], lb [Do], delta_b a scalar tensor")
+        self._rc(self.lib.lk_kron_quaddiag_linear_f32(_ptr(u), _ptr(v), _ptr(l1), _ptr(l2), _ptr(delta), B, C, Do, Di, _ptr(ub),
+                                                      _ptr(lb), _ptr(delta_b), _ptr(fvar_diag), self._stream(u.device)),
+                 "lk_kron_quaddiag_linear_f32")
+        return fvar_diag
+
+    def diag_quaddiag_linear(self, a, g, var_w, var_b, fvar_diag):
+        """nn.Linear layer, operands as :meth:`diag_quadform_linear` (``a [B, Di]``, ``g [C, B, Do]``); ``fvar_diag [B, C] +=``"""
+        for t, nm in ((a, "a"), (g, "g"), (var_w, "var_w"), (fvar_diag, "fvar_diag")):
+            _check(t, nm)
+        if g.dim() != 3 or a.dim() != 2:
+            raise LaplaceHipError("diag_quaddiag_linear: a [B, Di], g [C, B, Do]")
+        C, B, Do = g.shape
+        Di = a.shape[1]
+        if a.shape[0] != B or fvar_diag.shape != (B, C) or var_w.numel() != Do * Di:
+            raise LaplaceHipError("diag_quaddiag_linear: a [B, Di], var_w [Do, Di], fvar_diag [B, C]")
+        if var_b is not None:
+            _check(var_b, "var_b")
+            if var_b.numel() != Do:
+                raise LaplaceHipError("diag_quaddiag_linear: var_b [Do]")
+        self._rc(self.lib.lk_diag_quaddiag_linear_f32(_ptr(a), _ptr(g), _ptr(var_w), _ptr(var_b), B, C, Do, Di, _ptr(fvar_diag),
+                                                      self._stream(a.device)), "lk_diag_quaddiag_linear_f32")
+        return fvar_diag
+
+    def quaddiag_variant(self, form, B, C, Do, Dk, L, aligned16=True):
+        """lk_quaddiag_variant: the path a shape takes through the weight-sharing diagonal-output kernel (host only), or
+        ``None`` for a shape it does not serve: ``arith``, ``resident`` (the v panel stays in LDS across the output chunks),
+        ``chunks`` of 8 outputs per super-tile, ``rem = C % 8``, ``split`` workgroups per sample"""
+        r = int(self.lib.lk_quaddiag_variant(int(form), int(B), int(C), int(Do), int(Dk), int(L), int(bool(aligned16))))
+        if r < 0:
+            return None
+        return {"arith": r & 1, "resident": bool(r & 2), "rem": (r >> 2) & 7, "chunks": (r >> 5) & 1023, "split": r >> 15}
 
     # ---- prior-precision grid (csrc/lk_grid.hip): var [G, B, C] of all grid points in one pass ----------------------------
     #: weight forms of the grid kernels: Kron, damped Kron, diagonal

@@ -848,12 +848,13 @@ class HipKronLaplace(_HipLaplace):
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
         post = self.posterior_precision
         try:
-            f_mu, f_var = _pred.glm_variance_kron(self.backend, X, post)  # fused, no [B, C, P] Jacobian
+            # fused, no [B, C, P] Jacobian; [B, C] already where the diagonal-output kernels served the call
+            f_mu, f_var = _pred.glm_variance_kron(self.backend, X, post, diagonal=diagonal_output)
         except NotImplementedError:
             Js, f_mu = (self.backend.last_layer_jacobians(X) if self.subset_of_weights == "last_layer"
                         else self.backend.jacobians(X))
             f_var = post.inv_square_form(Js)
-        if diagonal_output:
+        if diagonal_output and f_var.dim() == 3:
             f_var = torch.diagonal(f_var, dim1=-2, dim2=-1)
         return f_mu.detach(), f_var.detach()
 
@@ -903,12 +904,12 @@ class HipDiagLaplace(_HipLaplace):
 
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
         try:
-            f_mu, f_var = _pred.glm_variance_diag(self.backend, X, self.posterior_variance)
+            f_mu, f_var = _pred.glm_variance_diag(self.backend, X, self.posterior_variance, diagonal=diagonal_output)
         except NotImplementedError:
             Js, f_mu = (self.backend.last_layer_jacobians(X) if self.subset_of_weights == "last_layer"
                         else self.backend.jacobians(X))
             f_var = self.functional_variance(Js)
-        if diagonal_output:
+        if diagonal_output and f_var.dim() == 3:
             f_var = torch.diagonal(f_var, dim1=-2, dim2=-1)
         return f_mu.detach(), f_var.detach()
 
@@ -1166,14 +1167,14 @@ def glm_predictive(la, X, diagonal_output: bool = False, fallback=None):
     la.model.eval()
     try:
         if hasattr(la, "H_facs"):
-            f_mu, f_var = _pred.glm_variance_kron(backend, X, la.posterior_precision)
+            f_mu, f_var = _pred.glm_variance_kron(backend, X, la.posterior_precision, diagonal=diagonal_output)
         elif torch.is_tensor(la.H) and la.H.ndim == 1:
-            f_mu, f_var = _pred.glm_variance_diag(backend, X, la.posterior_variance)
+            f_mu, f_var = _pred.glm_variance_diag(backend, X, la.posterior_variance, diagonal=diagonal_output)
         else:
             f_mu, f_var = _pred.glm_variance_full_last_layer(backend, X, la.posterior_covariance)
     except NotImplementedError:
         return (fallback or la._glm_predictive_distribution)(X, diagonal_output=diagonal_output)
-    if diagonal_output:
+    if diagonal_output and f_var.dim() == 3:
         f_var = torch.diagonal(f_var, dim1=-2, dim2=-1)
     return f_mu.detach(), f_var.detach()
 

@@ -20,6 +20,10 @@ the posterior (Kron: laplace/utils/matrix.py:406-461; diag: baselaplace.py:2113-
 * more than 10 outputs (the kernel's accumulator budget): pairs of 5-output blocks of the same kernel where that is
   cheaper than the as-written route — the layer's Jacobian block assembled by ``lk_jac_conv_f32`` (only that block,
   never the full ``[B, C, P]``) and contracted with the block's posterior — which serves the rest.
+* ``diagonal=True`` (``diagonal_output=True``: all the probit link reads) with more than 10 outputs: the per-output
+  variances have no pair structure, ``f_var[n, c] = sum_oi (Q1^T J_nc Q2)_oi^2 w_oi`` — ``lk_*_quaddiag_shared_f32`` /
+  ``lk_*_quaddiag_linear_f32`` form each output's tile product once, in ONE launch per layer for up to 4096 outputs, and
+  write ``[B, C]``.
 """
 from __future__ import annotations
 
@@ -138,13 +142,29 @@ def _kron_blocks(post, tape, grads):
         yield tap, g, Q1, Q2, l1, l2, delta, Qb, lb, delta_b
 
 
-def glm_variance_kron(backend, x, post):
+#: ``diagonal=True`` (the public ``diagonal_output=True``) takes the diagonal-output kernels (csrc/lk_quaddiag.hip): ``f_var``
+#: is ``[B, C]`` from the start, one launch per layer for any number of outputs.  Off: the ``[B, C, C]`` route and its diagonal.
+use_diag_output_kernels = True
+#: fewest outputs at which they are taken: every call the pair-sum kernel serves in ONE launch (C <= 10) keeps its route and
+#: its bits.  1 forces the new route.
+diag_output_min_outputs = 11
+
+
+def _diag_output_route(K, diagonal: bool, C: int) -> bool:
+    return bool(diagonal and use_diag_output_kernels and hasattr(K, "kron_quaddiag_shared")
+                and diag_output_min_outputs <= C <= K.QUADDIAG_MAX_C)
+
+
+def glm_variance_kron(backend, x, post, diagonal: bool = False):
     """``(f_mu, f_var)`` under a :class:`HipKronDecomposed` posterior precision ``post``
-    (= ``H * H_factor + prior_precision``), i.e. KronLaplace.functional_variance."""
+    (= ``H * H_factor + prior_precision``), i.e. KronLaplace.functional_variance.  ``diagonal``: only the per-output
+    variances are wanted; ``f_var`` comes back ``[B, C]`` where the diagonal-output kernels serve the call (see
+    ``use_diag_output_kernels``) and ``[B, C, C]`` otherwise — the caller takes the diagonal of the latter."""
     K = get_kernels()
     f, tape, grads = _kron_sweep(backend, x)
     B, C = f.shape
-    fvar = torch.zeros(B, C, C, dtype=torch.float32, device=f.device)
+    diag_out = _diag_output_route(K, diagonal, C)
+    fvar = torch.zeros((B, C) if diag_out else (B, C, C), dtype=torch.float32, device=f.device)
     for tap, g, Q1, Q2, l1, l2, delta, Qb, lb, delta_b in _kron_blocks(post, tape, grads):
         if post.damping:
             # laplace/utils/matrix.py:397-399, 441-444: the damped block is (Q1 (l1 + sqrt d) Q1^T) x (Q2 (l2 + sqrt d) Q2^T) —
@@ -160,9 +180,16 @@ def glm_variance_kron(backend, x, post):
             u = (g2 @ Q1).reshape(C, B, Do).contiguous()
             v = (a @ Q2).contiguous()
             ub = (g2 @ Qb).reshape(C, B, Do).contiguous() if Qb is not None else None
-            K.kron_quadform_linear(u, v, l1.contiguous(), l2.contiguous(), d1, fvar, ub,
-                                   None if lb is None else lb.contiguous(),
-                                   None if delta_b is None else delta_b.detach().reshape(1).contiguous())
+            (K.kron_quaddiag_linear if diag_out else K.kron_quadform_linear)(
+                u, v, l1.contiguous(), l2.contiguous(), d1, fvar, ub, None if lb is None else lb.contiguous(),
+                None if delta_b is None else delta_b.detach().reshape(1).contiguous())
+        elif diag_out:  # one launch for all C outputs, no [B, C, C] and no pair blocks
+            bnd = {}
+            u, v, gsum = _shared_operands(tap, g, B, C, Q1, Q2, bounds=bnd, planes=False)
+            K.kron_quaddiag_shared(u, v, l1.contiguous(), l2.contiguous(), d1, fvar, seed_major=bool(bnd.get("u_seed_major")))
+            if Qb is not None:
+                ub = gsum @ Qb
+                fvar += torch.einsum("cno,cno,o->nc", ub, ub, 1.0 / (lb + delta_b))
         else:
             bnd = {}
             u, v, gsum = _shared_operands(tap, g, B, C, Q1, Q2, bounds=bnd)
@@ -195,8 +222,9 @@ def glm_variance_kron(backend, x, post):
     return f, fvar
 
 
-def glm_variance_diag(backend, x, post_var: torch.Tensor):
-    """``(f_mu, f_var)`` under a diagonal posterior with variances ``post_var[P]``."""
+def glm_variance_diag(backend, x, post_var: torch.Tensor, diagonal: bool = False):
+    """``(f_mu, f_var)`` under a diagonal posterior with variances ``post_var[P]``; ``diagonal`` as in
+    :func:`glm_variance_kron`."""
     _fp32_only(backend)
     K = get_kernels()
     f, tape, grad_fn = backend._forward(x, extra=True)
@@ -206,25 +234,37 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor):
     B, C = f.shape
     grads = grad_fn(_identity_seeds(f))
     post_var = post_var.detach().to(torch.float32).contiguous()
-    fvar = torch.zeros(B, C, C, dtype=torch.float32, device=f.device)
+    diag_out = _diag_output_route(K, diagonal, C)
+    fvar = torch.zeros((B, C) if diag_out else (B, C, C), dtype=torch.float32, device=f.device)
     for tap, g in zip(backend._served_taps(tape), grads):
         if tap.kind in backend.BLOCK_KINDS:  # the layer's own Jacobian block against its slices of the posterior variance
             for n0, Jl, spans in backend._tap_blocks(tap, g):
                 var = [post_var[off:off + n] for _, n, off in spans]
                 var = torch.cat(var) if len(var) > 1 else var[0]
-                fvar[n0:n0 + Jl.shape[0]].add_(K.diag_quadform_js(Jl, var.contiguous()))
+                blk = K.diag_quadform_js(Jl, var.contiguous())
+                fvar[n0:n0 + Jl.shape[0]].add_(torch.diagonal(blk, dim1=1, dim2=2) if diag_out else blk)
             continue
         if tap.kind == "embed":  # run sums against the rows of the posterior variance, no Jacobian block (csrc/lk_embed.hip)
             m = tap.module
+            blk = torch.zeros(B, C, C, dtype=torch.float32, device=f.device) if diag_out else fvar
             K.diag_quadform_embed(g.contiguous(), backend._embed_ids(tap), m.num_embeddings, m.padding_idx,
-                                  post_var[tap.w_off:tap.w_off + m.weight.numel()].contiguous(), fvar)
+                                  post_var[tap.w_off:tap.w_off + m.weight.numel()].contiguous(), blk)
+            if diag_out:
+                fvar += torch.diagonal(blk, dim1=1, dim2=2)
             continue
         m = tap.module
         n_w = m.weight.numel()
         vw = post_var[tap.w_off:tap.w_off + n_w]
         if tap.kind == "linear" and tap.a.ndim == 2:
             vb = post_var[tap.b_off:tap.b_off + m.out_features] if tap.has_bias else None
-            K.diag_quadform_linear(tap.a.to(torch.float32).contiguous(), g.contiguous(), vw, vb, fvar)
+            (K.diag_quaddiag_linear if diag_out else K.diag_quadform_linear)(
+                tap.a.to(torch.float32).contiguous(), g.contiguous(), vw.contiguous(), None if vb is None else vb.contiguous(),
+                fvar)
+        elif diag_out:  # one launch for all C outputs
+            u, v, gsum = _shared_operands(tap, g, B, C)
+            K.diag_quaddiag_shared(u, v, vw.reshape(u.shape[2], v.shape[1]).contiguous(), fvar)
+            if tap.has_bias:
+                fvar += torch.einsum("cno,cno,o->nc", gsum, gsum, post_var[tap.b_off:tap.b_off + u.shape[2]])
         elif C <= K.quadform_shared_max_outputs or tap.kind != "conv2d":
             u, v, gsum = _shared_operands(tap, g, B, C)
             vw2 = vw.reshape(u.shape[2], v.shape[1]).contiguous()
