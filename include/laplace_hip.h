@@ -1305,6 +1305,38 @@ int lk_glm_link_f32(const float* f_mu, const float* f_var, const float* z, int64
                     int diag, float* probs, int32_t* info, void* stream);
 int lk_glm_link_variant(int64_t B, int64_t C, int64_t n_samples, int link, int diag);
 
+/* The same link approximations for LK_LINK_MAX_C < C <= LK_LINK_WIDE_MAX_C classes (csrc/lk_linkwide.hip), where the factor of a
+ * sample no longer fits the LDS: ImageNet-1k heads, vocabulary-sized heads.  Replaces the same reference lines
+ * (baselaplace.py:598-695, utils/utils.py:337-378), which at this width also form diag_embed(f_var) [B][C][C] for mc with the
+ * marginal variances.  Arguments, link codes, layouts, the info / NaN-row convention and the checks are those of lk_glm_link_f32.
+ * Three kernels, each one launch, a workgroup of 256 threads per sample:
+ *   mc, full covariance (C <= LK_LINK_WIDE_MAX_C_FULL, the range checked on a device so far): a LEFT-looking blocked Cholesky with 32-wide column panels.  The panel is
+ *     staged in LDS, the earlier columns of L are streamed from the workgroup's slab of `work` (global memory, L2 resident) and
+ *     subtracted on the exact fp32 matrix instruction in ascending k, the 32 x 32 diagonal block is factored in the registers of
+ *     one wave, the rows below are solved a thread per row, the panel is stored to the slab.  f = f_mu + L z then runs on the same
+ *     instruction, z staged 16 draws at a time, softmax statistics by shuffles and LDS, sum_s p_s per class in registers.  The
+ *     workgroups are persistent over b = blockIdx.x, blockIdx.x + slots, ...; f_var is read once and never written.
+ *   mc, marginal variances: a thread owns classes t, t + 256, ... (at most 16) with f_mu and sqrt(f_var) in registers; z is read
+ *     four draws at a time (16-byte loads where n_samples % 4 == 0); no [n][B][C] tensor, no factorisation; info = 0.
+ *   probit, bridge(_norm): the streaming pass of lk_glm_link_f32 for rows longer than the workgroup (up to 16 classes a thread; the
+ *     bridge's rows split over the four waves, the four partial column sums added in wave order).
+ * One owner per output element, a fixed reduction order, plain stores, no atomics: two equal calls are bit-equal.
+ *   work        only for mc with the full covariance (ignored and may be null otherwise): slots >= 1 slabs of CP * CP floats,
+ *               CP = 32 * ceil(C / 32); the entry point uses slots = min(B, work_bytes / slab) of them.  16-byte aligned, overlaps
+ *               no argument.  Its contents after the call are unspecified.
+ * Contract: as lk_glm_link_f32, with LK_LINK_MAX_C < C <= LK_LINK_WIDE_MAX_C (mc with diag == 0: <= LK_LINK_WIDE_MAX_C_FULL; a
+ *   smaller C belongs to lk_glm_link_f32 and is refused).  B == 0 returns LK_OK before any device call.
+ * lk_glm_link_wide_work_bytes (host only): the bytes of min(B, 256) slabs for mc with the full covariance, 0 where no workspace is
+ *   needed or the shape is outside the contract.
+ * lk_glm_link_wide_variant (host only): 0 streaming (probit, bridge), 1 mc with marginal variances, 2 mc with the full covariance;
+ *   negative for a shape the entry point refuses. */
+#define LK_LINK_WIDE_MAX_C 4096
+#define LK_LINK_WIDE_MAX_C_FULL 224
+int lk_glm_link_wide_f32(const float* f_mu, const float* f_var, const float* z, int64_t B, int64_t C, int64_t n_samples, int link,
+                         int diag, float* probs, int32_t* info, void* work, int64_t work_bytes, void* stream);
+int64_t lk_glm_link_wide_work_bytes(int64_t B, int64_t C, int link, int diag);
+int lk_glm_link_wide_variant(int64_t B, int64_t C, int64_t n_samples, int link, int diag);
+
 /* The two reductions of KFAC-reduce (csrc/lk_kfacreduce.hip): with kfac_approx="reduce" (laplace/curvature/curvlinops.py:95-98
  * hands it to curvlinops' KFAC) a weight-sharing layer's output gradients are summed and its inputs averaged over the shared
  * positions before the outer products.  They replace the torch sequences  g.float().sum((1, 2)),  g.reshape(S B, Do, L).sum(2),

@@ -203,6 +203,9 @@ SIGNATURES = {
     "lk_spectral_variant": (_int, [_int, _i64, _i64, _i64, _i64, _int]),
     "lk_glm_link_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
     "lk_glm_link_variant": (_int, [_i64, _i64, _i64, _int, _int]),
+    "lk_glm_link_wide_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _i64, _vp]),
+    "lk_glm_link_wide_work_bytes": (_i64, [_i64, _i64, _int, _int]),
+    "lk_glm_link_wide_variant": (_int, [_i64, _i64, _i64, _int, _int]),
     "lk_possum_f32": (_int, [_vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
     "lk_possum_f16x2": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
     "lk_possum_variant": (_int, [_i64, _i64, _i64, _int, _int]),
@@ -2778,6 +2781,52 @@ class HipKernels:
         for a shape it refuses"""
         code = self.LINKS[link] if isinstance(link, str) else int(link)
         r = int(self.lib.lk_glm_link_variant(int(B), int(C), int(n_samples), code, 1 if diag else 0))
+        return None if r < 0 else r
+
+    # ---- the same links for 193 to 4096 classes (csrc/lk_linkwide.hip) ------------------------------------------------
+    LINK_WIDE_MAX_C = 4096       # LK_LINK_WIDE_MAX_C (include/laplace_hip.h)
+    LINK_WIDE_MAX_C_FULL = 224  # LK_LINK_WIDE_MAX_C_FULL: mc with the full covariance
+
+    def glm_link_wide(self, f_mu, f_var, z, link, diag=False, probs=None, info=None, work=None):
+        """:meth:`glm_link` for ``LINK_MAX_C < C <= LINK_WIDE_MAX_C`` classes (mc with the full covariance:
+        ``C <= LINK_WIDE_MAX_C_FULL``), in one launch.  ``work``: a 16-byte aligned fp32 buffer of one or more slabs of
+        ``CP * CP`` floats (``CP = 32 ceil(C / 32)``) for the factors of mc with the full covariance; allocated from
+        ``lk_glm_link_wide_work_bytes`` when not given, unused by the other links."""
+        code = self.LINKS[link] if isinstance(link, str) else int(link)
+        _check(f_mu, "f_mu"), _check(f_var, "f_var")
+        B, C = f_mu.shape
+        if f_var.shape != ((B, C) if diag else (B, C, C)):
+            raise LaplaceHipError(f"glm_link_wide: f_var must be {'[B, C]' if diag else '[B, C, C]'} for f_mu [B, C]")
+        n = 0
+        if code == 1:
+            _check(z, "z")
+            if z.dim() != 2 or z.shape[0] != C:
+                raise LaplaceHipError("glm_link_wide: z must be [C, n_samples]")
+            n = z.shape[1]
+        if probs is None:
+            probs = torch.empty(B, C, dtype=torch.float32, device=f_mu.device)
+        if info is None:
+            info = torch.empty(B, dtype=torch.int32, device=f_mu.device)
+        _check(probs, "probs"), _check(info, "info", torch.int32)
+        if probs.shape != (B, C) or info.shape != (B,):
+            raise LaplaceHipError("glm_link_wide: probs must be [B, C] and info [B]")
+        if work is None:
+            need = int(self.lib.lk_glm_link_wide_work_bytes(B, C, code, 1 if diag else 0))
+            if need:
+                work = torch.empty(need // 4, dtype=torch.float32, device=f_mu.device)
+        if work is not None:
+            _check(work, "work")
+        self._rc(self.lib.lk_glm_link_wide_f32(_ptr(f_mu), _ptr(f_var), _ptr(z) if code == 1 else None, B, C, n, code,
+                                               1 if diag else 0, _ptr(probs), _ptr(info), _ptr(work) if work is not None else None,
+                                               work.numel() * 4 if work is not None else 0, self._stream(f_mu.device)),
+                 "lk_glm_link_wide_f32")
+        return probs, info
+
+    def glm_link_wide_variant(self, B, C, n_samples=1, link="mc", diag=False):
+        """the kernel ``lk_glm_link_wide_f32`` takes for a shape (host only): 0 streaming (probit, bridge), 1 mc with the marginal
+        variances, 2 mc with the full covariance, ``None`` for a shape it refuses"""
+        code = self.LINKS[link] if isinstance(link, str) else int(link)
+        r = int(self.lib.lk_glm_link_wide_variant(int(B), int(C), int(n_samples), code, 1 if diag else 0))
         return None if r < 0 else r
 
 

@@ -21,10 +21,11 @@
 //             boustrophedon (their cost grows with the row); maximum and sum of a sample column are reduced over the lane groups by
 //             shuffles and over the waves through LDS; sum_s p_s is kept per class in registers and the 16 columns of a stage are
 //             added in ascending s.
-//   C > 192   refused (the factor does not fit the LDS).
+//   C > 192   refused (the factor does not fit the LDS); lk_linkwide.hip serves 193 to 4096 classes through an entry point of its own.
 // Probit and bridge have no factorisation and keep no matrix: ONE streaming pass over the block (lanes along the columns keep the
 // column sums, a shuffle tree per row gives the row sum, the diagonal is picked up on the way), with the geometry of the regime.
 // Every output element has one owner, every reduction a fixed order, stores are plain: two equal calls are bit-equal.
+#include "lk_linkdev.h"  // wave_max, lane_bcast, chol_rows
 #include "lk_stream.h"
 
 #include <float.h>
@@ -36,41 +37,6 @@ constexpr int LINK_WAVE_C = 64;          // largest C of the wave-per-sample reg
 constexpr int LINK_MAX_C = LK_LINK_MAX_C;
 constexpr int LINK_NS = 16;              // draws per z stage = columns of one matrix-instruction tile
 constexpr int LINK_MAXT = 3;             // row tiles per wave: ceil(LINK_MAX_C / 16 / 4)
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// the value of lane `src` (a compile-time constant after unrolling) as a scalar
-__device__ __forceinline__ float lane_bcast(float v, int src) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
-// Right-looking Cholesky of the leading n x n block, a lane per row: a[k] is column k of this lane's row (k > lane is never used;
-// rows and columns >= n are identity).  Returns 0, or j + 1 for the first pivot that is <= 0 or not finite.  On success a[] is
-// the row of L, zeros above the diagonal.  The subtractions of one element run in ascending column order.
-template <int N>
-__device__ __forceinline__ int chol_rows(float (&a)[N], int lane, int n) {
-  int bad = 0;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    if (j < n && bad == 0) {  // (uniform)
-      const float d = lane_bcast(a[j], j);
-      if (!(d > 0.f) || d > FLT_MAX) {
-        bad = j + 1;
-      } else {
-        const float piv = sqrtf(d);
-        const float l = lane > j ? a[j] / piv : (lane == j ? piv : 0.f);
-        a[j] = l;
-#pragma unroll
-        for (int k = j + 1; k < N; ++k) a[k] = fmaf(-l, lane_bcast(l, k), a[k]);
-      }
-    }
-  }
-  return bad;
-}
 
 // ---- mc, C <= 64: a wave per sample ---------------------------------------------------------------------------------------------
 template <int NC>

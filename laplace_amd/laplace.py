@@ -443,12 +443,17 @@ class _HipLaplace:
             return self._nn_predictive_samples(x, n_samples, generator).mean(dim=0)
         if joint and self.likelihood == "regression":  # joint=True only applies to regression (baselaplace.py:646-648)
             return self._glm_joint_distribution(x)
+        if self.likelihood == "classification" and link_approx == "probit" and self._link_wide_probit():
+            diagonal_output = True  # probit reads the marginal variances and nothing else: one launch per layer gives them
         f_mu, f_var = self._glm_predictive_distribution(x, diagonal_output=diagonal_output)
         if self.likelihood == "regression":
             return f_mu, f_var
         K = self._link_kernels(f_mu, f_var)
         if K is not None:
             return self._glm_link(K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator)
+        K = self._link_wide_kernels(f_mu, link_approx, diagonal_output)
+        if K is not None:
+            return self._glm_link(K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator, wide=True)
         if link_approx == "mc":
             fv = f_var if not diagonal_output else torch.diag_embed(f_var)
             return self._glm_predictive_samples(f_mu, fv, n_samples, diagonal_output, generator).mean(dim=0)
@@ -471,7 +476,33 @@ class _HipLaplace:
         K = _pred.get_kernels()
         return K if hasattr(K, "glm_link") and 1 <= f_mu.shape[1] <= getattr(K, "LINK_MAX_C", 0) else None
 
-    def _glm_link(self, K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator):
+    #: beyond ``LINK_MAX_C`` outputs, route the link through the wide kernels (csrc/lk_linkwide.hip): up to ``LINK_WIDE_MAX_C``
+    #: classes, mc with the full covariance up to ``LINK_WIDE_MAX_C_FULL``.  Needs ``use_link_kernels``.  Off, or outside that
+    #: range: the torch sequences of ``__call__``.  The default follows the gate of tools/link_bench.py (README, the
+    #: ``lk_linkwide.hip`` row).
+    use_link_wide_kernels = False
+
+    def _link_wide_kernels(self, f_mu, link_approx, diagonal_output):
+        """the kernel provider when the wide link kernels serve this call, else ``None`` (the torch path runs)"""
+        if not (self.use_link_kernels and self.use_link_wide_kernels and f_mu.is_cuda and f_mu.dtype == torch.float32
+                and f_mu.dim() == 2):
+            return None
+        K = _pred.get_kernels()
+        if not hasattr(K, "glm_link_wide"):
+            return None
+        full = link_approx != "probit" and not (link_approx == "mc" and diagonal_output)  # (the bridge asks for the full block)
+        top = K.LINK_WIDE_MAX_C_FULL if link_approx == "mc" and full else K.LINK_WIDE_MAX_C
+        return K if K.LINK_MAX_C < f_mu.shape[1] <= top else None
+
+    def _link_wide_probit(self):
+        """the probit link will run on the wide kernels: ask the predictive for the marginal variances only"""
+        if not (self.use_link_kernels and self.use_link_wide_kernels and self._device.type == "cuda"
+                and self._dtype == torch.float32 and self.n_outputs is not None):
+            return False
+        K = _pred.get_kernels()
+        return hasattr(K, "glm_link_wide") and K.LINK_MAX_C < self.n_outputs <= K.LINK_WIDE_MAX_C
+
+    def _glm_link(self, K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator, wide=False):
         """``link_approx`` of ``(f_mu, f_var)`` in one launch; 'mc' consumes the draw ``_glm_functional_samples`` makes."""
         z = None
         if link_approx == "mc":
@@ -479,7 +510,8 @@ class _HipLaplace:
         elif link_approx != "probit" and diagonal_output:
             f_mu, f_var = self._glm_predictive_distribution(x)  # the bridge needs the full output covariance
             diagonal_output = False
-        probs, info = K.glm_link(f_mu.contiguous(), f_var.contiguous(), z, link_approx, diag=diagonal_output)
+        link = K.glm_link_wide if wide else K.glm_link
+        probs, info = link(f_mu.contiguous(), f_var.contiguous(), z, link_approx, diag=diagonal_output)
         if link_approx == "mc" and not diagonal_output:
             status = info.cpu()  # (the one host read of the call, as torch.linalg.cholesky reads its status)
             if bool(status.any()):
