@@ -1380,6 +1380,45 @@ int lk_patch_mean_f32(const float* x, int64_t B, int64_t C, int64_t H, int64_t W
 int lk_patch_mean_variant(int64_t B, int64_t C, int64_t H, int64_t W, int channels_last, int kh, int kw, int sh, int sw, int ph,
                           int pw, int dh, int dw, int aligned);
 
+/* The `nn` (weight-space sampling) predictive of a last-layer posterior (csrc/lk_nnhead.hip): S sampled nn.Linear heads applied to
+ * the same features, each followed by a row softmax, averaged over the draws.  Replaces laplace/lllaplace.py:257-314 (per draw a
+ * vector_to_parameters scatter and a head launch, then a stacked [S][B][C] tensor, a softmax tensor of that size and a mean) and
+ * the regression moments of laplace/baselaplace.py:1344-1394 (samples.mean(0), samples.var(0)).
+ *   phi    [B][D] the head's input
+ *   theta  [S][ld] the rows sample() returns: the weight W_s [C][D] row-major at offset 0, the bias b_s [C] at offset C D when
+ *          has_bias; ld >= P = C D (+ C).  The kernel consumes the draws and draws nothing itself.
+ *   mode   LK_NN_HEAD_PROBS    out[b][c] = (1 / S) sum_s softmax_c(f_s[b]),  f_s[b][c] = phi_b . W_s[c] + b_s[c]; the row maximum
+ *                              is subtracted; the draws of a group add in ascending s, the groups in ascending order
+ *          LK_NN_HEAD_MOMENTS  out[b][c] the mean and out2[b][c] the unbiased variance over s of f_s[b][c] (torch's .var(dim=0);
+ *                              S == 1: NaN): Welford's update over the draws of a group, Chan's over the groups
+ *          LK_NN_HEAD_SAMPLES  out[s][b][c] = f_s[b][c], or softmax_c(f_s[b]) with `softmax` non-zero
+ *          out2 is read by LK_NN_HEAD_MOMENTS only, `softmax` by LK_NN_HEAD_SAMPLES only.
+ * A workgroup owns 16, 32 or 64 batch rows (by C) and a contiguous chunk of draws.  Its phi rows are staged in LDS (whole, or in
+ * 256-column chunks per draw where they do not fit) and reused by every draw and class tile; theta streams from HBM straight into
+ * the operand registers of the exact fp32 matrix instruction (16-byte loads where D % 4 == 0 and ld % 4 == 0), each element once
+ * per batch tile, in a fixed k order that does not depend on the load width.  A draw's logits, the softmax statistics and the
+ * running sums stay in registers: no [S][B][C] tensor exists outside LK_NN_HEAD_SAMPLES.  Two regimes: C <= 64 a wave per draw
+ * (no barrier between draws), C <= LK_NN_HEAD_MAX_C a workgroup per draw (class tile t on wave t % 4).  The draws are split over
+ * G groups so that a launch fills the device at any B; with G > 1 the groups' partial sums go to `work` and a second small
+ * launch adds them in ascending group order: at most two launches.  One owner per output element, fixed reduction orders, plain
+ * stores, no atomics: two equal calls are bit-equal.
+ *   work   G > 1 in LK_NN_HEAD_PROBS / _MOMENTS only (else ignored, may be null): lk_nn_head_work_bytes bytes, 16-byte aligned,
+ *          overlapping no argument; contents unspecified afterwards.  Too small: LK_EWORKSPACE.
+ * Contract: phi, theta, out (out2 for the moments) non-null and 16-byte aligned; 1 <= C <= LK_NN_HEAD_MAX_C (what 64 accumulator
+ *   and 64 running-sum registers a lane hold at 16 rows); 1 <= D < 2^20; 1 <= S < 2^20; 0 <= B < 2^31; ld >= P; mode in 0..2; no
+ *   output overlaps an input, the workspace or the other output.  B == 0 returns LK_OK before any device call.
+ * lk_nn_head_work_bytes (host only): the bytes of the G partials, 0 where none are needed or the shape is outside the contract.
+ * lk_nn_head_variant (host only): regime | class tiles per wave << 1 | 16-row tiles per workgroup << 6 | phi restaged per draw
+ *   << 9 | G << 10, or a negative value for a shape the entry point refuses. */
+#define LK_NN_HEAD_MAX_C 1024
+#define LK_NN_HEAD_PROBS 0
+#define LK_NN_HEAD_MOMENTS 1
+#define LK_NN_HEAD_SAMPLES 2
+int lk_nn_head_f32(const float* phi, const float* theta, int64_t B, int64_t C, int64_t D, int64_t S, int64_t ld, int has_bias,
+                   int mode, int softmax, float* out, float* out2, void* work, int64_t work_bytes, void* stream);
+int64_t lk_nn_head_work_bytes(int64_t B, int64_t C, int64_t D, int64_t S, int mode);
+int lk_nn_head_variant(int64_t B, int64_t C, int64_t D, int64_t S, int mode);
+
 #ifdef __cplusplus
 }
 #endif

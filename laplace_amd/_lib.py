@@ -206,6 +206,9 @@ SIGNATURES = {
     "lk_glm_link_wide_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _i64, _vp]),
     "lk_glm_link_wide_work_bytes": (_i64, [_i64, _i64, _int, _int]),
     "lk_glm_link_wide_variant": (_int, [_i64, _i64, _i64, _int, _int]),
+    "lk_nn_head_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _i64, _vp]),
+    "lk_nn_head_work_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
+    "lk_nn_head_variant": (_int, [_i64, _i64, _i64, _i64, _int]),
     "lk_possum_f32": (_int, [_vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
     "lk_possum_f16x2": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
     "lk_possum_variant": (_int, [_i64, _i64, _i64, _int, _int]),
@@ -2828,6 +2831,52 @@ class HipKernels:
         code = self.LINKS[link] if isinstance(link, str) else int(link)
         r = int(self.lib.lk_glm_link_wide_variant(int(B), int(C), int(n_samples), code, 1 if diag else 0))
         return None if r < 0 else r
+
+    # ---- the `nn` predictive of a last-layer posterior: sampled heads on cached features (csrc/lk_nnhead.hip) ---------
+    NN_HEAD_MODES = {"probs": 0, "moments": 1, "samples": 2}
+    NN_HEAD_MAX_C = 1024  # LK_NN_HEAD_MAX_C (include/laplace_hip.h)
+
+    def nn_head(self, phi, theta, C, has_bias=True, mode="probs", softmax=False, out=None, out2=None, work=None):
+        """``S`` sampled ``nn.Linear`` heads on the features ``phi [B, D]``: ``theta [S, >= P]`` holds the rows of ``sample()``
+        (weight ``[C, D]``, then the bias).  ``mode`` 'probs' -> the mean over the draws of the row softmax ``[B, C]``; 'moments'
+        -> ``(mean, var)`` of the outputs over the draws (unbiased, as ``.var(dim=0)``); 'samples' -> ``[S, B, C]`` outputs, or
+        their softmax.  ``out`` / ``out2`` / ``work``: 16-byte aligned buffers to write into (``work`` of
+        ``lk_nn_head_work_bytes`` bytes, allocated when not given)."""
+        code = self.NN_HEAD_MODES[mode] if isinstance(mode, str) else int(mode)
+        _check(phi, "phi"), _check(theta, "theta")
+        if phi.dim() != 2 or theta.dim() != 2:
+            raise LaplaceHipError("nn_head: phi must be [B, D] and theta [S, ld]")
+        (B, D), (S, ld), C = phi.shape, theta.shape, int(C)
+        shape = (S, B, C) if code == 2 else (B, C)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=phi.device)
+        if out2 is None and code == 1:
+            out2 = torch.empty(shape, dtype=torch.float32, device=phi.device)
+        _check(out, "out")
+        if out.shape != shape or (code == 1 and out2.shape != shape):
+            raise LaplaceHipError(f"nn_head: the outputs must be {list(shape)}")
+        if code == 1:
+            _check(out2, "out2")
+        if work is None:
+            need = int(self.lib.lk_nn_head_work_bytes(B, C, D, S, code))
+            if need:
+                work = torch.empty(need // 4, dtype=torch.float32, device=phi.device)
+        if work is not None:
+            _check(work, "work")
+        self._rc(self.lib.lk_nn_head_f32(_ptr(phi), _ptr(theta), B, C, D, S, ld, 1 if has_bias else 0, code, 1 if softmax else 0,
+                                         _ptr(out), _ptr(out2) if code == 1 else None, _ptr(work) if work is not None else None,
+                                         work.numel() * 4 if work is not None else 0, self._stream(phi.device)), "lk_nn_head_f32")
+        return (out, out2) if code == 1 else out
+
+    def nn_head_variant(self, B, C, D, S, mode="probs"):
+        """what ``lk_nn_head_f32`` launches for a shape (host only): ``dict(regime, tiles, rows, restaged, groups)`` - regime 0 a
+        wave per draw, 1 a workgroup per draw; class tiles per wave; batch rows per workgroup; phi restaged per draw in K-chunks;
+        draw groups (> 1: partial sums and a second launch) - or ``None`` for a shape it refuses"""
+        code = self.NN_HEAD_MODES[mode] if isinstance(mode, str) else int(mode)
+        r = int(self.lib.lk_nn_head_variant(int(B), int(C), int(D), int(S), code))
+        if r < 0:
+            return None
+        return {"regime": r & 1, "tiles": (r >> 1) & 31, "rows": 16 * ((r >> 6) & 7), "restaged": bool(r & 512), "groups": r >> 10}
 
 
 _KERNELS = None

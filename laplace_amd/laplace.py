@@ -437,6 +437,9 @@ class _HipLaplace:
         if pred_type == "nn":
             if link_approx != "mc":
                 raise ValueError("Only mc link approximation is supported for nn prediction type.")
+            fused = self._nn_head(x, n_samples, generator, "moments" if self.likelihood == "regression" else "probs")
+            if fused is not None:
+                return fused
             if self.likelihood == "regression":
                 samples = self._nn_predictive_samples(x, n_samples, generator)
                 return samples.mean(dim=0), samples.var(dim=0)
@@ -594,18 +597,69 @@ class _HipLaplace:
     def _randn(self, *shape, generator=None):
         return torch.randn(*shape, device=self._device, dtype=self._dtype, generator=generator)
 
+    #: route the `nn` predictive of a last-layer posterior through the sampled-heads kernel (csrc/lk_nnhead.hip): ONE feature
+    #: pass, ONE ``sample()``, one or two launches and no parameter of the model touched.  It applies to an ``nn.Linear`` head
+    #: whose weight (and bias, if any) is tracked, on 2-D fp32 device features, outside training mode, up to ``NN_HEAD_MAX_C``
+    #: outputs, with a kernel provider that has ``nn_head``.  Off, or outside that range: the loop of ``_nn_functional_samples``.
+    #: The default follows the gate of tools/nn_head_bench.py (README, the ``lk_nnhead.hip`` row).
+    use_nn_head_kernels = False
+
+    def _nn_features(self, X, swept=False):
+        """the head's input from ONE feature pass when the `nn` predictive can reuse it for every draw (lllaplace.py:266-277:
+        only the head changes between the draws of a last-layer posterior), else ``None``: all weights sampled, or training
+        mode.  ``swept``: through the backend's feature pass (the grid search's), not ``forward_with_features``."""
+        if self.subset_of_weights != "last_layer" or getattr(self.model, "model", self.model).training:
+            return None
+        if hasattr(X, "phi"):
+            return X.phi
+        X = X.to(self._device) if torch.is_tensor(X) else X
+        return self.backend.cache_features(X).phi if swept else self.model.forward_with_features(X)[1]
+
+    def _nn_head(self, X, n_samples, generator, mode, softmax=False):
+        """the `nn` predictive in ``mode`` ('probs', 'moments', 'samples') on the sampled-heads kernel, or ``None`` where the
+        route does not apply (see ``use_nn_head_kernels``)"""
+        head = getattr(self.model, "last_layer", None)
+        if not (self.use_nn_head_kernels and self.subset_of_weights == "last_layer" and isinstance(head, nn.Linear)
+                and head.weight.requires_grad and (head.bias is None or head.bias.requires_grad)
+                and head.weight.dtype == torch.float32 and self.backend.last_layer):
+            return None
+        from laplace_amd._lib import HipKernels
+
+        K = _pred.get_kernels()
+        if not (hasattr(K, "nn_head") and 1 <= head.out_features <= getattr(K, "NN_HEAD_MAX_C", 0)):
+            return None
+        phi = self._nn_features(X, swept=True)
+        if phi is None or phi.dim() != 2 or phi.dtype != torch.float32:
+            return None
+        phi = phi.contiguous()
+        if not phi.is_cuda and isinstance(K, HipKernels):  # (a stand-in provider serves the tensors it is given)
+            return None
+        theta = self.sample(n_samples, generator).contiguous()
+        return K.nn_head(phi, theta, head.out_features, has_bias=head.bias is not None, mode=mode, softmax=softmax)
+
     @torch.no_grad()
     def _nn_functional_samples(self, X, n_samples: int = 100, generator=None) -> torch.Tensor:
+        fused = self._nn_head(X, n_samples, generator, "samples")
+        if fused is not None:
+            return fused
+        phi = self._nn_features(X)
         fs = []
         try:
             for sample in self.sample(n_samples, generator):
                 vector_to_parameters(sample, self.params)
-                fs.append(self.model(X.to(self._device) if torch.is_tensor(X) else X).detach())
+                if phi is not None:  # (the backbone ran once, only the head sees the draw)
+                    fs.append(self.model.last_layer(phi).detach())
+                else:
+                    fs.append(self.model(X.to(self._device) if torch.is_tensor(X) else X).detach())
         finally:
             vector_to_parameters(self.mean, self.params)
         return torch.stack(fs)
 
     def _nn_predictive_samples(self, X, n_samples: int = 100, generator=None) -> torch.Tensor:
+        if self.likelihood == "classification":
+            fused = self._nn_head(X, n_samples, generator, "samples", softmax=True)
+            if fused is not None:
+                return fused
         fs = self._nn_functional_samples(X, n_samples, generator)
         return torch.softmax(fs, dim=-1) if self.likelihood == "classification" else fs
 
