@@ -1419,6 +1419,38 @@ int lk_nn_head_f32(const float* phi, const float* theta, int64_t B, int64_t C, i
 int64_t lk_nn_head_work_bytes(int64_t B, int64_t C, int64_t D, int64_t S, int mode);
 int lk_nn_head_variant(int64_t B, int64_t C, int64_t D, int64_t S, int mode);
 
+/* The JOINT GLM predictive covariance of one nn.Linear layer over a batch (csrc/lk_joint.hip), from the factors of its Jacobian:
+ *   cov[(n, c)][(m, k)] += sum_o u[c][n][o] u[k][m][o] T[n][m][o] + sum_o ub[c][n][o] ub[k][m][o] bw[o],
+ *   T[n][m][o] = sum_i v[n][i] v[m][i] w[o][i]
+ * lk_kron_joint_linear_f32: u [C][B][Do] = g Q1, v [B][Di] = a Q2, ub [C][B][Do] = g Qb (NULL: no bias block), the eigenvalues
+ *   l1 [Do], l2 [Di], lb [Do] and the one-element device tensors delta, delta_b: w[o][i] = 1 / (l1[o] l2[i] + delta),
+ *   bw[o] = 1 / (lb[o] + delta_b).  Replaces laplace/utils/matrix.py:406-461 as laplace/baselaplace.py:1837-1843 calls it on
+ *   Js [1][B C][P]: every row rotated through both eigenbases and back and a [B C, P] x [P, B C] product.
+ * lk_diag_joint_linear_f32: the same contraction with u = ub = g [C][B][Do], v = a [B][Di], w = var_w [Do][Di] read from memory and
+ *   bw = var_b [Do] (NULL: no bias block).  Replaces the einsum of laplace/baselaplace.py:2117-2122.
+ * cov [B C][B C] is row-major with row n C + c (the reference's order) and is ADDED to: the layers of a model accumulate into one
+ * matrix.  Nothing of size P per sample is stored and B^2 Do Di multiply-adds are made whatever C is.  A workgroup owns 16 x 16
+ * sample pairs of the upper block triangle and a range of 32-wide Do tiles; T is formed on the exact fp32 matrix instruction with the
+ * products v[n][i] v[m][i] made in registers, stays in accumulators and is folded with u u in a fixed order; both triangles of cov
+ * are written from one value by one thread.  Where the pair blocks alone leave the device idle the Do tiles are split over the
+ * grid: the partial sums go to `ws` with plain stores and a second small launch adds them in ascending order.  No atomics: two
+ * equal calls are bit-equal, and a symmetric cov stays exactly symmetric.
+ *   ws     lk_joint_linear_workspace_bytes bytes (0: not read, may be null), overlapping no argument; contents unspecified
+ *          afterwards.  Null or too small: LK_EWORKSPACE with the bytes needed in the message.
+ * Contract: non-null u, v, weights, cov (ub needs lb, and delta_b in Kron mode); 1 <= C <= LK_JOINT_MAX_C (the C x C running sums
+ *   of a lane's pair, twice, in registers); 0 <= B and B C < 2^31; 1 <= Do, Di <= 2^30, no alignment asked of any of them; cov
+ *   overlaps no input, the workspace neither cov nor an input.  B == 0 returns LK_OK before any device call.
+ * lk_joint_linear_variant (host only; mode 0 Kron, 1 diag): template tier of C (1, 2, 4) | Do tiles split << 3 | splits << 4, or a
+ *   negative value for a shape the entry points refuse. */
+#define LK_JOINT_MAX_C 4
+int lk_kron_joint_linear_f32(const float* u, const float* v, const float* l1, const float* l2, const float* delta, int64_t B,
+                             int64_t C, int64_t Do, int64_t Di, const float* ub, const float* lb, const float* delta_b, float* cov,
+                             void* ws, int64_t ws_bytes, void* stream);
+int lk_diag_joint_linear_f32(const float* a, const float* g, const float* var_w, const float* var_b, int64_t B, int64_t C, int64_t Do,
+                             int64_t Di, float* cov, void* ws, int64_t ws_bytes, void* stream);
+int64_t lk_joint_linear_workspace_bytes(int64_t B, int64_t C, int64_t Do, int64_t Di);
+int lk_joint_linear_variant(int mode, int64_t B, int64_t C, int64_t Do, int64_t Di);
+
 #ifdef __cplusplus
 }
 #endif

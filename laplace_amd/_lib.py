@@ -209,6 +209,10 @@ SIGNATURES = {
     "lk_nn_head_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _i64, _vp]),
     "lk_nn_head_work_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
     "lk_nn_head_variant": (_int, [_i64, _i64, _i64, _i64, _int]),
+    "lk_kron_joint_linear_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "lk_diag_joint_linear_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "lk_joint_linear_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "lk_joint_linear_variant": (_int, [_int, _i64, _i64, _i64, _i64]),
     "lk_possum_f32": (_int, [_vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
     "lk_possum_f16x2": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp]),
     "lk_possum_variant": (_int, [_i64, _i64, _i64, _int, _int]),
@@ -2877,6 +2881,66 @@ class HipKernels:
         if r < 0:
             return None
         return {"regime": r & 1, "tiles": (r >> 1) & 31, "rows": 16 * ((r >> 6) & 7), "restaged": bool(r & 512), "groups": r >> 10}
+
+    # ---- the joint GLM predictive covariance of an nn.Linear layer over a batch (csrc/lk_joint.hip) --------------------
+    JOINT_MAX_C = 4  # LK_JOINT_MAX_C (include/laplace_hip.h)
+    JOINT_MODES = {"kron": 0, "diag": 1}
+
+    def _joint_work(self, B, C, Do, Di, cov, work):
+        """``(address, bytes)`` of the workspace of a joint call: ``work`` (an fp32 buffer) or the provider's own"""
+        if cov.shape != (B * C, B * C):
+            raise LaplaceHipError(f"joint_linear: cov must be [{B * C}, {B * C}]")
+        if work is None:
+            need = int(self.lib.lk_joint_linear_workspace_bytes(B, C, Do, Di))
+            if not need:
+                return None, 0
+            return self._workspace(need, cov.device).data_ptr(), need
+        _check(work, "work")
+        return _ptr(work), work.numel() * 4
+
+    def kron_joint_linear(self, u, v, l1, l2, delta, cov, ub=None, lb=None, delta_b=None, work=None):
+        """``cov [B C, B C] +=`` the joint covariance of a Linear layer under the Kronecker posterior: ``u [C, B, Do]``,
+        ``v [B, Di]`` (eigenbasis projections), ``l1 [Do]``, ``l2 [Di]``, ``delta [1]``; ``ub``, ``lb``, ``delta_b``: the bias
+        block.  ``work``: an fp32 buffer of ``lk_joint_linear_workspace_bytes`` bytes (the provider's own when not given)."""
+        for t, nm in ((u, "u"), (v, "v"), (l1, "l1"), (l2, "l2"), (delta, "delta"), (cov, "cov")):
+            _check(t, nm)
+        (C, B, Do), Di = u.shape, v.shape[1]
+        if v.shape[0] != B or l1.numel() != Do or l2.numel() != Di:
+            raise LaplaceHipError("kron_joint_linear: u [C, B, Do], v [B, Di], l1 [Do], l2 [Di]")
+        if ub is not None:
+            _check(ub, "ub"), _check(lb, "lb"), _check(delta_b, "delta_b")
+            if ub.shape != u.shape or lb.numel() != Do:
+                raise LaplaceHipError("kron_joint_linear: ub [C, B, Do], lb [Do]")
+        ws, ws_bytes = self._joint_work(B, C, Do, Di, cov, work)
+        self._rc(self.lib.lk_kron_joint_linear_f32(_ptr(u), _ptr(v), _ptr(l1), _ptr(l2), _ptr(delta), B, C, Do, Di, _ptr(ub),
+                                                   _ptr(lb), _ptr(delta_b), _ptr(cov), ws, ws_bytes, self._stream(u.device)),
+                 "lk_kron_joint_linear_f32")
+        return cov
+
+    def diag_joint_linear(self, a, g, var_w, var_b, cov, work=None):
+        """``cov [B C, B C] +=`` the same under a diagonal posterior: ``a [B, Di]``, ``g [C, B, Do]``, ``var_w [Do * Di]`` the
+        variances of the weight (row-major ``[Do, Di]``), ``var_b [Do]`` those of the bias or ``None``."""
+        for t, nm in ((a, "a"), (g, "g"), (var_w, "var_w"), (cov, "cov")):
+            _check(t, nm)
+        (C, B, Do), Di = g.shape, a.shape[1]
+        if a.shape[0] != B or var_w.numel() != Do * Di:
+            raise LaplaceHipError("diag_joint_linear: g [C, B, Do], a [B, Di], var_w [Do, Di]")
+        if var_b is not None:
+            _check(var_b, "var_b")
+            if var_b.numel() != Do:
+                raise LaplaceHipError("diag_joint_linear: var_b [Do]")
+        ws, ws_bytes = self._joint_work(B, C, Do, Di, cov, work)
+        self._rc(self.lib.lk_diag_joint_linear_f32(_ptr(a), _ptr(g), _ptr(var_w), _ptr(var_b), B, C, Do, Di, _ptr(cov), ws,
+                                                   ws_bytes, self._stream(a.device)), "lk_diag_joint_linear_f32")
+        return cov
+
+    def joint_linear_variant(self, mode, B, C, Do, Di):
+        """what the joint kernels launch for a shape (host only): ``dict(tier, splits)`` - the template tier of C and the number
+        of workgroups the Do tiles of a pair block are split over (> 1: partial sums in the workspace and a second launch) - or
+        ``None`` for a shape they refuse"""
+        code = self.JOINT_MODES[mode] if isinstance(mode, str) else int(mode)
+        r = int(self.lib.lk_joint_linear_variant(code, int(B), int(C), int(Do), int(Di)))
+        return None if r < 0 else {"tier": r & 7, "splits": r >> 4}
 
 
 _KERNELS = None

@@ -36,15 +36,17 @@ def reference_classes() -> dict:
     from laplace.baselaplace import DiagLaplace, FullLaplace, KronLaplace
     from laplace.lllaplace import DiagLLLaplace, FullLLLaplace, KronLLLaplace
 
-    from laplace_amd.laplace import fit_kron, glm_predictive
+    from laplace_amd.laplace import fit_kron, glm_joint_predictive, glm_predictive
 
     class _FusedPredictive:
         def __init__(self, model, likelihood, *args, backend=HipGGN, **kwargs):
             super().__init__(model, likelihood, *args, backend=backend, **kwargs)
 
         def _glm_predictive_distribution(self, X, joint: bool = False, diagonal_output: bool = False):
-            if joint or self.enable_backprop or not _ours(self):
+            if self.enable_backprop or not _ours(self) or (joint and self.likelihood != "regression"):
                 return super()._glm_predictive_distribution(X, joint=joint, diagonal_output=diagonal_output)
+            if joint:  # Kron and diag flavours: the joint kernels (csrc/lk_joint.hip); anything else: the reference's route
+                return glm_joint_predictive(self, X, fallback=super()._glm_predictive_distribution)
             return glm_predictive(self, X, diagonal_output=diagonal_output,
                                   fallback=super()._glm_predictive_distribution)
 

@@ -418,10 +418,41 @@ class _HipLaplace:
         return (self.backend.last_layer_jacobians(X) if self.subset_of_weights == "last_layer"
                 else self.backend.jacobians(X))
 
+    #: route ``la(X, joint=True)`` of the Kron and diag flavours through the joint kernels (csrc/lk_joint.hip): no ``Js [B, C, P]``,
+    #: nn.Linear layers in one or two launches each, every other layer through its own block.  It applies to fp32 device
+    #: tensors with grad disabled and a kernel provider that has ``kron_joint_linear``.  Off, or outside that range: the
+    #: Jacobian route of ``_glm_joint_distribution``.  The default follows the gate of tools/joint_bench.py (README, the
+    #: ``lk_joint.hip`` row).
+    use_joint_kernels = True
+
+    def _glm_joint_fused(self, X):
+        """the flavour's :mod:`laplace_amd.predictive` joint function on ``X``; ``NotImplementedError``: not served"""
+        raise NotImplementedError
+
+    def _joint_kernels(self, X):
+        """the joint kernels serve this call (see ``use_joint_kernels``)"""
+        on = getattr(self, "use_joint_kernels", _HipLaplace.use_joint_kernels)  # (the drop-in classes read the class switch)
+        if not (on and self._dtype == torch.float32 and hasattr(self.backend, "_forward")):
+            return False
+        from laplace_amd._lib import HipKernels
+
+        K = _pred.get_kernels()
+        if not hasattr(K, "kron_joint_linear"):
+            return False
+        on_device = X.is_cuda if torch.is_tensor(X) else self._device.type == "cuda"
+        return on_device or not isinstance(K, HipKernels)  # (a stand-in provider serves the tensors it is given)
+
     @torch.no_grad()
     def _glm_joint_distribution(self, X):
-        """baselaplace.py:1329-1331: the joint predictive over a batch needs the materialised Jacobians (the
-        cross-sample blocks couple all rows), assembled by the HIP Jacobian kernels."""
+        """baselaplace.py:1329-1331, the joint predictive over a batch.  Kron and diag posteriors: from the per-layer factors of
+        the Jacobian (``use_joint_kernels``); otherwise from the materialised Jacobians (the cross-sample blocks couple all
+        rows), assembled by the HIP Jacobian kernels."""
+        if self._joint_kernels(X):
+            try:
+                f_mu, cov = self._glm_joint_fused(X)
+                return f_mu.detach(), cov.detach()
+            except NotImplementedError:
+                pass
         Js, f_mu = self._jacobians(X)
         return f_mu.flatten().detach(), self.functional_covariance(Js).detach()
 
@@ -931,6 +962,9 @@ class HipKronLaplace(_HipLaplace):
     def _glm_variance_grid(self, X, deltas):
         return _pred.glm_variance_kron_grid(self.backend, X, self.H * self._H_factor, deltas)
 
+    def _glm_joint_fused(self, X):
+        return _pred.glm_covariance_kron(self.backend, X, self.posterior_precision)
+
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
         post = self.posterior_precision
         try:
@@ -987,6 +1021,9 @@ class HipDiagLaplace(_HipLaplace):
 
     def _glm_variance_grid(self, X, deltas):
         return _pred.glm_variance_diag_grid(self.backend, X, self._H_factor * self.H, deltas)
+
+    def _glm_joint_fused(self, X):
+        return _pred.glm_covariance_diag(self.backend, X, self.posterior_variance)
 
     def _glm_predictive_distribution(self, X, diagonal_output: bool = False):
         try:
@@ -1263,6 +1300,27 @@ def glm_predictive(la, X, diagonal_output: bool = False, fallback=None):
     if diagonal_output and f_var.dim() == 3:
         f_var = torch.diagonal(f_var, dim1=-2, dim2=-1)
     return f_mu.detach(), f_var.detach()
+
+
+def glm_joint_predictive(la, X, fallback=None):
+    """:func:`glm_predictive` for ``joint=True``: ``(f_mu.flatten(), cov [B C, B C])`` of a regression posterior of the
+    REFERENCE's Kron or diag classes from the joint kernels (:func:`laplace_amd.predictive.glm_covariance_kron` /
+    ``_diag``), the reference's own method where they do not serve the call or ``_HipLaplace.use_joint_kernels`` is off."""
+    backend = la.backend
+    fallback = fallback or la._glm_predictive_distribution
+    kron, diag = hasattr(la, "H_facs"), torch.is_tensor(la.H) and la.H.ndim == 1
+    if not ((kron or diag) and _HipLaplace._joint_kernels(la, X)):
+        return fallback(X, joint=True)
+    la.model.eval()
+    try:
+        with torch.no_grad():
+            if kron:
+                f_mu, cov = _pred.glm_covariance_kron(backend, X, la.posterior_precision)
+            else:
+                f_mu, cov = _pred.glm_covariance_diag(backend, X, la.posterior_variance)
+    except NotImplementedError:
+        return fallback(X, joint=True)
+    return f_mu.detach(), cov.detach()
 
 
 _FLAVOURS = {"kron": HipKronLaplace, "diag": HipDiagLaplace, "full": HipFullLaplace}

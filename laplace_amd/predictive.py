@@ -281,6 +281,110 @@ def glm_variance_diag(backend, x, post_var: torch.Tensor, diagonal: bool = False
     return f, fvar
 
 
+# ---- the joint predictive over a batch (csrc/lk_joint.hip) ----------------------------------------------------------------
+def _joint_kernels(K, C: int) -> bool:
+    return hasattr(K, "kron_joint_linear") and 1 <= C <= getattr(K, "JOINT_MAX_C", 0)
+
+
+def _weighted_gram(cov, M, w):
+    """``cov [N, N] += (M * w) M^T`` for the stacked rows ``M [N, n]`` of a layer's own block and its weights ``w [n]``"""
+    cov.addmm_(M * w, M.T)
+
+
+def _linear_block(tap, g, B, C):
+    """``[B, C, Do, Di]``: the weight block of the Jacobian of an nn.Linear (along a sequence: summed over its positions)"""
+    a = tap.a.to(torch.float32)
+    a = a.reshape(B, -1, a.shape[-1])
+    return torch.einsum("cnlo,nli->ncoi", g.reshape(C, B, a.shape[1], -1), a)
+
+
+def glm_covariance_kron(backend, x, post):
+    """``(f_mu.flatten(), cov [B C, B C])``: the joint GLM predictive over the batch under a :class:`HipKronDecomposed`
+    posterior precision (KronLaplace.functional_covariance, baselaplace.py:1837-1843) without ``Js [B, C, P]``.  A plain
+    nn.Linear goes to ``lk_kron_joint_linear_f32`` after the two small rotations of :func:`glm_variance_kron`; every other
+    layer (weight sharing, more than ``JOINT_MAX_C`` outputs) contributes through its own rotated block and one weighted
+    product."""
+    K = get_kernels()
+    if not hasattr(K, "kron_joint_linear"):
+        raise NotImplementedError("the kernel provider has no joint kernels")
+    f, tape, grads = _kron_sweep(backend, x)
+    B, C = f.shape
+    cov = torch.zeros(B * C, B * C, dtype=torch.float32, device=f.device)
+    for tap, g, Q1, Q2, l1, l2, delta, Qb, lb, delta_b in _kron_blocks(post, tape, grads):
+        if post.damping:  # (shifted eigenvalues and no additive term: see glm_variance_kron)
+            sq = torch.sqrt(delta.detach().to(l1.dtype))
+            l1, l2, delta = l1 + sq, l2 + sq, torch.zeros_like(delta)
+        if tap.kind == "linear" and tap.a.ndim == 2 and _joint_kernels(K, C):
+            Do = g.shape[-1]
+            g2 = g.reshape(C * B, Do)
+            u = (g2 @ Q1).reshape(C, B, Do).contiguous()
+            v = (tap.a.to(torch.float32) @ Q2).contiguous()
+            ub = (g2 @ Qb).reshape(C, B, Do).contiguous() if Qb is not None else None
+            K.kron_joint_linear(u, v, l1.contiguous(), l2.contiguous(), delta.detach().reshape(1).contiguous(), cov, ub,
+                                None if lb is None else lb.contiguous(),
+                                None if delta_b is None else delta_b.detach().reshape(1).contiguous())
+            continue
+        Do, Dk = len(l1), len(l2)
+        if tap.kind == "conv2d":
+            Jl, width = _conv_block_jacobian(tap, g, B, C)
+            W, gb = Jl[:, :, :width].reshape(B * C, Do, Dk), Jl[:, :, width:]
+        else:
+            W = _linear_block(tap, g, B, C).reshape(B * C, Do, Dk)
+            gb = g.reshape(C, B, -1, Do).sum(2).transpose(0, 1)
+        M = (Q1.T @ W @ Q2).reshape(B * C, Do * Dk)
+        _weighted_gram(cov, M, (1.0 / (torch.outer(l1, l2) + delta)).reshape(-1))
+        if Qb is not None:
+            _weighted_gram(cov, gb.reshape(B * C, Do) @ Qb, 1.0 / (lb + delta_b))
+    tape.release()
+    return f.flatten(), cov
+
+
+def glm_covariance_diag(backend, x, post_var: torch.Tensor):
+    """``(f_mu.flatten(), cov [B C, B C])`` under a diagonal posterior with variances ``post_var [P]``
+    (DiagLaplace.functional_covariance, baselaplace.py:2117-2122) without ``Js [B, C, P]``: nn.Linear layers on
+    ``lk_diag_joint_linear_f32``, every other layer through its own block.  An embedding table has no block route here:
+    NotImplementedError, the caller's Jacobian route serves it."""
+    _fp32_only(backend)
+    K = get_kernels()
+    if not hasattr(K, "diag_joint_linear"):
+        raise NotImplementedError("the kernel provider has no joint kernels")
+    f, tape, grad_fn = backend._forward(x, extra=True)
+    taps = backend._served_taps(tape)
+    if tape.unserved_by(tape.route) or any(tap.kind == "embed" for tap in taps):
+        tape.release()
+        raise NotImplementedError("fused joint diagonal predictive needs Linear / Conv2d / affine normalisation layers only")
+    B, C = f.shape
+    grads = grad_fn(_identity_seeds(f))
+    post_var = post_var.detach().to(torch.float32).contiguous()
+    cov = torch.zeros(B * C, B * C, dtype=torch.float32, device=f.device)
+    for tap, g in zip(taps, grads):
+        if tap.kind in backend.BLOCK_KINDS:
+            parts = list(backend._tap_blocks(tap, g))
+            Jl = torch.cat([p[1] for p in parts]) if len(parts) > 1 else parts[0][1]
+            for col, n, off in parts[0][2]:
+                if n:
+                    _weighted_gram(cov, Jl[:, :, col:col + n].reshape(B * C, n), post_var[off:off + n])
+            continue
+        m = tap.module
+        vw = post_var[tap.w_off:tap.w_off + m.weight.numel()]
+        if tap.kind == "linear" and tap.a.ndim == 2 and _joint_kernels(K, C):
+            vb = post_var[tap.b_off:tap.b_off + m.out_features].contiguous() if tap.has_bias else None
+            K.diag_joint_linear(tap.a.to(torch.float32).contiguous(), g.contiguous(), vw.contiguous(), vb, cov)
+            continue
+        if tap.kind == "conv2d":
+            Jl, width = _conv_block_jacobian(tap, g, B, C)
+            W, gb = Jl[:, :, :width], Jl[:, :, width:]
+        else:
+            W = _linear_block(tap, g, B, C)
+            gb = g.reshape(C, B, -1, W.shape[2]).sum(2).transpose(0, 1)
+        _weighted_gram(cov, W.reshape(B * C, -1), vw)
+        if tap.has_bias:
+            nb = gb.shape[-1]
+            _weighted_gram(cov, gb.reshape(B * C, nb), post_var[tap.b_off:tap.b_off + nb])
+    tape.release()
+    return f.flatten(), cov
+
+
 def _grid_deltas(deltas, dev):
     d = torch.as_tensor(deltas).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
     if d.numel() == 0:
