@@ -1337,6 +1337,38 @@ int lk_glm_link_wide_f32(const float* f_mu, const float* f_var, const float* z, 
 int64_t lk_glm_link_wide_work_bytes(int64_t B, int64_t C, int link, int diag);
 int lk_glm_link_wide_variant(int64_t B, int64_t C, int64_t n_samples, int link, int diag);
 
+/* Samples of the GLM predictive, written out (csrc/lk_glmsamples.hip): replaces laplace/utils/utils.py:337-378 (normal_samples)
+ * behind baselaplace.py _glm_functional_samples / _glm_predictive_samples: a batched vendor Cholesky, a batched product with the
+ * shared draw, a broadcast add into [B][C][n] handed out through permute(2, 0, 1), and for classification a softmax tensor of the
+ * same size.  One launch:
+ *     out[s][b][c] = f_mu[b][c] + sum_{j <= c} L_b[c][j] z[j][s],   L_b = chol(f_var_b) (lower, fp32)
+ *   f_mu     [B][C]
+ *   f_var    [B][C][C] (its lower triangle and diagonal are read), or with `diag` non-zero the marginal variances [B][C]: the sum
+ *            is then sqrt(f_var[b][c]) z[c][s]
+ *   z        [C][n_samples] standard-normal draws shared by all samples of the batch; the kernel consumes them and draws nothing
+ *   softmax  0: out holds the logits; non-zero: the row softmax of each draw (the maximum subtracted)
+ *   out      [n_samples][B][C], contiguous, draw-major
+ *   info     [B]: 0, or j + 1 where the factorisation met a pivot <= 0 or a non-finite pivot at column j; all n_samples rows of
+ *            that sample are NaN, every other sample is unaffected.  With `diag` always 0.
+ * The kernel is bound by its output stream, so the work is split over (sample, draw chunk): chunks of 16 ceil(stages / want) draws,
+ * stages = ceil(n / 16), want = min(stages, ceil(512 / W)), W the workgroups one chunk needs (two workgroups a CU where B n allows
+ * it).  Every chunk factorises its sample again (the same arithmetic, the same bits); chunk 0 writes info.  Three regimes:
+ * full covariance, C <= 64: a wave per (sample, chunk), the factor in registers a lane per row, L z a j-ascending fmaf chain, a
+ * draw's row one coalesced store; full covariance, C <= LK_LINK_MAX_C: a workgroup per (sample, chunk), L resident in LDS, a
+ * blocked factorisation with 16-wide panels whose trailing update and L z run on the exact fp32 matrix instruction, z staged 16
+ * draws at a time, the logits tile stored (or normalised) straight from the accumulators; marginal variances,
+ * C <= LK_LINK_WIDE_MAX_C: streaming, 16 classes a thread, z transposed through LDS so that global reads run along n, 16-byte
+ * stores where C % 4 == 0.  One owner per output element, fixed reduction orders, plain stores, no atomics: two equal calls are
+ * bit-equal.
+ * Contract: every pointer non-null and 16-byte aligned; 1 <= C <= LK_LINK_MAX_C (diag: <= LK_LINK_WIDE_MAX_C); 0 <= B < 2^31;
+ *   1 <= n_samples < 2^20; n_samples * B * C < 2^40; out and info overlap neither an input nor each other.  B == 0 returns LK_OK
+ *   before any device call.
+ * lk_glm_samples_variant (host only): regime | chunks << 8 with regime 0 (wave), 1 (workgroup, L in LDS) or 2 (marginal
+ *   variances), or a negative value for a shape the entry point refuses. */
+int lk_glm_samples_f32(const float* f_mu, const float* f_var, const float* z, int64_t B, int64_t C, int64_t n_samples, int diag,
+                       int softmax, float* out, int32_t* info, void* stream);
+int lk_glm_samples_variant(int64_t B, int64_t C, int64_t n_samples, int diag, int softmax);
+
 /* The two reductions of KFAC-reduce (csrc/lk_kfacreduce.hip): with kfac_approx="reduce" (laplace/curvature/curvlinops.py:95-98
  * hands it to curvlinops' KFAC) a weight-sharing layer's output gradients are summed and its inputs averaged over the shared
  * positions before the outer products.  They replace the torch sequences  g.float().sum((1, 2)),  g.reshape(S B, Do, L).sum(2),

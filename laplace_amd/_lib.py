@@ -206,6 +206,8 @@ SIGNATURES = {
     "lk_glm_link_wide_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _i64, _vp]),
     "lk_glm_link_wide_work_bytes": (_i64, [_i64, _i64, _int, _int]),
     "lk_glm_link_wide_variant": (_int, [_i64, _i64, _i64, _int, _int]),
+    "lk_glm_samples_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
+    "lk_glm_samples_variant": (_int, [_i64, _i64, _i64, _int, _int]),
     "lk_nn_head_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _i64, _vp]),
     "lk_nn_head_work_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
     "lk_nn_head_variant": (_int, [_i64, _i64, _i64, _i64, _int]),
@@ -2835,6 +2837,40 @@ class HipKernels:
         code = self.LINKS[link] if isinstance(link, str) else int(link)
         r = int(self.lib.lk_glm_link_wide_variant(int(B), int(C), int(n_samples), code, 1 if diag else 0))
         return None if r < 0 else r
+
+    # ---- samples of the GLM predictive, written out (csrc/lk_glmsamples.hip) ---------------------------------------------
+    GLM_SAMPLES_MAX_C_DIAG = 4096  # LK_LINK_WIDE_MAX_C: marginal variances; the full covariance is served up to LINK_MAX_C
+
+    def glm_samples(self, f_mu, f_var, z, diag=False, softmax=False, out=None, info=None):
+        """``(out [n, B, C], info [B])``: ``out[s] = f_mu + L z[:, s]`` with ``L = chol(f_var_b)`` (``f_var`` ``[B, C, C]``), or
+        ``f_mu + sqrt(f_var) * z[:, s]`` with ``diag`` (``f_var`` ``[B, C]``), for the shared draw ``z [C, n]``, in one launch;
+        ``softmax``: the row softmax of each draw instead of the logits.  ``info[b] = j + 1`` where the factorisation met a pivot
+        that is not positive at column ``j`` (all ``n`` rows of sample ``b`` are then NaN).  ``out`` / ``info``: buffers to write
+        into (16-byte aligned)."""
+        _check(f_mu, "f_mu"), _check(f_var, "f_var"), _check(z, "z")
+        B, C = f_mu.shape
+        if f_var.shape != ((B, C) if diag else (B, C, C)):
+            raise LaplaceHipError(f"glm_samples: f_var must be {'[B, C]' if diag else '[B, C, C]'} for f_mu [B, C]")
+        if z.dim() != 2 or z.shape[0] != C:
+            raise LaplaceHipError("glm_samples: z must be [C, n_samples]")
+        n = z.shape[1]
+        if out is None:
+            out = torch.empty(n, B, C, dtype=torch.float32, device=f_mu.device)
+        if info is None:
+            info = torch.empty(B, dtype=torch.int32, device=f_mu.device)
+        _check(out, "out"), _check(info, "info", torch.int32)
+        if out.shape != (n, B, C) or info.shape != (B,):
+            raise LaplaceHipError("glm_samples: out must be [n_samples, B, C] and info [B]")
+        self._rc(self.lib.lk_glm_samples_f32(_ptr(f_mu), _ptr(f_var), _ptr(z), B, C, n, 1 if diag else 0, 1 if softmax else 0,
+                                             _ptr(out), _ptr(info), self._stream(f_mu.device)), "lk_glm_samples_f32")
+        return out, info
+
+    def glm_samples_variant(self, B, C, n_samples, diag=False, softmax=False):
+        """what ``lk_glm_samples_f32`` launches for a shape (host only): ``dict(regime, chunks)`` with regime 0 a wave per
+        (sample, draw chunk), 1 a workgroup with the factor in LDS, 2 streaming over marginal variances; ``None`` for a shape
+        it refuses"""
+        r = int(self.lib.lk_glm_samples_variant(int(B), int(C), int(n_samples), 1 if diag else 0, 1 if softmax else 0))
+        return None if r < 0 else {"regime": r & 255, "chunks": r >> 8}
 
     # ---- the `nn` predictive of a last-layer posterior: sampled heads on cached features (csrc/lk_nnhead.hip) ---------
     NN_HEAD_MODES = {"probs": 0, "moments": 1, "samples": 2}

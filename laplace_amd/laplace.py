@@ -490,7 +490,7 @@ class _HipLaplace:
             return self._glm_link(K, x, f_mu, f_var, link_approx, n_samples, diagonal_output, generator, wide=True)
         if link_approx == "mc":
             fv = f_var if not diagonal_output else torch.diag_embed(f_var)
-            return self._glm_predictive_samples(f_mu, fv, n_samples, diagonal_output, generator).mean(dim=0)
+            return self._glm_predictive_samples(f_mu, fv, n_samples, diagonal_output, generator, kernels=False).mean(dim=0)
         if link_approx in ("bridge", "bridge_norm"):
             if diagonal_output:
                 f_mu, f_var = self._glm_predictive_distribution(x)  # the bridge needs the full output covariance
@@ -694,9 +694,50 @@ class _HipLaplace:
         fs = self._nn_functional_samples(X, n_samples, generator)
         return torch.softmax(fs, dim=-1) if self.likelihood == "classification" else fs
 
-    def _glm_functional_samples(self, f_mu, f_var, n_samples, diagonal_output=False, generator=None):
+    #: route the GLM samples of ``functional_samples`` / ``predictive_samples`` through the samples kernel
+    #: (csrc/lk_glmsamples.hip): one launch writes the contiguous ``[n, B, C]`` samples, or their softmax, from the draw made
+    #: here.  It applies to fp32 device tensors with a kernel provider that has ``glm_samples``, up to ``LINK_MAX_C`` outputs
+    #: with the full covariance and ``GLM_SAMPLES_MAX_C_DIAG`` with ``diagonal_output``.  Off, or outside that range: the torch
+    #: sequence below.  The default follows the gate of tools/glm_samples_bench.py (README, the ``lk_glmsamples.hip`` row).
+    use_glm_sample_kernels = False
+
+    def _glm_sample_kernels(self, f_mu, f_var, diagonal_output):
+        """the kernel provider when the samples kernel serves ``(f_mu, f_var)``, else ``None`` (the torch path runs)"""
+        if not (self.use_glm_sample_kernels and f_mu.dtype == f_var.dtype == torch.float32 and f_mu.dim() == 2
+                and f_var.shape == (*f_mu.shape, f_mu.shape[1])):
+            return None
+        from laplace_amd._lib import HipKernels
+
+        K = _pred.get_kernels()
+        if not (f_mu.is_cuda and f_var.is_cuda) and isinstance(K, HipKernels):  # (a stand-in provider serves the tensors it is given)
+            return None
+        top = getattr(K, "GLM_SAMPLES_MAX_C_DIAG" if diagonal_output else "LINK_MAX_C", 0)
+        return K if hasattr(K, "glm_samples") and 1 <= f_mu.shape[1] <= top else None
+
+    def _glm_samples_fused(self, f_mu, f_var, n_samples, diagonal_output, generator, softmax=False):
+        """``[n_samples, B, C]`` GLM samples (their softmax with ``softmax``) in one launch from the draw
+        ``_glm_functional_samples`` makes, or ``None`` where the route does not apply (see ``use_glm_sample_kernels``)"""
+        K = self._glm_sample_kernels(f_mu, f_var, diagonal_output)
+        if K is None:
+            return None
+        z = torch.randn(f_mu.shape[1], n_samples, device=f_mu.device, dtype=f_mu.dtype, generator=generator)
+        if diagonal_output:
+            f_var = torch.diagonal(f_var, dim1=1, dim2=2)
+        out, info = K.glm_samples(f_mu.contiguous(), f_var.contiguous(), z, diag=diagonal_output, softmax=softmax)
+        if not diagonal_output:
+            status = info.cpu()  # (the one host read of the call, as torch.linalg.cholesky reads its status)
+            if bool(status.any()):
+                b = int(status.nonzero()[0])
+                raise torch.linalg.LinAlgError(f"glm_samples: the predictive covariance of sample {b} is not positive-definite "
+                                               f"(pivot {int(status[b])} of its Cholesky factorisation)")
+        return out
+
+    def _glm_functional_samples(self, f_mu, f_var, n_samples, diagonal_output=False, generator=None, kernels=True):
         """utils/utils.py:337-378 (normal_samples): the same ``[C, n_samples]`` standard-normal draw is shared by
-        all points of the batch, exactly as in the reference."""
+        all points of the batch, exactly as in the reference.  ``kernels=False`` keeps the torch sequence (``__call__``)."""
+        fused = self._glm_samples_fused(f_mu, f_var, n_samples, diagonal_output, generator) if kernels else None
+        if fused is not None:
+            return fused
         if f_var.shape != (f_mu.shape[0], f_mu.shape[1], f_mu.shape[1]):
             raise ValueError("f_var must be [batch, outputs, outputs]")
         z = torch.randn(f_mu.shape[1], n_samples, device=f_mu.device, dtype=f_mu.dtype, generator=generator)
@@ -706,8 +747,12 @@ class _HipLaplace:
             scaled = torch.matmul(torch.linalg.cholesky(f_var), z.unsqueeze(0))
         return (f_mu.unsqueeze(-1) + scaled).permute(2, 0, 1)
 
-    def _glm_predictive_samples(self, f_mu, f_var, n_samples, diagonal_output=False, generator=None):
-        fs = self._glm_functional_samples(f_mu, f_var, n_samples, diagonal_output, generator)
+    def _glm_predictive_samples(self, f_mu, f_var, n_samples, diagonal_output=False, generator=None, kernels=True):
+        if kernels and self.likelihood == "classification":  # the softmax in the same launch: no second [n, B, C] tensor
+            fused = self._glm_samples_fused(f_mu, f_var, n_samples, diagonal_output, generator, softmax=True)
+            if fused is not None:
+                return fused
+        fs = self._glm_functional_samples(f_mu, f_var, n_samples, diagonal_output, generator, kernels)
         return torch.softmax(fs, dim=-1) if self.likelihood == "classification" else fs
 
     @torch.no_grad()
